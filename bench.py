@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """DRBA hot-path benchmark: interpolated frames/s, `rife -t 2`, 1080p (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1080p|4k|480p|4k_s1] [--no-cpu-baseline] [--no-extra]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1080p|4k|480p|4k_s1] [--dump-outputs DIR]
+                    [--full [--no-roofline] [--no-cpu-baseline] [--no-extra]]
 
 A *step* = one source frame of the driver's steady state: the next uint8 frame (already resident in HBM) -> to_inp
 (u8 HWC -> fp32 NCHW + bilinear resize to the network size) -> warm RIFE.inference_ts_drba(I0, I1, I2, ts=[0.75, 1.25],
@@ -11,17 +12,24 @@ starting and ending in pinned host memory.  value = model-generated frames of AL
 As in drba_amd.infer.interpolate_stream the loop reads two frames ahead: the next step's coarse flow and
 low-resolution stages run on a side stream under this step's full-resolution stages, and the frame after that has its
 context encoder and the coarse flow of the pair it forms with its predecessor started on a third stream (`tools/ab_bench.py --no-lookahead` disables both); every frame is converted and encoded exactly
-once either way, one new frame per step, and the K timed steps contain K steps of work.
+once either way, one new frame per step, and the K timed steps contain K steps of work: the headline times exactly K steps
+(`ms_per_step` = their wall time / K), after the W warm-up steps and the untimed settling steps (step_loop).
+A plain run does only that and prints the line; `--full` adds every object listed under "Extra objects" below.
+`--dump-outputs DIR` (N = 1) writes the frames the last timed step returned (to_out's uint8 frames as float32,
+DIR/frame_t075.npy and DIR/frame_t125.npy; a fixed sample of each above 64 MB in all, e.g. at 4K): the settling steps end on a
+whole number of clip cycles, so the same arguments time the same frames in every run and two builds compare output for output
+(to within 1 per value, not bit for bit: the splats' fp32 atomics and the per-process autotuner's picks change the rounding of
+the fp32 frames, and the *255 truncation can turn that into a difference of 1).
 
 N = 1: the K-step loop above.
 N > 1 (launched by torch.distributed.run, one rank per GPU): ONE clip of N*K + 2 source frames is sharded with
 drba_amd.parallel.interpolate_shard (contiguous chunks, one-frame halo for the warm `reuse`, weak scaling: K steps per
 GPU), the finished uint8 frames travel to rank 0 (the writer) through StreamedGather -- the only data-path collective,
 RCCL over xGMI, inside the timed region.  `replica_loop` is the N = 1 loop run by every rank on its own clip (no halo,
-no collective) and `config5_sharded` BASELINE.json configs[4]: one FIXED 4K clip (-fps 60, scale 0.5, one planted scene
+no collective) and `config5_sharded` (`--full`) BASELINE.json configs[4]: one FIXED 4K clip (-fps 60, scale 0.5, one planted scene
 cut) sharded over the N ranks (strong scaling).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (`--full` only; null or absent in a plain run):
   roofline      the kernel SYMBOL with the largest total time over the instrumented steps: 4 consecutive steps of the same
                 loop, run right after the timed region with the library's kernel trace on for every launch (each launch
                 carries an event pair on its own dispatch packet, i.e. the kernel's own execution time as rocprofv3's
@@ -52,6 +60,7 @@ import argparse
 import collections
 import gc
 import json
+import math
 import os
 import sys
 import time
@@ -89,7 +98,7 @@ kClipWarmup = 24
 kMaxStepsInFlight = 16  # step_loop: the host waits for the step this many steps back (four groups of steps stay queued on the GPU; 32: the 4K runs stall again)
 kClipSteps = 40  # timed iterations of the driver-loop legs (extra_configs): 5 groups of 4 steps on each side of the planted cut
 SRC_FPS = 24.0
-kMinTimedSeconds = 0.25  # the K-step block is repeated until the timed region is at least this long (K = 20 steps at 2 ms are 40 ms: box-to-box noise)
+kMinTimedSeconds = 0.25  # pcie_inclusive / headline_three_term: the K-step block is repeated until the timed region is at least this long (K = 20 steps at 2 ms are 40 ms: box-to-box noise)
 # SURVEY.md 8(d) / BASELINE.md 3: algorithmic work of ONE model-generated frame (warm), per config: (GFLOP, conv-boundary GB)
 FRAME_WORK = {"1080p": (92.9, 1.59), "4k": (107.2, 2.13)}
 
@@ -103,6 +112,7 @@ LAST_SHARD = {"rank_dt": None, "path": None}  # this rank's own wall time of the
 LAST_PATH = {}  # RIFE.stats over the timed region of the last step_loop: which path the K timed calls took (reported on the line)
 LAST_BLOCKS = {"n": 1}  # K-step blocks the last step_loop timed back to back (kMinTimedSeconds)
 LAST_SETTLE = {"steps": 0}  # untimed settling steps the last step_loop ran after its W warm-up steps (reported on the line)
+LAST_OUT = {"frames": None}  # what the last timed step of the last step_loop returned (its to_out frames): --dump-outputs
 
 
 def log(msg):
@@ -130,7 +140,16 @@ def parse():
     p.add_argument("--conv-families", default=None,
                    help="kernel families the conv autotuner may pick from (default 0,1,2,3,4); 0,1,2,3 keeps every MFMA operand "
                         "at 24 bits (three bf16 terms) instead of the two-term fp16 form -- the number of the previous rounds")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline: roofline, pcie_inclusive, cpu_baseline / max_abs_vs_oracle, "
+                        "extra_configs (N > 1: config5_sharded); the --no-* switches above narrow it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="N = 1: write the frames the last timed step returned to DIR/<name>.npy (float32, at most 64 MB in all)")
     args = p.parse_args()
+    if args.dump_outputs is not None and args.gpus != 1:
+        p.error("--dump-outputs needs --gpus 1")
+    if not args.full:  # a plain run: set up, warm up, time the K steps (and write the outputs); nothing else
+        args.no_roofline = args.no_extra = args.no_cpu_baseline = True
     if args.conv_families is not None:
         from drba_amd import ops
         ops.CONV_FAMILIES = {int(x) for x in args.conv_families.split(",")}
@@ -592,10 +611,12 @@ def _quiet_gc():
     gc.freeze()
 
 
-def step_loop(model, frames, n_steps_total, args, world, trace=True, pcie=False, settle=True, check_path=True):
+def step_loop(model, frames, n_steps_total, args, world, trace=True, pcie=False, settle=True, check_path=True,
+              min_timed=kMinTimedSeconds):
     """The N = 1 loop of the module docstring over `frames` (sequence of uint8 HWC frames: device tensors, or -- with
-    pcie=True -- pinned host tensors with the outputs copied back to pinned host buffers).
-    -> (seconds for args.steps steps, host-side enqueue seconds, trace records, instrumented steps)."""
+    pcie=True -- pinned host tensors with the outputs copied back to pinned host buffers).  The K-step block is timed
+    back to back until the region lasts min_timed seconds (0: exactly K timed steps).
+    -> (seconds for args.steps * LAST_BLOCKS["n"] steps, host-side enqueue seconds, trace records, instrumented steps)."""
     from drba_amd import ops
     from drba_amd.models.utils import tools
     H, W = frames[0].shape[:2]
@@ -652,7 +673,8 @@ def step_loop(model, frames, n_steps_total, args, world, trace=True, pcie=False,
     # each instead of 1.0 ms (allocator growth, first touches) and a 20-step timed region started there reads 508 instead
     # of 670 frames/s (profiles/README.md).  So the untimed warm-up goes on for kSettleSeconds of steps.
     t_settle, settled = time.perf_counter() + (kSettleSeconds if settle else 0.0), 0
-    while time.perf_counter() < t_settle:
+    phase = math.lcm(nf, int(getattr(model, "GROUP", 1)))
+    while time.perf_counter() < t_settle or settled % phase:  # whole clip cycles (and groups): the same frames are timed in every run
         step()
         settled += 1
         if settled % 8 == 0:
@@ -669,17 +691,18 @@ def step_loop(model, frames, n_steps_total, args, world, trace=True, pcie=False,
     t0 = time.perf_counter()
     per_step = []
     blocks = 0
-    while True:  # EXACTLY K steps per block; blocks are repeated (whole blocks, one fence at the end) until the region is long enough to quote
+    while True:  # EXACTLY K steps per block; blocks are repeated (whole blocks, one fence at the end) until the region lasts min_timed
         for k in range(args.steps):
-            step()
+            last = step()
             per_step.append(time.perf_counter())
         blocks += 1
-        if world > 1 or not settle or not args.steps or time.perf_counter() - t0 >= kMinTimedSeconds or blocks >= 64:  # (N > 1: every rank times one block)
+        if world > 1 or not settle or not args.steps or time.perf_counter() - t0 >= min_timed or blocks >= 64:  # (N > 1: every rank times one block)
             break
     t_host = time.perf_counter() - t0 - throttle[0]  # all launches enqueued: the host side of a step (the GPU may still be working)
     _fence(world)
     dt = time.perf_counter() - t0
     LAST_BLOCKS["n"] = blocks
+    LAST_OUT["frames"] = last if args.steps else None
     LAST_PATH.clear()
     LAST_PATH.update({k: v - stats0.get(k, 0) for k, v in getattr(model, "stats", {}).items()})
     grp = int(getattr(model, "GROUP", 1))
@@ -894,8 +917,10 @@ def gpu_leg(args, rank, world):
     r = {"desc": desc, "dev": dev, "model": model}
     clip = DeviceClip(min(n_total + 2, 12), H, W, 1234 + rank, dev)
     frames = [clip[k] for k in range(len(clip))]
-    dt, t_host, recs, traced, dst = step_loop(model, frames, n_total, args, world, trace=not args.no_roofline)
-    r["blocks"] = LAST_BLOCKS["n"]  # K-step blocks timed back to back (one region): every per-step figure divides by K * blocks
+    dt, t_host, recs, traced, dst = step_loop(model, frames, n_total, args, world, trace=not args.no_roofline, min_timed=0.0)
+    r["blocks"] = LAST_BLOCKS["n"]  # 1: the headline times exactly K steps (--steps)
+    if args.dump_outputs is not None:  # the frames the last timed step returned, read back before anything else runs
+        r["outputs"] = {f"frame_t{round(t * 100):03d}": y.cpu().numpy() for t, y in zip(TS, LAST_OUT["frames"])}
     r["dst_size"] = dst
     r["settle_steps"] = LAST_SETTLE["steps"]
     r["path"] = dict(LAST_PATH, group=int(getattr(model, "GROUP", 1)), what="RIFE.stats over the K timed calls of this rank")
@@ -1031,6 +1056,24 @@ def cpu_leg(args, model):
     return base, parity
 
 
+kDumpBytes = 64_000_000  # --dump-outputs: all arrays together, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  If they exceed kDumpBytes together, each larger array is
+    replaced by a fixed sample of its elements (seed 0, ascending flat indices, the same in every run), all within the budget."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = kDumpBytes - 256 * len(arrays)  # (a .npy header is 128 bytes)
+    keep = budget // 4 // len(arrays)
+    sample = 4 * sum(a.size for a in arrays.values()) > budget
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if sample and a.size > keep:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {out_dir}: " + ", ".join(sorted(arrays)) + (" (sampled)" if sample else ""))
+
+
 def describe_job(rank, world, r):
     """What torch.distributed saw: backend, world size, the device of every rank, the RCCL version, every rank's time for
     the timed sharded run -- so that a scaling record can be checked for "did RCCL run with N ranks on N GPUs"."""
@@ -1113,6 +1156,8 @@ def main():
             r["model"] = None
             torch.cuda.empty_cache()
             extra = extra_configs(args, r["dev"])
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, r["outputs"])
     if rank == 0:
         wl = r["desc"] + "; warm inference_ts_drba ts=[0.75,1.25] + to_inp/to_out on device"
         if world > 1:

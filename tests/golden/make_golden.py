@@ -462,7 +462,37 @@ def golden_trained():
     print("undamped GMFlow: reference flow moves by", floor, "under a 1e-7 input perturbation; |flow| max", float(r["flow01"].abs().max()))
 
 
+def golden_pickles():
+    """The reference mount's CUDA-tagged pickles, weights/{train_log_gmfss,train_log_gmfss_union}/{feat,metric}.pkl, as
+    skeletons under weight_pickles/: every member of the torch zip archive as it is (the pickle program with its keys, shapes,
+    dtypes and cuda:0 storage tags) except the tensor payloads (data/<n>), which are zeroed, so each file deflates to a few KiB;
+    plus weight_pickles/sha256.json, the sha256 of every original tensor's bytes (keyed dir / net / state-dict key)."""
+    import hashlib
+    import re
+    import zipfile
+    out_dir = os.path.join(HERE, "weight_pickles")
+    sha = {}
+    for d in ("train_log_gmfss", "train_log_gmfss_union"):
+        os.makedirs(os.path.join(out_dir, d), exist_ok=True)
+        for net in ("feat", "metric"):
+            src = os.path.join(REF, "weights", d, net + ".pkl")
+            sd = torch.load(src, map_location="cpu", weights_only=True)
+            sha.setdefault(d, {})[net] = {k: hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest() for k, v in sd.items()}
+            dst = os.path.join(out_dir, d, net + ".pkl")
+            with zipfile.ZipFile(src) as zi, zipfile.ZipFile(dst, "w", zipfile.ZIP_DEFLATED) as zo:
+                for info in zi.infolist():
+                    b = zi.read(info)
+                    if re.search(r"/data/\d+$", info.filename):
+                        b = bytes(len(b))
+                    zo.writestr(zipfile.ZipInfo(info.filename, date_time=(1980, 1, 1, 0, 0, 0)), b, zipfile.ZIP_DEFLATED)
+            sk = torch.load(dst, map_location="cpu", weights_only=True)
+            assert list(sk) == list(sd) and all(sk[k].shape == sd[k].shape and sk[k].dtype == sd[k].dtype for k in sd), (d, net)
+            print(f"wrote weight_pickles/{d}/{net}.pkl: {os.path.getsize(dst) / 1024:.0f} KiB")
+    with open(os.path.join(out_dir, "sha256.json"), "w") as f:
+        json.dump(sha, f, indent=1)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["ops", "drm", "scdet", "schedule", "rife", "gmfss", "gmfss_plain", "trained"]
+    which = sys.argv[1:] or ["ops", "drm", "scdet", "schedule", "rife", "gmfss", "gmfss_plain", "trained", "pickles"]
     for w in which:
         globals()["golden_" + w]()

@@ -147,7 +147,7 @@ def test_bench_two_rank_rehearsal_over_gloo():
     env = dict(os.environ, DRBA_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--config",
-                        "480p"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "480p", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)

@@ -8,7 +8,7 @@ cp drba_amd/csrc/libdrba_hip.so /tmp/lib_new.so
 for round in 1 2; do
   for which in new base; do
     if [ $which = new ]; then cp /tmp/lib_new.so drba_amd/csrc/libdrba_hip.so; else cp $OTHER drba_amd/csrc/libdrba_hip.so; fi
-    timeout 600 python bench.py --no-extra --no-cpu-baseline "$@" > $OUT/bench_${which}_$round.json 2> $OUT/bench_${which}_$round.err
+    timeout 600 python bench.py --full --no-extra --no-cpu-baseline "$@" > $OUT/bench_${which}_$round.json 2> $OUT/bench_${which}_$round.err
     python - <<PY
 import json
 d = json.load(open("$OUT/bench_${which}_$round.json"))

@@ -1,7 +1,7 @@
 #!/bin/bash
 OUT=gpurun_out/r06_d
 mkdir -p $OUT
-timeout 900 python bench.py --no-cpu-baseline > $OUT/bench_1080p.json 2> $OUT/bench_1080p.err; echo bench exit $?
+timeout 900 python bench.py --full --no-cpu-baseline > $OUT/bench_1080p.json 2> $OUT/bench_1080p.err; echo bench exit $?
 python - <<PY
 import json
 r=json.loads(open("$OUT/bench_1080p.json").read().strip().splitlines()[-1])
@@ -17,7 +17,7 @@ for n in base split100 base2 split100b; do
 import json,sys
 r=json.loads(open('$OUT/ab_$n.json').read().strip().splitlines()[-1]); print('$n', r['value'], r['ms_per_step'])"
 done
-timeout 600 python bench.py --config 4k --no-extra --no-cpu-baseline > $OUT/bench_4k.json 2> $OUT/bench_4k.err
+timeout 600 python bench.py --config 4k --full --no-extra --no-cpu-baseline > $OUT/bench_4k.json 2> $OUT/bench_4k.err
 python -c "
 import json
 r=json.loads(open('$OUT/bench_4k.json').read().strip().splitlines()[-1]); print('4k', r['value'], r['ms_per_step'], r['roofline']['kernel'], r['roofline']['frac'])"

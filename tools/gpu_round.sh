@@ -40,9 +40,9 @@ if [ -n "$F4" ] && [ -n "$W4" ]; then
   DRBA_PMC_MERGE=1 python tools/pmc_traffic.py $F4 $W4 $OUT/pmc_manifest_4k.json $OUT/pmc_traffic_4k.md > /dev/null && cp profiles/pmc_traffic.json $OUT/pmc_traffic.json
 fi
 rm -rf $OUT/pmc4k_fetch/*kernel_trace.csv $OUT/pmc4k_write/*kernel_trace.csv
-timeout 900 python bench.py > $OUT/bench_1080p.json 2> $OUT/bench_1080p.err; echo "bench exit $?"
+timeout 900 python bench.py --full > $OUT/bench_1080p.json 2> $OUT/bench_1080p.err; echo "bench exit $?"
 for c in 4k 480p 4k_s1; do
-  timeout 600 python bench.py --config $c --no-extra --no-cpu-baseline > $OUT/bench_$c.json 2>> $OUT/bench_other.err
+  timeout 600 python bench.py --config $c --full --no-extra --no-cpu-baseline > $OUT/bench_$c.json 2>> $OUT/bench_other.err
 done
 python tools/step_timeline.py --steps 2 > $OUT/timeline_1080p.txt 2>/dev/null
 export TMPDIR=/tmp
