@@ -49,6 +49,16 @@ def main():
                 import traceback
                 traceback.print_exc()
                 sections.append((f"gmfss_union s={scale}", [("EXC", float("inf"), 0.0, repr(e))]))
+        if os.environ.get("DRBA_REPORT_FULLSIZE", "1") == "1":  # BASELINE config 4 at its size: ~1 min of oracle time
+            try:
+                from tests.test_gpu_fullsize import TS_T2, _net_frames
+                frames = _net_frames(3, 1080, 1920, (1152, 1920), seed=4321)
+                sections.append(("gmfss_union 1152x1920 warm step (config 4): end to end, spliced, decisions",
+                                 gpu_checks.check_gmfss_union_warm_step(hip, ora, frames, TS_T2)))
+            except Exception as e:  # noqa: BLE001
+                import traceback
+                traceback.print_exc()
+                sections.append(("gmfss_union 1152x1920", [("EXC", float("inf"), 0.0, repr(e))]))
         try:
             sections.append(("gmfss (non-union)", gpu_checks.check_gmfss_plain(hip, ora, np.load(os.path.join(GOLD, "gmfss.npz")))))
         except Exception as e:  # noqa: BLE001

@@ -86,7 +86,9 @@ def test_gmfss_subnets_parity(hip_backend):
 def test_gmfss_union_end_to_end_parity(hip_backend, oracle_backend, golden_dir, scale, size):
     """GMFSS_UNION through the reference call surface: every output (frames, flows, metrics, features) within
     1e-3 max-abs -- flat -- of the oracle and of the reference's own outputs in the fixture; at most 0.02 % of an
-    output's elements (discontinuous splat / mask decisions) above it, none above 5e-2 (gpu_checks.check_gmfss_union)."""
+    output's elements (discontinuous splat / mask decisions) above it, none above 5e-2 (gpu_checks.check_gmfss_union).
+    Beside each budgeted warm / non-linear frame: the spliced rows of gpu_checks.union_spliced_step -- flat 1e-3 against the
+    oracle on HIP's own pair states, and the decisions pixel by pixel."""
     rows = gpu_checks.check_gmfss_union(hip_backend, oracle_backend, np.load(os.path.join(golden_dir, "gmfss_union.npz")),
                                         scale, size)
     _assert_rows(rows)
