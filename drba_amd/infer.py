@@ -323,6 +323,10 @@ def main(argv=None):
     args = parse_args(argv)
     if not os.path.exists(args.input):
         raise FileNotFoundError(f"can't find the video file {args.input}")
+    # the command line keeps the conv autotuner's winners across runs unless DRBA_TUNE_CACHE=0 (drba_amd/tunecache.py; the library
+    # alone leaves the store off); nothing is written before the first winner is stored
+    from drba_amd import tunecache
+    tunecache.default_on()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1:
         model = load_model(args.model_type, scale=args.scale)

@@ -39,6 +39,11 @@ class GMFSS:
     supports_lookahead = True
     _look = None
 
+    def reset_stream_state(self):
+        """Drop the pending side-stream work of the last call (the lookahead pair state): the next call starts as on a new model."""
+        if self._look is not None:
+            self._look.pending = None
+
     def warm_reuse(self, Ia, Ib):
         """The `reuse` a DRBA step ending on the pair (Ia, Ib) hands to the next step (gmfss.py:70-72): model.reuse(Ia, Ib)
         with the roles swapped.  Used by drba_amd.parallel to rebuild the state entering a shard."""

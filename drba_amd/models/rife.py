@@ -358,6 +358,14 @@ class RIFE:
         self._group_out = [(F[j], F[j + 1], F[j + 2], ts_list[j], reuses[j], res[j], reuses[j + 1]) for j in range(1, g)]
         return res[0], reuses[1]
 
+    def reset_stream_state(self):
+        """Drop what a run of a driver loop leaves on the model: the steps of a group computed ahead and the pending side-stream
+        work (one-step lookahead, staged group).  The next call starts as on a new model; the counters are the caller's."""
+        self._group_out = ()
+        for look in (self._look, self._look2):
+            if look is not None:
+                look.pending = None
+
     def inference_ts_drba(self, I0, I1, I2, ts, reuse=None, linear=False, lookahead=None):
         """reference rife.py:77-109.  `lookahead` (not in the reference): the frame that will be I2 of the next call,
         or (that frame, the next call's ts).  calc_flow(I2, next) -- and, when the timesteps are known, the DRM maps

@@ -5,11 +5,13 @@ takes CUDA tensors, hands raw pointers to libdrba_hip.so on torch's current stre
 returns freshly allocated output tensors.  No arithmetic happens in torch.
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
 
 from drba_amd import _lib
+from drba_amd import tunecache as _tunecache
 
 _MODES = {"sum": 0, "avg": 1, "linear": 2, "soft": 3}
 _EPS = {None: 0, "addeps": 0, "zeroeps": 1, "clipeps": 2}
@@ -529,16 +531,63 @@ def _tuned_get(shape_key, families=None):
     return _tuned.get((shape_key, tuple(sorted(CONV_FAMILIES if families is None else families))))
 
 
-def _tune(shape_key, candidates, run, reps=3, families=None):
+class NoKernelConfig(_lib.DrbaHipError):
+    """No kernel configuration accepts a shape (every candidate's warm launch refused it)."""
+
+
+_no_config = set()  # keys of _tuned's kind for which every candidate refused: not asked again in this process
+TUNE_IGNORE_HITS = False  # drba_amd.tune --retune: stored winners are not read, every shape met is tuned afresh and its entry replaced
+_TUNE_STAT_KEYS = ("full_tunes", "timing_passes", "cache_hits", "negative_hits", "rejected", "stored")
+_tune_stats = dict.fromkeys(_TUNE_STAT_KEYS, 0)
+
+
+def tune_stats():
+    """What the autotuner did in this process so far: shapes tuned in full, timing passes (one device synchronisation each),
+    winners taken from the store (drba_amd.tunecache; `negative_hits`: stored "no configuration accepts"), stored entries that were
+    rejected, entries written."""
+    return dict(_tune_stats)
+
+
+_EUNSUPPORTED = -2  # DRBA_EUNSUPPORTED (include/drba_hip.h): the shape is outside what the configuration was built for
+
+
+def _tune(shape_key, candidates, run, reps=3, families=None, persist=False, device=None):
+    """persist: the winner is looked up in / written to the store of drba_amd.tunecache when DRBA_TUNE_CACHE turns it on (the
+    three convolution wrappers below pass it, with the index of the device the layer runs on; keys of any other caller are never
+    stored)."""
     # a winner of one family set is not offered to another
-    shape_key = (shape_key, tuple(sorted(CONV_FAMILIES if families is None else families)))
+    fams = tuple(sorted(CONV_FAMILIES if families is None else families))
+    kind_key, shape_key = shape_key, (shape_key, fams)
     if shape_key in _tuned:
         return _tuned[shape_key]
+    if shape_key in _no_config:
+        raise NoKernelConfig(f"no kernel configuration accepts {shape_key}")
+    # (with the library's debug range check armed a launch can return DRBA_EUNSUPPORTED for what is in the DATA: nothing such a
+    # process learns is a property of the shape, so it neither reads nor writes the store)
+    store = _tunecache.active(device) if persist and os.environ.get("DRBA_CHECK_RANGE", "0") in ("", "0") else None
+    if store is not None and not TUNE_IGNORE_HITS:
+        hit = store.get(kind_key, fams)
+        if hit is not None:
+            if hit.get("none"):
+                _tune_stats["negative_hits"] += 1
+                _no_config.add(shape_key)
+                raise NoKernelConfig(f"no kernel configuration accepts {shape_key}")
+            # an id from the file is launched only if this process offers it for the layer itself; its one warm launch must succeed
+            code = run(hit["cfg"]) if hit["cfg"] in candidates else _EUNSUPPORTED
+            if code == 0:
+                _tune_stats["cache_hits"] += 1
+                _tuned[shape_key] = hit["cfg"]
+                return hit["cfg"]
+            if code != _EUNSUPPORTED:  # a launch failure / bad argument says nothing about the entry: not rejected, not re-tuned over
+                raise _lib.DrbaHipError(f"warm launch of the stored configuration {hit['cfg']} for {shape_key} failed ({code})")
+            _tune_stats["rejected"] += 1
+
     def timed(cfg):
         # the candidates are timed on an otherwise idle device: the first call for a shape usually comes from inside the
         # three-stream pipeline, and a candidate timed beside another stream's kernels loses to one that was not (round 4: a
         # 590 us stride-2 tile picked over a 321 us one for the largest conv0 layer, -1.5 % on the step)
         torch.cuda.synchronize()
+        _tune_stats["timing_passes"] += 1
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(reps):
@@ -547,18 +596,32 @@ def _tune(shape_key, candidates, run, reps=3, families=None):
         e1.synchronize()
         return e0.elapsed_time(e1)
 
-    ok = [cfg for cfg in candidates if run(cfg) == 0]  # warm: packs weights, faults pages; a configuration that refuses the shape is not a candidate
+    _tune_stats["full_tunes"] += 1
+    codes = {cfg: run(cfg) for cfg in candidates}  # warm: packs weights, faults pages; a configuration that refuses the shape is not a candidate
+    ok = [cfg for cfg in candidates if codes[cfg] == 0]
     if not ok:
-        raise _lib.DrbaHipError(f"no kernel configuration accepts {shape_key}")
+        if any(c != _EUNSUPPORTED for c in codes.values()):
+            # a launch failure (DRBA_ELAUNCH, a sticky earlier error) or a bad argument is not a property of the shape: it is
+            # reported as it always was and remembered nowhere, neither in the process nor in the store
+            raise _lib.DrbaHipError(f"no kernel configuration accepts {shape_key}: the warm launches failed with {sorted(set(codes.values()))}")
+        _no_config.add(shape_key)  # no candidate, or every one answered DRBA_EUNSUPPORTED
+        if store is not None and store.put(kind_key, fams, None):
+            _tune_stats["stored"] += 1
+        raise NoKernelConfig(f"no kernel configuration accepts {shape_key}")
     first = {cfg: timed(cfg) for cfg in ok}
     # Every candidate is read twice (the second pass in reverse order) and its smaller reading counts.  Round 6: 38 convolution
     # configurations, several within a few percent of each other on most layers, and one reading in a few hundred carries a one-off
     # delay of milliseconds (tools/exp/cfg37_probe.py: the same launch 94 us and 4111 us) -- a single pass picked a 4 % slower
     # tile for a layer in some runs and could lose the true best to such a reading (the 24-bit headline leg read 880 once, 950-976
-    # otherwise).  ~20 ms per layer shape, once per process.
+    # otherwise).  ~20 ms per layer shape, once per process (once per machine and build with the store on).
     second = {cfg: timed(cfg) for cfg in reversed(ok)} if len(ok) > 1 else first
-    best = min(ok, key=lambda c: min(first[c], second[c]))
+    reading = {c: min(first[c], second[c]) for c in ok}
+    best = min(ok, key=lambda c: reading[c])
     _tuned[shape_key] = best
+    if store is not None:
+        us = sorted(reading[c] for c in ok if c != best)
+        if store.put(kind_key, fams, best, reading[best] * 1e3 / reps, us[0] * 1e3 / reps if us else None):
+            _tune_stats["stored"] += 1
     return best
 
 
@@ -621,7 +684,7 @@ class Conv3x3:
                      and lib.drba_conv3x3_packed_floats(self.cin, self.cout, c) > 0]  # 0: the config cannot run this layer
             cfg = _tune(("conv3x3", n, cin, self.cout, h, w, self.stride), cands, lambda c: lib.drba_conv3x3(
                 _p(x), _p(self._pack(c)), _p(self.bias), _p(self.beta), _p(res), _p(res2), _p(out), n, cin, h, w,
-                self.cout, self.stride, self.act, self.post_slope, pre, ps, c, _stream()), families=fam)
+                self.cout, self.stride, self.act, self.post_slope, pre, ps, c, _stream()), families=fam, persist=True, device=x.device.index)
             self._keep.add(cfg)  # a layer can have one winner per batch size (block0: N=1 in calc_flow, N=2 stacked)
             for c in [c for c in self._packed if c not in self._keep]:
                 del self._packed[c]  # drop the packings of the losing candidates
@@ -653,10 +716,14 @@ def conv3x3_shuffle(layer, x):
     run = lambda c: lib.drba_conv3x3_shuffle(_p(x), _p(layer._pack(c)), _p(layer.bias), _p(out), n, cin, h, w, layer.cout,  # noqa: E731
                                              layer.act, layer.post_slope, c, _stream())
     try:
-        cfg = _tune(("conv3x3_shuffle", n, cin, layer.cout, h, w), cands, run, families=(4,))
-    except _lib.DrbaHipError:
+        cfg = _tune(("conv3x3_shuffle", n, cin, layer.cout, h, w), cands, run, families=(4,), persist=True, device=x.device.index)
+    except NoKernelConfig:  # remembered per shape (in the process and in the store): the next call comes here without a launch
+        for c in [c for c in layer._packed if c not in layer._keep]:
+            del layer._packed[c]
         return pixel_shuffle2(layer(x))
     layer._keep.add(cfg)
+    for c in [c for c in layer._packed if c not in layer._keep]:
+        del layer._packed[c]  # drop the packings of the losing candidates
     _lib.check(_timed("conv3x3", (cfg, cin, layer.cout, h, w, 1, n, "ps"), 2.0 * layer.cout * cin * 9 * h * w * n, "flop", lambda: run(cfg)),
                "drba_conv3x3_shuffle")
     return out
@@ -703,7 +770,7 @@ class Deconv4x4:
                      and lib.drba_deconv4x4_packed_floats(cin, self.cout, c) > 0]
             cfg = _tune(("deconv4x4", n, cin, self.cout, h, w, self.ps), cands,
                         lambda c: lib.drba_deconv4x4s2(_p(x), _p(self._pack(c)), _p(self.bias), _p(out), n, cin, h, w,
-                                                       self.cout, self.ps, pre, ps_, c, _stream()), families=fam)
+                                                       self.cout, self.ps, pre, ps_, c, _stream()), families=fam, persist=True, device=x.device.index)
             self._keep.add(cfg)
             for c in [c for c in self._packed if c not in self._keep]:
                 del self._packed[c]
