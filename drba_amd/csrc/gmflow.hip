@@ -75,6 +75,10 @@ conv_direct_kernel(const float *__restrict__ in, const float *__restrict__ w, co
 // it: pass 1 reduces every chunk to (mean, M2) with the two-pass formula inside the chunk, pass 2 merges the chunk
 // statistics of its plane (Chan's parallel update, exact mean/variance algebra) and normalises its chunk.
 // Two reads + one write of the tensor instead of three reads by one workgroup per plane.
+// All of it in a frame shifted by the plane's first element (the chunk means are stored relative to it): the statistics of a
+// plane whose mean dwarfs its spread keep their digits (x - x0 is exact for values within a factor of two of x0; summing
+// and merging |mean| ~ 1e3 values in fp32 cost 1e-2 of the normalised output at std 1e-2), and a constant plane gives
+// exactly 0 instead of rounding noise over sqrt(eps).
 constexpr int kInChunks = 32;
 __global__ void __launch_bounds__(256)
 instance_norm_stats_kernel(const float *__restrict__ in, float *__restrict__ part, size_t HW) {
@@ -82,13 +86,14 @@ instance_norm_stats_kernel(const float *__restrict__ in, float *__restrict__ par
   const size_t clen = (HW + kInChunks - 1) / kInChunks;
   const size_t lo = (size_t)blockIdx.x * clen, hi = min(lo + clen, HW);
   const float *p = in + (size_t)blockIdx.y * HW;
+  const float x0 = p[0];
   float s = 0.f;
-  for (size_t i = lo + threadIdx.x; i < hi; i += 256) s += p[i];
+  for (size_t i = lo + threadIdx.x; i < hi; i += 256) s += p[i] - x0;
   const float cntf = hi > lo ? (float)(hi - lo) : 0.f;
-  const float mean = cntf > 0.f ? block_sum256(s, red) / cntf : 0.f;
+  const float mean = cntf > 0.f ? block_sum256(s, red) / cntf : 0.f;  // of x - x0
   float v = 0.f;
   for (size_t i = lo + threadIdx.x; i < hi; i += 256) {
-    const float d = p[i] - mean;
+    const float d = (p[i] - x0) - mean;
     v += d * d;
   }
   const float m2 = block_sum256(v, red);
@@ -119,8 +124,9 @@ instance_norm_apply_kernel(const float *__restrict__ in, const float *__restrict
   const size_t lo = (size_t)blockIdx.x * clen, hi = min(lo + clen, HW);
   const float *p = in + (size_t)blockIdx.y * HW;
   float *o = out + (size_t)blockIdx.y * HW;
+  const float x0 = p[0];  // (mean is the mean of x - x0)
   for (size_t i = lo + threadIdx.x; i < hi; i += 256) {
-    const float y = (p[i] - mean) * inv;
+    const float y = ((p[i] - x0) - mean) * inv;
     o[i] = relu ? fmaxf(y, 0.f) : y;
   }
 }

@@ -716,8 +716,11 @@ __global__ void __launch_bounds__(256) fill_holes_kernel(const float *__restrict
 }
 
 // drm.py:10-62.  The scalar bracket walk (double, like Python floats) is data independent;
-// every lane replays it and applies the matching map update in fp32.
+// every lane replays it and applies the matching map update in fp32.  Every update rounds the product and the difference
+// separately, as the reference's tensor expressions do (no contraction into an FMA: the walk is ~10 dependent roundings
+// and the result is compared bit for bit).
 __global__ void __launch_bounds__(256) drm_retime_kernel(const float *__restrict__ drm, float *__restrict__ out, double t, double prec, size_t n) {
+#pragma clang fp contract(off)
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     double x = 0.5, lo = 0.0, hi = 1.0;
     const double frac = 0.5;

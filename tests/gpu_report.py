@@ -8,7 +8,7 @@ import time
 import numpy as np
 import torch
 
-from tests import cases, gpu_checks
+from tests import cases, gpu_checks, op_checks
 from tests.backends import HipBackend, OracleBackend
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -26,6 +26,13 @@ def main():
     sections.append(("linear (split-bf16)", gpu_checks.check_linear_split(hip.dev)))
     sections.append(("feature splats", gpu_checks.check_splat_quad(hip.dev)))
     sections.append(("scdet", gpu_checks.check_scdet(hip, np.load(os.path.join(GOLD, "scdet.npz")))))
+    for title, check in op_checks.CHECKS:  # every glue operator on its own against fp64 (tests/op_checks.py)
+        try:
+            sections.append((title, check(hip.dev)))
+        except Exception as e:  # noqa: BLE001
+            import traceback
+            traceback.print_exc()
+            sections.append((title, [("EXC", float("inf"), 0.0, repr(e))]))
     gold = np.load(os.path.join(GOLD, "rife.npz"))
     for scale, size in cases.RIFE_CONFIGS:
         try:

@@ -1,0 +1,603 @@
+"""Per-operator fp64 parity checks of the GMFlow / GMFSS glue kernels (gmflow.hip, gmfss_glue.hip, the small kernels of
+splat_warp.hip and the layout kernels of ifnet_glue.hip), shared by tests/test_gpu_op_parity.py, tests/test_op_checks_cpu.py and
+the diagnostic report (python -m tests.gpu_report).
+
+Every check takes the device the inputs go to and the `ops` namespace under test (default: drba_amd.ops; the CPU test hands
+in a torch stand-in, with and without a planted defect) and returns rows (name, err, tol, extra) with the pass rule of every
+parity row, `err <= tol`.
+
+References are plain torch on the CPU in float64, written from the formulas of the reference model that the kernel comments
+cite (oracle/*.py restates them), never from the kernels.  Value rows use one rule,
+
+    tol = max(2e-5 * max(1, |ref|max), 3 * floor),
+
+where `floor` is the max error of the fp32 oracle / fp32 torch evaluation of the same formula on the same input against the
+fp64 reference: measured per row, printed in the row, never calibrated against the code under test.  Decisions (masks, hole
+tests, the DRM retiming walk) and pure data movement are compared bit for bit: err = number of differing elements, tol = 0.
+
+Two places where ATen's CPU result is not the specification are written out instead of taken from ATen:
+  * a zeros-padding bilinear sample at a non-finite coordinate is 0 (every tap is outside the image; ATen's CPU kernel forms
+    0 * NaN there, its CUDA kernel -- what the reference model runs on -- skips the taps);
+  * InstanceNorm of a one-element plane is 0 (variance 0; F.instance_norm refuses the shape).
+Inputs regenerate from seeds (cases.rnd, synth._smooth_field)."""
+import torch
+import torch.nn.functional as F
+
+from drba_amd.utils import synth
+from oracle import drm as odrm
+from oracle import gmflow as ogm
+from oracle import ops as oops
+from tests import cases
+
+
+class Row(tuple):
+    """(name, err, tol, extra) -- what _assert_rows / report.record / gpu_report take -- that also carries the operator family,
+    the measured fp32 floor and |ref|max of a value row (None for bit-exact rows)."""
+
+    def __new__(cls, op, name, err, tol, extra="", floor=None, refmax=None):
+        self = super().__new__(cls, (f"{op} {name}", err, tol, extra))
+        self.op, self.floor, self.refmax = op, floor, refmax
+        return self
+
+
+def default_ops():
+    from drba_amd import ops
+    return ops
+
+
+def rule_tol(refmax, floor):
+    return max(2e-5 * max(1.0, refmax), 3.0 * floor)
+
+
+def _err(got, ref):
+    """max |got - ref| in float64 over the elements where ref is finite; inf when the shapes differ or the non-finite elements
+    of ref (NaN, +inf, -inf) are not the same values at the same places in got."""
+    g, r = got.detach().double().cpu(), ref.detach().double().cpu()
+    if g.shape != r.shape:
+        return float("inf")
+    fin = torch.isfinite(r)
+    if not torch.equal(torch.isfinite(g), fin):
+        return float("inf")
+    if not bool(fin.all()):
+        gn, rn = g[~fin], r[~fin]
+        if not (torch.equal(gn.isnan(), rn.isnan()) and torch.equal(torch.nan_to_num(gn, 0.0, 1.0, -1.0), torch.nan_to_num(rn, 0.0, 1.0, -1.0))):
+            return float("inf")
+    d = (g[fin] - r[fin]).abs()
+    return float(d.max()) if d.numel() else 0.0
+
+
+def value_row(op, name, got, ref64, ref32, extra=""):
+    fin = ref64[torch.isfinite(ref64)]
+    refmax = float(fin.abs().max()) if fin.numel() else 0.0
+    floor = _err(ref32, ref64)
+    return Row(op, name, _err(got, ref64), rule_tol(refmax, floor), f"fp32_floor={floor:.2e} |ref|max={refmax:.3g} {extra}".rstrip(),
+               floor, refmax)
+
+
+def _mismatches(got, want):
+    """elements that differ bit for bit (any NaN equals any NaN; -0 differs from +0)"""
+    g, w = got.detach().cpu().contiguous(), want.detach().cpu().contiguous()
+    if g.shape != w.shape or g.dtype != w.dtype:
+        return float("inf")
+    if g.dtype == torch.float32:
+        same = (g.view(torch.int32) == w.view(torch.int32)) | (g.isnan() & w.isnan())
+    else:
+        same = g == w
+    return float((~same).sum())
+
+
+def exact_row(op, name, got, want, extra=""):
+    return Row(op, name, _mismatches(got, want), 0.0, f"bit-exact, {want.numel()} elements {extra}".rstrip())
+
+
+def _smooth(c, h, w, seed):
+    return synth._smooth_field(c, h, w, seed)
+
+
+# ----------------------------------------------------------------------------------------- softmax_rows_
+SOFTMAX_COLS = (1, 2, 63, 64, 65, 576, 577, 1024, 1025, 2304, 2305, 8704, 8705)  # both sides of every dispatch bound of drba_softmax_rows
+SOFTMAX_MASKED = (35, 700, 2000, 5000, 9000)  # one per dispatch branch (<= 576, <= 1024, <= 2304, <= 8704, the three-pass kernel)
+
+
+def block_mask(n_masks, rows, cols, seed):
+    """[n_masks, rows, cols] of 0 / -100 the way shift_window_mask builds it: -100 where the row's and the column's region
+    labels differ (transformer.py:19-43), with seeded labels so that rows != cols is possible."""
+    g = torch.Generator().manual_seed(seed)
+    rl = torch.randint(0, 3, (n_masks, rows, 1), generator=g)
+    cl = torch.randint(0, 3, (n_masks, 1, cols), generator=g)
+    cl[:, :, 0] = rl[:, 0]  # (no row of the first label is masked everywhere)
+    m = torch.zeros(n_masks, rows, cols)
+    return m.masked_fill(rl != cl, -100.0)
+
+
+def _softmax_ref(scores, scale, mask):
+    s = scores / scale
+    if mask is not None:
+        m, n = scores.shape[0], mask.shape[0]
+        s = s + mask.to(s.dtype).repeat((m + n - 1) // n, 1, 1)[:m]  # matrix i takes mask i % n_masks (transformer.py:85)
+    return torch.softmax(s, dim=-1)
+
+
+def check_softmax_rows(dev, ops=None):
+    ops = ops or default_ops()
+    op, rows = "softmax_rows_", []
+
+    def one(name, scores, scale, mask):
+        got = ops.softmax_rows_(scores.to(dev).clone(), scale, None if mask is None else mask.to(dev))
+        rows.append(value_row(op, name, got, _softmax_ref(scores.double(), scale, mask), _softmax_ref(scores, scale, mask)))
+
+    for k, cols in enumerate(SOFTMAX_COLS):  # 3 matrices of 5 rows: 15 rows, the last block of 4 is partial
+        one(f"cols={cols} [3x5 rows]", cases.rnd((3, 5, cols), 300 + k, 3.0), 1.0, None)
+    for k, cols in enumerate(SOFTMAX_MASKED):  # 5 matrices cycle 2 masks (5 % 2 != 0), 3 rows each
+        one(f"cols={cols} masked [5x3 rows, 2 masks]", cases.rnd((5, 3, cols), 320 + k, 3.0), 1.0, block_mask(2, 3, cols, 330 + k))
+    # the mask of a real shifted 2 x 2 split of a 10 x 14 map (5 x 7 windows: L = cols = 35), 7 matrices over its 4 masks
+    one("cols=35 shift_window_mask [7x35 rows, 4 masks]", cases.rnd((7, 35, 35), 340, 3.0), 1.0, ogm.shift_window_mask(10, 14, 5, 7, 2, 3))
+    one("cols=65 |scores|~80", cases.rnd((3, 5, 65), 341, 80.0), 1.0, None)
+    one("cols=700 scale=sqrt(128)", cases.rnd((3, 5, 700), 342, 30.0), 128 ** 0.5, block_mask(2, 5, 700, 343))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- instance_norm
+IN_PLANES = ((1, 1), (1, 5), (1, 31), (4, 8), (3, 11), (37, 53), (144, 240))  # HW = 1, 5, 31, 32, 33, 37*53, 144*240
+
+
+def _inorm_ref(x, relu):
+    if x.shape[2] * x.shape[3] == 1:
+        y = torch.zeros_like(x)  # one element: it is its own mean
+    else:
+        y = F.instance_norm(x, eps=1e-5)  # backbone.py:7,17-20
+    return F.relu(y) if relu else y
+
+
+def check_instance_norm(dev, ops=None):
+    ops = ops or default_ops()
+    op, rows = "instance_norm", []
+
+    def one(name, x, relu):
+        got = ops.instance_norm(x.to(dev), relu=relu)
+        rows.append(value_row(op, f"{name} relu={int(relu)}", got, _inorm_ref(x.double(), relu), _inorm_ref(x, relu)))
+
+    for k, (h, w) in enumerate(IN_PLANES):
+        one(f"1x1x{h}x{w}", cases.rnd((1, 1, h, w), 400 + k, 2.0) + 0.3, relu=bool(k % 2))
+        one(f"2x3x{h}x{w}", cases.rnd((2, 3, h, w), 420 + k, 2.0) + 0.3, relu=not k % 2)
+    one("2x3x37x53", cases.rnd((2, 3, 37, 53), 440, 2.0), relu=True)
+    one("1x1x37x53", cases.rnd((1, 1, 37, 53), 441, 2.0), relu=True)
+    # a mean that dwarfs the spread: the fp32 inputs (exact in the fp64 reference) sit ~160 ulps apart at most
+    one("2x3x37x53 mean 1e3 std 1e-2", cases.rnd((2, 3, 37, 53), 442, 1e-2) + 1e3, relu=False)
+    one("1x2x144x240 mean 1e3 std 1e-2", cases.rnd((1, 2, 144, 240), 443, 1e-2) + 1e3, relu=False)
+    x = cases.rnd((1, 3, 37, 53), 444, 1.0)
+    x[0, 1] = 3.7  # a constant plane: variance 0, the output is 0 (and finite)
+    one("1x3x37x53 constant plane", x, relu=False)
+    got = ops.instance_norm(x.to(dev), relu=False)[0, 1]
+    rows.append(value_row(op, "constant plane alone -> 0", got, torch.zeros(37, 53, dtype=torch.float64), F.instance_norm(x, eps=1e-5)[0, 1]))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- conv_direct
+CONV_CASES = (  # (n, cin, cout, h, w, k, stride, pad, bias)
+    (1, 3, 64, 37, 61, 7, 2, 3, False), (1, 3, 64, 128, 256, 7, 2, 3, False), (2, 7, 70, 11, 19, 7, 2, 3, True),
+    (3, 5, 17, 13, 45, 3, 1, 1, True), (3, 5, 15, 13, 45, 3, 2, 1, True), (1, 6, 1, 9, 13, 3, 1, 1, False),
+    (1, 3, 70, 37, 61, 1, 1, 0, True), (3, 6, 17, 9, 13, 1, 1, 0, True), (3, 6, 15, 9, 13, 1, 2, 0, False),  # Cin % 4 != 0: not the MFMA path
+    (3, 8, 70, 9, 13, 1, 1, 0, True), (1, 8, 15, 5, 7, 1, 2, 0, False), (3, 8, 1, 9, 13, 1, 1, 0, True), (1, 8, 17, 37, 61, 1, 1, 0, True))
+
+
+def check_conv_direct(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    for i, (n, cin, cout, h, w, k, s, p, has_b) in enumerate(CONV_CASES):
+        x = cases.rnd((n, cin, h, w), 500 + i, 1.0)
+        wt = cases.rnd((cout, cin, k, k), 530 + i, 1.0 / (cin * k * k) ** 0.5)
+        b = cases.rnd((cout,), 560 + i, 0.5) if has_b else None
+        got = ops.conv_direct(x.to(dev), wt.to(dev), None if b is None else b.to(dev), s, p)
+        ref64 = F.conv2d(x.double(), wt.double(), None if b is None else b.double(), stride=s, padding=p)
+        rows.append(value_row("conv_direct", f"[{n}x{cin}->{cout} {h}x{w} k{k} s{s} p{p} bias={int(has_b)}]", got, ref64,
+                              F.conv2d(x, wt, b, stride=s, padding=p)))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- local_corr_flow
+LCORR_CASES = ((128, 1, 1), (128, 3, 70), (128, 13, 45), (128, 33, 64), (128, 65, 31),  # the MFMA kernel: width below / at / past a 64 tile
+               (96, 1, 1), (96, 3, 70), (96, 13, 45), (96, 33, 64), (96, 65, 31),        # the generic kernel (32-pixel tiles)
+               (32, 1, 1), (32, 13, 45), (32, 33, 64), (130, 3, 70), (130, 65, 31))
+
+
+def _lcorr_ref(f0, f1, r):
+    if f0.shape[2] == 1 and f0.shape[3] == 1:
+        return torch.zeros(1, 2, 1, 1, dtype=f0.dtype)  # one pixel: only the centre tap is in the image (matching.py:41-89 divides by W - 1)
+    return ogm.local_correlation_softmax(f0, f1, r)
+
+
+def check_local_corr_flow(dev, ops=None):
+    ops = ops or default_ops()
+    op, rows = "local_corr_flow", []
+
+    def one(name, f0, f1):
+        got = ops.local_corr_flow(f0.to(dev), f1.to(dev), 4)
+        rows.append(value_row(op, name, got, _lcorr_ref(f0.double(), f1.double(), 4), _lcorr_ref(f0, f1, 4)))
+
+    for i, (c, h, w) in enumerate(LCORR_CASES):
+        one(f"C={c} {h}x{w}", cases.rnd((1, c, h, w), 600 + i, 0.6), cases.rnd((1, c, h, w), 630 + i, 0.6))
+    for i, (c, h, w) in enumerate(((128, 13, 45), (96, 33, 64))):
+        # feature1 is feature0 moved by (+2, -1): that tap scores |f|^2 / sqrt(C) ~ 2.25 sqrt(C), the rest ~ N(0, 2.25^2)
+        f0 = cases.rnd((1, c, h, w), 660 + i, 1.5)
+        one(f"C={c} {h}x{w} one tap dominates", f0, torch.roll(f0, shifts=(2, -1), dims=(2, 3)).contiguous())
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- local_attn_flow
+LATTN_CASES = ((128, 1, 36, 60), (128, 4, 13, 45), (128, 4, 5, 7), (96, 1, 13, 45), (96, 4, 36, 60), (70, 4, 13, 45), (70, 1, 5, 7))
+
+
+def local_attn_ref(q_tok, k_tok, flow, r):
+    """transformer.py:374-409 in the F.unfold form of oracle/gmflow.py:219-225: keys and flow zero-padded, every one of the
+    (2r+1)^2 window positions takes part in the softmax (an out-of-image key scores 0, it is not masked)."""
+    _, _, h, w = flow.shape
+    c = q_tok.shape[-1]
+    q = q_tok.reshape(h * w, 1, c)
+    ks = 2 * r + 1
+    kp = k_tok.reshape(1, h * w, c).permute(0, 2, 1).reshape(1, c, h, w)
+    kw = F.unfold(kp, kernel_size=ks, padding=r).view(1, c, ks ** 2, h, w).permute(0, 3, 4, 1, 2).reshape(h * w, c, ks ** 2)
+    fw = F.unfold(flow, kernel_size=ks, padding=r).view(1, 2, ks ** 2, h, w).permute(0, 3, 4, 2, 1).reshape(h * w, ks ** 2, 2)
+    prob = torch.softmax(torch.matmul(q, kw) / (c ** 0.5), dim=-1)
+    return torch.matmul(prob, fw).view(1, h, w, 2).permute(0, 3, 1, 2).contiguous()
+
+
+def check_local_attn_flow(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    for i, (c, r, h, w) in enumerate(LATTN_CASES):
+        q, k = cases.rnd((h * w, c), 700 + i, 1.2), cases.rnd((h * w, c), 720 + i, 1.2)
+        flow = cases.rnd((1, 2, h, w), 740 + i, 10.0)
+        got = ops.local_attn_flow(q.to(dev), k.to(dev), flow.to(dev), r)
+        rows.append(value_row("local_attn_flow", f"C={c} r={r} {h}x{w}", got, local_attn_ref(q.double(), k.double(), flow.double(), r),
+                              local_attn_ref(q, k, flow, r)))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- convex_upsample
+CONVEX_CASES = ((4, 1, 1), (4, 5, 7), (4, 36, 60), (2, 5, 7), (2, 36, 60), (8, 1, 1), (8, 5, 7), (8, 13, 45))
+
+
+def convex_upsample_ref(mask, flow, factor):
+    """gmflow.py:76-89 (oracle/gmflow.py:232-236): softmax over the 9 taps of mask [1, 9 K K, h, w], weighted sum of the 3 x 3
+    zero-padded neighbourhood of K * flow, sub-pixel (ii, jj) of mask channel (t K + ii) K + jj goes to (K y + ii, K x + jj)."""
+    b, fc, h, w = flow.shape
+    m = torch.softmax(mask.view(b, 1, 9, factor, factor, h, w), dim=2)
+    up = F.unfold(factor * flow, [3, 3], padding=1).view(b, fc, 9, 1, 1, h, w)
+    up = torch.sum(m * up, dim=2).permute(0, 1, 4, 2, 5, 3)
+    return up.reshape(b, fc, factor * h, factor * w)
+
+
+def check_convex_upsample(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    for i, (k, h, w) in enumerate(CONVEX_CASES):
+        mask, flow = cases.rnd((1, 9 * k * k, h, w), 800 + i, 5.0), cases.rnd((1, 2, h, w), 820 + i, 3.0)
+        got = ops.convex_upsample(mask.to(dev), flow.to(dev), k)
+        rows.append(value_row("convex_upsample", f"x{k} {h}x{w}", got, convex_upsample_ref(mask.double(), flow.double(), k),
+                              convex_upsample_ref(mask, flow, k)))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- flow_warp / backwarp
+WARP_MAPS = ((2, 2), (13, 45), (37, 83))
+
+
+def _nonfinite_to_zero(out, flow):
+    bad = ~(torch.isfinite(flow[:, 0:1]) & torch.isfinite(flow[:, 1:2]))
+    return torch.where(bad, torch.zeros_like(out), out)
+
+
+def flow_warp_ref(x, flow):
+    return _nonfinite_to_zero(ogm.flow_warp(x, flow), flow)  # geometry.py:53-84
+
+
+def backwarp_ref(x, flow, padding):
+    """warplayer.py:8-22 (border) / MetricNet.py:10-20 (zeros) as oracle/ops.py states them, the base grid made in the dtype
+    of the inputs (the oracle's is always fp32)."""
+    n, _, h, w = flow.shape
+    gx = torch.linspace(-1.0, 1.0, w, dtype=x.dtype).view(1, 1, 1, w).expand(n, 1, h, w)
+    gy = torch.linspace(-1.0, 1.0, h, dtype=x.dtype).view(1, 1, h, 1).expand(n, 1, h, w)
+    fx = flow[:, 0:1] / ((w - 1.0) / 2.0)
+    fy = flow[:, 1:2] / ((h - 1.0) / 2.0)
+    grid = (torch.cat([gx, gy], 1) + torch.cat([fx, fy], 1)).permute(0, 2, 3, 1)
+    out = F.grid_sample(x, grid, mode="bilinear", padding_mode=padding, align_corners=True)
+    return _nonfinite_to_zero(out, flow) if padding == "zeros" else out
+
+
+def warp_flows(n, h, w, seed):
+    """name -> flow [n, 2, h, w]: smooth, mostly out of the image, and exactly integer (with the last row / column, one past
+    them, far outside, and an infinite component)."""
+    flows = {"smooth": (_smooth(2 * n, h, w, seed).view(n, 2, h, w) - 0.5) * 8.0, "amp30": cases.rnd((n, 2, h, w), seed + 1, 30.0)}
+    g = torch.Generator().manual_seed(seed + 2)
+    f = torch.randint(-3, 4, (n, 2, h, w), generator=g).float()
+    f[:, 0, 0, 0], f[:, 1, 0, 0] = w - 1.0, h - 1.0       # (0, 0) samples the last column of the last row
+    f[:, 0, 0, 1], f[:, 1, 0, 1] = w - 1.0, 0.0           # (1, 0): one past the last column
+    f[:, 0, 1, 0], f[:, 1, 1, 0] = 0.0, h - 1.0           # (0, 1): one past the last row
+    f[:, 0, 1, 1], f[:, 1, 1, 1] = -2.0, -2.0             # (1, 1): one before the first row and column
+    if h > 2:
+        f[:, 0, 2, 3], f[:, 1, 2, 3] = float("inf"), 1.0
+        f[:, 0, 3, 2], f[:, 1, 3, 2] = 1.0, float("-inf")
+        f[:, 0, 4, 4], f[:, 1, 4, 4] = -1000.0, 2000.0
+    else:
+        f[:, 0, 1, 1] = float("inf")
+    flows["integer"] = f
+    return flows
+
+
+def check_flow_warp(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    for i, (c, (h, w)) in enumerate(((1, WARP_MAPS[0]), (16, WARP_MAPS[0]), (16, WARP_MAPS[1]), (128, WARP_MAPS[1]), (1, WARP_MAPS[2]),
+                                     (16, WARP_MAPS[2]), (128, WARP_MAPS[2]))):
+        x = cases.rnd((1, c, h, w), 900 + i, 1.0)
+        for name, flow in warp_flows(1, h, w, 920 + 3 * i).items():
+            got = ops.flow_warp(x.to(dev), flow.to(dev))
+            rows.append(value_row("flow_warp", f"C={c} {h}x{w} {name}", got, flow_warp_ref(x.double(), flow.double()), flow_warp_ref(x, flow)))
+    return rows
+
+
+def check_backwarp(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    for i, (n, c, (h, w)) in enumerate(((1, 1, WARP_MAPS[0]), (2, 16, WARP_MAPS[0]), (1, 16, WARP_MAPS[1]), (2, 128, WARP_MAPS[1]),
+                                        (2, 1, WARP_MAPS[2]), (1, 128, WARP_MAPS[2]))):
+        x = cases.rnd((n, c, h, w), 1000 + i, 1.0)
+        for name, flow in warp_flows(n, h, w, 1020 + 3 * i).items():
+            for padding in ("zeros", "border"):
+                got = ops.backwarp(x.to(dev), flow.to(dev), padding)
+                rows.append(value_row("backwarp", f"{padding} N={n} C={c} {h}x{w} {name}", got, backwarp_ref(x.double(), flow.double(), padding),
+                                      backwarp_ref(x, flow, padding)))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- resize_bilinear_ac
+RESIZE_CASES = (  # (nc, hin, win, hout, wout, mul)
+    (6, 18, 30, 36, 60, 2.0), (6, 36, 60, 18, 30, 1.0), (6, 13, 45, 13, 45, 2.0), (6, 13, 45, 1, 45, 1.0), (6, 13, 45, 13, 1, 2.0),
+    (6, 13, 45, 1, 1, 2.0), (6, 1, 45, 7, 90, 2.0), (6, 1, 1, 5, 7, 1.0), (2, 72, 120, 144, 240, 2.0), (6, 37, 53, 50, 31, 1.0))
+
+
+def resize_ac_ref(x, size, mul):
+    return F.interpolate(x, size=size, mode="bilinear", align_corners=True) * mul  # gmflow.py:131
+
+
+def check_resize_bilinear_ac(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    for i, (nc, hi, wi, ho, wo, mul) in enumerate(RESIZE_CASES):
+        shape = (nc // 2, 2, hi, wi) if nc % 2 == 0 and i % 2 else (1, nc, hi, wi)
+        x = cases.rnd(shape, 1100 + i, 2.0)
+        got = ops.resize_bilinear_ac(x.to(dev), (ho, wo), mul)
+        rows.append(value_row("resize_bilinear_ac", f"NC={nc} {hi}x{wi}->{ho}x{wo} mul={mul:g}", got, resize_ac_ref(x.double(), (ho, wo), mul),
+                              resize_ac_ref(x, (ho, wo), mul)))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- layernorm / gelu / bmm / pointwise
+BIG = (1 << 20) + 77  # above kMaxBlocks * 256 elements: the grid-stride loops go round more than once
+SMALL = 1000          # not a multiple of the 256-thread block
+BIG_MAP = (1025, 1031)  # the same for the kernels whose loop runs over the pixels of one sample
+
+
+def check_layernorm(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    for i, (nrows, cols) in enumerate(((5, 1), (7, 63), (5, 64), (6, 65), (13, 128), (3, 200), (1, 128))):
+        x = cases.rnd((nrows, cols), 1200 + i, 2.0) + 0.5
+        w, b = cases.rnd((cols,), 1220 + i, 1.0), cases.rnd((cols,), 1240 + i, 0.5)
+        for res in (None, cases.rnd((nrows, cols), 1260 + i, 1.0)):
+            got = ops.layernorm(x.to(dev), w.to(dev), b.to(dev), residual=None if res is None else res.to(dev))
+            ref64 = F.layer_norm(x.double(), (cols,), w.double(), b.double())
+            ref32 = F.layer_norm(x, (cols,), w, b)
+            if res is not None:
+                ref64, ref32 = res.double() + ref64, res + ref32
+            rows.append(value_row("layernorm", f"{nrows}x{cols} residual={int(res is not None)}", got, ref64, ref32))
+    return rows
+
+
+def check_gelu(dev, ops=None):
+    ops = ops or default_ops()
+    inf = float("inf")
+    x = torch.cat([torch.linspace(-6.0, 6.0, 4801), torch.tensor([0.0, -0.0, 6.0, -6.0, inf, -inf, 1e-30, -1e-30, 30.0, -30.0]),
+                   cases.rnd((2000,), 1300, 2.0).clamp(-6, 6)])
+    # (the fp32 floor is the erf formula of nn.GELU written out: ATen's vectorised fp32 CPU gelu answers NaN at +inf, where the
+    # formula and ATen's own fp64 give +inf; at -inf both give -inf * 0 = NaN)
+    g32 = lambda v: 0.5 * v * (1.0 + torch.erf(v * 0.7071067811865476))  # noqa: E731
+    rows = [value_row("gelu", f"|x|<=6, 0, +-inf [{x.numel()}]", ops.gelu(x.to(dev)), F.gelu(x.double()), g32(x))]
+    xb = cases.rnd((BIG,), 1301, 2.0)
+    rows.append(value_row("gelu", f"[{BIG}]", ops.gelu(xb.to(dev)), F.gelu(xb.double()), g32(xb)))
+    return rows
+
+
+def check_bmm(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    for i, (bs, m, n, k) in enumerate(((1, 1, 1, 1), (3, 7, 5, 130), (2, 130, 3, 17), (5, 33, 129, 65), (2, 1, 130, 1), (1, 65, 1, 127))):
+        for trans_b in (True, False):
+            a = cases.rnd((bs, m, k), 1400 + i, 1.0)
+            b = cases.rnd((bs, n, k) if trans_b else (bs, k, n), 1420 + i, 1.0)
+            got = ops.bmm(a.to(dev), b.to(dev), trans_b)
+            mm = lambda p, q: torch.matmul(p, q.transpose(1, 2) if trans_b else q)  # noqa: E731
+            rows.append(value_row("bmm", f"[{bs}x{m}x{k}] x [{n if trans_b else k}x{k if trans_b else n}] trans_b={int(trans_b)}", got,
+                                  mm(a.double(), b.double()), mm(a, b)))
+    return rows
+
+
+def check_pointwise(dev, ops=None):
+    """add_act, channel_normalize3, mul_map, affine (values) and clamp (bit-exact)."""
+    ops = ops or default_ops()
+    rows = []
+    for n in (SMALL, BIG):
+        a, b = cases.rnd((n,), 1500, 2.0), cases.rnd((n,), 1501, 2.0)
+        for relu in (False, True):
+            ref = lambda p, q: F.relu(p + q) if relu else p + q  # noqa: E731  (backbone.py:36 / gmflow.py flow + pred)
+            rows.append(value_row("add_act", f"[{n}] relu={int(relu)}", ops.add_act(a.to(dev), b.to(dev), relu=relu), ref(a.double(), b.double()), ref(a, b)))
+        for mul, add in ((2.0, 0.0), (-0.37, 1.0)):
+            rows.append(value_row("affine", f"[{n}] *{mul:g} +{add:g}", ops.affine(a.to(dev), mul, add), a.double() * mul + add, a * mul + add))
+    mean, std = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+    m32, s32 = torch.tensor(mean).view(1, 3, 1, 1), torch.tensor(std).view(1, 3, 1, 1)  # gmflow.py:13-18: fp32 tensors
+    for shape in ((1, 3, 9, 37), (2, 3, 419, 419)):
+        x = torch.rand(shape, generator=torch.Generator().manual_seed(1510))
+        rows.append(value_row("channel_normalize3", f"{list(shape)}", ops.channel_normalize3(x.to(dev), mean, std), (x.double() - m32.double()) / s32.double(),
+                              (x - m32) / s32))
+    for shape in ((2, 5, 13, 45), (1, 2) + BIG_MAP):
+        x, m = cases.rnd(shape, 1520, 1.0), cases.rnd((shape[0], 1) + shape[2:], 1521, 1.0)
+        rows.append(value_row("mul_map", f"{list(shape)}", ops.mul_map(x.to(dev), m.to(dev)), x.double() * m.double(), x * m))
+    inf, nan, lo, hi = float("inf"), float("nan"), -0.5, 0.75
+    edge = torch.tensor([nan, inf, -inf, lo, hi, -0.0, 0.0, 0.75000006, 0.74999994, -0.50000006, -0.49999997, 1e38, -1e38, 1e-45])
+    for n in (SMALL, BIG):
+        x = torch.cat([edge, cases.rnd((n - edge.numel(),), 1530, 1.0)])
+        rows.append(exact_row("clamp", f"[{n}] NaN, +-inf, the bounds", ops.clamp(x.to(dev), lo, hi), torch.clamp(x, lo, hi)))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- layout kernels
+def check_layouts(dev, ops=None):
+    """pixel_shuffle2, pair_interleaved, quad_interleaved, rgbx and the [H, W, 4] copy ops.to_inp attaches: pure data movement,
+    bit-exact against torch indexing."""
+    ops = ops or default_ops()
+    rows = []
+    for i, shape in enumerate(((2, 12, 5, 7), (1, 4, 37, 53), (3, 8, 1, 1), (1, 16, 13, 45))):
+        x = cases.rnd(shape, 1600 + i, 1.0)
+        rows.append(exact_row("pixel_shuffle2", f"{list(shape)}", ops.pixel_shuffle2(x.to(dev)), F.pixel_shuffle(x, 2)))
+    for i, (c, h, w) in enumerate(((16, 13, 45), (2, 1, 1), (6, 37, 53))):
+        x = cases.rnd((1, c, h, w), 1610 + i, 1.0)
+        want = x[0].view(c // 2, 2, h, w).permute(0, 2, 3, 1).contiguous()
+        rows.append(exact_row("pair_interleaved", f"[1, {c}, {h}, {w}]", ops.pair_interleaved(x.to(dev)), want))
+    for i, (n, c, h, w) in enumerate(((1, 16, 13, 45), (2, 20, 37, 53), (3, 16, 1, 1))):
+        x = cases.rnd((n, c, h, w), 1620 + i, 1.0)
+        want = x.view(n, c // 4, 4, h * w).permute(0, 1, 3, 2).contiguous()
+        rows.append(exact_row("quad_interleaved", f"[{n}, {c}, {h}, {w}]", ops.quad_interleaved(x.to(dev)), want))
+    for i, (h, w) in enumerate(((13, 45), (1, 1), (37, 53))):
+        x = cases.rnd((1, 3, h, w), 1630 + i, 1.0)
+        want = torch.cat([x[0].permute(1, 2, 0), torch.zeros(h, w, 1)], 2).contiguous()
+        rows.append(exact_row("rgbx", f"[1, 3, {h}, {w}]", ops.rgbx(x.to(dev)), want))
+    for i, ((h, w), (ho, wo)) in enumerate((((37, 53), (37, 53)), ((37, 53), (64, 96)), ((45, 83), (32, 64)))):
+        img = torch.randint(0, 256, (h, w, 3), generator=torch.Generator().manual_seed(1640 + i), dtype=torch.uint8)
+        out = ops.to_inp(img.to(dev), (ho, wo))
+        x4 = getattr(out, "_drba_x4", None)
+        if x4 is None or x4[1] != out._version:
+            rows.append(Row("to_inp", f"x4 copy {h}x{w}->{ho}x{wo}", float("inf"), 0.0, "no current _drba_x4 copy on the frame"))
+            continue
+        want = torch.cat([out[0].detach().cpu().permute(1, 2, 0), torch.zeros(ho, wo, 1)], 2).contiguous()
+        rows.append(exact_row("to_inp", f"x4 copy {h}x{w}->{ho}x{wo}", x4[0], want))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- hole tests
+def cover_values(n, seed):
+    """Cover maps around the 0.999f hole test: exactly 0.999f, its two fp32 neighbours, 0, 1, NaN, +-inf, then seeded values."""
+    t = torch.tensor(0.999, dtype=torch.float32)
+    one = torch.tensor(1.0)
+    edge = torch.stack([t, torch.nextafter(t, one), torch.nextafter(t, -one), torch.tensor(0.0), one, torch.tensor(float("nan")),
+                        torch.tensor(float("inf")), torch.tensor(float("-inf")), torch.tensor(0.9989), torch.tensor(0.9991)])
+    g = torch.Generator().manual_seed(seed)
+    return torch.cat([edge, 0.99 + 0.012 * torch.rand(n - edge.numel(), generator=g)])
+
+
+def check_hole_tests(dev, ops=None):
+    """timestep_fix (GMFSS.py:120-122) and fill_holes (drm.py: torch.where(cover < 0.999, value, aligned)): bit-exact."""
+    ops = ops or default_ops()
+    rows = []
+    for n in (SMALL, BIG):
+        c0 = cover_values(n, 1700).view(1, 1, 1, n)
+        c1 = torch.roll(cover_values(n, 1701), 16).view(1, 1, 1, n)  # the edge values of one map meet ordinary values of the other
+        t0, t1 = cases.rnd((1, 1, 1, n), 1702, 1.0), cases.rnd((1, 1, 1, n), 1703, 1.0)
+        o0, o1 = ops.timestep_fix(t0.to(dev), t1.to(dev), c0.to(dev), c1.to(dev))
+        bad = (c0 < 0.999) | (c1 < 0.999)
+        rows.append(exact_row("timestep_fix", f"[{n}] out0", o0, torch.where(bad, torch.ones_like(t0), t0)))
+        rows.append(exact_row("timestep_fix", f"[{n}] out1", o1, torch.where(bad, torch.ones_like(t1), t1)))
+        assert 0 < int(bad.sum()) < n
+        got = ops.fill_holes(t0.to(dev), c0.to(dev), t1.to(dev))
+        rows.append(exact_row("fill_holes", f"[{n}]", got, torch.where(c0 < 0.999, t1, t0)))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- drm
+def check_drm(dev, ops=None):
+    """drm_ratio against oracle.drm's ratio maps (the distances in fp32, as the reference computes them: tools.py:77-80) and
+    drm_retime bit for bit against the fp32 walk of oracle.drm.drm_to_t (a chain of roundings, no tolerance against fp64)."""
+    ops = ops or default_ops()
+    rows = []
+    for i, (n, h, w) in enumerate(((1, 37, 53), (2, 37, 53), (1,) + BIG_MAP)):
+        f10, f12 = cases.rnd((n, 2, h, w), 1800 + i, 5.0), cases.rnd((n, 2, h, w), 1810 + i, 3.0)
+        f10[:, :, 3, 4] = 0.0
+        f12[:, :, 3, 4] = 0.0  # both flows zero: 0 / 0 = NaN without eps (drm.py:110-155), 0.5 with it
+        f10[:, :, 5, 6] = 0.0   # one of them zero: ratio 0 / 1
+        for eps in (1e-4, 0.0):
+            r10, r12 = ops.drm_ratio(f10.to(dev), f12.to(dev), eps)
+            w10, w12 = odrm._ratio_maps(f10.double(), f12.double(), eps)
+            v10, v12 = odrm._ratio_maps(f10, f12, eps)
+            rows.append(value_row("drm_ratio", f"{n}x{h}x{w} eps={eps:g} drm10", r10, w10, v10))
+            rows.append(value_row("drm_ratio", f"{n}x{h}x{w} eps={eps:g} drm12", r12, w12, v12))
+    for i, (h, w) in enumerate(((37, 53), BIG_MAP)):
+        d = torch.rand(1, 1, h, w, generator=torch.Generator().manual_seed(1820 + i))
+        d[0, 0, 0, :4] = torch.tensor([0.0, 1.0, 0.5, float("nan")])
+        for t in (0.2, 0.5, 0.8) if i == 0 else (0.3,):
+            rows.append(exact_row("drm_retime", f"{h}x{w} t={t}", ops.drm_retime(d.to(dev), t), odrm.drm_to_t(d, t)))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- metric_input
+METRIC_CASES = ((37, 53, 6.0), (64, 96, 12.0), (135, 240, 12.0))
+UNSTABLE_CAP = 0.005
+CLASS_MIN = 0.10
+
+
+def metric_inputs(h, w, amp, seed):
+    img0, img1 = _smooth(3, h, w, seed), _smooth(3, h, w, seed + 1)
+    f01 = (_smooth(2, h, w, seed + 2) - 0.5) * amp
+    f10 = -f01 + (_smooth(2, h, w, seed + 3) - 0.5) * 1.5  # nearly the inverse flow: the consistency test is undecided a priori
+    return img0, img1, f01, f10
+
+
+def fb_margins(fwd, bwd, alpha=0.01, beta=0.5):
+    """geometry.py:87-108 (oracle.gmfss.fb_consistency) up to the comparison: d - thr per pixel, forward and backward."""
+    mag = torch.norm(fwd, dim=1) + torch.norm(bwd, dim=1)
+    d_f = torch.norm(fwd + ogm.flow_warp(bwd, fwd), dim=1)
+    d_b = torch.norm(bwd + ogm.flow_warp(fwd, bwd), dim=1)
+    thr = alpha * mag + beta
+    return d_f - thr, d_b - thr
+
+
+def metric_values_ref(img0, img1, f01, f10):
+    """channels 0-11 of MetricNet's input (model_gmfss_union/MetricNet.py:45-60, oracle/gmfss.py:43-48)"""
+    m0 = F.l1_loss(img0, backwarp_ref(img1, f01, "zeros"), reduction="none").mean([1], True)
+    m1 = F.l1_loss(img1, backwarp_ref(img0, f10, "zeros"), reduction="none").mean([1], True)
+    h, w = f01.shape[2:]
+    nf = lambda f: torch.cat([f[:, 0:1] / ((w - 1.0) / 2.0), f[:, 1:2] / ((h - 1.0) / 2.0)], 1)  # noqa: E731
+    return torch.cat((img0, img1, -m0, -m1, nf(f01), nf(f10)), 1)
+
+
+def check_metric_input(dev, ops=None):
+    ops = ops or default_ops()
+    op, rows = "metric_input", []
+    for i, (h, w, amp) in enumerate(METRIC_CASES):
+        img0, img1, f01, f10 = metric_inputs(h, w, amp, 1900 + 10 * i)
+        got = ops.metric_input(img0.to(dev), img1.to(dev), f01.to(dev), f10.to(dev)).detach().cpu()
+        rows.append(value_row(op, f"{h}x{w} channels 0-11", got[:, :12], metric_values_ref(img0.double(), img1.double(), f01.double(), f10.double()),
+                              metric_values_ref(img0, img1, f01, f10)))
+        m64 = fb_margins(f01.double(), f10.double())
+        m32 = fb_margins(f01, f10)
+        for ch, name, a, b in ((12, "fwd_occ", m64[0], m32[0]), (13, "bwd_occ", m64[1], m32[1])):
+            band = 4.0 * float((b.double() - a).abs().max())  # how far an fp32 evaluation of the margin strays, x 4
+            ref, stable = a > 0, a.abs() > band
+            ones, n_st = int((ref & stable).sum()), int(stable.sum())
+            share = min(ones, n_st - ones) / max(n_st, 1)
+            assert share >= CLASS_MIN, f"{name} {h}x{w}: {ones}/{n_st} stable ones: the input no longer exercises both classes"
+            mask = got[:, ch]
+            wrong = int(((mask != ref.float()) & stable).sum()) + int(((mask != 0) & (mask != 1)).sum())
+            unstable = 1.0 - n_st / stable.numel()
+            extra = f"band={band:.2e} ones={ones / max(n_st, 1):.1%} of {n_st} stable pixels"
+            rows.append(Row(op, f"{h}x{w} {name} wrong stable decisions", float(wrong), 0.0, extra))
+            rows.append(Row(op, f"{h}x{w} {name} unstable share", unstable, UNSTABLE_CAP, f"band={band:.2e} cap={UNSTABLE_CAP:.1%}"))
+    return rows
+
+
+CHECKS = (  # (section title, check): one operator family each
+    ("op softmax_rows_", check_softmax_rows), ("op instance_norm", check_instance_norm), ("op conv_direct", check_conv_direct),
+    ("op local_corr_flow", check_local_corr_flow), ("op local_attn_flow", check_local_attn_flow),
+    ("op convex_upsample", check_convex_upsample), ("op flow_warp", check_flow_warp), ("op backwarp", check_backwarp),
+    ("op resize_bilinear_ac", check_resize_bilinear_ac), ("op layernorm", check_layernorm), ("op gelu", check_gelu), ("op bmm", check_bmm),
+    ("op pointwise", check_pointwise), ("op layouts", check_layouts), ("op hole tests", check_hole_tests), ("op drm", check_drm),
+    ("op metric_input", check_metric_input))

@@ -1,0 +1,358 @@
+"""CPU (-m "not gpu"): the per-operator checks of tests/op_checks.py CAN fail, and their references are right.
+
+The "implementation under test" here is a torch-fp32 stand-in for drba_amd.ops, written tap by tap the way the kernels are
+(explicit window loops, explicit bilinear gathers, explicit index arithmetic) -- not with the unfold / grid_sample /
+F.interpolate forms the fp64 references use -- so that two independent statements of every formula meet:
+  1. every fp64 reference agrees with the fp32 oracle / torch form of the same formula within fp32 roundoff (the measured
+     floor of each row is bounded by a figure derived from the number format and the operation's conditioning);
+  2. the stand-in passes every row;
+  3. with one planted defect at a time (a one-line variant of one stand-in function) the row meant to catch it fails, and
+     only rows of that operator fail."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import drm as odrm
+from tests import op_checks
+
+CPU = torch.device("cpu")
+EPS32 = 2.0 ** -24
+
+
+# ----------------------------------------------------------------------------------------- the stand-in
+def _softmax_rows_(scores, scale, mask=None, defect=False):
+    for i in range(scores.shape[0]):
+        s = scores[i] / scale
+        if mask is not None:
+            if not (defect and i >= mask.shape[0]):
+                s = s + mask[i % mask.shape[0]]
+        s = s - s.max(dim=-1, keepdim=True).values
+        e = s.exp()
+        scores[i] = e / e.sum(dim=-1, keepdim=True)
+    return scores
+
+
+def _instance_norm(x, relu=False, eps=1e-5, defect=False):
+    hw = x.shape[2] * x.shape[3]
+    mean = x.sum((2, 3), keepdim=True) / hw
+    m2 = ((x - mean) ** 2).sum((2, 3), keepdim=True)
+    y = (x - mean) / torch.sqrt(m2 / ((hw - 1) if defect else hw) + eps)
+    return y.clamp(min=0) if relu else y
+
+
+def _conv_direct(x, w, bias, stride, pad, defect=False):
+    if defect and bias is not None:
+        bias = bias.clone()
+        bias[16:] = 0.0
+    return F.conv2d(x, w, bias, stride=stride, padding=pad)
+
+
+def _window(t, r, dy, dx):
+    """t [.., h, w] moved by (dy, dx) with zeros from outside the image"""
+    h, w = t.shape[-2:]
+    return F.pad(t, (r, r, r, r))[..., r + dy:r + dy + h, r + dx:r + dx + w]
+
+
+def _local_corr_flow(f0, f1, radius):
+    _, c, h, w = f0.shape
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    sc, cx, cy = [], [], []
+    for dy in range(-radius, radius + 1):
+        for dx in range(-radius, radius + 1):
+            inside = (ys + dy >= 0) & (ys + dy < h) & (xs + dx >= 0) & (xs + dx < w)
+            s = (f0[0] * _window(f1[0], radius, dy, dx)).sum(0) / c ** 0.5
+            sc.append(torch.where(inside, s, torch.full_like(s, -1e4)))
+            cx.append(xs + dx)
+            cy.append(ys + dy)
+    p = torch.softmax(torch.stack(sc), 0)
+    return torch.stack([(p * torch.stack(cx)).sum(0) - xs, (p * torch.stack(cy)).sum(0) - ys])[None]
+
+
+def _local_attn_flow(q_tok, k_tok, flow, radius, defect=False):
+    _, _, h, w = flow.shape
+    c = q_tok.shape[-1]
+    q, k = q_tok.reshape(h, w, c).permute(2, 0, 1), k_tok.reshape(h, w, c).permute(2, 0, 1)
+    inside_src = torch.ones(h, w)
+    sc, fl = [], []
+    for dy in range(-radius, radius + 1):
+        for dx in range(-radius, radius + 1):
+            s = (q * _window(k, radius, dy, dx)).sum(0) / c ** 0.5  # an out-of-image key is a zero vector: score 0
+            if defect:
+                s = torch.where(_window(inside_src, radius, dy, dx) > 0, s, torch.full_like(s, float("-inf")))
+            sc.append(s)
+            fl.append(_window(flow[0], radius, dy, dx))
+    p = torch.softmax(torch.stack(sc), 0)
+    return (p.unsqueeze(1) * torch.stack(fl)).sum(0)[None]
+
+
+def _convex_upsample(mask, flow, factor, defect=False):
+    _, _, h, w = flow.shape
+    k = factor
+    m = torch.softmax(mask.view(9, k, k, h, w), 0)  # [tap, ii, jj, y, x]
+    if defect:
+        m = m.transpose(1, 2)
+    up = torch.zeros(2, k, k, h, w)
+    for t in range(9):
+        up += m[t].unsqueeze(0) * (k * _window(flow[0], 1, t // 3 - 1, t % 3 - 1)).view(2, 1, 1, h, w)
+    return up.permute(0, 3, 1, 4, 2).reshape(1, 2, k * h, k * w)  # [c, y, ii, x, jj]
+
+
+def _bilinear(x, sx, sy, padding):
+    """x [N, C, H, W] sampled at pixel coordinates sx, sy [N, H, W]: four bounds-checked taps (zeros) or clamped coordinates
+    (border); a non-finite coordinate has no tap inside the image."""
+    n, c, h, w = x.shape
+    if padding == "border":
+        sx, sy = sx.clamp(0, w - 1), sy.clamp(0, h - 1)
+    fin = torch.isfinite(sx) & torch.isfinite(sy)
+    sx, sy = torch.where(fin, sx, torch.full_like(sx, -9.0)), torch.where(fin, sy, torch.full_like(sy, -9.0))
+    x0, y0 = sx.floor(), sy.floor()
+    wx1, wy1 = sx - x0, sy - y0
+    out = torch.zeros_like(x)
+    flat = x.reshape(n, c, h * w)
+    for dx, dy, wgt in ((0, 0, (1 - wx1) * (1 - wy1)), (1, 0, wx1 * (1 - wy1)), (0, 1, (1 - wx1) * wy1), (1, 1, wx1 * wy1)):
+        xi, yi = x0 + dx, y0 + dy
+        ok = fin & (xi >= 0) & (xi < w) & (yi >= 0) & (yi < h)
+        idx = (yi.clamp(0, h - 1) * w + xi.clamp(0, w - 1)).long().view(n, 1, h * w).expand(n, c, h * w)
+        out += flat.gather(2, idx).view(n, c, h, w) * (wgt * ok).unsqueeze(1)
+    return out
+
+
+def _grid(n, h, w):
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    return xs.expand(n, h, w), ys.expand(n, h, w)
+
+
+def _flow_warp(x, flow):
+    n, _, h, w = x.shape
+    xs, ys = _grid(n, h, w)
+    gx, gy = 2 * (xs + flow[:, 0]) / (w - 1) - 1, 2 * (ys + flow[:, 1]) / (h - 1) - 1
+    return _bilinear(x, (gx + 1) * ((w - 1) / 2), (gy + 1) * ((h - 1) / 2), "zeros")
+
+
+def _backwarp(x, flow, padding="border"):
+    n, _, h, w = x.shape
+    gx = torch.linspace(-1.0, 1.0, w).view(1, 1, w) + flow[:, 0] / ((w - 1.0) / 2.0)
+    gy = torch.linspace(-1.0, 1.0, h).view(1, h, 1) + flow[:, 1] / ((h - 1.0) / 2.0)
+    return _bilinear(x, (gx + 1) * ((w - 1.0) / 2.0), (gy + 1) * ((h - 1.0) / 2.0), padding)
+
+
+def _resize_bilinear_ac(x, size, mul=1.0, defect=False):
+    if defect:
+        return F.interpolate(x, size=size, mode="bilinear", align_corners=False) * mul
+    (hi, wi), (ho, wo) = x.shape[2:], size
+
+    def axis(n_in, n_out):
+        s = torch.arange(n_out, dtype=torch.float32) * ((n_in - 1) / (n_out - 1) if n_out > 1 else 0.0)
+        i0 = s.floor().clamp(max=n_in - 1)
+        return i0.long(), (i0 + 1).clamp(max=n_in - 1).long(), s - i0
+
+    y0, y1, ly = axis(hi, ho)
+    x0, x1, lx = axis(wi, wo)
+    ly = ly.view(-1, 1)
+    top = x[:, :, y0][:, :, :, x0] * (1 - lx) + x[:, :, y0][:, :, :, x1] * lx
+    bot = x[:, :, y1][:, :, :, x0] * (1 - lx) + x[:, :, y1][:, :, :, x1] * lx
+    return (top * (1 - ly) + bot * ly) * mul
+
+
+def _layernorm(x, w, b, residual=None, eps=1e-5):
+    mean = x.mean(-1, keepdim=True)
+    y = (x - mean) / torch.sqrt(((x - mean) ** 2).mean(-1, keepdim=True) + eps) * w + b
+    return y if residual is None else residual + y
+
+
+def _timestep_fix(t0, t1, c0, c1, defect=False):
+    bad = ((c0 <= 0.999) | (c1 <= 0.999)) if defect else ((c0 < 0.999) | (c1 < 0.999))
+    return torch.where(bad, torch.ones_like(t0), t0), torch.where(bad, torch.ones_like(t1), t1)
+
+
+def _drm_ratio(f10, f12, eps):
+    a, b = (f10[:, 0:1] ** 2 + f10[:, 1:2] ** 2).sqrt(), (f12[:, 0:1] ** 2 + f12[:, 1:2] ** 2).sqrt()
+    if eps:
+        a, b = a + eps, b + eps
+    return a / (a + b), b / (a + b)
+
+
+def _retime_regrouped(drm, t, precision):
+    """oracle.drm.drm_to_t with every map update regrouped (x - (x - l) f -> x (1 - f) + l f): equal in exact arithmetic, and
+    within an ulp or two in fp32 -- what a tolerance would wave through and the bit-exact row must not"""
+    x, lo, hi = 0.5, 0.0, 1.0
+    xm, fm = drm.clone(), drm.clone()
+    lom, him = xm * 0, xm * 0 + 1
+    while abs(x - t) > precision:
+        if x > t:
+            hi, x, him = x, x - (x - lo) * 0.5, xm.clone()
+            xm = xm * (1 - fm) + lom * fm
+        if x < t:
+            lo, x, lom = x, x + (hi - x) * 0.5, xm.clone()
+            xm = xm * (1 - fm) + him * fm
+    return xm
+
+
+def _metric_input(img0, img1, f01, f10, defect=False):
+    _, _, h, w = img0.shape
+    m0 = (img0 - _backwarp(img1, f01, "zeros")).abs().sum(1, keepdim=True) / 3
+    m1 = (img1 - _backwarp(img0, f10, "zeros")).abs().sum(1, keepdim=True) / 3
+    hx, hy = (w - 1.0) / 2.0, (h - 1.0) / 2.0
+    norm = lambda f: (f[:, 0:1] ** 2 + f[:, 1:2] ** 2).sqrt()  # noqa: E731
+    thr = 0.01 * (norm(f01) + norm(f10)) + (0.49 if defect else 0.5)
+    df, db = norm(f01 + _flow_warp(f10, f01)), norm(f10 + _flow_warp(f01, f10))
+    occ = lambda d: ((d >= thr) if defect else (d > thr)).float()  # noqa: E731
+    return torch.cat([img0, img1, -m0, -m1, f01[:, 0:1] / hx, f01[:, 1:2] / hy, f10[:, 0:1] / hx, f10[:, 1:2] / hy, occ(df), occ(db)], 1)
+
+
+def _to_inp(img_u8, dst_size):
+    out = F.interpolate(img_u8.permute(2, 0, 1)[None].float() / 255.0, size=tuple(dst_size), mode="bilinear", align_corners=False)
+    x4 = torch.zeros(dst_size[0], dst_size[1], 4)
+    x4[..., :3] = out[0].permute(1, 2, 0)
+    out._drba_x4 = (x4, out._version)
+    return out
+
+
+STANDIN = dict(
+    softmax_rows_=_softmax_rows_, instance_norm=_instance_norm, conv_direct=_conv_direct, local_corr_flow=_local_corr_flow,
+    local_attn_flow=_local_attn_flow, convex_upsample=_convex_upsample, flow_warp=_flow_warp, backwarp=_backwarp,
+    resize_bilinear_ac=_resize_bilinear_ac, layernorm=_layernorm, timestep_fix=_timestep_fix, drm_ratio=_drm_ratio,
+    metric_input=_metric_input, to_inp=_to_inp,
+    gelu=lambda x: 0.5 * x * (1 + torch.erf(x * 0.7071067811865476)),
+    bmm=lambda a, b, trans_b: torch.einsum("bmk,bnk->bmn", a, b) if trans_b else torch.einsum("bmk,bkn->bmn", a, b),
+    add_act=lambda a, b, relu=False: (a + b).clamp(min=0) if relu else a + b,
+    affine=lambda a, mul, add: a * mul + add,
+    channel_normalize3=lambda x, mean, std: (x - torch.tensor(mean).view(1, 3, 1, 1)) / torch.tensor(std).view(1, 3, 1, 1),
+    mul_map=lambda x, m: x * m,
+    clamp=lambda x, lo, hi: torch.where(x != x, x, torch.minimum(torch.maximum(x, torch.tensor(lo)), torch.tensor(hi))),
+    pixel_shuffle2=lambda x: torch.stack([x[:, i::4] for i in range(4)], 2).view(x.shape[0], x.shape[1] // 4, 2, 2, *x.shape[2:])
+    .permute(0, 1, 4, 2, 5, 3).reshape(x.shape[0], x.shape[1] // 4, 2 * x.shape[2], 2 * x.shape[3]),
+    pair_interleaved=lambda f: torch.stack([f[0, 0::2], f[0, 1::2]], -1),
+    quad_interleaved=lambda x: torch.stack([x[:, i::4].flatten(2) for i in range(4)], -1),
+    rgbx=lambda img: torch.stack([img[0, 0], img[0, 1], img[0, 2], torch.zeros_like(img[0, 0])], -1),
+    fill_holes=lambda aligned, cover, value: torch.where(cover < 0.999, value, aligned),
+    drm_retime=lambda d, t, precision=1e-3: odrm.drm_to_t(d, t, precision),
+)
+
+
+class Recorder:
+    """The stand-in namespace; remembers which operators a check asked for."""
+
+    def __init__(self, **override):
+        self.fns, self.used = dict(STANDIN, **override), set()
+
+    def __getattr__(self, name):
+        if name not in self.fns:
+            raise AttributeError(name)
+        self.used.add(name)
+        return self.fns[name]
+
+
+def _passes(row):
+    return bool(row[1] <= row[2])  # the pass test of every parity row (_assert_rows, report.record)
+
+
+@pytest.fixture(scope="module")
+def clean():
+    """{section: (rows, operators the check called)} of the stand-in without a defect"""
+    out = {}
+    for title, check in op_checks.CHECKS:
+        ns = Recorder()
+        with torch.no_grad():
+            out[title] = (check(CPU, ns), set(ns.used))
+    return out
+
+
+# ----------------------------------------------------------------------------------------- 1. the references
+# What an fp32 evaluation may differ from the fp64 reference by, from the number format and the conditioning alone.  Default:
+# the rule's own first term, 2e-5 * max(1, |ref|max) (a few hundred ulps of the largest value: sums of up to ~1e3 rounded terms).
+# Ill-conditioned rows, by name:
+FLOOR_BOUNDS = (
+    # (x - mean) / sqrt(var + eps) with |mean| = 1e3, var = 1e-4: rounding the mean (or x - mean) to fp32 moves the numerator by
+    # up to 2^-24 * 1e3 = 6e-5, i.e. the output by 6e-5 / sqrt(1.1e-4) = 5.7e-3; two such roundings (sum, mean)
+    ("instance_norm", "mean 1e3", 2 * EPS32 * 1e3 / (1e-4 + 1e-5) ** 0.5),
+    # a constant plane 3.7: the fp32 mean of 1961 equal values is off by a few ulps (4 * 2^-24 * 3.7), over sqrt(eps)
+    ("instance_norm", "constant plane", 16 * EPS32 * 3.7 / 1e-5 ** 0.5),
+    # exp(s - max) with |s| up to ~4 * 80: the fp32 score difference carries 2^-24 * 640 relative error into every term
+    ("softmax_rows_", "|scores|~80", 4 * EPS32 * 640),
+)
+
+
+def _floor_bound(row):
+    for op, key, bound in FLOOR_BOUNDS:
+        if row.op == op and key in row[0]:
+            return bound
+    return 2e-5 * max(1.0, row.refmax)
+
+
+def test_fp64_references_agree_with_the_fp32_forms(clean):
+    n = 0
+    for title, (rows, _) in clean.items():
+        for row in rows:
+            if row.floor is None:
+                continue
+            n += 1
+            assert row.floor <= _floor_bound(row), f"{row[0]}: fp32 form vs fp64 reference {row.floor:.3e} > {_floor_bound(row):.3e}"
+            assert row[2] == op_checks.rule_tol(row.refmax, row.floor)  # the one tolerance rule, nothing else
+    assert n > 200
+
+
+def test_references_where_aten_is_not_the_specification():
+    """The two written-out cases of op_checks: zeros padding at a non-finite coordinate, InstanceNorm of one element."""
+    x = torch.arange(24.0).view(1, 2, 3, 4)
+    flow = torch.zeros(1, 2, 3, 4)
+    flow[0, 0, 1, 1], flow[0, 1, 2, 2] = float("inf"), float("-inf")
+    for ref in (op_checks.flow_warp_ref(x, flow), op_checks.backwarp_ref(x, flow, "zeros")):
+        assert float(ref[0, :, 1, 1].abs().max()) == 0.0 and float(ref[0, :, 2, 2].abs().max()) == 0.0
+        keep = torch.ones(3, 4, dtype=torch.bool)
+        keep[1, 1] = keep[2, 2] = False
+        assert torch.allclose(ref[0][:, keep], x[0][:, keep], atol=1e-5)  # zero flow elsewhere: the identity
+    border = op_checks.backwarp_ref(x, flow, "border")  # border padding clamps the coordinate: a finite answer, from ATen
+    assert torch.allclose(border[0, :, 1, 1], x[0, :, 1, 3], atol=1e-5) and torch.allclose(border[0, :, 2, 2], x[0, :, 0, 2], atol=1e-5)
+    assert torch.equal(op_checks._inorm_ref(torch.full((2, 3, 1, 1), 5.0), False), torch.zeros(2, 3, 1, 1))
+
+
+# ----------------------------------------------------------------------------------------- 2. the stand-in passes
+def test_standin_passes_every_check(clean):
+    bad = [r for rows, _ in clean.values() for r in rows if not _passes(r)]
+    assert not bad, "\n".join(f"{r[0]}: err={r[1]:.3e} tol={r[2]:.1e} {r[3]}" for r in bad)
+    ops_seen = set().union(*(used for _, used in clean.values()))
+    assert ops_seen == set(STANDIN), sorted(set(STANDIN) ^ ops_seen)  # every operator of the issue is exercised by some check
+
+
+def test_metric_input_masks_are_mostly_stable_and_two_sided(clean):
+    rows = clean["op metric_input"][0]
+    shares = [r for r in rows if "unstable share" in r[0]]
+    assert len(shares) == 6 and all(r[1] <= op_checks.UNSTABLE_CAP for r in shares)
+    assert len([r for r in rows if "wrong stable decisions" in r[0]]) == 6
+
+
+# ----------------------------------------------------------------------------------------- 3. planted defects
+def _with(fn):
+    return lambda *a, **k: fn(*a, defect=True, **k)
+
+
+DEFECTS = (  # (operator of the stand-in, its defective variant, the operator family that must fail, a row that must fail)
+    ("softmax_rows_", _with(_softmax_rows_), "softmax_rows_", "masked"),
+    ("instance_norm", _with(_instance_norm), "instance_norm", "1x5"),
+    ("local_attn_flow", _with(_local_attn_flow), "local_attn_flow", "5x7"),
+    ("convex_upsample", _with(_convex_upsample), "convex_upsample", "x4 5x7"),
+    ("resize_bilinear_ac", _with(_resize_bilinear_ac), "resize_bilinear_ac", "18x30->36x60"),
+    ("metric_input", _with(_metric_input), "metric_input", "wrong stable decisions"),
+    ("timestep_fix", _with(_timestep_fix), "timestep_fix", "out0"),
+    ("conv_direct", _with(_conv_direct), "conv_direct", "->17"),
+    # beyond the issue's eight: the wrong hole test in fill_holes, an fp64-exact but differently rounded retiming walk, a
+    # border clamp where zeros padding is meant, the -1e4 of out-of-image correlation taps forgotten
+    ("fill_holes", lambda a, c, v: torch.where(c <= 0.999, v, a), "fill_holes", "fill_holes"),
+    ("drm_retime", lambda d, t, precision=1e-3: _retime_regrouped(d, t, precision), "drm_retime", "t=0.2"),
+    ("flow_warp", lambda x, f: _backwarp(x, f, "border"), "flow_warp", "amp30"),
+    ("local_corr_flow", lambda a, b, r: _local_corr_flow(F.pad(a, (r, r, r, r)), F.pad(b, (r, r, r, r)), r)[:, :, r:-r, r:-r].contiguous(),
+     "local_corr_flow", "13x45"),
+)
+
+
+@pytest.mark.parametrize("name,variant,family,must_fail", DEFECTS, ids=[d[0] for d in DEFECTS])
+def test_planted_defect_fails_its_row_and_only_its_operator(clean, name, variant, family, must_fail):
+    touched = [(title, check) for title, check in op_checks.CHECKS if name in clean[title][1]]
+    assert touched  # (a check that never calls the operator cannot change: its rows are the clean ones, which pass)
+    failed = []
+    for title, check in touched:
+        with torch.no_grad():
+            failed += [r for r in check(CPU, Recorder(**{name: variant})) if not _passes(r)]
+    assert any(r.op == family and must_fail in r[0] for r in failed), [r[0] for r in failed]
+    assert all(r.op == family for r in failed), [r[0] for r in failed if r.op != family]
