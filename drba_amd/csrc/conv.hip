@@ -529,88 +529,11 @@ int env_override(const char *name, int ntab) {  // (compiled out of the release 
   return (id >= 0 && id < ntab) ? id : -1;
 }
 
-}  // namespace
-
-extern "C" {
-
-// cfg ids: 0..kNumConvCfg-1 the fp32 MFMA table above, then the split-bf16 family of conv_split.hip (stride 1, Cin a
-// multiple of 32; drba_conv3x3_packed_floats returns 0 for a layer a config cannot run).  DRBA_CONV_SPLIT=0 hides it (TUNING builds only).
-static bool split_enabled() {
-  static const bool on = env_int("DRBA_CONV_SPLIT", 1) != 0;
-  return on;
-}
-// ... then the LDS-DMA family of conv_dma.hip (same arithmetic, same constraints plus W % 4 == 0)
-static int first_dma_cfg() { return kNumConvCfg + (split_enabled() ? conv_split_num_cfgs() : 0); }
-// ... then the K-split family of conv_ks.hip (Cin = 64 / 96 / 128 / 192)
-static int first_ks_cfg() { return first_dma_cfg() + (split_enabled() ? conv_dma_num_cfgs() : 0); }
-// ... then the two-term fp16 family (family 4; conv_split.hip "Two-term form"): 22-bit operands instead of 24, half the
-// matrix-core work.  A caller opts in by offering these ids to its tuner; none of the ids before them changes meaning.
-static int first_f16_cfg() { return first_ks_cfg() + (split_enabled() ? conv_ks_num_cfgs() : 0); }
-static int first_f16_dma_cfg() { return first_f16_cfg() + (split_enabled() ? conv_split_num_cfgs() : 0); }
-static int first_f16_ks_cfg() { return first_f16_dma_cfg() + (split_enabled() ? conv_dma_num_cfgs() : 0); }
-// ... and its stride-2 tiles (family 4, stride 2: conv_split.hip MODE 2)
-static int first_f16_s2_cfg() { return first_f16_ks_cfg() + (split_enabled() ? conv_ks_num_cfgs() : 0); }
-// ... and (round 6) its stride-1 tiles whose waves split rows and couts (conv_split.hip CS = 2): appended, family 4, stride 1
-static int first_f16_cs_cfg() { return first_f16_s2_cfg() + (split_enabled() ? conv_split_s2_num_cfgs() : 0); }
-int drba_conv3x3_num_cfgs(void) { return first_f16_cs_cfg() + (split_enabled() ? conv_split_cs_num_cfgs() : 0); }
-int drba_conv3x3_cfg_stride(int cfg) {
-  if (cfg >= first_f16_cs_cfg() && cfg < drba_conv3x3_num_cfgs()) return conv_split_cfg_stride(cfg - first_f16_cs_cfg() + conv_split_cs_first());
-  if (cfg >= first_f16_s2_cfg() && cfg < first_f16_cs_cfg()) return 2;
-  if (cfg >= kNumConvCfg && cfg < drba_conv3x3_num_cfgs()) return 1;
-  return (cfg < 0 || cfg >= kNumConvCfg) ? DRBA_EINVAL : kConv[cfg].S;
-}
-int drba_conv3x3_cfg_family(int cfg) {
-  if (cfg < 0 || cfg >= drba_conv3x3_num_cfgs()) return DRBA_EINVAL;
-  return cfg < kNumConvCfg ? 0 : (cfg < first_dma_cfg() ? 1 : (cfg < first_ks_cfg() ? 2 : (cfg < first_f16_cfg() ? 3 : 4)));
-}
-int drba_deconv4x4_num_cfgs(void) { return kNumDeconvCfg + (split_enabled() ? deconv_split_total_cfgs() : 0); }
-int drba_deconv4x4_cfg_family(int cfg) {
-  if (cfg < 0 || cfg >= drba_deconv4x4_num_cfgs()) return DRBA_EINVAL;
-  return cfg < kNumDeconvCfg ? 0 : (cfg - kNumDeconvCfg < deconv_split_f16_first() ? 1 : 4);
-}
-
-// DRBA_CONV_CFG=<id> / DRBA_DECONV_CFG=<id> in the environment override the choice (experiments only).
-int drba_conv3x3_pick_cfg(int Cin, int Cout, int Ho, int Wo, int stride) {
-  if (stride != 1 && stride != 2) return DRBA_EUNSUPPORTED;
-  if (Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0) return DRBA_EINVAL;
-  const int ov = env_override("DRBA_CONV_CFG", kNumConvCfg);
-  if (ov >= 0 && kConv[ov].S == stride) return ov;
-  return pick(kConv, kNumConvCfg, stride, Cin, Cout, Ho, Wo, 1);
-}
-
-size_t drba_conv3x3_packed_floats(int Cin, int Cout, int cfg) {
-  if (cfg >= first_f16_cs_cfg())
-    return cfg < drba_conv3x3_num_cfgs() ? conv_split_packed_floats(Cin, Cout, cfg - first_f16_cs_cfg() + conv_split_cs_first()) : 0;
-  if (cfg >= first_f16_s2_cfg())
-    return conv_split_packed_floats(Cin, Cout, cfg - first_f16_s2_cfg() + conv_split_s2_first());
-  if (cfg >= first_f16_ks_cfg()) return conv_ks_packed_floats(Cin, Cout, cfg - first_f16_ks_cfg() + conv_ks_f16_first());
-  if (cfg >= first_f16_dma_cfg()) return conv_dma_packed_floats(Cin, Cout, cfg - first_f16_dma_cfg() + conv_dma_f16_first());
-  if (cfg >= first_f16_cfg()) return conv_split_packed_floats(Cin, Cout, cfg - first_f16_cfg() + conv_split_f16_first());
-  if (cfg >= first_ks_cfg()) return conv_ks_packed_floats(Cin, Cout, cfg - first_ks_cfg());
-  if (cfg >= first_dma_cfg()) return conv_dma_packed_floats(Cin, Cout, cfg - first_dma_cfg());
-  if (cfg >= kNumConvCfg) return conv_split_packed_floats(Cin, Cout, cfg - kNumConvCfg);
-  if (cfg < 0 || cfg >= kNumConvCfg || Cin <= 0 || Cout <= 0) return 0;
-  return packed_floats(kConv[cfg], Cin, Cout, 1);
-}
-
 // fragment order: packed[(((cz*nchunks + q)*9 + tap)*CG + cg)*NT + nt][lane] =
 //   w[cz*NTC + nt*16 + (lane&15)][q*CK + cg*4 + (lane>>4)][tap], zero outside Cout/Cin
-int drba_conv3x3_pack(const float *w, float *packed, int Cin, int Cout, int cfg) {
-  if (cfg >= first_f16_cs_cfg() && cfg < drba_conv3x3_num_cfgs())
-    return conv_split_pack(w, packed, Cin, Cout, cfg - first_f16_cs_cfg() + conv_split_cs_first());
-  if (cfg >= first_f16_s2_cfg() && cfg < first_f16_cs_cfg())
-    return conv_split_pack(w, packed, Cin, Cout, cfg - first_f16_s2_cfg() + conv_split_s2_first());
-  if (cfg >= first_f16_ks_cfg() && cfg < first_f16_s2_cfg())
-    return conv_ks_pack(w, packed, Cin, Cout, cfg - first_f16_ks_cfg() + conv_ks_f16_first());
-  if (cfg >= first_f16_dma_cfg() && cfg < first_f16_ks_cfg())
-    return conv_dma_pack(w, packed, Cin, Cout, cfg - first_f16_dma_cfg() + conv_dma_f16_first());
-  if (cfg >= first_f16_cfg() && cfg < first_f16_dma_cfg())
-    return conv_split_pack(w, packed, Cin, Cout, cfg - first_f16_cfg() + conv_split_f16_first());
-  if (cfg >= first_ks_cfg() && cfg < first_f16_cfg()) return conv_ks_pack(w, packed, Cin, Cout, cfg - first_ks_cfg());
-  if (cfg >= first_dma_cfg() && cfg < first_ks_cfg()) return conv_dma_pack(w, packed, Cin, Cout, cfg - first_dma_cfg());
-  if (cfg >= kNumConvCfg && cfg < first_dma_cfg()) return conv_split_pack(w, packed, Cin, Cout, cfg - kNumConvCfg);
-  if (!w || !packed || cfg < 0 || cfg >= kNumConvCfg || Cin <= 0 || Cout <= 0) return DRBA_EINVAL;
-  const CfgInfo &c = kConv[cfg];
+int conv_fp32_pack(const float *w, float *packed, int Cin, int Cout, int id) {
+  if (!w || !packed || Cin <= 0 || Cout <= 0) return DRBA_EINVAL;
+  const CfgInfo &c = kConv[id];
   const int n_ct = (Cout + c.NTC - 1) / c.NTC, nch = (Cin + c.CK - 1) / c.CK, CG = c.CK / 4;
   memset(packed, 0, sizeof(float) * packed_floats(c, Cin, Cout, 1));
   for (int cz = 0; cz < n_ct; ++cz)
@@ -627,103 +550,11 @@ int drba_conv3x3_pack(const float *w, float *packed, int Cin, int Cout, int cfg)
   return DRBA_OK;
 }
 
-int drba_conv3x3(const float *in, const float *packed_w, const float *bias, const float *beta, const float *residual,
-                 const float *residual2, float *out, int N, int Cin, int H, int W, int Cout, int stride, int act,
-                 float post_slope, int pre_act, float pre_slope, int cfg, void *stream) {
-  if (!in || !packed_w || !out || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DRBA_EINVAL;
-  if (beta && !residual) return DRBA_EINVAL;
-  if (residual2 && !residual) return DRBA_EINVAL;
-  if (act < 0 || act > 4) return DRBA_EINVAL;
-  // (family 4: with drba_set_range_check on, the output is scanned for the inf / NaN an fp16 overflow of an operand leaves)
-  const size_t n_out = (size_t)N * Cout * ((H - 1) / (stride > 0 ? stride : 1) + 1) * ((W - 1) / (stride > 0 ? stride : 1) + 1);
-  if (cfg >= first_f16_cs_cfg() && cfg < drba_conv3x3_num_cfgs()) {
-    if (stride != conv_split_cfg_stride(cfg - first_f16_cs_cfg() + conv_split_cs_first())) return DRBA_EINVAL;
-    return range_checked(conv_split_launch(cfg - first_f16_cs_cfg() + conv_split_cs_first(), in, packed_w, bias, beta, residual, residual2, out, N,
-                                           Cin, H, W, Cout, act, post_slope, pre_act, pre_slope, stream), out, n_out, stream);
-  }
-  if (cfg >= first_f16_s2_cfg() && cfg < first_f16_cs_cfg()) {
-    if (stride != 2) return DRBA_EINVAL;
-    return range_checked(conv_split_launch(cfg - first_f16_s2_cfg() + conv_split_s2_first(), in, packed_w, bias, beta, residual, residual2, out, N,
-                                           Cin, H, W, Cout, act, post_slope, pre_act, pre_slope, stream), out, n_out, stream);
-  }
-  if (cfg >= first_f16_ks_cfg() && cfg < first_f16_s2_cfg()) {
-    if (stride != 1) return DRBA_EINVAL;
-    return range_checked(conv_ks_launch(cfg - first_f16_ks_cfg() + conv_ks_f16_first(), in, packed_w, bias, beta, residual, residual2, out, N, Cin,
-                                        H, W, Cout, act, post_slope, pre_act, pre_slope, stream), out, n_out, stream);
-  }
-  if (cfg >= first_f16_dma_cfg() && cfg < first_f16_ks_cfg()) {
-    if (stride != 1) return DRBA_EINVAL;
-    return range_checked(conv_dma_launch(cfg - first_f16_dma_cfg() + conv_dma_f16_first(), in, packed_w, bias, beta, residual, residual2, out, N,
-                                         Cin, H, W, Cout, act, post_slope, pre_act, pre_slope, stream), out, n_out, stream);
-  }
-  if (cfg >= first_f16_cfg() && cfg < first_f16_dma_cfg()) {
-    if (stride != 1) return DRBA_EINVAL;
-    return range_checked(conv_split_launch(cfg - first_f16_cfg() + conv_split_f16_first(), in, packed_w, bias, beta, residual, residual2, out,
-                                           N, Cin, H, W, Cout, act, post_slope, pre_act, pre_slope, stream), out, n_out, stream);
-  }
-  if (cfg >= first_ks_cfg() && cfg < first_f16_cfg()) {
-    if (stride != 1) return DRBA_EINVAL;
-    return conv_ks_launch(cfg - first_ks_cfg(), in, packed_w, bias, beta, residual, residual2, out, N, Cin, H, W, Cout, act,
-                          post_slope, pre_act, pre_slope, stream);
-  }
-  if (cfg >= first_dma_cfg() && cfg < first_ks_cfg()) {
-    if (stride != 1) return DRBA_EINVAL;
-    return conv_dma_launch(cfg - first_dma_cfg(), in, packed_w, bias, beta, residual, residual2, out, N, Cin, H, W, Cout, act,
-                           post_slope, pre_act, pre_slope, stream);
-  }
-  if (cfg >= kNumConvCfg && cfg < first_dma_cfg()) {
-    if (stride != 1) return DRBA_EINVAL;
-    return conv_split_launch(cfg - kNumConvCfg, in, packed_w, bias, beta, residual, residual2, out, N, Cin, H, W, Cout, act,
-                             post_slope, pre_act, pre_slope, stream);
-  }
-  if (cfg < 0 || cfg >= kNumConvCfg || kConv[cfg].S != stride) return DRBA_EINVAL;
-  const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-  hipStream_t s = (hipStream_t)stream;
-#define DRBA_CASE(ID, T) \
-  case ID:               \
-    return launch<T>(in, packed_w, bias, beta, residual, residual2, out, N, Cin, H, W, Cout, Ho, Wo, act, post_slope, \
-                     pre_act, pre_slope, 0, s);
-  switch (cfg) {
-    DRBA_CASE(0, C0)
-    DRBA_CASE(1, C1)
-    DRBA_CASE(2, C2)
-    DRBA_CASE(3, C3)
-    DRBA_CASE(4, C4)
-    DRBA_CASE(5, C5)
-    DRBA_CASE(6, C6)
-    DRBA_CASE(7, C7)
-    DRBA_CASE(8, C8)
-    DRBA_CASE(9, C9)
-    DRBA_CASE(10, C10)
-    DRBA_CASE(11, C11)
-    DRBA_CASE(12, C12)
-    DRBA_CASE(13, C13)
-  }
-#undef DRBA_CASE
-  return DRBA_EUNSUPPORTED;
-}
-
-int drba_deconv4x4_pick_cfg(int Cin, int Cout, int H, int W) {
-  if (Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DRBA_EINVAL;
-  const int ov = env_override("DRBA_DECONV_CFG", kNumDeconvCfg);
-  if (ov >= 0) return ov;
-  return pick(kDeconv, kNumDeconvCfg, 1, Cin, Cout, H, W, 2);  // two row-phase workgroups per tile
-}
-
-size_t drba_deconv4x4_packed_floats(int Cin, int Cout, int cfg) {
-  if (cfg >= kNumDeconvCfg)
-    return cfg < drba_deconv4x4_num_cfgs() ? deconv_split_packed_floats(Cin, Cout, cfg - kNumDeconvCfg) : 0;
-  if (cfg < 0 || cfg >= kNumDeconvCfg || Cin <= 0 || Cout <= 0) return 0;
-  return packed_floats(kDeconv[cfg], Cin, Cout, 4);
-}
-
 // w: [Cin, Cout, 4, 4].  packed[((((cz*4 + phase)*nchunks + q)*4 + tap)*CG + cg)*NT + nt][lane], tap = 2a+b,
 // ky = py ? (a ? 2 : 0) : (a ? 3 : 1), kx likewise from (px, b).
-int drba_deconv4x4_pack(const float *w, float *packed, int Cin, int Cout, int cfg) {
-  if (cfg >= kNumDeconvCfg && cfg < drba_deconv4x4_num_cfgs())
-    return deconv_split_pack(w, packed, Cin, Cout, cfg - kNumDeconvCfg);
-  if (!w || !packed || cfg < 0 || cfg >= kNumDeconvCfg || Cin <= 0 || Cout <= 0) return DRBA_EINVAL;
-  const CfgInfo &c = kDeconv[cfg];
+int deconv_fp32_pack(const float *w, float *packed, int Cin, int Cout, int id) {
+  if (!w || !packed || Cin <= 0 || Cout <= 0) return DRBA_EINVAL;
+  const CfgInfo &c = kDeconv[id];
   const int n_ct = (Cout + c.NTC - 1) / c.NTC, nch = (Cin + c.CK - 1) / c.CK, CG = c.CK / 4;
   memset(packed, 0, sizeof(float) * packed_floats(c, Cin, Cout, 4));
   for (int cz = 0; cz < n_ct; ++cz)
@@ -747,22 +578,40 @@ int drba_deconv4x4_pack(const float *w, float *packed, int Cin, int Cout, int cf
   return DRBA_OK;
 }
 
-int drba_deconv4x4s2(const float *in, const float *packed_w, const float *bias, float *out, int N, int Cin, int H,
-                     int W, int Cout, int pixel_shuffle, int pre_act, float pre_slope, int cfg, void *stream) {
-  if (!in || !packed_w || !out || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DRBA_EINVAL;
-  if (pixel_shuffle && (Cout & 3)) return DRBA_EINVAL;
-  if (cfg >= kNumDeconvCfg && cfg < drba_deconv4x4_num_cfgs()) {
-    const int rc = deconv_split_launch(cfg - kNumDeconvCfg, in, packed_w, bias, out, N, Cin, H, W, Cout, pixel_shuffle, pre_act,
-                                       pre_slope, stream);
-    return drba_deconv4x4_cfg_family(cfg) == 4 ? range_checked(rc, out, (size_t)N * Cout * 4 * H * W, stream) : rc;
+int conv_fp32_launch(int id, const float *in, const float *packed_w, const float *bias, const float *beta, const float *residual,
+                     const float *residual2, float *out, int N, int Cin, int H, int W, int Cout, int Ho, int Wo, int act,
+                     float post_slope, int pre_act, float pre_slope, hipStream_t s) {
+#define DRBA_CASE(ID, T) \
+  case ID:               \
+    return launch<T>(in, packed_w, bias, beta, residual, residual2, out, N, Cin, H, W, Cout, Ho, Wo, act, post_slope, \
+                     pre_act, pre_slope, 0, s);
+  switch (id) {
+    DRBA_CASE(0, C0)
+    DRBA_CASE(1, C1)
+    DRBA_CASE(2, C2)
+    DRBA_CASE(3, C3)
+    DRBA_CASE(4, C4)
+    DRBA_CASE(5, C5)
+    DRBA_CASE(6, C6)
+    DRBA_CASE(7, C7)
+    DRBA_CASE(8, C8)
+    DRBA_CASE(9, C9)
+    DRBA_CASE(10, C10)
+    DRBA_CASE(11, C11)
+    DRBA_CASE(12, C12)
+    DRBA_CASE(13, C13)
   }
-  if (cfg < 0 || cfg >= kNumDeconvCfg) return DRBA_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
+#undef DRBA_CASE
+  return DRBA_EUNSUPPORTED;
+}
+
+int deconv_fp32_launch(int id, const float *in, const float *packed_w, const float *bias, float *out, int N, int Cin, int H, int W,
+                       int Cout, int pixel_shuffle, int pre_act, float pre_slope, hipStream_t s) {
 #define DRBA_CASE(ID, T) \
   case ID:               \
     return launch<T>(in, packed_w, bias, nullptr, nullptr, nullptr, out, N, Cin, H, W, Cout, 2 * H, 2 * W, 0, 0.f,     \
                      pre_act, pre_slope, pixel_shuffle, s);
-  switch (cfg) {
+  switch (id) {
     DRBA_CASE(0, D0)
     DRBA_CASE(1, D1)
     DRBA_CASE(2, D2)
@@ -774,6 +623,202 @@ int drba_deconv4x4s2(const float *in, const float *packed_w, const float *bias, 
   return DRBA_EUNSUPPORTED;
 }
 
+// ------------------------------------------------------------------------------------------ public cfg ids
+// THE order of the public configuration ids of drba_conv3x3 / drba_deconv4x4s2: runs of consecutive ids, each a run of one
+// backend's own ids.  Ids are only ever appended (a new run at the end), so that no id changes meaning.
+//   family (drba_conv3x3_cfg_family): 0 fp32 MFMA (this file), 1 three-term bf16 split with register staging (conv_split.hip),
+//   2 three-term LDS-DMA (conv_dma.hip), 3 three-term K-split (conv_ks.hip), 4 every two-term fp16 form: 22-bit operands
+//   instead of 24 and half the matrix-core work; a caller opts in by offering these ids to its tuner.
+enum Backend { kFp32, kSplit, kDma, kKs };
+struct Run {
+  Backend backend;
+  int first, count, family;  // first: the backend's own id of the run's first configuration
+};
+constexpr Run kConvRuns[] = {
+    {kFp32, 0, 14, 0},   // C0 .. C13
+    {kSplit, 0, 5, 1},   // three-term tiles
+    {kDma, 0, 1, 2},
+    {kKs, 0, 1, 3},
+    {kSplit, 5, 5, 4},   // the same tiles, two-term
+    {kDma, 1, 1, 4},
+    {kKs, 1, 1, 4},
+    {kSplit, 10, 4, 4},  // stride-2 tiles
+    {kSplit, 14, 6, 4},  // tiles whose waves split rows and couts (CS = 2), either stride
+};
+constexpr Run kDeconvRuns[] = {
+    {kFp32, 0, 6, 0},   // D0 .. D5
+    {kSplit, 0, 2, 1},  // three-term tiles
+    {kSplit, 2, 2, 4},  // the same tiles, two-term
+    {kSplit, 4, 5, 4},  // CS = 2 and both-row-phase tiles
+};
+// the runs of a backend lie back to back in its own id space and cover `total` ids
+template <size_t R>
+constexpr bool runs_cover(const Run (&runs)[R], Backend b, int total) {
+  int next = 0;
+  for (size_t i = 0; i < R; ++i)
+    if (runs[i].backend == b) {
+      if (runs[i].first != next) return false;
+      next += runs[i].count;
+    }
+  return next == total;
+}
+template <size_t R>
+constexpr int runs_total(const Run (&runs)[R]) {
+  int n = 0;
+  for (size_t i = 0; i < R; ++i) n += runs[i].count;
+  return n;
+}
+constexpr int kMaxCfgs = 64;
+static_assert(runs_total(kConvRuns) <= kMaxCfgs && runs_total(kDeconvRuns) <= kMaxCfgs, "CfgTable capacity");
+static_assert(runs_cover(kConvRuns, kFp32, kNumConvCfg) && runs_cover(kConvRuns, kSplit, kConvSplitCfgs) &&
+                  runs_cover(kConvRuns, kDma, kConvDmaCfgs) && runs_cover(kConvRuns, kKs, kConvKsCfgs),
+              "kConvRuns must list every configuration of every backend once");
+static_assert(runs_cover(kDeconvRuns, kFp32, kNumDeconvCfg) && runs_cover(kDeconvRuns, kSplit, kDeconvSplitCfgs),
+              "kDeconvRuns must list every configuration of every backend once");
+
+struct Resolved {
+  Backend backend;
+  int id, family, stride;  // id: the backend's own; all three DRBA_EINVAL for a cfg outside the table
+};
+constexpr Resolved kNoCfg = {kFp32, DRBA_EINVAL, DRBA_EINVAL, DRBA_EINVAL};
+struct CfgTable {
+  int n = 0;
+  Resolved e[kMaxCfgs];
+};
+// DRBA_CONV_SPLIT=0 (TUNING builds only: common.hpp env_int) leaves the fp32 run alone in both tables
+template <size_t R, class StrideOf>
+CfgTable make_table(const Run (&runs)[R], StrideOf stride_of) {
+  static_assert(R > 0, "the fp32 run comes first");
+  const bool split_enabled = env_int("DRBA_CONV_SPLIT", 1) != 0;
+  CfgTable t;
+  for (size_t i = 0; i < (split_enabled ? R : 1); ++i)
+    for (int k = 0; k < runs[i].count; ++k, ++t.n)
+      t.e[t.n] = {runs[i].backend, runs[i].first + k, runs[i].family, stride_of(runs[i].backend, runs[i].first + k)};
+  return t;
+}
+// built on first use, then a bounds check and an array read per call
+const CfgTable &conv_table() {
+  static const CfgTable t = make_table(kConvRuns, [](Backend b, int id) {
+    return b == kFp32 ? kConv[id].S : b == kSplit ? conv_split_desc(id).stride : b == kDma ? conv_dma_desc(id).stride : conv_ks_desc(id).stride;
+  });
+  return t;
+}
+const CfgTable &deconv_table() {
+  static const CfgTable t = make_table(kDeconvRuns, [](Backend b, int id) { return b == kFp32 ? 1 : deconv_split_desc(id).stride; });
+  return t;
+}
+Resolved resolve(const CfgTable &t, int cfg) { return (cfg >= 0 && cfg < t.n) ? t.e[cfg] : kNoCfg; }
+
+}  // namespace
+
+extern "C" {
+
+int drba_conv3x3_num_cfgs(void) { return conv_table().n; }
+int drba_conv3x3_cfg_stride(int cfg) { return resolve(conv_table(), cfg).stride; }
+int drba_conv3x3_cfg_family(int cfg) { return resolve(conv_table(), cfg).family; }
+int drba_deconv4x4_num_cfgs(void) { return deconv_table().n; }
+int drba_deconv4x4_cfg_family(int cfg) { return resolve(deconv_table(), cfg).family; }
+
+// DRBA_CONV_CFG=<id> / DRBA_DECONV_CFG=<id> in the environment override the choice (experiments only).
+int drba_conv3x3_pick_cfg(int Cin, int Cout, int Ho, int Wo, int stride) {
+  if (stride != 1 && stride != 2) return DRBA_EUNSUPPORTED;
+  if (Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0) return DRBA_EINVAL;
+  const int ov = env_override("DRBA_CONV_CFG", kNumConvCfg);
+  if (ov >= 0 && kConv[ov].S == stride) return ov;
+  return pick(kConv, kNumConvCfg, stride, Cin, Cout, Ho, Wo, 1);
+}
+
+// (0 for a layer a configuration cannot run, and for a cfg outside the table)
+size_t drba_conv3x3_packed_floats(int Cin, int Cout, int cfg) {
+  const Resolved r = resolve(conv_table(), cfg);
+  if (r.id < 0) return 0;
+  switch (r.backend) {
+    case kFp32: return (Cin <= 0 || Cout <= 0) ? 0 : packed_floats(kConv[r.id], Cin, Cout, 1);
+    case kSplit: return conv_split_packed_floats(Cin, Cout, r.id);
+    case kDma: return conv_dma_packed_floats(Cin, Cout, r.id);
+    case kKs: return conv_ks_packed_floats(Cin, Cout, r.id);
+  }
+  return 0;
+}
+
+int drba_conv3x3_pack(const float *w, float *packed, int Cin, int Cout, int cfg) {
+  const Resolved r = resolve(conv_table(), cfg);
+  if (r.id < 0) return DRBA_EINVAL;
+  switch (r.backend) {
+    case kFp32: return conv_fp32_pack(w, packed, Cin, Cout, r.id);
+    case kSplit: return conv_split_pack(w, packed, Cin, Cout, r.id);
+    case kDma: return conv_dma_pack(w, packed, Cin, Cout, r.id);
+    case kKs: return conv_ks_pack(w, packed, Cin, Cout, r.id);
+  }
+  return DRBA_EINVAL;
+}
+
+int drba_conv3x3(const float *in, const float *packed_w, const float *bias, const float *beta, const float *residual,
+                 const float *residual2, float *out, int N, int Cin, int H, int W, int Cout, int stride, int act,
+                 float post_slope, int pre_act, float pre_slope, int cfg, void *stream) {
+  if (!in || !packed_w || !out || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DRBA_EINVAL;
+  if (beta && !residual) return DRBA_EINVAL;
+  if (residual2 && !residual) return DRBA_EINVAL;
+  if (act < 0 || act > 4) return DRBA_EINVAL;
+  const Resolved r = resolve(conv_table(), cfg);
+  if (r.id < 0 || r.stride != stride) return DRBA_EINVAL;
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  int rc = DRBA_EUNSUPPORTED;
+  switch (r.backend) {
+    case kFp32:
+      rc = conv_fp32_launch(r.id, in, packed_w, bias, beta, residual, residual2, out, N, Cin, H, W, Cout, Ho, Wo, act, post_slope,
+                            pre_act, pre_slope, (hipStream_t)stream);
+      break;
+    case kSplit:
+      rc = conv_split_launch(r.id, in, packed_w, bias, beta, residual, residual2, out, N, Cin, H, W, Cout, act, post_slope, pre_act,
+                             pre_slope, stream);
+      break;
+    case kDma:
+      rc = conv_dma_launch(r.id, in, packed_w, bias, beta, residual, residual2, out, N, Cin, H, W, Cout, act, post_slope, pre_act,
+                           pre_slope, stream);
+      break;
+    case kKs:
+      rc = conv_ks_launch(r.id, in, packed_w, bias, beta, residual, residual2, out, N, Cin, H, W, Cout, act, post_slope, pre_act,
+                          pre_slope, stream);
+      break;
+  }
+  // (family 4: with drba_set_range_check on, the output is scanned for the inf / NaN an fp16 overflow of an operand leaves)
+  return r.family == 4 ? range_checked(rc, out, (size_t)N * Cout * Ho * Wo, stream) : rc;
+}
+
+int drba_deconv4x4_pick_cfg(int Cin, int Cout, int H, int W) {
+  if (Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DRBA_EINVAL;
+  const int ov = env_override("DRBA_DECONV_CFG", kNumDeconvCfg);
+  if (ov >= 0) return ov;
+  return pick(kDeconv, kNumDeconvCfg, 1, Cin, Cout, H, W, 2);  // two row-phase workgroups per tile
+}
+
+size_t drba_deconv4x4_packed_floats(int Cin, int Cout, int cfg) {
+  const Resolved r = resolve(deconv_table(), cfg);
+  if (r.id < 0) return 0;
+  if (r.backend == kSplit) return deconv_split_packed_floats(Cin, Cout, r.id);
+  return (Cin <= 0 || Cout <= 0) ? 0 : packed_floats(kDeconv[r.id], Cin, Cout, 4);
+}
+
+int drba_deconv4x4_pack(const float *w, float *packed, int Cin, int Cout, int cfg) {
+  const Resolved r = resolve(deconv_table(), cfg);
+  if (r.id < 0) return DRBA_EINVAL;
+  return r.backend == kSplit ? deconv_split_pack(w, packed, Cin, Cout, r.id) : deconv_fp32_pack(w, packed, Cin, Cout, r.id);
+}
+
+int drba_deconv4x4s2(const float *in, const float *packed_w, const float *bias, float *out, int N, int Cin, int H,
+                     int W, int Cout, int pixel_shuffle, int pre_act, float pre_slope, int cfg, void *stream) {
+  if (!in || !packed_w || !out || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DRBA_EINVAL;
+  if (pixel_shuffle && (Cout & 3)) return DRBA_EINVAL;
+  const Resolved r = resolve(deconv_table(), cfg);
+  if (r.id < 0) return DRBA_EINVAL;
+  const int rc = r.backend == kSplit
+                     ? deconv_split_launch(r.id, in, packed_w, bias, out, N, Cin, H, W, Cout, pixel_shuffle, pre_act, pre_slope, stream)
+                     : deconv_fp32_launch(r.id, in, packed_w, bias, out, N, Cin, H, W, Cout, pixel_shuffle, pre_act, pre_slope,
+                                          (hipStream_t)stream);
+  return r.family == 4 ? range_checked(rc, out, (size_t)N * Cout * 4 * H * W, stream) : rc;
+}
+
 // drba_conv3x3 (stride 1, bias, activation; no residual operands, no pre-activation) storing through PixelShuffle(2):
 // out is [N, Cout / 4, 2H, 2W].  Only configurations whose tile carries that store form accept (two-term 4 x 32 x 64 tiles of
 // conv_split.hip); every other id returns DRBA_EUNSUPPORTED, and the caller runs drba_conv3x3 + drba_pixel_shuffle2 instead.
@@ -782,13 +827,10 @@ int drba_conv3x3_shuffle(const float *in, const float *packed_w, const float *bi
   if (!in || !packed_w || !out || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return DRBA_EINVAL;
   if (act < 0 || act > 4) return DRBA_EINVAL;
   if ((Cout & 3) || (W & 3)) return DRBA_EUNSUPPORTED;
-  const size_t n_out = (size_t)N * Cout * H * W;
-  int id = -1;
-  if (cfg >= first_f16_cs_cfg() && cfg < drba_conv3x3_num_cfgs()) id = cfg - first_f16_cs_cfg() + conv_split_cs_first();
-  else if (cfg >= first_f16_cfg() && cfg < first_f16_dma_cfg()) id = cfg - first_f16_cfg() + conv_split_f16_first();
-  if (id < 0 || conv_split_cfg_stride(id) != 1) return DRBA_EUNSUPPORTED;
-  return range_checked(conv_split_launch(id, in, packed_w, bias, nullptr, nullptr, nullptr, out, N, Cin, H, W, Cout, act, post_slope, 0,
-                                         0.f, stream, 1), out, n_out, stream);
+  const Resolved r = resolve(conv_table(), cfg);
+  if (r.id < 0 || r.backend != kSplit || r.family != 4 || r.stride != 1) return DRBA_EUNSUPPORTED;
+  return range_checked(conv_split_launch(r.id, in, packed_w, bias, nullptr, nullptr, nullptr, out, N, Cin, H, W, Cout, act, post_slope, 0,
+                                         0.f, stream, 1), out, (size_t)N * Cout * H * W, stream);
 }
 
 // A chain of convolutions launched from one call (the IFBlock cores and the context encoder are 4..11 dependent

@@ -26,6 +26,7 @@
 // ResConv layers (residual == input): the epilogue reads the residual from the window in LDS (exact fp32).
 #include "common.hpp"
 #include "conv_split.hpp"
+#include "device_helpers.hpp"
 
 #include <string.h>
 
@@ -59,18 +60,6 @@ constexpr int lds_bytes(int PL) { return off_idx(PL) + 32; }
 constexpr int NTHREADS = 9 * 64;         // 8 MFMA waves + the loader
 static_assert(CS % 32 == 16 && A_BYTES % 1024 == 0 && lds_bytes(3) <= 160 * 1024, "window layout");
 [[maybe_unused]] constexpr unsigned kOOB = 0x7FFFFFF0u;  // beyond any num_records: the load returns 0 (zero padding), never faults
-
-// compile-time loop: f(std::integral_constant<int, 0>{}) ... f(<N - 1>) -- the block schedule below is a table indexed by
-// the group number, which must be a constant in every copy of the body (hipcc does not fully unroll an 18 x 12 body on
-// `#pragma unroll` alone)
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 struct Item {  // scalar (wave-uniform) description of a work item
   int x0, y0, n;
@@ -675,16 +664,15 @@ int launch(const float *in, const float *wpk, const float *bias, const float *be
 
 namespace drba {
 
-int conv_dma_num_cfgs() { return drba_conv_dma::kNum; }
-int conv_dma_f16_first() { return drba_conv_dma::kNum; }
-static int planes_of(int id) { return id < drba_conv_dma::kNum ? 3 : 2; }
+static_assert(2 * drba_conv_dma::kNum == kConvDmaCfgs, "conv_split.hpp count");
+SplitDesc conv_dma_desc(int id) { return (id < 0 || id >= kConvDmaCfgs) ? SplitDesc{0, 0} : SplitDesc{planes(id, drba_conv_dma::kNum), 1}; }
 
 bool conv_dma_supports(int Cin, int Cout, int id) {
-  return id >= 0 && id < 2 * drba_conv_dma::kNum && Cin == drba_conv_dma::CK && Cout > 0 && Cout <= drba_conv_dma::NTC;
+  return id >= 0 && id < kConvDmaCfgs && Cin == drba_conv_dma::CK && Cout > 0 && Cout <= drba_conv_dma::NTC;
 }
 
 size_t conv_dma_packed_floats(int Cin, int Cout, int id) {
-  return conv_dma_supports(Cin, Cout, id) ? (size_t)drba_conv_dma::w_bytes(planes_of(id)) / 4 : 0;
+  return conv_dma_supports(Cin, Cout, id) ? (size_t)drba_conv_dma::w_bytes(planes(id, drba_conv_dma::kNum)) / 4 : 0;
 }
 
 // packed (16-byte units): [dy][dx][nt][plane h/m/l or h/l][lane] = 8 x 16 bit (split_weight_terms), element i =
@@ -692,26 +680,11 @@ size_t conv_dma_packed_floats(int Cin, int Cout, int id) {
 int conv_dma_pack(const float *w, float *packed, int Cin, int Cout, int id) {
   using namespace drba_conv_dma;
   if (!w || !packed || !conv_dma_supports(Cin, Cout, id)) return DRBA_EINVAL;
-  const int PL = planes_of(id);
-  if (PL == 2 && !two_term_weights_ok(w, (size_t)Cout * Cin * 9)) return DRBA_EUNSUPPORTED;
-  memset(packed, 0, w_bytes(PL));
-  unsigned short *dst = reinterpret_cast<unsigned short *>(packed);
-  for (int tap = 0; tap < 9; ++tap)
-    for (int nt = 0; nt < NT; ++nt)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int co = nt * 16 + (lane & 15);
-        if (co >= Cout) continue;
-        for (int i = 0; i < 8; ++i) {
-          const int ci = 4 * i + (lane >> 4);
-          unsigned short term[3];
-          split_weight_terms(w[((size_t)co * Cin + ci) * 9 + tap], PL, term);
-          for (int pl = 0; pl < PL; ++pl) {
-            const size_t unit = ((size_t)tap * NT + nt) * PL + pl;
-            dst[(unit * 64 + lane) * 8 + i] = term[pl];
-          }
-        }
-      }
-  return DRBA_OK;
+  return pack_fragments(w, (size_t)Cout * Cin * 9, packed, 9 * NT, planes(id, kNum), [&](size_t unit, int lane, int i) -> const float * {
+    const int nt = (int)(unit % NT), tap = (int)(unit / NT);
+    const int co = nt * 16 + (lane & 15), ci = 4 * i + (lane >> 4);
+    return co < Cout ? &w[((size_t)co * Cin + ci) * 9 + tap] : nullptr;
+  });
 }
 
 int conv_dma_launch(int id, const float *in, const float *packed_w, const float *bias, const float *beta,
@@ -721,7 +694,7 @@ int conv_dma_launch(int id, const float *in, const float *packed_w, const float 
   if (!conv_dma_supports(Cin, Cout, id)) return DRBA_EUNSUPPORTED;
   if ((W & 3) != 0) return DRBA_EUNSUPPORTED;  // the window moves in 16-byte units
   if ((size_t)Cin * H * W * 4 >= (1ull << 31) - 64) return DRBA_EUNSUPPORTED;  // 32-bit byte offsets inside an image, below kOOB
-  return planes_of(id) == 3 ? launch<3>(in, packed_w, bias, beta, residual, residual2, out, N, H, W, Cout, act, post_slope, pre_act,
+  return planes(id, kNum) == 3 ? launch<3>(in, packed_w, bias, beta, residual, residual2, out, N, H, W, Cout, act, post_slope, pre_act,
                                         pre_slope, (hipStream_t)stream)
                             : launch<2>(in, packed_w, bias, beta, residual, residual2, out, N, H, W, Cout, act, post_slope, pre_act,
                                         pre_slope, (hipStream_t)stream);

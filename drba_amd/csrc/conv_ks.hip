@@ -22,6 +22,7 @@
 // 16-byte units ([4 rows][18 columns]) and store scalars.
 #include "common.hpp"
 #include "conv_split.hpp"
+#include "device_helpers.hpp"
 
 #include <string.h>
 
@@ -42,15 +43,6 @@ constexpr int CK = 32, NT = 2, NTC = 32;
 // PL = 16-bit terms per operand: 3 = bf16 h + m + l, 2 = the two-term fp16 form (conv_split.hip "Two-term form")
 constexpr int frag_u4(int PL) { return 9 * NT * PL * 64; }  // 16-byte units of packed weights per (cout tile, chunk)
 [[maybe_unused]] constexpr unsigned kOOB = 0x7FFFFFF0u;
-
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 // window geometry: DW = false: columns x0-4 .. x0+19 in 16-byte units; DW = true: columns x0-1 .. x0+16 in dwords.
 // Channel stride == 16 (mod 32) dwords: the 32 lanes a ds_read_b32 services together (kq = 0, 1) hit distinct banks.
@@ -379,19 +371,18 @@ int launch(const float *in, const float *wpk, const float *bias, const float *be
 
 namespace drba {
 
-int conv_ks_num_cfgs() { return drba_conv_ks::kNum; }
-int conv_ks_f16_first() { return drba_conv_ks::kNum; }
-static int ks_planes(int id) { return id < drba_conv_ks::kNum ? 3 : 2; }
+static_assert(2 * drba_conv_ks::kNum == kConvKsCfgs, "conv_split.hpp count");
+SplitDesc conv_ks_desc(int id) { return (id < 0 || id >= kConvKsCfgs) ? SplitDesc{0, 0} : SplitDesc{planes(id, drba_conv_ks::kNum), 1}; }
 
 bool conv_ks_supports(int Cin, int Cout, int id) {
   const int kw = Cin / drba_conv_ks::CK;
-  return id >= 0 && id < 2 * drba_conv_ks::kNum && Cout > 0 && Cin % drba_conv_ks::CK == 0 && (kw == 2 || kw == 3 || kw == 4 || kw == 6);
+  return id >= 0 && id < kConvKsCfgs && Cout > 0 && Cin % drba_conv_ks::CK == 0 && (kw == 2 || kw == 3 || kw == 4 || kw == 6);
 }
 
 size_t conv_ks_packed_floats(int Cin, int Cout, int id) {
   if (!conv_ks_supports(Cin, Cout, id)) return 0;
   const size_t n_ct = (Cout + drba_conv_ks::NTC - 1) / drba_conv_ks::NTC, nch = Cin / drba_conv_ks::CK;
-  return n_ct * nch * drba_conv_ks::frag_u4(ks_planes(id)) * 4;
+  return n_ct * nch * drba_conv_ks::frag_u4(planes(id, drba_conv_ks::kNum)) * 4;
 }
 
 // packed (16-byte units): [cout tile][chunk][dy][dx][nt][plane h/m/l or h/l][lane] = 8 x 16 bit (split_weight_terms), element i =
@@ -399,28 +390,12 @@ size_t conv_ks_packed_floats(int Cin, int Cout, int id) {
 int conv_ks_pack(const float *w, float *packed, int Cin, int Cout, int id) {
   using namespace drba_conv_ks;
   if (!w || !packed || !conv_ks_supports(Cin, Cout, id)) return DRBA_EINVAL;
-  const int n_ct = (Cout + NTC - 1) / NTC, nch = Cin / CK, PL = ks_planes(id);
-  if (PL == 2 && !two_term_weights_ok(w, (size_t)Cout * Cin * 9)) return DRBA_EUNSUPPORTED;
-  memset(packed, 0, sizeof(float) * conv_ks_packed_floats(Cin, Cout, id));
-  unsigned short *dst = reinterpret_cast<unsigned short *>(packed);
-  for (int cz = 0; cz < n_ct; ++cz)
-    for (int q = 0; q < nch; ++q)
-      for (int tap = 0; tap < 9; ++tap)
-        for (int nt = 0; nt < NT; ++nt)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int co = cz * NTC + nt * 16 + (lane & 15);
-            if (co >= Cout) continue;
-            for (int i = 0; i < 8; ++i) {
-              const int ci = q * CK + 4 * i + (lane >> 4);
-              unsigned short term[3];
-              split_weight_terms(w[((size_t)co * Cin + ci) * 9 + tap], PL, term);
-              for (int pl = 0; pl < PL; ++pl) {
-                const size_t unit = ((((size_t)cz * nch + q) * 9 + tap) * NT + nt) * PL + pl;
-                dst[(unit * 64 + lane) * 8 + i] = term[pl];
-              }
-            }
-          }
-  return DRBA_OK;
+  const size_t n_ct = (Cout + NTC - 1) / NTC, nch = Cin / CK;
+  return pack_fragments(w, (size_t)Cout * Cin * 9, packed, n_ct * nch * 9 * NT, planes(id, kNum), [&](size_t unit, int lane, int i) -> const float * {
+    const int nt = (int)(unit % NT), tap = (int)(unit / NT % 9), q = (int)(unit / NT / 9 % nch), cz = (int)(unit / NT / 9 / nch);
+    const int co = cz * NTC + nt * 16 + (lane & 15), ci = q * CK + 4 * i + (lane >> 4);
+    return co < Cout ? &w[((size_t)co * Cin + ci) * 9 + tap] : nullptr;
+  });
 }
 
 int conv_ks_launch(int id, const float *in, const float *packed_w, const float *bias, const float *beta, const float *residual,
@@ -433,7 +408,7 @@ int conv_ks_launch(int id, const float *in, const float *packed_w, const float *
   hipStream_t s = (hipStream_t)stream;
 #define DRBA_CASE(K)                                                                                                          \
   case K:                                                                                                                     \
-    return ks_planes(id) == 3                                                                                                 \
+    return planes(id, kNum) == 3                                                                                              \
                ? launch<K, 3>(in, packed_w, bias, beta, residual, residual2, out, N, H, W, Cout, act, post_slope, pre_act, pre_slope, s) \
                : launch<K, 2>(in, packed_w, bias, beta, residual, residual2, out, N, H, W, Cout, act, post_slope, pre_act, pre_slope, s);
   switch (Cin / CK) {

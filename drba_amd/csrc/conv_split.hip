@@ -22,6 +22,7 @@
 // Accumulator layout as in conv.hip: lane holds cout lane % 16 for pixels 4*(lane/16)..+3 -> one float4 store along x.
 #include "common.hpp"
 #include "conv_split.hpp"
+#include "device_helpers.hpp"
 
 #include <string.h>
 
@@ -94,20 +95,6 @@ struct SplitCfg {
   static constexpr int MINB = (DRBA_SPLIT_MINB3 && MODE == 0 && RW * MW * NT <= 4 && PL == 3 && CS == 1) ? 3 : 2;
 };
 
-// fp32 -> (h, m, l) bf16 with round-to-nearest-even at every step; returns the three terms of 2 values packed
-__device__ __forceinline__ void split2(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  auto pk = [](float x, float y) -> unsigned {
-    const bf16x2 p = __builtin_convertvector(f32x2{x, y}, bf16x2);
-    return __builtin_bit_cast(unsigned, p);
-  };
-  h = pk(a, b);
-  const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-  m = pk(ra, rb);
-  l = pk(ra - __uint_as_float(m << 16), rb - __uint_as_float(m & 0xffff0000u));
-}
-
 // Two-term form (PL = 2): x * 2^-kActShift = h + 2^-11 * l with h = fp16(x'), l = fp16((x' - h) * 2^11): the remainder is
 // exact in fp32 (13 bits), l keeps 11 of them, so h + 2^-11 l carries 22 bits of x (relative error <= 2^-22; values
 // below fp16's normal range keep an absolute error <= 2^-25 * 2^kActShift whether or not denormals are flushed, because
@@ -115,17 +102,8 @@ __device__ __forceinline__ void split2(float a, float b, unsigned &h, unsigned &
 // products therefore go to two accumulators -- h*h, and (h*l + l*h) whose weight is 2^-11 -- joined in the epilogue.
 // l*l (2^-22 of the product) is dropped.  Three v_mfma_f32_16x16x32_f16 per fragment pair instead of six bf16 ones.
 // The activations are pre-scaled by 2^-kActShift (undone exactly in the epilogue): finite up to 65504 * 2^kActShift.
-constexpr int kActShift = drba::kSplitActShift;
-__device__ __forceinline__ void split2_f16(float a, float b, unsigned &h, unsigned &l) {
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = (f32x2){a, b} * (1.f / (float)(1 << kActShift));
-  const f16x2 hh = __builtin_convertvector(v, f16x2);
-  const f32x2 r = (v - __builtin_convertvector(hh, f32x2)) * 2048.f;
-  const f16x2 ll = __builtin_convertvector(r, f16x2);
-  h = __builtin_bit_cast(unsigned, hh);
-  l = __builtin_bit_cast(unsigned, ll);
-}
+// (the split itself: split2_f16, device_helpers.hpp)
+[[maybe_unused]] constexpr int kActShift = drba::kSplitActShift;
 
 struct TileCtx {
   int x0, y0, cz, n, py;
@@ -152,7 +130,6 @@ __device__ long long g_phase[1024 * 4 * 4];  // [workgroup][wave][slot]: written
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the wave's global-memory queue
 // (s_waitcnt vmcnt(0)): here that would expose, once per tile, the latency of the epilogue stores just issued.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // RL ("residual from LDS", MODE 0, 32-cout tiles, residual == input, Cin == Cout): the residual of a ResConv IS the input
 // tile, and x = h + m + l holds exactly (8 + 8 + 8 mantissa bits, each remainder exact), so the epilogue rebuilds it from
@@ -782,13 +759,14 @@ using Y4 = SplitCfg<2, 2, 1, 3, 2, 2>;  // stride 2: 4x16 output px x 96 cout
 using Y5 = SplitCfg<0, 2, 1, 3, 2, 2>;  // stride 1: 4x16 px x 96 cout (one staged window for all couts of a 96-channel layer)
 constexpr int kNumY = 6;  // (the same tile with 128 couts: 32.5 against 32.5 us on the 128-channel 34 x 60 layer -- not built)
 struct Info {
-  int NT, NTC, frag_u4, PL;
+  int NT, NTC, frag_u4, PL, stride;
 };
 template <class C>
 constexpr Info info() {
-  return {C::NTT, C::NTC, C::FRAG_U4, C::PL};  // (NT here: the cout tiles of a packed tile)
+  return {C::NTT, C::NTC, C::FRAG_U4, C::PL, C::MODE == 2 ? 2 : 1};  // (NT here: the cout tiles of a packed tile)
 }
-const Info kInfo[2 * kNum + kNumX + kNumY] = {info<S0>(), info<S1>(), info<S2>(), info<S3>(), info<S4>(),
+static_assert(2 * kNum + kNumX + kNumY == kConvSplitCfgs, "conv_split.hpp count");
+const Info kInfo[kConvSplitCfgs] = {info<S0>(), info<S1>(), info<S2>(), info<S3>(), info<S4>(),
                                               info<F0>(), info<F1>(), info<F2>(), info<F3>(), info<F4>(),
                                               info<X0>(), info<X1>(), info<X2>(), info<X3>(), info<Y0>(), info<Y1>(), info<Y2>(), info<Y3>(), info<Y4>(), info<Y5>()};
 using Z0 = SplitCfg<1, 2, 2, 2, 2, 2>;  // transposed, two-term, the waves split rows and couts: 4x32 input px x 64 cout (round 6)
@@ -797,7 +775,8 @@ using Z2 = SplitCfg<1, 2, 2, 1, 2, 2, 1>;  // Z1 with both row phases per work i
 using Z3 = SplitCfg<1, 1, 2, 2, 2, 1, 1>;  // G0 with both row phases per work item
 using Z4 = SplitCfg<1, 2, 1, 2, 2, 2, 1>;  // 4x16 input px x 64 cout, rows and couts split across the waves, both row phases
 constexpr int kNumZ = 5;
-const Info kInfoT[2 * kNumT + kNumZ] = {info<T0>(), info<T1>(), info<G0>(), info<G1>(), info<Z0>(), info<Z1>(), info<Z2>(), info<Z3>(), info<Z4>()};
+static_assert(2 * kNumT + kNumZ == kDeconvSplitCfgs, "conv_split.hpp count");
+const Info kInfoT[kDeconvSplitCfgs] = {info<T0>(), info<T1>(), info<G0>(), info<G1>(), info<Z0>(), info<Z1>(), info<Z2>(), info<Z3>(), info<Z4>()};
 
 template <class Cfg, bool PRE, bool RL = false, bool PSH = false>
 hipError_t lds_limit() {
@@ -876,21 +855,15 @@ int launch(const float *in, const float *wpk, const float *bias, const float *be
 namespace drba {
 
 // ids 0 .. kNum-1: three-term bf16; kNum .. 2*kNum-1: the same tiles in the two-term fp16 form; then the stride-2 tiles
-// (two-term form, any Cin)
-int conv_split_num_cfgs() { return drba_conv_split::kNum; }
-int conv_split_f16_first() { return drba_conv_split::kNum; }
-int conv_split_s2_first() { return 2 * drba_conv_split::kNum; }
-int conv_split_s2_num_cfgs() { return drba_conv_split::kNumX; }
-int conv_split_cs_first() { return 2 * drba_conv_split::kNum + drba_conv_split::kNumX; }
-int conv_split_cs_num_cfgs() { return drba_conv_split::kNumY; }
-int conv_split_cfg_stride(int id) { return (id >= 2 * drba_conv_split::kNum && id != 14 && id != 15 && id < 19) ? 2 : 1; }  // (Y0, Y1 = ids 14, 15 are the stride-1 tiles behind the X's)
+// (two-term form, any Cin: the last chunk is padded with zeros) and the CS = 2 tiles of either stride
+SplitDesc conv_split_desc(int id) {
+  if (id < 0 || id >= kConvSplitCfgs) return {0, 0};
+  return {drba_conv_split::kInfo[id].PL, drba_conv_split::kInfo[id].stride};
+}
 
 bool conv_split_supports(int Cin, int Cout, int id) {
   using namespace drba_conv_split;
-  if (id >= 2 * kNum + kNumX)  // two-term, CS = 2: the stride-1 tiles need whole chunks, the stride-2 tile takes any Cin
-    return id < 2 * kNum + kNumX + kNumY && Cin > 0 && Cout > 0 && (conv_split_cfg_stride(id) == 2 || Cin % CK == 0);
-  if (id >= 2 * kNum) return Cin > 0 && Cout > 0;
-  return id >= 0 && Cin > 0 && Cout > 0 && Cin % CK == 0;
+  return id >= 0 && id < kConvSplitCfgs && Cin > 0 && Cout > 0 && (kInfo[id].stride == 2 || Cin % CK == 0);
 }
 
 size_t conv_split_packed_floats(int Cin, int Cout, int id) {
@@ -906,29 +879,12 @@ int conv_split_pack(const float *w, float *packed, int Cin, int Cout, int id) {
   using namespace drba_conv_split;
   if (!w || !packed || !conv_split_supports(Cin, Cout, id)) return DRBA_EINVAL;
   const Info &c = kInfo[id];
-  if (c.PL == 2 && !two_term_weights_ok(w, (size_t)Cout * Cin * 9)) return DRBA_EUNSUPPORTED;
-  const int n_ct = (Cout + c.NTC - 1) / c.NTC, nch = (Cin + CK - 1) / CK;
-  memset(packed, 0, sizeof(float) * conv_split_packed_floats(Cin, Cout, id));
-  unsigned short *dst = reinterpret_cast<unsigned short *>(packed);
-  for (int cz = 0; cz < n_ct; ++cz)
-    for (int q = 0; q < nch; ++q)
-      for (int tap = 0; tap < 9; ++tap)
-        for (int nt = 0; nt < c.NT; ++nt)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int co = cz * c.NTC + nt * 16 + (lane & 15);
-            if (co >= Cout) continue;
-            for (int i = 0; i < 8; ++i) {
-              const int ci = q * CK + 8 * (lane >> 4) + i;
-              if (ci >= Cin) continue;  // (stride-2 ids: the last chunk of a ragged Cin)
-              unsigned short term[3];
-              split_weight_terms(w[((size_t)co * Cin + ci) * 9 + tap], c.PL, term);
-              for (int pl = 0; pl < c.PL; ++pl) {
-                const size_t unit = ((((size_t)cz * nch + q) * 9 + tap) * c.NT + nt) * c.PL + pl;
-                dst[(unit * 64 + lane) * 8 + i] = term[pl];
-              }
-            }
-          }
-  return DRBA_OK;
+  const size_t n_ct = (Cout + c.NTC - 1) / c.NTC, nch = (Cin + CK - 1) / CK;
+  return pack_fragments(w, (size_t)Cout * Cin * 9, packed, n_ct * nch * 9 * c.NT, c.PL, [&](size_t unit, int lane, int i) -> const float * {
+    const int nt = (int)(unit % c.NT), tap = (int)(unit / c.NT % 9), q = (int)(unit / c.NT / 9 % nch), cz = (int)(unit / c.NT / 9 / nch);
+    const int co = cz * c.NTC + nt * 16 + (lane & 15), ci = q * CK + 8 * (lane >> 4) + i;
+    return (co < Cout && ci < Cin) ? &w[((size_t)co * Cin + ci) * 9 + tap] : nullptr;  // (ci: the last chunk of a ragged Cin, stride-2 ids)
+  });
 }
 
 int conv_split_launch(int id, const float *in, const float *packed_w, const float *bias, const float *beta,
@@ -970,13 +926,13 @@ int conv_split_launch(int id, const float *in, const float *packed_w, const floa
 }
 
 // ---- transposed convolution (ConvTranspose2d k=4, s=2, p=1), cfg ids after conv.hip's fp32 deconv table
-int deconv_split_num_cfgs() { return drba_conv_split::kNumT; }
+SplitDesc deconv_split_desc(int id) {
+  if (id < 0 || id >= kDeconvSplitCfgs) return {0, 0};
+  return {drba_conv_split::kInfoT[id].PL, 1};
+}
 
-int deconv_split_f16_first() { return drba_conv_split::kNumT; }
-
-int deconv_split_total_cfgs() { return 2 * drba_conv_split::kNumT + drba_conv_split::kNumZ; }  // ids >= 2 kNumT: two-term, CS = 2
 bool deconv_split_supports(int Cin, int Cout, int id) {
-  return id >= 0 && id < deconv_split_total_cfgs() && Cin > 0 && Cout > 0 && Cin % drba_conv_split::CK == 0;
+  return id >= 0 && id < kDeconvSplitCfgs && Cin > 0 && Cout > 0 && Cin % drba_conv_split::CK == 0;
 }
 
 size_t deconv_split_packed_floats(int Cin, int Cout, int id) {
@@ -987,40 +943,20 @@ size_t deconv_split_packed_floats(int Cin, int Cout, int id) {
 }
 
 // w: [Cin, Cout, 4, 4].  packed (16-byte units): [cout tile][phase = 2*py + px][chunk][tap = 2a + b][nt][plane][lane],
-// ky = py ? (a ? 2 : 0) : (a ? 3 : 1), kx likewise from (px, b) -- the phase algebra of conv.hip's drba_deconv4x4_pack
+// ky = py ? (a ? 2 : 0) : (a ? 3 : 1), kx likewise from (px, b) -- the phase algebra of conv.hip's deconv_fp32_pack
 int deconv_split_pack(const float *w, float *packed, int Cin, int Cout, int id) {
   using namespace drba_conv_split;
   if (!w || !packed || !deconv_split_supports(Cin, Cout, id)) return DRBA_EINVAL;
   const Info &c = kInfoT[id];
-  if (c.PL == 2 && !two_term_weights_ok(w, (size_t)Cin * Cout * 16)) return DRBA_EUNSUPPORTED;
-  const int n_ct = (Cout + c.NTC - 1) / c.NTC, nch = Cin / CK;
-  memset(packed, 0, sizeof(float) * deconv_split_packed_floats(Cin, Cout, id));
-  unsigned short *dst = reinterpret_cast<unsigned short *>(packed);
-  for (int cz = 0; cz < n_ct; ++cz)
-    for (int phase = 0; phase < 4; ++phase) {
-      const int py = phase >> 1, px = phase & 1;
-      for (int q = 0; q < nch; ++q)
-        for (int tap = 0; tap < 4; ++tap) {
-          const int a = tap >> 1, b = tap & 1;
-          const int ky = py ? (a ? 2 : 0) : (a ? 3 : 1);
-          const int kx = px ? (b ? 2 : 0) : (b ? 3 : 1);
-          for (int nt = 0; nt < c.NT; ++nt)
-            for (int lane = 0; lane < 64; ++lane) {
-              const int co = cz * c.NTC + nt * 16 + (lane & 15);
-              if (co >= Cout) continue;
-              for (int i = 0; i < 8; ++i) {
-                const int ci = q * CK + 8 * (lane >> 4) + i;
-                unsigned short term[3];
-                split_weight_terms(w[(((size_t)ci * Cout + co) * 4 + ky) * 4 + kx], c.PL, term);
-                for (int pl = 0; pl < c.PL; ++pl) {
-                  const size_t unit = ((((((size_t)cz * 4 + phase) * nch + q) * 4 + tap) * c.NT + nt) * c.PL + pl);
-                  dst[(unit * 64 + lane) * 8 + i] = term[pl];
-                }
-              }
-            }
-        }
-    }
-  return DRBA_OK;
+  const size_t n_ct = (Cout + c.NTC - 1) / c.NTC, nch = Cin / CK;
+  return pack_fragments(w, (size_t)Cin * Cout * 16, packed, n_ct * 4 * nch * 4 * c.NT, c.PL, [&](size_t unit, int lane, int i) -> const float * {
+    const int nt = (int)(unit % c.NT), tap = (int)(unit / c.NT % 4), q = (int)(unit / c.NT / 4 % nch);
+    const int phase = (int)(unit / c.NT / 4 / nch % 4), cz = (int)(unit / c.NT / 4 / nch / 4);
+    const int py = phase >> 1, px = phase & 1, a = tap >> 1, b = tap & 1;
+    const int ky = py ? (a ? 2 : 0) : (a ? 3 : 1), kx = px ? (b ? 2 : 0) : (b ? 3 : 1);
+    const int co = cz * c.NTC + nt * 16 + (lane & 15), ci = q * CK + 8 * (lane >> 4) + i;
+    return co < Cout ? &w[(((size_t)ci * Cout + co) * 4 + ky) * 4 + kx] : nullptr;
+  });
 }
 
 int deconv_split_launch(int id, const float *in, const float *packed_w, const float *bias, float *out, int N, int Cin, int H,

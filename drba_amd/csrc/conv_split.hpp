@@ -1,6 +1,9 @@
-// Split-bf16 3x3 convolution family (conv_split.hip), reached through drba_conv3x3 with cfg ids that follow the fp32
-// table of conv.hip.
+// Split-operand 3x3 convolution backends (conv_split.hip, conv_dma.hip, conv_ks.hip) behind drba_conv3x3 /
+// drba_deconv4x4s2.  Every backend numbers its own configurations from 0; conv.hip's run table (kConvRuns / kDeconvRuns) is
+// the one place that says where they sit among the public cfg ids.
 #pragma once
+#include "common.hpp"
+
 #include <stddef.h>
 #include <string.h>
 
@@ -33,14 +36,39 @@ static inline void split_weight_terms(float x, int PL, unsigned short *bits) {
   }
 }
 
-int conv_split_num_cfgs();   // ids 0 .. n-1: three-term bf16 split; ids n .. 2n-1: the same tiles, two-term fp16 split
-int conv_split_f16_first();  // = n
-int conv_split_s2_first();   // = 2n: then conv_split_s2_num_cfgs() stride-2 tiles in the two-term form (any Cin; H, W = the INPUT map)
-int conv_split_s2_num_cfgs();
-int conv_split_cs_first();     // behind the stride-2 tiles: stride-1 two-term tiles whose waves split rows and couts (round 6)
-int conv_split_cs_num_cfgs();
-int conv_split_cfg_stride(int id);  // 1 or 2, for any id of this file's table
-bool conv_split_supports(int Cin, int Cout, int id);  // stride 1, Cin a multiple of 32
+// what conv.hip's table needs to know about a backend's configuration: 16-bit terms per operand (3 bf16 / 2 fp16) and the
+// convolution stride it was built for; {0, 0} for an id outside the backend's table
+struct SplitDesc {
+  int planes, stride;
+};
+// a backend table of n_three_term three-term ids followed by their two-term forms
+constexpr int planes(int id, int n_three_term) { return id < n_three_term ? 3 : 2; }
+
+// Packed weights of every split backend: [unit][plane][lane][8 x 16 bit], the PL terms of weight(unit, lane, i) in element i
+// (split_weight_terms).  `weight` returns the address of the fp32 weight, or nullptr for padding (stays zero).  The two-term
+// form refuses weights beyond fp16 (DRBA_EUNSUPPORTED, common.hpp two_term_weights_ok).
+template <class F>
+int pack_fragments(const float *w, size_t n_weights, float *packed, size_t units, int PL, F &&weight) {
+  if (PL == 2 && !two_term_weights_ok(w, n_weights)) return DRBA_EUNSUPPORTED;
+  unsigned short *dst = reinterpret_cast<unsigned short *>(packed);
+  memset(dst, 0, units * PL * 64 * 8 * sizeof(unsigned short));
+  for (size_t unit = 0; unit < units; ++unit)
+    for (int lane = 0; lane < 64; ++lane)
+      for (int i = 0; i < 8; ++i) {
+        const float *x = weight(unit, lane, i);
+        if (!x) continue;
+        unsigned short term[3];
+        split_weight_terms(*x, PL, term);
+        for (int pl = 0; pl < PL; ++pl) dst[((unit * PL + pl) * 64 + lane) * 8 + i] = term[pl];
+      }
+  return DRBA_OK;
+}
+
+// conv_split.hip: three-term and two-term tiles, stride 1 (Cin a multiple of 32) and stride 2 (two-term, any Cin; H, W = the
+// INPUT map)
+constexpr int kConvSplitCfgs = 20;
+SplitDesc conv_split_desc(int id);
+bool conv_split_supports(int Cin, int Cout, int id);
 size_t conv_split_packed_floats(int Cin, int Cout, int id);
 int conv_split_pack(const float *w, float *packed, int Cin, int Cout, int id);
 int conv_split_launch(int id, const float *in, const float *packed_w, const float *bias, const float *beta,
@@ -48,11 +76,10 @@ int conv_split_launch(int id, const float *in, const float *packed_w, const floa
                       int act, float post_slope, int pre_act, float pre_slope, void *stream, int pixel_shuffle = 0);
 // (pixel_shuffle: MODE 0 tiles that carry the PixelShuffle(2) store form -- the two-term 4 x 32 x 64 ones -- else DRBA_EUNSUPPORTED)
 
-
 // the same arithmetic with every operand streamed by LDS-DMA and the activations split on the way into the MFMAs
-// (conv_dma.hip); cfg ids follow the conv_split family
-int conv_dma_num_cfgs();   // n three-term ids, then n two-term ones (conv_dma_f16_first)
-int conv_dma_f16_first();
+// (conv_dma.hip): Cin = 32, Cout <= 32, W % 4 == 0
+constexpr int kConvDmaCfgs = 2;
+SplitDesc conv_dma_desc(int id);
 bool conv_dma_supports(int Cin, int Cout, int id);
 size_t conv_dma_packed_floats(int Cin, int Cout, int id);
 int conv_dma_pack(const float *w, float *packed, int Cin, int Cout, int id);
@@ -61,9 +88,9 @@ int conv_dma_launch(int id, const float *in, const float *packed_w, const float 
                     int act, float post_slope, int pre_act, float pre_slope, void *stream);
 
 // the same per-wave program with the K dimension split across the waves of a workgroup, for multi-chunk layers on small
-// maps (conv_ks.hip); cfg ids follow the conv_dma family
-int conv_ks_num_cfgs();   // n three-term ids, then n two-term ones (conv_ks_f16_first)
-int conv_ks_f16_first();
+// maps (conv_ks.hip): Cin = 64 / 96 / 128 / 192
+constexpr int kConvKsCfgs = 2;
+SplitDesc conv_ks_desc(int id);
 bool conv_ks_supports(int Cin, int Cout, int id);
 size_t conv_ks_packed_floats(int Cin, int Cout, int id);
 int conv_ks_pack(const float *w, float *packed, int Cin, int Cout, int id);
@@ -71,10 +98,9 @@ int conv_ks_launch(int id, const float *in, const float *packed_w, const float *
                    const float *residual2, float *out, int N, int Cin, int H, int W, int Cout, int act, float post_slope,
                    int pre_act, float pre_slope, void *stream);
 
-// transposed convolution 4x4 s2 p1 (cfg ids after conv.hip's fp32 deconv table)
-int deconv_split_num_cfgs();   // as above: n three-term ids, then n two-term ones
-int deconv_split_f16_first();
-int deconv_split_total_cfgs();  // 2 n + the two-term tiles whose waves split rows and couts (appended, round 6)
+// transposed convolution 4x4 s2 p1 (conv_split.hip MODE 1)
+constexpr int kDeconvSplitCfgs = 9;
+SplitDesc deconv_split_desc(int id);
 bool deconv_split_supports(int Cin, int Cout, int id);
 size_t deconv_split_packed_floats(int Cin, int Cout, int id);
 int deconv_split_pack(const float *w, float *packed, int Cin, int Cout, int id);

@@ -19,6 +19,7 @@
 //   a wave holds whole output rows -- LayerNorm(128) with its affine and the residual add.
 #include "common.hpp"
 #include "conv_split.hpp"
+#include "device_helpers.hpp"
 
 #include <string.h>
 
@@ -34,33 +35,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CK = 32;    // K per chunk = the K of one bf16 MFMA
-__device__ __forceinline__ void split2(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  auto pk = [](float x, float y) -> unsigned {
-    const bf16x2 p = __builtin_convertvector(f32x2{x, y}, bf16x2);
-    return __builtin_bit_cast(unsigned, p);
-  };
-  h = pk(a, b);
-  const float ra = a - __uint_as_float(h << 16), rb = b - __uint_as_float(h & 0xffff0000u);
-  m = pk(ra, rb);
-  l = pk(ra - __uint_as_float(m << 16), rb - __uint_as_float(m & 0xffff0000u));
-}
-
-// two-term fp16 form (conv_split.hip "Two-term form"): x * 2^-shift = h + 2^-11 l
-__device__ __forceinline__ void split2_f16(float a, float b, unsigned &h, unsigned &l) {
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = (f32x2){a, b} * (1.f / (float)(1 << drba::kSplitActShift));
-  const f16x2 hh = __builtin_convertvector(v, f16x2);
-  const f32x2 r = (v - __builtin_convertvector(hh, f32x2)) * 2048.f;
-  const f16x2 ll = __builtin_convertvector(r, f16x2);
-  h = __builtin_bit_cast(unsigned, hh);
-  l = __builtin_bit_cast(unsigned, ll);
-}
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
 
 typedef __attribute__((address_space(3))) void *lds_ptr;

@@ -20,6 +20,7 @@
 // that own a pixel, as in ifblock_input_lds<.., FOLD = true, ..>; per-point arithmetic is that kernel's, term by term.
 // Exact fp32 products (fp32 MFMA): the result differs from the unfused pair only by the accumulation order.
 #include "common.hpp"
+#include "device_helpers.hpp"
 #include "flow_terms.hpp"
 
 #include <string.h>
@@ -63,15 +64,6 @@ __host__ __device__ constexpr int chan_of(int g, int j) {
 }
 static_assert(chan_of(2, 0) == 6 && chan_of(2, 1) == 7 && chan_of(2, 2) == 22 && chan_of(2, 3) == 23, "pair groups");
 static_assert(chan_of(9, 1) == 21 && chan_of(9, 3) == 37 && chan_of(10, 0) == 40 && chan_of(12, 3) == 51, "tail groups");
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-  static_for_impl<N>(f, std::make_integer_sequence<int, N>{});
-}
 
 struct StageItems {
   drba_stage_item_t it[DRBA_MAX_STAGE_ITEMS];

@@ -527,6 +527,17 @@ def _families(layer_ok=True):
     return CONV_FAMILIES if layer_ok else CONV_FAMILIES - {4}
 
 
+def _candidates(lib, stride, families, cin, cout, deconv=False):
+    """The configuration ids a tuner may time for a cin -> cout layer: built for `stride` (None for the transposed convolution,
+    whose ids carry none), of one of `families`, and able to run the layer (packed_floats 0: the configuration cannot)."""
+    if deconv:
+        n, family, packed = lib.drba_deconv4x4_num_cfgs(), lib.drba_deconv4x4_cfg_family, lib.drba_deconv4x4_packed_floats
+    else:
+        n, family, packed = lib.drba_conv3x3_num_cfgs(), lib.drba_conv3x3_cfg_family, lib.drba_conv3x3_packed_floats
+    return [c for c in range(n) if (stride is None or lib.drba_conv3x3_cfg_stride(c) == stride)
+            and family(c) in families and packed(cin, cout, c) > 0]
+
+
 def _tuned_get(shape_key, families=None):
     return _tuned.get((shape_key, tuple(sorted(CONV_FAMILIES if families is None else families))))
 
@@ -679,9 +690,7 @@ class Conv3x3:
             cfg = self.force_cfg
         elif AUTOTUNE and x.is_cuda:
             fam = _families(self.two_term_ok)
-            cands = [c for c in range(lib.drba_conv3x3_num_cfgs()) if lib.drba_conv3x3_cfg_stride(c) == self.stride
-                     and lib.drba_conv3x3_cfg_family(c) in fam
-                     and lib.drba_conv3x3_packed_floats(self.cin, self.cout, c) > 0]  # 0: the config cannot run this layer
+            cands = _candidates(lib, self.stride, fam, self.cin, self.cout)
             cfg = _tune(("conv3x3", n, cin, self.cout, h, w, self.stride), cands, lambda c: lib.drba_conv3x3(
                 _p(x), _p(self._pack(c)), _p(self.bias), _p(self.beta), _p(res), _p(res2), _p(out), n, cin, h, w,
                 self.cout, self.stride, self.act, self.post_slope, pre, ps, c, _stream()), families=fam, persist=True, device=x.device.index)
@@ -711,8 +720,7 @@ def conv3x3_shuffle(layer, x):
     if not usable:
         return pixel_shuffle2(layer(x))
     out = torch.empty((n, layer.cout // 4, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
-    cands = [c for c in range(lib.drba_conv3x3_num_cfgs()) if lib.drba_conv3x3_cfg_stride(c) == 1
-             and lib.drba_conv3x3_cfg_family(c) == 4 and lib.drba_conv3x3_packed_floats(layer.cin, layer.cout, c) > 0]
+    cands = _candidates(lib, 1, (4,), layer.cin, layer.cout)
     run = lambda c: lib.drba_conv3x3_shuffle(_p(x), _p(layer._pack(c)), _p(layer.bias), _p(out), n, cin, h, w, layer.cout,  # noqa: E731
                                              layer.act, layer.post_slope, c, _stream())
     try:
@@ -766,8 +774,7 @@ class Deconv4x4:
             cfg = self.force_cfg
         elif AUTOTUNE and x.is_cuda:
             fam = _families(self.two_term_ok)
-            cands = [c for c in range(lib.drba_deconv4x4_num_cfgs()) if lib.drba_deconv4x4_cfg_family(c) in fam
-                     and lib.drba_deconv4x4_packed_floats(cin, self.cout, c) > 0]
+            cands = _candidates(lib, None, fam, cin, self.cout, deconv=True)
             cfg = _tune(("deconv4x4", n, cin, self.cout, h, w, self.ps), cands,
                         lambda c: lib.drba_deconv4x4s2(_p(x), _p(self._pack(c)), _p(self.bias), _p(out), n, cin, h, w,
                                                        self.cout, self.ps, pre, ps_, c, _stream()), families=fam, persist=True, device=x.device.index)

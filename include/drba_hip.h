@@ -218,6 +218,9 @@ int drba_ssim3d_32(const float *x1, const float *x2, float *out, void *stream);
 int drba_conv3x3_pick_cfg(int Cin, int Cout, int Ho, int Wo, int stride); /* cost-model default */
 int drba_conv3x3_num_cfgs(void);         /* configs are 0..num-1; a host may time them and keep the fastest */
 int drba_conv3x3_cfg_stride(int cfg);    /* the stride (1 or 2) a config was built for */
+/* Which ids belong to which kernel family is stated once, in the run tables of drba_amd/csrc/conv.hip (kConvRuns /
+ * kDeconvRuns); runs are only appended.  A host asks drba_conv3x3_cfg_family / drba_conv3x3_cfg_stride /
+ * drba_deconv4x4_cfg_family per id instead of assuming a boundary (all return DRBA_EINVAL outside 0..num-1). */
 /* kernel family of a config: 0 = fp32 MFMA (conv.hip), 1 = split-bf16 with register staging (conv_split.hip: stride 1,
  * Cin % 32 == 0), 2 = split-bf16 with every operand streamed by LDS-DMA (conv_dma.hip: additionally W % 4 == 0; the
  * launch returns DRBA_EUNSUPPORTED otherwise: Cin == 32, Cout <= 32), 3 = split-bf16 with K split across the waves of a

@@ -108,10 +108,15 @@ def check_conv_layers(dev):
         except Exception as e:  # noqa: BLE001
             rows.append((name, float("inf"), 0.0, f"EXC {type(e).__name__}: {e}"))
     # every kernel configuration, pinned explicitly, on ragged shapes (tile-edge masks, split-K reduce, cout padding)
-    S1 = [0, 1, 2, 3, 4, 5, 6, 7]
-    S2 = [8, 9, 10, 11, 12, 13]
-    for cfg in S1 + S2:
-        stride = 1 if cfg in S1 else 2
+    # (which ids are the fp32 kernels and which the split families is the library's to say: conv.hip kConvRuns / kDeconvRuns)
+    lib = ops._lib.load()
+    conv_fp32 = [c for c in range(lib.drba_conv3x3_num_cfgs()) if lib.drba_conv3x3_cfg_family(c) == 0]
+    conv_split = [c for c in range(lib.drba_conv3x3_num_cfgs()) if lib.drba_conv3x3_cfg_family(c) != 0]
+    deconv_fp32 = [c for c in range(lib.drba_deconv4x4_num_cfgs()) if lib.drba_deconv4x4_cfg_family(c) == 0]
+    deconv_split = [c for c in range(lib.drba_deconv4x4_num_cfgs()) if lib.drba_deconv4x4_cfg_family(c) != 0]
+    assert conv_fp32 + conv_split == list(range(38)) and deconv_fp32 + deconv_split == list(range(15)), "every id, in id order"
+    for cfg in conv_fp32:
+        stride = lib.drba_conv3x3_cfg_stride(cfg)
         for (cin, cout, h, w) in ((20, 40, 11, 45), (7, 16, 5, 70)):
             try:
                 x = torch.randn(1, cin, h, w, generator=g)
@@ -124,9 +129,7 @@ def check_conv_layers(dev):
                 rows.append((f"conv cfg{cfg}", float("inf"), 0.0, f"EXC {type(e).__name__}: {e}"))
     # the split-bf16 family (conv_split.hip: fp32 operands as three bf16 terms, six MFMA products): same tolerance as
     # the fp32 kernels, against the fp64-accumulated CPU convolution so that the check measures THIS kernel's error
-    lib = ops._lib.load()
-    n_fp32 = 14
-    for cfg in range(n_fp32, lib.drba_conv3x3_num_cfgs()):
+    for cfg in conv_split:
         if lib.drba_conv3x3_cfg_stride(cfg) != 1:
             continue  # (the stride-2 tiles of the two-term form: below)
         # (the LDS-DMA family: 32 input channels, at most 32 output channels, widths that are multiples of 4 -- its windows
@@ -169,7 +172,7 @@ def check_conv_layers(dev):
     # operand's magnitude does not matter between fp16's normal range and 65504 * 16; below |x| ~ 1e-3 the error is bounded
     # absolutely instead, 2^-32) -- |x| up to 1.0e6 (uniform: the documented bound is 65504 * 16 = 1.048e6) and |x| ~ 1e-2,
     # same relative bound
-    for cfg in range(n_fp32, lib.drba_conv3x3_num_cfgs()):
+    for cfg in conv_split:
         if lib.drba_conv3x3_cfg_family(cfg) != 4 or lib.drba_conv3x3_cfg_stride(cfg) != 1 or lib.drba_conv3x3_packed_floats(64, 64, cfg) == 0:
             continue
         for mag in (1e6, 1e-2):
@@ -184,7 +187,7 @@ def check_conv_layers(dev):
                 rows.append((f"conv two-term cfg{cfg} |x| ~ {mag:g}", float("inf"), 0.0, f"EXC {type(e).__name__}: {e}"))
     # stride 2 in the two-term form (conv_split.hip MODE 2): ragged Cin (the last chunk padded), odd and even maps, widths that
     # are and are not multiples of 4 on the output side, a batch, the PReLU pre-activation, Cout past one tile; against fp64
-    for cfg in range(n_fp32, lib.drba_conv3x3_num_cfgs()):
+    for cfg in conv_split:
         if lib.drba_conv3x3_cfg_stride(cfg) != 2:
             continue
         for (nb, cin, cout, h, w, kind) in ((1, 52, 32, 22, 90, "conv"), (2, 39, 96, 17, 31, "conv"), (1, 16, 32, 40, 64, "conv"),
@@ -204,7 +207,7 @@ def check_conv_layers(dev):
                              5e-6 * max(1.0, scale), f"|ref|max={scale:.2f}"))
             except Exception as e:  # noqa: BLE001
                 rows.append((f"conv split s2 cfg{cfg} {kind}", float("inf"), 0.0, f"EXC {type(e).__name__}: {e}"))
-    for cfg in range(6):
+    for cfg in deconv_fp32:
         for (cin, cout, h, w, ps) in ((20, 52, 11, 45, True), (9, 16, 6, 70, False)):
             try:
                 x = torch.randn(1, cin, h, w, generator=g)
@@ -218,7 +221,7 @@ def check_conv_layers(dev):
             except Exception as e:  # noqa: BLE001
                 rows.append((f"deconv cfg{cfg}", float("inf"), 0.0, f"EXC {type(e).__name__}: {e}"))
     # split-bf16 transposed convolution (cfg ids after the fp32 deconv table), against fp64
-    for cfg in range(6, lib.drba_deconv4x4_num_cfgs()):
+    for cfg in deconv_split:
         for (nb, cin, cout, h, w, ps, pre) in ((1, 32, 52, 11, 45, True, None), (2, 64, 16, 6, 70, False, None), (1, 96, 40, 9, 33, False, 0.25),
                                                 (1, 32, 52, 8, 64, True, None)):
             try:

@@ -110,11 +110,11 @@ def test_split_conv_weight_packing_reconstructs_fp32():
     up to its last mantissa bit) or as two fp16 terms h, (w - h) * 2^11 (family 4: h + 2^-11 l carries 22 bits), every weight
     exactly once, and a layer a family cannot run (Cin not a multiple of 32) reports 0 packed floats so that hosts skip it."""
     lib = _lib.load()
-    n_fp32 = 14
-    assert lib.drba_conv3x3_num_cfgs() > n_fp32
+    split = [c for c in range(lib.drba_conv3x3_num_cfgs()) if lib.drba_conv3x3_cfg_family(c) != 0]
+    assert split == list(range(14, 38))
     g = torch.Generator().manual_seed(5)
     seen = set()
-    for cfg in range(n_fp32, lib.drba_conv3x3_num_cfgs()):
+    for cfg in split:
         fam = lib.drba_conv3x3_cfg_family(cfg)
         seen.add(fam)
         if lib.drba_conv3x3_cfg_stride(cfg) == 2:  # the two-term form's stride-2 tiles take any Cin (last chunk padded with zeros)

@@ -32,7 +32,8 @@ int main(int argc, char **argv) {
   float *dp = nullptr, *dy = nullptr;
   int dcfg = 0;
   if (dcout) {
-    dcfg = drba::deconv_split_f16_first() + cfg;
+    while (drba::deconv_split_desc(dcfg).planes == 3) ++dcfg;  // the first two-term id
+    dcfg += cfg;
     const size_t dpf = drba::deconv_split_packed_floats(C, dcout, dcfg);
     if (!dpf) return 3;
     std::vector<float> dw((size_t)C * dcout * 16), dpk(dpf);
