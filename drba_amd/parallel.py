@@ -7,17 +7,19 @@ per GPU, torch.distributed; backend "nccl" = RCCL over xGMI on the GPUs, "gloo" 
 Each rank rebuilds the state the sequential driver would carry into its first step from a
 halo of one extra leading frame:
 
-    cut_left = check_scene(frame[a-1... see below])      (only with scene detection on)
-    reuse    = swap(model.calc_flow(frame[a], frame[a+1])) if the previous step was a DRBA step else None
+    cut_left = check_scene(frame[a], frame[a+1])         (only with scene detection on)
+    reuse    = swap(model.calc_flow(frame[a], frame[a+1])) if step a-1 was a DRBA step (no cut on either side) else None
 
-which is exactly what step a-1 of the sequential run returns (reference models/rife.py:82-85,109),
-so the sharded result equals the sequential one (up to fp32 atomic-order jitter of the splats).
+which is exactly what step a-1 of the sequential run returns (reference models/rife.py:82-85,109), and then runs the
+sequential driver's loop (drba_amd/driver.py) over its frames, so the sharded result equals the sequential one (on the
+GPU up to which steps share a stacked pass: tests/test_gpu_parallel.py).
 The only collective in the data path is the gather of finished uint8 frames to rank 0; a 1080p
 frame is 6.2 MB, i.e. ~0.2 GB/s per xGMI link at 8 x 30 fps -- no ring tuning needed.
 """
 import numpy as np
 import torch
 
+from drba_amd import driver
 from drba_amd.models.utils import tools as _tools
 
 
@@ -67,70 +69,18 @@ def interpolate_shard(model, frames, src_fps, dst_fps, rank, world, times=-1, en
     function returns []."""
     to_inp = to_inp or _tools.to_inp
     to_out = to_out or _tools.to_out
-    # the library's own scene test can be asked for ahead of its use (tools.SceneChecks); an injected one is called in place
-    ahead_checks = _tools.SceneChecks(scdet_threshold) if (check_scene is None and enable_scdet) else None
-    check_scene = check_scene or _tools.check_scene
     if dst_fps <= src_fps:
         raise ValueError(f"dst fps should be greater than src fps, but got dst_fps={dst_fps} and src_fps={src_fps}")
     n = len(frames)
-    n_loop = max(n - 2, 0)
-    a, b = partition(n_loop, world)[rank]
+    a, b = partition(max(n - 2, 0), world)[rank]
+    head, tail = rank == 0, rank == world - 1
+    out = []
+    if a == b and not (head or tail):  # more ranks than loop iterations: nothing to do here
+        return out
     size = _tools.get_valid_net_inp_size(frames[0], model.scale, div=model.pad_size)
     src_size, dst_size = size["src_size"], size["dst_size"]
     mapper = _tools.TMapper(src_fps, dst_fps, times)
-    cache = {}
-
-    intake = [None]  # the model's intake stream (RIFE: its prefetch stream), set where the loop starts reading ahead
-
-    def inp(k):
-        if k not in cache:
-            cache[k] = to_inp(frames[k], dst_size)
-        return cache[k]
-
-    def take_in(j):
-        """Frame j read ahead: to_inp, the scene test of the pair (j - 1, j) and the model's prefetches on the intake stream, clear
-        of the synthesis queue (drba_amd/infer.py `read`: the decision is needed before the frame can be announced as part of a
-        group of steps; behind the caller's queue, waiting for it put host and GPU in lock step)."""
-        s = intake[0]
-        if s is None or j in cache:
-            x = inp(j)
-            cm = None
-        else:
-            main = torch.cuda.current_stream(s.device)
-            cm = torch.cuda.stream(s)
-            cm.__enter__()
-            x = inp(j)
-            if x.is_cuda:
-                ev = torch.cuda.Event()
-                ev.record(s)
-                main.wait_event(ev)
-                x.record_stream(main)
-                x4 = getattr(x, "_drba_x4", None)
-                if x4 is not None:
-                    x4[0].record_stream(main)
-        try:
-            if ahead_checks is not None and j - 1 not in cuts:
-                ahead_checks.submit(j - 1, inp(j - 1), x)  # the cut test the iterations before j - 1 will ask for
-            prefetch(x)
-            if prefetch_pair is not None:
-                prefetch_pair(inp(j - 1), x)
-        finally:
-            if cm is not None:
-                cm.__exit__(None, None, None)
-
-    cuts = {}
-
-    def cut(k):  # scene cut between frame k and k+1 (each pair is tested once: the loop looks one step ahead)
-        if not enable_scdet:
-            return False
-        if k not in cuts:
-            if ahead_checks is not None and inp(k).is_cuda:
-                cuts[k] = ahead_checks.cut(k, inp(k), inp(k + 1))
-            else:
-                cuts[k] = bool(check_scene(inp(k), inp(k + 1), scdet_threshold))
-        return cuts[k]
-
-    out = []
+    cuts = driver.SceneCuts(enable_scdet, scdet_threshold, check_scene)
 
     def emit(xs):
         fr = [to_out(x, src_size) for x in xs]
@@ -139,74 +89,22 @@ def interpolate_shard(model, frames, src_fps, dst_fps, rank, world, times=-1, en
         else:
             out.extend(fr)
 
-    # ---- head (rank 0 only): infer.py:93-110
-    if rank == 0:
-        ts = _tools.calc_t(0, times, mapper)
-        if cut(0):
-            emit([inp(0) for _ in ts])
-        else:
-            emit([inp(0) for _ in ts[ts < 1]] + list(model.inference_ts(inp(0), inp(1), ts[ts >= 1] - 1)))
-
-    # ---- state entering loop iteration a, as the sequential driver would have it
-    cut_left = cut(a) if (a < b or rank == world - 1) and n >= 2 else False
-    reuse = None
-    if a > 0 and a < b and not cut_left and not cut(a - 1):
+    # ---- state entering loop iteration a, as the sequential driver would have it (rank 0 starts cold, with the head)
+    pair = [to_inp(frames[a], dst_size), to_inp(frames[a + 1], dst_size)]
+    cut_left, reuse = False, None
+    if a > 0 and a < b:
+        cut_left = cuts.cut(a, *pair)
         # iteration a-1 had (left, right) = (cut(a-1), cut(a)): a DRBA step iff both are False
-        reuse = warm_reuse(model, inp(a), inp(a + 1))
+        if not cut_left and not cuts.cut(a - 1, to_inp(frames[a - 1], dst_size), pair[0]):
+            reuse = warm_reuse(model, *pair)
 
-    # ---- loop iterations [a, b): infer.py:112-156 with idx == k
-    can_look = bool(getattr(model, "supports_lookahead", False))
-    prefetch = getattr(model, "prefetch_frame", None) if can_look else None
-    prefetch_pair = getattr(model, "prefetch_pair", None) if can_look else None
-    prefetched = set()
-    depth = max(3, 2 * int(getattr(model, "GROUP", 1)) - 1) if prefetch is not None else 1
-    for k in range(a, b):
-        I0, I1, I2 = inp(k), inp(k + 1), inp(k + 2)
-        ts = _tools.calc_t(k, times, mapper)
-        cut_right = cut(k + 1)
-        if cut_left and cut_right:
-            res, reuse = [I1 for _ in ts], None
-        elif cut_left:
-            reuse = None
-            res = [I1 for _ in ts[ts < 1]] + list(model.inference_ts(I1, I2, ts[ts >= 1] - 1))
-        elif cut_right:
-            reuse = None
-            res = list(model.inference_ts(I0, I1, ts[ts <= 1])) + [I1 for _ in ts[ts > 1] - 1]
-        elif can_look and k + 1 < b and k + 3 < n:
-            # lookahead inside the shard (drba_amd/models/lookahead.py): frame k+3 is I2 of iteration k+1.  A model that can
-            # (RIFE) has the encoder and the coarse flow of every frame up to three ahead started on the prefetch stream, as
-            # the sequential driver does, and is told the next iterations' frames and timesteps: it computes iterations k and
-            # k+1 in one stacked pass when there is no cut on k+1's right (RIFE._drba_pair)
-            look = (inp(k + 3), _tools.calc_t(k + 1, times, mapper))
-            if prefetch is not None:
-                far = min(k + 2 + depth, b + 1, n - 1)  # last frame this shard may name: iteration b - 1 reads frame b + 1
-                if intake[0] is None and getattr(model, "intake_stream", None) is not None and I2.is_cuda:
-                    intake[0] = model.intake_stream(I2.device)
-                    if intake[0] is not None:
-                        intake[0].wait_stream(torch.cuda.current_stream(I2.device))  # frames made on the caller's stream so far
-                for j in range(k + 3, far + 1):
-                    if j not in prefetched:
-                        prefetched.add(j)
-                        take_in(j)
-                # the following iterations of this shard, as far as they are DRBA steps too (no cut up to the last frame named)
-                entries = []
-                for j in range(k + 3, far + 1):  # entry: iteration j - 2, whose I2 is frame j
-                    if cut(j - 1):
-                        break
-                    entries += [inp(j), _tools.calc_t(j - 2, times, mapper)]
-                if len(entries) >= 4:
-                    look = tuple(entries)
-            res, reuse = model.inference_ts_drba(I0, I1, I2, ts, reuse, linear=True, lookahead=look)
-        else:
-            res, reuse = model.inference_ts_drba(I0, I1, I2, ts, reuse, linear=True)
-        emit(res)
-        cut_left = cut_right
-        cache.pop(k, None)
-
-    # ---- tail (last rank only): infer.py:158-169, idx == n-2
-    if rank == world - 1 and n >= 2:
-        ts = _tools.calc_t(n - 2, times, mapper)
-        emit(list(model.inference_ts(inp(n - 2), inp(n - 1), ts[ts <= 1])) + [inp(n - 1) for _ in ts[ts > 1] - 1])
+    # ---- the head (rank 0), loop iterations [a, b) and the tail (last rank): the sequential loop over the frames up to b + 1,
+    # the I2 of iteration b - 1.  (announce_ungrouped: a shard has always named the following iterations to a prefetching
+    # model with GROUP = 1 too, where the sequential driver names one; such a model reads the first entry alone.  Kept.)
+    hi = min(b + 1, n - 1)
+    driver.run(model, lambda k: frames[k] if k <= hi else None, pair, a, to_inp=lambda raw: to_inp(raw, dst_size), emit=emit,
+               cuts=cuts, ts_of=lambda idx: _tools.calc_t(idx, times, mapper), state=(cut_left, reuse), head=head, tail=tail,
+               announce_ungrouped=True)
     return out
 
 

@@ -38,13 +38,18 @@ def _sharded_vs_sequential(model, frames, dst_fps, times, scdet, world, dev, max
         assert len(mine) == sum(counts[rank]), (rank, len(mine), counts[rank])  # what StreamedGather sizes its rounds by
         parts += mine
     torch.cuda.synchronize()
-    assert len(parts) == len(io.written)
+    _assert_same_frames(parts, io.written, max_lsb, max_frac)
+
+
+def _assert_same_frames(parts, written, max_lsb=1, max_frac=1e-4):
+    assert len(parts) == len(written)
     worst, differing = 0, 0
-    for a, b in zip(parts, io.written):
+    for a, b in zip(parts, written):
         d = np.abs(a.astype(np.int16) - b.astype(np.int16))
         worst, differing = max(worst, int(d.max())), differing + int((d > 0).sum())
     total = sum(a.size for a in parts)
-    # same kernels on the same inputs; only the atomic arrival order inside the splats differs between the runs
+    # same kernels on the same inputs (the splats are a sorted gather: no float atomics, no arrival order); the runs differ in
+    # which steps share a stacked pass and in where a shard's first `reuse` is made (warm_reuse)
     assert worst <= max_lsb and differing / total < max_frac, (worst, differing / total)
 
 
@@ -62,5 +67,32 @@ def test_gmfss_union_world2_sequential_ranks_equal_sequential_driver(hip_backend
     frames = synth.make_clip(7, 128, 256, seed=32)
     model = hip_backend.make_gmfss_union(synth.gmfss_union_state_dicts(seed=0), 1.0)
     # the soft splats' exp(10 tanh) weights and the swap masks are discontinuous decisions: a last-bit difference in a
-    # splat sum (atomic arrival order) can move a small patch by up to 5e-2 (gpu_checks.check_gmfss_union) = 13 LSB
+    # splat sum can move a small patch by up to 5e-2 (gpu_checks.check_gmfss_union) = 13 LSB
     _sharded_vs_sequential(model, frames, 60.0, -1, False, 2, hip_backend.dev, max_lsb=13, max_frac=1e-3)
+
+
+def test_rife_world1_shard_takes_the_sequential_drivers_path(hip_backend):
+    """interpolate_shard(rank 0, world 1) is interpolate_stream's loop over the same frames: the model's path counters (groups
+    formed and staged, collects, single steps, encoder / pair-flow prefetch hits and misses) move by the same amounts."""
+    frames = synth.make_clip(12, 256, 448, seed=31)
+    model = hip_backend.make_rife(synth.ifnet_state_dict(seed=0), 1.0)
+    to_inp, to_out = _hooks(hip_backend.dev)
+
+    def sequential():
+        io = ListIO(frames, 24.0)
+        drv.interpolate_stream(model, io, 48.0, times=2, enable_scdet=False, to_inp=to_inp, to_out=to_out)
+        torch.cuda.synchronize()
+        model.reset_stream_state()
+        return io.written, dict(model.stats)
+
+    _, s0 = sequential()  # every shape is tuned before the counted runs
+    written, s1 = sequential()
+    mine = parallel.interpolate_shard(model, frames, 24.0, 48.0, 0, 1, times=2, enable_scdet=False, to_inp=to_inp, to_out=to_out)
+    torch.cuda.synchronize()
+    s2 = dict(model.stats)
+    model.reset_stream_state()
+    seq, shard = {k: s1[k] - s0[k] for k in s1}, {k: s2[k] - s1[k] for k in s2}
+    print("sequential", seq, "shard", shard)
+    assert shard == seq
+    assert seq["groups_formed"] > 0 and seq["encoder_prefetch_hits"] > 0  # (the counters counted something)
+    _assert_same_frames(mine, written)
