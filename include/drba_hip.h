@@ -32,7 +32,9 @@ extern "C" {
 #define DRBA_EUNSUPPORTED (-2) /* shape/config outside what the kernels were built for */
 #define DRBA_ELAUNCH (-3)  /* hipGetLastError() reported a launch failure */
 
-/* ABI version.  9: drba_conv3x3_shuffle (a 3x3 convolution storing through PixelShuffle(2): GridNet's tail); drba_quad_interleave / drba_softsplat_index / drba_softsplat_gather_quad (drba_softsplat in pieces: the interleaved copy of a feature tensor kept by the caller).  8: configuration ids appended behind every earlier id of drba_conv3x3 (three, family 4: the waves of a workgroup split rows and
+/* ABI version.  10: drba_ssim3d / drba_ssim3d_ws_floats (ssim_matlab at full size, fp64 accumulation) and drba_frame_error_u8 /
+ * drba_frame_error_f32 / drba_frame_error_ws_floats (exact frame differences): additions only, no earlier entry changes.
+ * 9: drba_conv3x3_shuffle (a 3x3 convolution storing through PixelShuffle(2): GridNet's tail); drba_quad_interleave / drba_softsplat_index / drba_softsplat_gather_quad (drba_softsplat in pieces: the interleaved copy of a feature tensor kept by the caller).  8: configuration ids appended behind every earlier id of drba_conv3x3 (three, family 4: the waves of a workgroup split rows and
  * cout tiles) and drba_deconv4x4s2 (four: rows and couts split across the waves, both row phases per work item); drba_status_word / drba_status_clear (the always-on, synchronisation-free overflow report of kernel family 4); the
  * *_pack entry points of family 4 refuse (DRBA_EUNSUPPORTED) a weight the two-term fp16 form cannot hold (|w| >= 65504 or non-finite).
  * 7: drba_rife_splat_ws_floats -- the workspace of drba_flow_reverse / drba_drm_rife_linear(_batch) grew by a reach map in
@@ -47,7 +49,7 @@ extern "C" {
  * workspace that must be ZERO on entry (they leave it zero on return: self-cleaning accumulator) instead of clearing it
  * themselves; batched stage entry points added; drba_conv3x3_cfg_family added and configuration ids 19 (LDS-DMA, 32
  * channels) / 20 (K split across waves) behind drba_conv3x3; the allocation exception above.  1: the first release. */
-#define DRBA_ABI_VERSION 9  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
+#define DRBA_ABI_VERSION 10  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
 int drba_abi_version(void);
 const char *drba_error_string(int code);
 /* ABI 6, debug: with the range check on, every entry point that ran a kernel of family 4 (two fp16 terms per operand:
@@ -207,6 +209,33 @@ int drba_to_out(const float *in, uint8_t *out_hwc, int Hin, int Win, int Hout, i
 /* ---- scene-cut metric: tools.py:27-30 + pytorch_msssim/__init__.py:83-136 (ssim_matlab)
  * x1, x2: [1,3,32,32] thumbnails (already resized); out: 1 float on device. */
 int drba_ssim3d_32(const float *x1, const float *x2, float *out, void *stream);
+
+/* ---- picture metrics on finished frames (ABI 10; metrics.hip) ---------------------------------------------------------
+ * drba_ssim3d replaces: models/pytorch_msssim/__init__.py:83-136 (ssim_matlab) at full size, the figure the RIFE family's
+ * benchmarks report: the mean over all 3*H*W voxels of the SSIM map of N image pairs, window 11 (sigma 1.5, built as for
+ * drba_ssim3d_32) along x, y AND the channel axis, replicate padding 5 on all three, C1 = (0.01 L)^2, C2 = (0.03 L)^2.
+ * dtype 0: img1 / img2 are fp32 planar [N,3,H,W]; dtype 1: uint8 [N,H,W,3] (what drba_to_out writes), scaled by 1/255 as they
+ * are read.  val_range > 0 is L; val_range = 0 infers L per item from img1 by the reference's rule (max > 128 ? 255 : 1, minus
+ * (min < -0.5 ? -1 : 0)) in a pre-pass on the device.  out: N doubles (8-byte aligned).  ws: drba_ssim3d_ws_floats(N, H, W)
+ * floats, 8-byte aligned, any content.
+ * The value is that of the DEFINITION, not of the reference's fp32 evaluation of it: the blurs are accumulated in fp64, where
+ * blur(a a) - blur(a)^2 does not cancel on flat areas (the fp32 form is off by up to 1.4e-3 there; drba_ssim3d_32 keeps the fp32
+ * form because the scene decision must match the reference's).  Identical images give exactly 1.  Tile sums are added in a fixed
+ * order in fp64, no floating-point atomics: the same bits on every run, and for an item alone or inside a batch.
+ * H or W < 11: DRBA_EUNSUPPORTED (the reference shrinks its window and the output there). */
+size_t drba_ssim3d_ws_floats(int N, int H, int W);
+int drba_ssim3d(const void *img1, const void *img2, double *out, float *ws, int N, int H, int W, int dtype, double val_range,
+                void *stream);
+/* Exact differences of N pairs of n_per_item elements, item k at element k * n_per_item of a and b (no alignment is asked of
+ * either: the byte kernel reads 16 bytes per load between the unaligned ends).  out, per item, 4 x 8 bytes (8-byte aligned):
+ *   _u8 : sum d^2, sum |d|, max |d|, number of d != 0 -- unsigned long long, integer accumulation;
+ *   _f32: sum d^2, sum |d|, max |d| over the FINITE differences as doubles (fp64 accumulation in a fixed order), then the number
+ *         of non-finite differences as an unsigned long long.
+ * ws: drba_frame_error_ws_floats(N, n_per_item) floats, 8-byte aligned, any content. */
+size_t drba_frame_error_ws_floats(int N, size_t n_per_item);
+int drba_frame_error_u8(const uint8_t *a, const uint8_t *b, unsigned long long *out, float *ws, int N, size_t n_per_item,
+                        void *stream);
+int drba_frame_error_f32(const float *a, const float *b, double *out, float *ws, int N, size_t n_per_item, void *stream);
 
 /* ---- convolutions (models/rife_426_heavy/IFNet_HDv3.py:11-16, :28-47, :50-59, :65-82) ------
  * fp32 implicit GEMM on v_mfma_f32_16x16x4_f32.  Weights must be pre-packed by the matching
