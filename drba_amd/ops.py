@@ -5,6 +5,7 @@ takes CUDA tensors, hands raw pointers to libdrba_hip.so on torch's current stre
 returns freshly allocated output tensors.  No arithmetic happens in torch.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -469,13 +470,18 @@ def to_out(x, src_size, rgb=False):
     return out
 
 
-def ssim_thumb32(x1, x2):
-    """check_scene's metric: 32x32 bilinear thumbnails -> 3-D gaussian SSIM.  Returns a Python float
-    (one D2H read: the driver branches on it, exactly like the reference's `if check_scene(...)`)."""
+def _ssim_thumb32_enqueue(x1, x2):
+    """The two thumbnails and the SSIM kernel on the current stream -> the device tensor [1] the value lands in."""
     a, b = resize_bilinear(x1, (32, 32)), resize_bilinear(x2, (32, 32))
     out = torch.empty(1, dtype=torch.float32, device=a.device)
     _lib.check(_lib.load().drba_ssim3d_32(_p(a), _p(b), _p(out), _stream()), "drba_ssim3d_32")
-    return float(out.item())
+    return out
+
+
+def ssim_thumb32(x1, x2):
+    """check_scene's metric: 32x32 bilinear thumbnails -> 3-D gaussian SSIM.  Returns a Python float
+    (one D2H read: the driver branches on it, exactly like the reference's `if check_scene(...)`)."""
+    return float(_ssim_thumb32_enqueue(x1, x2).item())
 
 
 def ssim_thumb32_async(x1, x2):
@@ -483,13 +489,11 @@ def ssim_thumb32_async(x1, x2):
     pair when the second frame is READ -- three iterations before it branches on it -- and reads the value after
     event.synchronize(): by then the two small kernels have long run, and the host no longer drains the whole queue of
     synthesis kernels once per source frame to learn one float."""
-    a, b = resize_bilinear(x1, (32, 32)), resize_bilinear(x2, (32, 32))
-    out = torch.empty(1, dtype=torch.float32, device=a.device)
-    _lib.check(_lib.load().drba_ssim3d_32(_p(a), _p(b), _p(out), _stream()), "drba_ssim3d_32")
+    out = _ssim_thumb32_enqueue(x1, x2)
     host = torch.empty(1, dtype=torch.float32, pin_memory=True)
     host.copy_(out, non_blocking=True)
     ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream(a.device))
+    ev.record(torch.cuda.current_stream(out.device))
     return host, ev
 
 
@@ -522,19 +526,24 @@ def two_term_ok(w):
     return bool(torch.isfinite(w).all()) and (w.numel() == 0 or float(w.abs().max()) < 65504.0)
 
 
+def _two_term(forced, weights_ok=True):
+    """Kernel family 4 (two fp16 terms per operand) or a 24-bit form, wherever a kernel exists in both: a forced value (the
+    *_TWO_TERM switches: tests, A/B) wins, otherwise family 4 must be allowed (read at every call: set_precision) and able to hold
+    the weights (two_term_ok)."""
+    return bool(forced) if forced is not None else (4 in CONV_FAMILIES and bool(weights_ok))
+
+
 def _families(layer_ok=True):
     """The kernel families a layer may use: CONV_FAMILIES, without family 4 for a layer whose weights it cannot hold."""
     return CONV_FAMILIES if layer_ok else CONV_FAMILIES - {4}
 
 
-def _candidates(lib, stride, families, cin, cout, deconv=False):
-    """The configuration ids a tuner may time for a cin -> cout layer: built for `stride` (None for the transposed convolution,
-    whose ids carry none), of one of `families`, and able to run the layer (packed_floats 0: the configuration cannot)."""
-    if deconv:
-        n, family, packed = lib.drba_deconv4x4_num_cfgs(), lib.drba_deconv4x4_cfg_family, lib.drba_deconv4x4_packed_floats
-    else:
-        n, family, packed = lib.drba_conv3x3_num_cfgs(), lib.drba_conv3x3_cfg_family, lib.drba_conv3x3_packed_floats
-    return [c for c in range(n) if (stride is None or lib.drba_conv3x3_cfg_stride(c) == stride)
+def _candidates(lib, kind, stride, families, cin, cout):
+    """The configuration ids a tuner may time for a cin -> cout layer of `kind` ("conv3x3" / "deconv4x4"): built for `stride` (None
+    for the transposed convolution, whose ids carry none), of one of `families`, and able to run the layer (packed_floats 0: the
+    configuration cannot)."""
+    num, family, packed = (getattr(lib, f"drba_{kind}_{what}") for what in ("num_cfgs", "cfg_family", "packed_floats"))
+    return [c for c in range(num()) if (stride is None or lib.drba_conv3x3_cfg_stride(c) == stride)
             and family(c) in families and packed(cin, cout, c) > 0]
 
 
@@ -642,69 +651,121 @@ def conv_state_reset():
     _lib.check(_lib.load().drba_conv_state_reset(_stream()), "drba_conv_state_reset")
 
 
-class Conv3x3:
+def _pack_once(nfloats, pack, what, device):
+    """The "pack on first use" step of every weight holder: `nfloats` host floats filled by `pack(dst)` (a *_pack entry point), then
+    moved to `device`.  The holder keeps the result."""
+    buf = torch.empty(nfloats, dtype=torch.float32)
+    _lib.check(pack(C.c_void_p(buf.data_ptr())), what)
+    return buf.to(device)
+
+
+def _prune(packed, keep):
+    """Drop the packings of the losing candidates: a tuner's warm launches pack the weights for every configuration it times."""
+    for c in [c for c in packed if c not in keep]:
+        del packed[c]
+
+
+class _ConvLayer:
+    """What Conv3x3 and Deconv4x4 share: the weights packed per kernel configuration on first use and the choice of that
+    configuration (forced, tuned, or the library's cost model).  KIND names the entry points (drba_<KIND>_pack, ...).  A layer
+    adds, for an [n, cin, h, w] input: _tune_key, _tune_stride, _pick_cfg, _out_hw / _out_shape and
+    _work(cfg, n, h, w) -> (FLOP, the trace label's key) of its one launch."""
+
+    def __init__(self, weight, bias, device, cfg, pre_slope):
+        self.force_cfg = cfg  # tests only: pin a kernel configuration
+        self.pre_slope = None if pre_slope is None else float(pre_slope)
+        self.w_host = weight.detach().float().cpu().contiguous()
+        self.two_term_ok = two_term_ok(self.w_host)  # False: family 4 is not offered to this layer
+        self.device = device
+        self.bias = None if bias is None else bias.detach().float().to(device).contiguous()
+        self._packed, self._keep = {}, set()
+
+    def _pack(self, cfg):
+        if cfg not in self._packed:
+            lib = _lib.load()
+            n = getattr(lib, f"drba_{self.KIND}_packed_floats")(self.cin, self.cout, cfg)
+            self._packed[cfg] = _pack_once(n, lambda dst: getattr(lib, f"drba_{self.KIND}_pack")(
+                C.c_void_p(self.w_host.data_ptr()), dst, self.cin, self.cout, cfg), f"drba_{self.KIND}_pack", self.device)
+        return self._packed[cfg]
+
+    def _known_cfg(self, n, h, w):
+        """The configuration a call on an [n, cin, h, w] input runs with, without tuning anything: the forced one, the tuner's
+        winner (None: not tuned yet) or the cost model's pick."""
+        if self.force_cfg is not None:
+            return self.force_cfg
+        if AUTOTUNE:
+            return _tuned_get(self._tune_key(n, h, w), _families(self.two_term_ok))
+        return self._pick_cfg(h, w)
+
+    def _choose_cfg(self, x, run):
+        """The configuration for this call on `x`; with the tuner on, the first call for a shape times `run(cfg)` for every candidate."""
+        n, _, h, w = x.shape
+        if self.force_cfg is not None:
+            cfg = self.force_cfg
+        elif AUTOTUNE and x.is_cuda:
+            fam = _families(self.two_term_ok)
+            cands = _candidates(_lib.load(), self.KIND, self._tune_stride(), fam, self.cin, self.cout)
+            cfg = _tune(self._tune_key(n, h, w), cands, run, families=fam, persist=True, device=x.device.index)
+            self._keep.add(cfg)  # a layer can have one winner per batch size (block0: N=1 in calc_flow, N=2 stacked)
+            _prune(self._packed, self._keep)
+        else:
+            cfg = self._pick_cfg(h, w)
+        _lib.check(min(cfg, 0), f"drba_{self.KIND}_pick_cfg")
+        return cfg
+
+
+class Conv3x3(_ConvLayer):
     """One 3x3 conv layer (pad 1) with fused epilogue; weights are packed per kernel config on first use."""
 
+    KIND = "conv3x3"
     ACTS = {None: 0, False: 0, "none": 0, True: 1, "lrelu": 1, "prelu": 2, "relu": 3, "tanh10": 4}
 
     def __init__(self, weight, bias, stride=1, act=True, beta=None, device=None, cfg=None, pre_slope=None,
                  post_slope=0.0):
         """act: True/'lrelu' LeakyReLU(0.2), 'prelu' (post_slope), 'relu', 'tanh10', None.  pre_slope: a float applies
         PReLU with that shared slope to the input inside the loader."""
-        self.force_cfg = cfg  # tests only: pin a kernel configuration
-        self.pre_slope = None if pre_slope is None else float(pre_slope)
-        self.post_slope = float(post_slope)
-        self.w_host = weight.detach().float().cpu().contiguous()
+        super().__init__(weight, bias, device, cfg, pre_slope)
         self.cout, self.cin = self.w_host.shape[:2]
-        self.two_term_ok = two_term_ok(self.w_host)  # False: family 4 is not offered to this layer
-        self.device = device
-        self.bias = None if bias is None else bias.detach().float().to(device).contiguous()
+        self.post_slope = float(post_slope)
         self.beta = None if beta is None else beta.detach().float().reshape(-1).to(device).contiguous()
         self.stride, self.act = int(stride), self.ACTS[act]
-        self._packed, self._keep = {}, set()
 
-    def _pack(self, cfg):
-        if cfg not in self._packed:
-            lib = _lib.load()
-            n = lib.drba_conv3x3_packed_floats(self.cin, self.cout, cfg)
-            buf = torch.empty(n, dtype=torch.float32)
-            _lib.check(lib.drba_conv3x3_pack(C.c_void_p(self.w_host.data_ptr()), C.c_void_p(buf.data_ptr()), self.cin,
-                                             self.cout, cfg), "drba_conv3x3_pack")
-            self._packed[cfg] = buf.to(self.device)
-        return self._packed[cfg]
+    def _out_hw(self, h, w):
+        return (h - 1) // self.stride + 1, (w - 1) // self.stride + 1
+
+    def _out_shape(self, n, h, w):
+        return (n, self.cout, *self._out_hw(h, w))
+
+    def _tune_key(self, n, h, w):
+        return ("conv3x3", n, self.cin, self.cout, h, w, self.stride)
+
+    def _tune_stride(self):
+        return self.stride
+
+    def _pick_cfg(self, h, w):
+        return _lib.load().drba_conv3x3_pick_cfg(self.cin, self.cout, *self._out_hw(h, w), self.stride)
+
+    def _work(self, cfg, n, h, w):
+        ho, wo = self._out_hw(h, w)
+        return 2.0 * self.cout * self.cin * 9 * ho * wo * n, (cfg, self.cin, self.cout, ho, wo, self.stride, n)
 
     def __call__(self, x, residual=None, out=None, residual2=None):
         x = _f32(x)
         n, cin, h, w = x.shape
         assert cin == self.cin, (cin, self.cin)
-        ho, wo = (h - 1) // self.stride + 1, (w - 1) // self.stride + 1
         lib = _lib.load()
         if out is None:
-            out = torch.empty((n, self.cout, ho, wo), dtype=torch.float32, device=x.device)
+            out = torch.empty(self._out_shape(n, h, w), dtype=torch.float32, device=x.device)
         if self.beta is not None:
             assert residual is not None
         res = None if residual is None else _f32(residual)
         res2 = None if residual2 is None else _f32(residual2)
         pre, ps = (0, 0.0) if self.pre_slope is None else (1, self.pre_slope)
-        if self.force_cfg is not None:
-            cfg = self.force_cfg
-        elif AUTOTUNE and x.is_cuda:
-            fam = _families(self.two_term_ok)
-            cands = _candidates(lib, self.stride, fam, self.cin, self.cout)
-            cfg = _tune(("conv3x3", n, cin, self.cout, h, w, self.stride), cands, lambda c: lib.drba_conv3x3(
-                _p(x), _p(self._pack(c)), _p(self.bias), _p(self.beta), _p(res), _p(res2), _p(out), n, cin, h, w,
-                self.cout, self.stride, self.act, self.post_slope, pre, ps, c, _stream()), families=fam, persist=True, device=x.device.index)
-            self._keep.add(cfg)  # a layer can have one winner per batch size (block0: N=1 in calc_flow, N=2 stacked)
-            for c in [c for c in self._packed if c not in self._keep]:
-                del self._packed[c]  # drop the packings of the losing candidates
-        else:
-            cfg = lib.drba_conv3x3_pick_cfg(self.cin, self.cout, ho, wo, self.stride)
-        _lib.check(min(cfg, 0), "drba_conv3x3_pick_cfg")
-        wp = self._pack(cfg)
-        key = (cfg, cin, self.cout, ho, wo, self.stride, n)
-        _lib.check(_timed("conv3x3", key, 2.0 * self.cout * cin * 9 * ho * wo * n, "flop", lambda: lib.drba_conv3x3(
-            _p(x), _p(wp), _p(self.bias), _p(self.beta), _p(res), _p(res2), _p(out), n, cin, h, w, self.cout,
-            self.stride, self.act, self.post_slope, pre, ps, cfg, _stream())), "drba_conv3x3")
+        run = lambda c: lib.drba_conv3x3(_p(x), _p(self._pack(c)), _p(self.bias), _p(self.beta), _p(res), _p(res2), _p(out), n, cin, h, w,  # noqa: E731
+                                         self.cout, self.stride, self.act, self.post_slope, pre, ps, c, _stream())
+        cfg = self._choose_cfg(x, run)
+        work, key = self._work(cfg, n, h, w)
+        _lib.check(_timed("conv3x3", key, work, "flop", lambda: run(cfg)), "drba_conv3x3")
         return out
 
 
@@ -720,46 +781,50 @@ def conv3x3_shuffle(layer, x):
     if not usable:
         return pixel_shuffle2(layer(x))
     out = torch.empty((n, layer.cout // 4, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
-    cands = _candidates(lib, 1, (4,), layer.cin, layer.cout)
+    cands = _candidates(lib, "conv3x3", 1, (4,), layer.cin, layer.cout)
     run = lambda c: lib.drba_conv3x3_shuffle(_p(x), _p(layer._pack(c)), _p(layer.bias), _p(out), n, cin, h, w, layer.cout,  # noqa: E731
                                              layer.act, layer.post_slope, c, _stream())
     try:
         cfg = _tune(("conv3x3_shuffle", n, cin, layer.cout, h, w), cands, run, families=(4,), persist=True, device=x.device.index)
     except NoKernelConfig:  # remembered per shape (in the process and in the store): the next call comes here without a launch
-        for c in [c for c in layer._packed if c not in layer._keep]:
-            del layer._packed[c]
+        _prune(layer._packed, layer._keep)
         return pixel_shuffle2(layer(x))
     layer._keep.add(cfg)
-    for c in [c for c in layer._packed if c not in layer._keep]:
-        del layer._packed[c]  # drop the packings of the losing candidates
+    _prune(layer._packed, layer._keep)
     _lib.check(_timed("conv3x3", (cfg, cin, layer.cout, h, w, 1, n, "ps"), 2.0 * layer.cout * cin * 9 * h * w * n, "flop", lambda: run(cfg)),
                "drba_conv3x3_shuffle")
     return out
 
 
-class Deconv4x4:
+class Deconv4x4(_ConvLayer):
     """ConvTranspose2d(k=4, s=2, p=1), optionally fused with PixelShuffle(2)."""
 
-    def __init__(self, weight, bias, pixel_shuffle=False, device=None, cfg=None, pre_slope=None):
-        self.force_cfg = cfg  # tests only
-        self.pre_slope = None if pre_slope is None else float(pre_slope)
-        self.w_host = weight.detach().float().cpu().contiguous()  # [Cin, Cout, 4, 4]
-        self.cin, self.cout = self.w_host.shape[:2]
-        self.two_term_ok = two_term_ok(self.w_host)
-        self.device = device
-        self.bias = None if bias is None else bias.detach().float().to(device).contiguous()
-        self.ps = 1 if pixel_shuffle else 0
-        self._packed, self._keep = {}, set()
+    KIND = "deconv4x4"
 
-    def _pack(self, cfg):
-        if cfg not in self._packed:
-            lib = _lib.load()
-            n = lib.drba_deconv4x4_packed_floats(self.cin, self.cout, cfg)
-            buf = torch.empty(n, dtype=torch.float32)
-            _lib.check(lib.drba_deconv4x4_pack(C.c_void_p(self.w_host.data_ptr()), C.c_void_p(buf.data_ptr()), self.cin,
-                                               self.cout, cfg), "drba_deconv4x4_pack")
-            self._packed[cfg] = buf.to(self.device)
-        return self._packed[cfg]
+    def __init__(self, weight, bias, pixel_shuffle=False, device=None, cfg=None, pre_slope=None):
+        super().__init__(weight, bias, device, cfg, pre_slope)
+        self.cin, self.cout = self.w_host.shape[:2]  # [Cin, Cout, 4, 4]
+        self.ps = 1 if pixel_shuffle else 0
+
+    def _out_hw(self, h, w):
+        """What a next layer of a chain would read: the transposed convolution's own output.  With PixelShuffle the layer's output is
+        _out_shape's [n, cout/4, 4h, 4w], which this does NOT describe: such a layer is valid as the LAST layer of a chain only."""
+        return 2 * h, 2 * w
+
+    def _out_shape(self, n, h, w):
+        return (n, self.cout // 4, 4 * h, 4 * w) if self.ps else (n, self.cout, 2 * h, 2 * w)
+
+    def _tune_key(self, n, h, w):
+        return ("deconv4x4", n, self.cin, self.cout, h, w, self.ps)
+
+    def _tune_stride(self):
+        return None  # (the transposed convolution's configuration ids carry no stride)
+
+    def _pick_cfg(self, h, w):
+        return _lib.load().drba_deconv4x4_pick_cfg(self.cin, self.cout, h, w)
+
+    def _work(self, cfg, n, h, w):
+        return 2.0 * self.cout * self.cin * 16 * h * w * n, (cfg, self.cin, self.cout, h, w, 2, n)
 
     def __call__(self, x, out=None):
         x = _f32(x)
@@ -767,65 +832,27 @@ class Deconv4x4:
         assert cin == self.cin
         lib = _lib.load()
         if out is None:
-            shape = (n, self.cout // 4, 4 * h, 4 * w) if self.ps else (n, self.cout, 2 * h, 2 * w)
-            out = torch.empty(shape, dtype=torch.float32, device=x.device)
+            out = torch.empty(self._out_shape(n, h, w), dtype=torch.float32, device=x.device)
         pre, ps_ = (0, 0.0) if self.pre_slope is None else (1, self.pre_slope)
-        if self.force_cfg is not None:
-            cfg = self.force_cfg
-        elif AUTOTUNE and x.is_cuda:
-            fam = _families(self.two_term_ok)
-            cands = _candidates(lib, None, fam, cin, self.cout, deconv=True)
-            cfg = _tune(("deconv4x4", n, cin, self.cout, h, w, self.ps), cands,
-                        lambda c: lib.drba_deconv4x4s2(_p(x), _p(self._pack(c)), _p(self.bias), _p(out), n, cin, h, w,
-                                                       self.cout, self.ps, pre, ps_, c, _stream()), families=fam, persist=True, device=x.device.index)
-            self._keep.add(cfg)
-            for c in [c for c in self._packed if c not in self._keep]:
-                del self._packed[c]
-        else:
-            cfg = lib.drba_deconv4x4_pick_cfg(self.cin, self.cout, h, w)
-        _lib.check(min(cfg, 0), "drba_deconv4x4_pick_cfg")
-        wp = self._pack(cfg)
-        key = (cfg, cin, self.cout, h, w, 2, n)
-        _lib.check(_timed("deconv4x4", key, 2.0 * self.cout * cin * 16 * h * w * n, "flop", lambda: lib.drba_deconv4x4s2(
-            _p(x), _p(wp), _p(self.bias), _p(out), n, cin, h, w, self.cout, self.ps, pre, ps_, cfg, _stream())),
-            "drba_deconv4x4s2")
+        run = lambda c: lib.drba_deconv4x4s2(_p(x), _p(self._pack(c)), _p(self.bias), _p(out), n, cin, h, w,  # noqa: E731
+                                             self.cout, self.ps, pre, ps_, c, _stream())
+        cfg = self._choose_cfg(x, run)
+        work, key = self._work(cfg, n, h, w)
+        _lib.check(_timed("deconv4x4", key, work, "flop", lambda: run(cfg)), "drba_deconv4x4s2")
         return out
-
-
-CHAIN_SPLIT_BYTES = 0  # > 0: a chain whose widest intermediate tensor exceeds this runs as two half-batches (A/B switch, see ConvChain.__call__)
 
 
 class ConvChain:
     """A fixed sequence of Conv3x3 / Deconv4x4 layers (`residual=True` entries are ResConv layers adding their own
     input) issued by ONE library call (drba_conv_chain): the host cost of an IFBlock core drops from eleven
-    Python/ctypes round trips to one.  The first call for a shape runs layer by layer (that is where the autotuner
-    picks each layer's configuration); so does any call while bench.py's per-launch timing is armed."""
+    Python/ctypes round trips to one.  A call for a shape some layer has no configuration for yet runs layer by layer (that
+    is where the autotuner picks each layer's configuration), and so does every call of a chain that has a layer the
+    library call cannot express (a pre_slope / post_slope) and every call on CPU tensors.  A traced call (bench.py's
+    per-launch timing) is the same library call: the library records one launch per layer and the plan carries their tags."""
 
     def __init__(self, layers):
         self.layers = [(l, bool(r)) for l, r in layers]  # (layer, residual)
         self._plans = {}
-
-    def _widest(self, n, h, w):
-        """Bytes of the largest tensor between two layers of the chain at this input size."""
-        best, hh, ww = 0, h, w
-        for layer, _ in self.layers:
-            if isinstance(layer, Deconv4x4):
-                hh, ww = 2 * hh, 2 * ww
-            else:
-                hh, ww = (hh - 1) // layer.stride + 1, (ww - 1) // layer.stride + 1
-            if layer is not self.layers[-1][0]:
-                best = max(best, 4 * n * layer.cout * hh * ww)
-        return best
-
-    def _out_shape(self, n, h, w):
-        hh, ww = h, w
-        for layer, _ in self.layers:
-            if isinstance(layer, Deconv4x4):
-                hh, ww = 2 * hh, 2 * ww
-            else:
-                hh, ww = (hh - 1) // layer.stride + 1, (ww - 1) // layer.stride + 1
-        last = self.layers[-1][0]
-        return (n, last.cout // 4, 2 * hh, 2 * ww) if (isinstance(last, Deconv4x4) and last.ps) else (n, last.cout, hh, ww)
 
     def _eager(self, x, out=None):
         for i, (layer, res) in enumerate(self.layers):
@@ -834,44 +861,28 @@ class ConvChain:
         return x
 
     def _plan(self, n, h, w, device):
-        lib = _lib.load()
         descs = (_lib.ConvLayer * len(self.layers))()
         keep, sizes, tags = [], [], []
-        hh, ww = h, w
-        for i, (layer, res) in enumerate(self.layers):
-            d = descs[i]
-            if isinstance(layer, Deconv4x4):
-                key = ("deconv4x4", n, layer.cin, layer.cout, hh, ww, layer.ps)
-                cfg = layer.force_cfg if layer.force_cfg is not None else (
-                    _tuned_get(key, _families(layer.two_term_ok)) if AUTOTUNE else lib.drba_deconv4x4_pick_cfg(layer.cin, layer.cout, hh, ww))
-                if cfg is None or layer.pre_slope is not None:
-                    return None
+        for d, (layer, res) in zip(descs, self.layers):
+            deconv = isinstance(layer, Deconv4x4)
+            cfg = layer._known_cfg(n, h, w)
+            if cfg is None or layer.pre_slope is not None or (not deconv and layer.post_slope != 0.0):
+                return None
+            if deconv:
                 d.deconv, d.pixel_shuffle, d.stride, d.act, d.residual = 1, layer.ps, 1, 0, 0
-                tags.append((2.0 * layer.cout * layer.cin * 16 * hh * ww * n, "flop",
-                             f"deconv4x4 {(cfg, layer.cin, layer.cout, hh, ww, 2, n)}"))
-                hh, ww = 2 * hh, 2 * ww
-                sizes.append(n * (layer.cout // 4 if layer.ps else layer.cout) * hh * ww * (4 if layer.ps else 1))
             else:
-                key = ("conv3x3", n, layer.cin, layer.cout, hh, ww, layer.stride)
-                ho, wo = (hh - 1) // layer.stride + 1, (ww - 1) // layer.stride + 1
-                cfg = layer.force_cfg if layer.force_cfg is not None else (
-                    _tuned_get(key, _families(layer.two_term_ok)) if AUTOTUNE else lib.drba_conv3x3_pick_cfg(layer.cin, layer.cout, ho, wo, layer.stride))
-                if cfg is None or layer.pre_slope is not None or layer.post_slope != 0.0:
-                    return None
                 d.deconv, d.pixel_shuffle, d.stride, d.act, d.residual = 0, 0, layer.stride, layer.act, 1 if res else 0
                 d.beta = 0 if layer.beta is None else layer.beta.data_ptr()
-                hh, ww = ho, wo
-                sizes.append(n * layer.cout * hh * ww)
-                tags.append((2.0 * layer.cout * layer.cin * 9 * ho * wo * n, "flop",
-                             f"conv3x3 {(cfg, layer.cin, layer.cout, ho, wo, layer.stride, n)}"))
+            work, key = layer._work(cfg, n, h, w)
+            tags.append((work, "flop", f"{layer.KIND} {key}"))
+            out_shape = layer._out_shape(n, h, w)
+            sizes.append(math.prod(out_shape))  # (the scratch buffers hold the widest tensor between two layers)
+            h, w = layer._out_hw(h, w)
             layer._keep.add(cfg)
             wp = layer._pack(cfg)
             keep.append(wp)
             d.packed_w, d.bias = wp.data_ptr(), (0 if layer.bias is None else layer.bias.data_ptr())
             d.cin, d.cout, d.cfg = layer.cin, layer.cout, cfg
-        last = self.layers[-1][0]
-        out_shape = ((n, last.cout // 4, 2 * hh, 2 * ww) if (isinstance(last, Deconv4x4) and last.ps)
-                     else (n, last.cout, hh, ww))
         return {"descs": descs, "keep": keep, "scratch": max(sizes[:-1]) if len(sizes) > 1 else 0, "out_shape": out_shape,
                 "bufs": {}, "tags": tags}
 
@@ -879,14 +890,6 @@ class ConvChain:
         """out (optional): a contiguous float32 destination of the chain's output shape (a batch slice of a larger tensor)."""
         x = _f32(x)
         n, _, h, w = x.shape
-        if out is None and CHAIN_SPLIT_BYTES and n >= 2 and n % 2 == 0 and x.is_cuda and self._widest(n, h, w) > CHAIN_SPLIT_BYTES:
-            # the chain as two half-batches back to back (A/B: tools/ab_bench.py --chain-split MB): layer l + 1 reads what layer l
-            # wrote; with the batch's widest tensor above the threshold input + output of a layer exceed the 256 MB Infinity Cache
-            # and every layer streams from HBM, the halves fit
-            whole = torch.empty(self._out_shape(n, h, w), dtype=torch.float32, device=x.device)
-            self(x[:n // 2], out=whole[:n // 2])
-            self(x[n // 2:], out=whole[n // 2:])
-            return whole
         key = (n, h, w)
         plan = self._plans.get(key)
         if plan is None and key in self._plans:  # known: not chainable
@@ -937,18 +940,14 @@ def head_fused(img, layers, holder, planar=True):
         return None
     lib = _lib.load()
     # the two-term fp16 form of the kernel (head_fused16.hip) when the conv tuner may use kernel family 4, else fp32 MFMA
-    two = HEAD_TWO_TERM if HEAD_TWO_TERM is not None else (4 in CONV_FAMILIES and all(l.two_term_ok for l in layers))
+    two = _two_term(HEAD_TWO_TERM, all(l.two_term_ok for l in layers))
     attr, sfx = ("_fused_pack16", "16") if two else ("_fused_pack", "")
     launch = getattr(lib, "drba_head_fused" + sfx)
     pk = getattr(holder, attr, None)
     if pk is None:
-        c0, c1, c2, c3 = layers
-        buf = torch.empty(getattr(lib, f"drba_head_fused{sfx}_packed_floats")(), dtype=torch.float32)
-        hb = [l.bias.detach().float().cpu().contiguous() for l in layers]
-        _lib.check(getattr(lib, f"drba_head_fused{sfx}_pack")(*(C.c_void_p(t.data_ptr()) for t in (c0.w_host, hb[0], c1.w_host, hb[1],
-                                                                                                    c2.w_host, hb[2], c3.w_host, hb[3])),
-                                                              C.c_void_p(buf.data_ptr())), f"drba_head_fused{sfx}_pack")
-        pk = buf.to(img.device)
+        src = [t for l in layers for t in (l.w_host, l.bias.detach().float().cpu().contiguous())]  # weight, bias of each layer in turn
+        pk = _pack_once(getattr(lib, f"drba_head_fused{sfx}_packed_floats")(), lambda dst: getattr(lib, f"drba_head_fused{sfx}_pack")(
+            *(C.c_void_p(t.data_ptr()) for t in src), dst), f"drba_head_fused{sfx}_pack", img.device)
         setattr(holder, attr, pk)
     f = torch.empty((1, 16, H, W), dtype=torch.float32, device=img.device) if planar else None
     fp = torch.empty((8, H, W, 2), dtype=torch.float32, device=img.device)
@@ -1052,6 +1051,28 @@ def rgbx(img):
     return x[0]
 
 
+def _stage_geometry(H, W, scale):
+    """-> (h, w, pts): a stage's resolution at 1/scale and the full-resolution sample points its gather reads per channel
+    (every pixel at scale <= 2, a 2x2 footprint per output point above)."""
+    h, w = int(np.floor(H * (1.0 / scale))), int(np.floor(W * (1.0 / scale)))
+    return h, w, (H * W if scale <= 2 else 4 * h * w)
+
+
+def _timestep(t):
+    """A timestep argument -> (its [1,1,H,W] map or None, its scalar value)."""
+    return (_f32(t), 0.0) if torch.is_tensor(t) else (None, float(t))
+
+
+# algorithmic bytes of a stage input per item: every full-resolution sample point read once per full-resolution channel (the 9
+# channels of mask / feat and flow come from the low-resolution head output) + the output written (+ the folded flow)
+def _input_bytes(nch, has_flow, pts, h, w):
+    return 4.0 * ((nch - (9 if has_flow else 0)) * pts + nch * h * w)
+
+
+def _input_lds_bytes(pts, h, w, fold):
+    return 4.0 * (43 * pts + 52 * h * w + (4 * pts if fold else 0))
+
+
 def ifblock_input(img0, img1, f0, f1, timestep, flow, tmp_prev, prev_scale, scale, out=None):
     """Stage input at 1/scale resolution (52 ch with flow, 39 without).  `timestep`: float or [1,1,H,W] map;
     `tmp_prev`: the previous stage's [1,13,hp,wp] head output (mask/feat are its x prev_scale upsample).
@@ -1059,8 +1080,8 @@ def ifblock_input(img0, img1, f0, f1, timestep, flow, tmp_prev, prev_scale, scal
     img0, img1 = _f32(img0), _f32(img1)
     (f0, f0p), (f1, f1p) = _feat2(f0, f1, flow is not None)
     _, _, H, W = img0.shape
-    h, w = int(np.floor(H * (1.0 / scale))), int(np.floor(W * (1.0 / scale)))
-    tmap, tsc = (None, float(timestep)) if not torch.is_tensor(timestep) else (_f32(timestep), 0.0)
+    h, w, pts = _stage_geometry(H, W, scale)
+    tmap, tsc = _timestep(timestep)
     nch = 52 if flow is not None else 39
     if out is None:
         out = torch.empty((1, nch, h, w), dtype=torch.float32, device=img0.device)
@@ -1071,10 +1092,8 @@ def ifblock_input(img0, img1, f0, f1, timestep, flow, tmp_prev, prev_scale, scal
     if flow is not None:
         flow, tmp_prev = _f32(flow), _f32(tmp_prev)
         hp, wp, ps = tmp_prev.shape[2], tmp_prev.shape[3], float(prev_scale)
-    # algorithmic bytes: every full-resolution sample point read once per full-res channel + the output written
-    pts = H * W if scale <= 2 else 4 * h * w
-    nbytes = 4.0 * ((nch - (9 if flow is not None else 0)) * pts + nch * h * w)
     lib = _lib.load()
+    nbytes = _input_bytes(nch, flow is not None, pts, h, w)
     _lib.check(_timed("ifblock_input", (nch, H, W, h, w), nbytes, "byte", lambda: lib.drba_ifblock_input(
         _p(img0), _p(img1), _p(f0), _p(f1), _p(f0p), _p(f1p), _p(tmap), tsc, _p(flow), _p(tmp_prev), hp, wp, ps, _p(out), H, W, h, w,
         float(scale), _stream())), "drba_ifblock_input")
@@ -1091,8 +1110,8 @@ def ifblock_input_lds(img0, img1, f0, f1, timestep, flow, tmp_prev, prev_scale, 
     img0, img1, tmp_prev = _f32(img0), _f32(img1), _f32(tmp_prev)
     (f0, f0p), (f1, f1p) = _feat2(f0, f1)
     _, _, H, W = img0.shape
-    h, w = int(np.floor(H * (1.0 / scale))), int(np.floor(W * (1.0 / scale)))
-    tmap, tsc = (None, float(timestep)) if not torch.is_tensor(timestep) else (_f32(timestep), 0.0)
+    h, w, pts = _stage_geometry(H, W, scale)
+    tmap, tsc = _timestep(timestep)
     if out is None:
         out = torch.empty((1, 52, h, w), dtype=torch.float32, device=img0.device)
     elif tuple(out.shape) != (1, 52, h, w) or not out.is_contiguous():
@@ -1100,9 +1119,8 @@ def ifblock_input_lds(img0, img1, f0, f1, timestep, flow, tmp_prev, prev_scale, 
     flow = None if flow is None else _f32(flow)
     flow_out = torch.empty((1, 4, H, W), dtype=torch.float32, device=img0.device) if fold else None
     hp, wp = tmp_prev.shape[2], tmp_prev.shape[3]
-    pts = H * W if scale <= 2 else 4 * h * w
-    nbytes = 4.0 * (43 * pts + 52 * h * w + (4 * pts if fold else 0))
     lib = _lib.load()
+    nbytes = _input_lds_bytes(pts, h, w, fold)
     _lib.check(_timed("ifblock_input_lds" + ("+fold" if fold else ""), (52, H, W, h, w), nbytes, "byte", lambda: lib.drba_ifblock_input_lds(
         _p(img0), _p(img1), _p(f0), _p(f1), _p(f0p), _p(f1p), _p(tmap), tsc, _p(flow), _p(tmp_prev), hp, wp, float(prev_scale),
         _p(flow_out), _p(out), H, W, h, w, float(scale), _stream())), "drba_ifblock_input_lds")
@@ -1133,6 +1151,46 @@ def _flow_terms(terms, B):
     return ft, ts
 
 
+def _frames(items, what):
+    """The two float32 frames of every item of a batched launch -> [(img0, img1), ...]."""
+    if len(items) > _lib.MAX_STAGE_ITEMS:
+        raise _lib.DrbaHipError(f"{what}: at most {_lib.MAX_STAGE_ITEMS} items per launch")
+    return [(_f32(it[0]), _f32(it[1])) for it in items]
+
+
+def _x4_pair(i0, i1):
+    """The [H,W,4] copies of an item's two frames where BOTH carry one (the kernels take an item's two pointers or neither), else None."""
+    x0, x1 = _x4_of(i0), _x4_of(i1)
+    return None if x0 is None or x1 is None else (x0, x1)
+
+
+def _stage_items(imgs, x4, out, tmp_prev, terms=(), feats=None, timesteps=None, flows=None, flow_out=None):
+    """The drba_stage_item_t[B] of a batched launch -> (the ctypes array, the tensors its pointers need alive beyond the caller's own).
+    imgs: _frames(items); x4: per item its _x4_pair or None (WHICH items get their copies is the caller's rule); out, tmp_prev,
+    flow_out and every tensor of `terms` are stacked [B, ...] tensors and item k takes their slice k; feats: _feat_batch(items);
+    timesteps: per item a float or a map; flows: per item the running flow or None."""
+    arr, keep = (_lib.StageItem * len(imgs))(), []
+    for k, (i0, i1) in enumerate(imgs):
+        a = arr[k]
+        a.img0, a.img1, a.out = i0.data_ptr(), i1.data_ptr(), out[k].data_ptr()
+        a.tmp_prev = None if tmp_prev is None else tmp_prev[k].data_ptr()
+        a.flow_out = None if flow_out is None else flow_out[k].data_ptr()
+        keep += [i0, i1]
+        if feats is not None:
+            (f0, f0p), (f1, f1p) = feats[k]
+            tmap, tsc = _timestep(timesteps[k])
+            fl = None if (flows is None or flows[k] is None) else _f32(flows[k])
+            a.f0, a.f1, a.f0_pair, a.f1_pair = _ptr(f0), _ptr(f1), _ptr(f0p), _ptr(f1p)
+            a.timestep_map, a.timestep_scalar, a.flow = _ptr(tmap), tsc, _ptr(fl)
+            keep += [f0, f1, f0p, f1p, tmap, fl]
+        if x4[k] is not None:
+            a.img0_x4, a.img1_x4 = x4[k][0].data_ptr(), x4[k][1].data_ptr()
+            keep += x4[k]
+        for i, t in enumerate(terms):
+            a.term[i] = t[k].data_ptr()
+    return arr, keep
+
+
 def stage_inputs(items, flows, tmp_prev, prev_scale, scale, out, fold=False, lds=True, terms=None):
     """The stage input of EVERY item of a stage in one launch (drba_ifblock_input[_lds]_batch).
     items: [(img0, img1, timestep, f0, f1), ...]; flows: per-item running flow (or None); tmp_prev: the previous stage's
@@ -1142,51 +1200,29 @@ def stage_inputs(items, flows, tmp_prev, prev_scale, scale, out, fold=False, lds
     of the earlier stages, oldest first; the kernel forms flow = sum(terms) + up(tmp_prev[:, :4]) * prev_scale at its sample
     points (drba_ifblock_input_lazy_batch) and nothing but `out` is written."""
     B = len(items)
-    if B > _lib.MAX_STAGE_ITEMS:
-        raise _lib.DrbaHipError(f"stage_inputs: at most {_lib.MAX_STAGE_ITEMS} items per launch")
+    imgs = _frames(items, "stage_inputs")
     lazy = terms is not None
     if lazy and (flows is not None or fold or not lds):
         raise _lib.DrbaHipError("stage_inputs: terms replace flows / fold (lds path only)")
     ft, tts = _flow_terms(terms, B) if lazy else (None, [])
-    img0 = _f32(items[0][0])
-    _, _, H, W = img0.shape
-    h, w = int(np.floor(H * (1.0 / scale))), int(np.floor(W * (1.0 / scale)))
+    _, _, H, W = imgs[0][0].shape
+    h, w, pts = _stage_geometry(H, W, scale)
     has_flow = flows is not None and flows[0] is not None
     nch = 52 if (has_flow or lds) else 39
     if tuple(out.shape) != (B, nch, h, w) or not out.is_contiguous():
         raise _lib.DrbaHipError(f"stage_inputs: out must be a contiguous [{B},{nch},{h},{w}] tensor")
     if lazy and tmp_prev is None:
         raise _lib.DrbaHipError("stage_inputs: terms need tmp_prev (the newest head output)")
-    flow_out = torch.empty((B, 4, H, W), dtype=torch.float32, device=img0.device) if fold else None
+    flow_out = torch.empty((B, 4, H, W), dtype=torch.float32, device=imgs[0][0].device) if fold else None
     hp = wp = 0
     ps = 1.0
     if tmp_prev is not None:
         tmp_prev = _f32(tmp_prev)
         hp, wp, ps = tmp_prev.shape[2], tmp_prev.shape[3], float(prev_scale)
-    arr = (_lib.StageItem * B)()
-    keep = []
-    feats = _feat_batch(items, lds or has_flow)
-    for k, (i0, i1, t, _f0, _f1) in enumerate(items):
-        i0, i1 = _f32(i0), _f32(i1)
-        (f0, f0p), (f1, f1p) = feats[k]
-        tmap, tsc = (None, float(t)) if not torch.is_tensor(t) else (_f32(t), 0.0)
-        fl = None if (flows is None or flows[k] is None) else _f32(flows[k])
-        keep += [i0, i1, f0, f1, tmap, fl, f0p, f1p]
-        a = arr[k]
-        a.img0, a.img1, a.f0, a.f1, a.f0_pair, a.f1_pair = _ptr(i0), _ptr(i1), _ptr(f0), _ptr(f1), _ptr(f0p), _ptr(f1p)
-        a.timestep_map, a.timestep_scalar, a.flow = _ptr(tmap), tsc, _ptr(fl)
-        a.tmp_prev = None if tmp_prev is None else tmp_prev[k].data_ptr()
-        a.flow_out = None if flow_out is None else flow_out[k].data_ptr()
-        a.out = out[k].data_ptr()
-        if lds and scale <= 2:  # the [H,W,4] copies where both frames carry one -- at scale <= 2 only: the sparser sample points of the
-            # coarser stages put a quad of lanes on more cache lines with 16-byte pixels (same box: scale 4 313-318 us against 309-312, scale 8 153 against 148)
-            x0, x1 = _x4_of(i0), _x4_of(i1)
-            if x0 is not None and x1 is not None:
-                keep += [x0, x1]
-                a.img0_x4, a.img1_x4 = _ptr(x0), _ptr(x1)
-        for i, t in enumerate(tts):
-            a.term[i] = t[k].data_ptr()
-    pts = H * W if scale <= 2 else 4 * h * w
+    # the [H,W,4] copies per item, where both of its frames carry one -- on the LDS path at scale <= 2 only: the sparser sample points of the
+    # coarser stages put a quad of lanes on more cache lines with 16-byte pixels (same box: scale 4 313-318 us against 309-312, scale 8 153 against 148)
+    x4 = [_x4_pair(i0, i1) if lds and scale <= 2 else None for i0, i1 in imgs]
+    arr, keep = _stage_items(imgs, x4, out, tmp_prev, tts, _feat_batch(items, lds or has_flow), [it[2] for it in items], flows, flow_out)
     lib = _lib.load()
     if lazy:
         nbytes = B * 4.0 * (39 * pts + 52 * h * w)  # no flow read, none written: the terms are a few KB per tile
@@ -1195,13 +1231,11 @@ def stage_inputs(items, flows, tmp_prev, prev_scale, scale, out, fold=False, lds
                                                                     float(scale), _stream())), "drba_ifblock_input_lazy_batch")
         return None
     if lds:
-        nbytes = B * 4.0 * (43 * pts + 52 * h * w + (4 * pts if fold else 0))
-        _lib.check(_timed("ifblock_input_lds" + ("+fold" if fold else ""), (52, H, W, h, w, B), nbytes, "byte",
+        _lib.check(_timed("ifblock_input_lds" + ("+fold" if fold else ""), (52, H, W, h, w, B), B * _input_lds_bytes(pts, h, w, fold), "byte",
                           lambda: lib.drba_ifblock_input_lds_batch(C.cast(arr, C.c_void_p), B, hp, wp, ps, H, W, h, w, float(scale),
                                                                    _stream())), "drba_ifblock_input_lds_batch")
     else:
-        nbytes = B * 4.0 * ((nch - (9 if has_flow else 0)) * pts + nch * h * w)
-        _lib.check(_timed("ifblock_input", (nch, H, W, h, w, B), nbytes, "byte",
+        _lib.check(_timed("ifblock_input", (nch, H, W, h, w, B), B * _input_bytes(nch, has_flow, pts, h, w), "byte",
                           lambda: lib.drba_ifblock_input_batch(C.cast(arr, C.c_void_p), B, hp, wp, ps, H, W, h, w, float(scale),
                                                                _stream())), "drba_ifblock_input_batch")
     return [flow_out[k:k + 1] for k in range(B)] if fold else None
@@ -1212,7 +1246,7 @@ STAGE_CONV_TWO_TERM = None  # None: follow CONV_FAMILIES (family 4 allowed -> st
 
 
 def _stage_conv_two_term(conv):
-    return bool(STAGE_CONV_TWO_TERM if STAGE_CONV_TWO_TERM is not None else (4 in CONV_FAMILIES and conv.two_term_ok))
+    return _two_term(STAGE_CONV_TWO_TERM, conv.two_term_ok)
 
 
 STAGE_CONV_S2 = True  # the scale-2 stage fused the same way (stage_conv16_s2; A/B: tools/ab_bench.py --no-stage-conv-s2)
@@ -1227,7 +1261,7 @@ def stage_conv0_ok(conv, H, W, scale, prev_scale, items=None):
     lib = _lib.load()
     if float(scale) == 2.0:
         if not (STAGE_CONV_S2 and _stage_conv_two_term(conv) and items is not None
-                and all(_x4_of(_f32(it[0])) is not None and _x4_of(_f32(it[1])) is not None for it in items)):
+                and all(_x4_pair(_f32(it[0]), _f32(it[1])) is not None for it in items)):
             return False
     if _stage_conv_two_term(conv):
         return bool(lib.drba_stage_conv16_supported(H, W, float(scale), float(prev_scale), conv.cout))
@@ -1244,27 +1278,24 @@ def stage_conv0(items, flows, tmp_prev, prev_scale, conv, fold=False, terms=None
     if lazy and (flows is not None or fold):
         raise _lib.DrbaHipError("stage_conv0: terms replace flows / fold")
     ft, tts = _flow_terms(terms, B) if lazy else (None, [])
-    if B > _lib.MAX_STAGE_ITEMS:
-        raise _lib.DrbaHipError(f"stage_conv0: at most {_lib.MAX_STAGE_ITEMS} items per launch")
-    img0 = _f32(items[0][0])
-    _, _, H, W = img0.shape
+    imgs = _frames(items, "stage_conv0")
+    _, _, H, W = imgs[0][0].shape
     sc = int(scale)
-    if sc not in (1, 2) or (sc == 2 and not (lazy and _stage_conv_two_term(conv))):
+    two = _stage_conv_two_term(conv)
+    if sc not in (1, 2) or (sc == 2 and not (lazy and two)):
         raise _lib.DrbaHipError("stage_conv0: scale 1, or scale 2 with the flow as terms in the two-term form")
     hs, ws_ = H // sc, W // sc                              # the stage's resolution
     Ho, Wo = (hs - 1) // 2 + 1, (ws_ - 1) // 2 + 1          # the convolution's output
-    dev = img0.device
-    two = _stage_conv_two_term(conv)
+    dev = imgs[0][0].device
     attr = "_stage_pack16" if two else "_stage_pack"
     if getattr(conv, attr, None) is None:
-        lib = _lib.load()
+        lib, w_host = _lib.load(), C.c_void_p(conv.w_host.data_ptr())
         if two:
-            buf = torch.empty(lib.drba_stage_conv16_packed_floats(conv.cout), dtype=torch.float32)
-            _lib.check(lib.drba_stage_conv16_pack(C.c_void_p(conv.w_host.data_ptr()), conv.cout, C.c_void_p(buf.data_ptr())), "drba_stage_conv16_pack")
+            packed = _pack_once(lib.drba_stage_conv16_packed_floats(conv.cout), lambda dst: lib.drba_stage_conv16_pack(w_host, conv.cout, dst),
+                                "drba_stage_conv16_pack", dev)
         else:
-            buf = torch.empty(lib.drba_stage_conv0_packed_floats(), dtype=torch.float32)
-            _lib.check(lib.drba_stage_conv0_pack(C.c_void_p(conv.w_host.data_ptr()), C.c_void_p(buf.data_ptr())), "drba_stage_conv0_pack")
-        setattr(conv, attr, buf.to(dev))
+            packed = _pack_once(lib.drba_stage_conv0_packed_floats(), lambda dst: lib.drba_stage_conv0_pack(w_host, dst), "drba_stage_conv0_pack", dev)
+        setattr(conv, attr, packed)
     packed = getattr(conv, attr)
     tmp_prev = _f32(tmp_prev)
     hp, wp = tmp_prev.shape[2], tmp_prev.shape[3]
@@ -1273,25 +1304,10 @@ def stage_conv0(items, flows, tmp_prev, prev_scale, conv, fold=False, terms=None
     elif tuple(out.shape) != (B, conv.cout, Ho, Wo) or not out.is_contiguous() or out.dtype != torch.float32:  # a batch slice of a wider tensor
         raise _lib.DrbaHipError(f"stage_conv0: out must be a contiguous float32 [{B},{conv.cout},{Ho},{Wo}] tensor")
     flow_out = torch.empty((B, 4, H, W), dtype=torch.float32, device=dev) if fold else None
-    arr = (_lib.StageItem * B)()
-    keep = []
-    feats = _feat_batch(items)
-    x4_all = all(_x4_of(_f32(it[0])) is not None and _x4_of(_f32(it[1])) is not None for it in items)  # (the items of a launch agree)
-    for k, (i0, i1, t, _f0, _f1) in enumerate(items):
-        i0, i1 = _f32(i0), _f32(i1)
-        (f0, f0p), (f1, f1p) = feats[k]
-        tmap, tsc = (None, float(t)) if not torch.is_tensor(t) else (_f32(t), 0.0)
-        fl = None if (flows is None or flows[k] is None) else _f32(flows[k])
-        keep += [i0, i1, f0, f1, tmap, fl, f0p, f1p]
-        a = arr[k]
-        a.img0, a.img1, a.f0, a.f1, a.f0_pair, a.f1_pair = _ptr(i0), _ptr(i1), _ptr(f0), _ptr(f1), _ptr(f0p), _ptr(f1p)
-        a.timestep_map, a.timestep_scalar, a.flow = _ptr(tmap), tsc, _ptr(fl)
-        a.tmp_prev, a.flow_out, a.out = tmp_prev[k].data_ptr(), (None if flow_out is None else flow_out[k].data_ptr()), out[k].data_ptr()
-        for i, t in enumerate(tts):
-            a.term[i] = t[k].data_ptr()
-        x0, x1 = (_x4_of(i0), _x4_of(i1)) if x4_all else (None, None)
-        keep += [x0, x1]
-        a.img0_x4, a.img1_x4 = _ptr(x0), _ptr(x1)
+    x4 = [_x4_pair(i0, i1) for i0, i1 in imgs]
+    if any(p is None for p in x4):  # the [H,W,4] copies for all items or for none (the items of a launch agree)
+        x4 = [None] * B
+    arr, keep = _stage_items(imgs, x4, out, tmp_prev, tts, _feat_batch(items), [it[2] for it in items], flows, flow_out)
     # algorithmic bytes: 43 source channels read once per full-resolution point, the 16-channel quarter-size output (and the
     # folded flow) written; 2 * 16 * 52 * 9 FLOP per output pixel ride along (50 us per 1080p sample at the fp32 MFMA peak,
     # 53 us of HBM time: the byte roofline is the binding one)
@@ -1344,27 +1360,13 @@ def warp_blend_lazy(items, terms, tmp_last, scale):
     """The final frames of every item of a stage in one launch, the flow before the last stage given as terms
     (drba_warp_blend_lazy_batch): items = [(img0, img1, ...), ...], tmp_last [B,13,h,w] -> list of [1,3,H,W]."""
     B = len(items)
-    if B > _lib.MAX_STAGE_ITEMS:
-        raise _lib.DrbaHipError(f"warp_blend_lazy: at most {_lib.MAX_STAGE_ITEMS} items per launch")
+    imgs = _frames(items, "warp_blend_lazy")
     tmp_last = _f32(tmp_last)
     ft, tts = _flow_terms(terms, B)
-    img0 = _f32(items[0][0])
-    _, _, H, W = img0.shape
+    _, _, H, W = imgs[0][0].shape
     h, w = tmp_last.shape[2], tmp_last.shape[3]
-    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=img0.device)
-    arr = (_lib.StageItem * B)()
-    keep = []
-    for k, it in enumerate(items):
-        i0, i1 = _f32(it[0]), _f32(it[1])
-        keep += [i0, i1]
-        a = arr[k]
-        a.img0, a.img1, a.tmp_prev, a.out = _ptr(i0), _ptr(i1), tmp_last[k].data_ptr(), out[k].data_ptr()
-        x0, x1 = _x4_of(i0), _x4_of(i1)
-        if x0 is not None and x1 is not None:
-            keep += [x0, x1]
-            a.img0_x4, a.img1_x4 = _ptr(x0), _ptr(x1)
-        for i, t in enumerate(tts):
-            a.term[i] = t[k].data_ptr()
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=imgs[0][0].device)
+    arr, keep = _stage_items(imgs, [_x4_pair(i0, i1) for i0, i1 in imgs], out, tmp_last, tts)  # the [H,W,4] copies per item
     nbytes = B * 4.0 * ((6 + 3) * H * W + 5 * h * w)
     _lib.check(_timed("warp_blend_lazy", (H, W, B), nbytes, "byte", lambda: _lib.load().drba_warp_blend_lazy_batch(
         C.cast(arr, C.c_void_p), B, C.cast(C.pointer(ft), C.c_void_p), h, w, float(scale), H, W, _stream())), "drba_warp_blend_lazy_batch")
@@ -1531,28 +1533,28 @@ class LinearSplit:
     @property
     def terms(self):
         """Resolved at every call (ops.set_precision may change the family set while the object lives)."""
-        return self._terms_arg if self._terms_arg is not None else (2 if (4 in CONV_FAMILIES and self.two_term_ok) else 3)
+        return self._terms_arg if self._terms_arg is not None else (2 if _two_term(None, self.two_term_ok) else 3)
 
     @property
     def packed(self):
         t = self.terms
         if t not in self._packs:  # packed once per term count on first use
             lib = _lib.load()
-            buf = torch.empty(lib.drba_linear_split_packed_floats(self.k, self.n, t), dtype=torch.float32)
-            _lib.check(lib.drba_linear_split_pack(C.c_void_p(self._w.data_ptr()), C.c_void_p(buf.data_ptr()), self.k, self.n, t),
-                       "drba_linear_split_pack")
-            self._packs[t] = buf.to(self._device)
+            self._packs[t] = _pack_once(lib.drba_linear_split_packed_floats(self.k, self.n, t), lambda dst: lib.drba_linear_split_pack(
+                C.c_void_p(self._w.data_ptr()), dst, self.k, self.n, t), "drba_linear_split_pack", self._device)
         return self._packs[t]
 
-    def _rows(self, x):
-        assert x.shape[-1] == self.k
-        x2 = x.reshape(-1, self.k)  # a view for contiguous inputs and for row-strided column slices
+    @staticmethod
+    def _rows(x, k):
+        """x [..., k] as rows [M, k] the kernels can read in place (`k`: the layer's input width, or one part of it in cat)."""
+        assert x.shape[-1] == k
+        x2 = x.reshape(-1, k)  # a view for contiguous inputs and for row-strided column slices
         if x2.dtype != torch.float32 or x2.stride(1) != 1 or x2.stride(0) % 4 or x2.data_ptr() % 16 or not x2.is_cuda:
             x2 = _f32(x2)
         return x2
 
     def __call__(self, x):
-        lead, x2 = x.shape[:-1], self._rows(x)
+        lead, x2 = x.shape[:-1], self._rows(x, self.k)
         m = x2.shape[0]
         out = torch.empty((m, self.n), dtype=torch.float32, device=x2.device)
         _lib.check(_timed("linear_split", (m, self.k, self.n, self.gelu), 2.0 * m * self.k * self.n, "flop", lambda: _lib.load().drba_linear_split(
@@ -1565,11 +1567,7 @@ class LinearSplit:
         k1, k2 = x1.shape[-1], x2.shape[-1]
         assert k1 + k2 == self.k and x1.shape[:-1] == x2.shape[:-1]
         lead = x1.shape[:-1]
-        self.k, keep = k1, self.k
-        a = self._rows(x1)
-        self.k = k2
-        b = self._rows(x2)
-        self.k = keep
+        a, b = self._rows(x1, k1), self._rows(x2, k2)
         m = a.shape[0]
         out = torch.empty((m, self.n), dtype=torch.float32, device=a.device)
         _lib.check(_timed("linear_split_cat", (m, k1, k2, self.n, self.gelu), 2.0 * m * (k1 + k2) * self.n, "flop",
@@ -1580,7 +1578,7 @@ class LinearSplit:
     def layernorm(self, x, ln_w, ln_b, residual=None, eps=1e-5):
         """residual + LayerNorm(self(x)) * ln_w + ln_b in the GEMM's epilogue (128 output features only)."""
         assert self.n == 128 and not self.gelu
-        lead, x2 = x.shape[:-1], self._rows(x)
+        lead, x2 = x.shape[:-1], self._rows(x, self.k)
         m = x2.shape[0]
         res = None if residual is None else _f32(residual)
         out = torch.empty((m, 128), dtype=torch.float32, device=x2.device)
@@ -1600,8 +1598,7 @@ def window_attention(q, k, v, h, w, splits, shift, scale, terms=None):
     q, k, v may be last-dim slices of a wider tensor (a fused projection output): only the row stride is used.
     terms: 3 = fp32 MFMA, 2 = the GEMM operands as two fp16 terms (default: 2 when kernel family 4 is allowed)."""
     if terms is None:
-        two = ATTN_TWO_TERM if ATTN_TWO_TERM is not None else (4 in CONV_FAMILIES)
-        terms = 2 if two else 3
+        terms = 2 if _two_term(ATTN_TWO_TERM) else 3
     b, n, c = q.shape
     assert n == h * w and k.shape == q.shape and v.shape == q.shape
 
