@@ -32,7 +32,7 @@ _f = C.c_float
 _d = C.c_double
 _z = C.c_size_t
 
-# name -> (restype, argtypes); mirrors include/drba_hip.h one to one
+
 class ConvLayer(C.Structure):
     """drba_conv_layer_t (include/drba_hip.h)."""
     _fields_ = [("packed_w", C.c_void_p), ("bias", C.c_void_p), ("beta", C.c_void_p), ("cin", C.c_int), ("cout", C.c_int),
@@ -40,6 +40,7 @@ class ConvLayer(C.Structure):
                 ("pixel_shuffle", C.c_int)]
 
 
+# name -> (restype, argtypes); mirrors include/drba_hip.h one to one
 SIGNATURES = {
     "drba_abi_version": (_i, []),
     "drba_rife_splat_ws_floats": (_z, [_i, _i, _i, _i]),

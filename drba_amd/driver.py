@@ -5,6 +5,7 @@ import contextlib
 
 import torch
 
+from drba_amd import handoff
 from drba_amd.models.utils import tools as _tools
 
 
@@ -104,16 +105,9 @@ def run(model, get, pair, first, to_inp, emit, cuts, ts_of, state=(False, None),
         with contextlib.nullcontext() if intake is None else torch.cuda.stream(intake):
             x = to_inp(raw)
             if intake is not None and x.is_cuda:
-                # the frame is consumed on the caller's stream later (the model's kernels, to_out of a pass-through copy): that
-                # stream waits for to_inp -- an event wait behind a queue that is far from reaching the frame -- and the
-                # allocator is told about the second stream
-                ev = torch.cuda.Event()
-                ev.record(intake)
-                main.wait_event(ev)
-                x.record_stream(main)
-                x4 = getattr(x, "_drba_x4", None)
-                if x4 is not None:
-                    x4[0].record_stream(main)
+                # the frame is consumed on the caller's stream later (the model's kernels, to_out of a pass-through copy): an
+                # event wait behind a queue that is far from reaching the frame
+                handoff.hand_to(main, x, handoff.event_on(intake))
             cuts.submit(nxt - 1, last, x)  # asked for in this or a later iteration
             if prefetch is not None:
                 prefetch(x)

@@ -8,6 +8,8 @@ two streams fills the chip.  The result is handed to the next call by frame iden
 pattern simply leaves it unused."""
 import torch
 
+from drba_amd import handoff
+
 
 _STREAMS = {}
 
@@ -64,17 +66,6 @@ def shared_stream(device, role):
     return s
 
 
-def _tensors(x):
-    if torch.is_tensor(x):
-        yield x
-    elif isinstance(x, (list, tuple)):
-        for y in x:
-            yield from _tensors(y)
-    elif isinstance(x, dict):
-        for y in x.values():
-            yield from _tensors(y)
-
-
 def split(lookahead):
     """`lookahead` argument of inference_ts_drba: the next frame, or (next frame, timesteps of the next call)."""
     if isinstance(lookahead, (tuple, list)):
@@ -85,36 +76,29 @@ def split(lookahead):
 class Lookahead:
     def __init__(self):
         self.side = None
-        self.pending = None  # (frame a, frame b, result, completion event on the side stream)
+        self.pending = None  # handoff.Ahead: key = (frame a, frame b), event recorded on the side stream
 
     def start(self, a, b, fn, inputs=()):
         """Run fn() on the side stream after everything enqueued so far on the caller's stream; keep its result for
         take(a, b).  `inputs`: further tensors fn reads (their memory must outlive the side-stream work)."""
         if not a.is_cuda:
             return
-        main = torch.cuda.current_stream(a.device)
         if self.side is None:
             self.side = shared_stream(a.device, "side")  # (stream priorities measured: no effect on the step, DESIGN.md)
-        ready = torch.cuda.Event()
-        ready.record(main)
+        main = torch.cuda.current_stream(a.device)
+        ready = handoff.event_on(main)
         with torch.cuda.stream(self.side):
-            self.side.wait_event(ready)
-            for t in _tensors((a, b, inputs)):
-                t.record_stream(self.side)
+            handoff.hand_to(self.side, (a, b, inputs), ready)
             res = fn()
-            done = torch.cuda.Event()
-            done.record(self.side)
-        for t in _tensors(res):
-            t.record_stream(main)  # consumed on the caller's stream by the next step
-            fp = getattr(t, "_drba_pair", None)  # the pair-interleaved copy hung on a feature tensor (ops.pair_interleaved):
-            if fp is not None:                   # allocated on the side / prefetch stream, read by the main stream's gathers
-                fp.record_stream(main)
-        self.pending = (a, b, res, done)
+            self.pending = handoff.Ahead(res, handoff.event_on(self.side), (a, b), None)
+        # the next step consumes the result on the caller's stream: the allocator is told here, so that take() -- in front of
+        # that step's first launch -- only has to wait
+        handoff.hand_to(main, res)
 
     def take(self, a, b):
         """The prefetched result for the pair (a, b), or None.  The caller's stream is made to wait for it."""
-        pend, self.pending = self.pending, None
-        if pend is not None and pend[0] is a and pend[1] is b:
-            torch.cuda.current_stream(a.device).wait_event(pend[3])
-            return pend[2]
-        return None
+        rec, self.pending = self.pending, None
+        if rec is None or rec.key[0] is not a or rec.key[1] is not b:
+            return None
+        handoff.hand_to(torch.cuda.current_stream(a.device), (), rec.event)  # (start() has told the allocator)
+        return rec.value

@@ -3,9 +3,8 @@ union=False): FeatureNet x2, GMFlow both directions, MetricNet (`reuse`), then s
 frames and the 3-level feature pyramid, timestep-map swap masks and GridNet fusion (`inference`)."""
 import torch
 
-from drba_amd import ops as _ops
+from drba_amd import handoff, ops as _ops
 from drba_amd.models.gmflow.gmflow import GMFlow
-from drba_amd.models.lookahead import _tensors
 from drba_amd.models.model_gmfss_union.FeatureNet import FeatureNet
 from drba_amd.models.model_gmfss_union.FusionNet import GridNet
 from drba_amd.models.model_gmfss_union.MetricNet import MetricNet
@@ -52,23 +51,12 @@ class Model:
 
     def _cached(self, frame, attr, key, make):
         """Per-frame cache on the frame tensor, keyed by (this model, key).  The value may have been produced on the
-        lookahead's side stream: the producing event travels with it and the consumer's stream waits on it (a scene cut
-        drops the lookahead RESULT without waiting, but these caches survive), and the allocator is told about the
-        second stream."""
-        key = (id(self), key)
-        c = getattr(frame, attr, None)
-        if c is not None and c[0] == key:
-            if c[2] is not None:
-                cur = torch.cuda.current_stream(frame.device)
-                cur.wait_event(c[2])
-                for t in _tensors(c[1]):
-                    t.record_stream(cur)
-            return c[1]
-        val = make()
-        if frame.is_cuda:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(frame.device))
-            setattr(frame, attr, (key, val, ev))
+        lookahead's side stream (a scene cut drops the lookahead RESULT without waiting, but these caches survive)."""
+        key = (handoff.token_of(self), key)
+        val = handoff.collect(frame, attr, key)
+        if val is None:
+            val = make()
+            handoff.publish(frame, attr, val, key)
         return val
 
     def _features(self, img):

@@ -7,12 +7,11 @@ Everything runs in fp32 (the reference's CPU autocast path is bf16 and deviates 
 its own fp32 evaluation; parity is against the fp32 evaluation).
 """
 import os
-import weakref
 
 import numpy as np
 import torch
 
-from drba_amd import ops as _ops
+from drba_amd import handoff, ops as _ops
 from drba_amd.models.lookahead import Lookahead, shared_stream
 from drba_amd.models.lookahead import split as split_lookahead
 from drba_amd.models.drm import calc_drm_rife
@@ -124,8 +123,7 @@ class RIFE:
         P, todo = [None] * n, []
         for j in range(n):
             a, b = F[j + 1], F[j + 2]
-            c = getattr(b, "_drba_pairflow", None)
-            if c is not None and c[0]() is a and c[3] == id(self):
+            if handoff.peek(b, "_drba_pairflow", handoff.token_of(self), a) is not None:
                 P[j] = self._pair_flow(a, b, None)
             else:
                 todo.append(j)
@@ -158,21 +156,16 @@ class RIFE:
         the result up by frame identity; without a prefetch it encodes in place as before."""
         if not I.is_cuda or getattr(I, "_drba_enc", None) is not None:
             return
-        dev = I.device
-        main = torch.cuda.current_stream(dev)
+        main = torch.cuda.current_stream(I.device)
         if getattr(self, "_enc_stream", None) is None:
-            self._enc_stream = main if self.ENC_ON_MAIN else shared_stream(dev, "prefetch")
-        ready = torch.cuda.Event()
-        ready.record(main)  # the frame was produced (to_inp) on the caller's stream
+            self._enc_stream = main if self.ENC_ON_MAIN else shared_stream(I.device, "prefetch")
+        ready = handoff.event_on(main)  # the frame was produced (to_inp) on the caller's stream
         with torch.cuda.stream(self._enc_stream):
-            self._enc_stream.wait_event(ready)
-            I.record_stream(self._enc_stream)
+            handoff.hand_to(self._enc_stream, I, ready)
             f = self.ifnet.encode(I, planar=False)
             if _ops.PAIR_FEATURES:
                 _ops.pair_interleaved(f)
-            done = torch.cuda.Event()
-            done.record(self._enc_stream)
-        I._drba_enc = (f, done, id(self))
+            handoff.publish(I, "_drba_enc", f, handoff.token_of(self), self._enc_stream)
 
     def prefetch_pair(self, a, b):
         """Optional: calc_flow(a, b) -- block0 on the 1/16-resolution map and the flow reversal, ~25 serial launches -- on
@@ -188,39 +181,22 @@ class RIFE:
         self.prefetch_frame(b)
         with torch.cuda.stream(self._enc_stream):
             res = self.calc_flow(a, b, f0=self._encoded(a), f1=self._encoded(b))
-            done = torch.cuda.Event()
-            done.record(self._enc_stream)
-        # (a weak reference to `a`: a strong one would chain every frame -- with its features -- to its successor for the
-        # length of the clip)
-        b._drba_pairflow = (weakref.ref(a), res, done, id(self))
+            handoff.publish(b, "_drba_pairflow", res, handoff.token_of(self), self._enc_stream, pred=a)
 
     def _pair_flow(self, a, b, fa=None):
         """calc_flow(a, b), from prefetch_pair if it was started there (the consumer's stream waits for it)."""
-        c = getattr(b, "_drba_pairflow", None)
-        if c is not None and c[0]() is a and c[3] == id(self):
-            cur = torch.cuda.current_stream(a.device)
-            cur.wait_event(c[2])
+        res = handoff.collect(b, "_drba_pairflow", handoff.token_of(self), a)
+        if res is not None:
             self._count("pairflow_prefetch_hits")
-            for t in c[1]:
-                t.record_stream(cur)
-                fp = getattr(t, "_drba_pair", None)
-                if fp is not None:
-                    fp.record_stream(cur)
-            return c[1]
+            return res
         return self.calc_flow(a, b, f0=fa)
 
     def _encoded(self, I):
         """encode(I), from prefetch_frame's stream if it was started there (the consumer's stream waits for it)."""
-        c = getattr(I, "_drba_enc", None)
-        if c is not None and c[2] == id(self):
-            cur = torch.cuda.current_stream(I.device)
-            cur.wait_event(c[1])
+        f = handoff.collect(I, "_drba_enc", handoff.token_of(self))
+        if f is not None:
             self._count("encoder_prefetch_hits")
-            c[0].record_stream(cur)
-            fp = getattr(c[0], "_drba_pair", None)
-            if fp is not None:
-                fp.record_stream(cur)
-            return c[0]
+            return f
         self._count("encoder_prefetch_misses")
         return self.ifnet.encode(I, planar=False)  # the pair-interleaved layout only: what the kernels read (ops.head_fused)
 

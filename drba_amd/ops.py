@@ -202,6 +202,19 @@ def softsplat(tenIn, tenFlow, tenMetric, strMode, out=None, keep_quad=False):
     return softsplat_many([tenIn], tenFlow, tenMetric, strMode, None if out is None else [out], keep_quad=keep_quad)[0]
 
 
+def _copy_of(t, attr, versioned=True):
+    """The layout copy kept on tensor `t` as `attr`, or None.  versioned: kept as (copy, t._version), and a tensor written in
+    place since has none (the library's own kernels write through raw pointers without bumping the version: see the callers)."""
+    c = getattr(t, attr, None)
+    if c is None or not versioned:
+        return c
+    return c[0] if c[1] == t._version else None
+
+
+def _set_copy(t, attr, copy, versioned=True):
+    setattr(t, attr, (copy, t._version) if versioned else copy)
+
+
 def quad_interleaved(x):
     """[N,C,H,W] (C >= 16, C % 4 == 0) -> the [N][C/4][H*W][4] copy the feature gathers of the splat read, made once per tensor
     and kept on it (with the tensor's version: a tensor written in place since gets a new copy), or None for other channel
@@ -210,12 +223,12 @@ def quad_interleaved(x):
     n, c, h, w = x.shape
     if c < 16 or c % 4:
         return None
-    q = getattr(x, "_drba_quad", None)
-    if q is None or q[1] != x._version:
+    qt = _copy_of(x, "_drba_quad")
+    if qt is None:
         qt = torch.empty((n, c // 4, h * w, 4), dtype=torch.float32, device=x.device)
         _lib.check(_lib.load().drba_quad_interleave(_p(x), _p(qt), n, c, h, w, _stream()), "drba_quad_interleave")
-        q = x._drba_quad = (qt, x._version)
-    return q[0]
+        _set_copy(x, "_drba_quad", qt)
+    return qt
 
 
 def softsplat_many(inputs, tenFlow, tenMetric, strMode, outs=None, reuse_index=False, keep_quad=False):
@@ -452,7 +465,7 @@ def to_inp(img_u8, dst_size):
     _lib.check(_timed("to_inp", (h, w, ho, wo), 3.0 * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
                       lambda: _lib.load().drba_to_inp_x4(_p(img_u8), _p(out), _p(x4), h, w, ho, wo, sy, sx, _stream())), "drba_to_inp_x4")
     if x4 is not None:
-        out._drba_x4 = (x4, out._version)
+        _set_copy(out, "_drba_x4", x4)
     return out
 
 
@@ -959,7 +972,7 @@ def head_fused(img, layers, holder, planar=True):
     if not planar:
         fp._drba_is_pair = True
         return fp
-    f._drba_pair = fp
+    _set_copy(f, "_drba_pair", fp, versioned=False)
     return f
 
 
@@ -1019,13 +1032,13 @@ def pair_interleaved(f):
     """[1,C,H,W] -> the [C/2,H,W,2] copy the stage-input gathers read; made once per feature tensor and kept on it."""
     if is_pair(f):
         return f
-    fp = getattr(f, "_drba_pair", None)
+    fp = _copy_of(f, "_drba_pair", versioned=False)
     if fp is None:
         n, c, h, w = f.shape
         fp = torch.empty((c // 2, h, w, 2), dtype=torch.float32, device=f.device)
         _lib.check(_timed("pair_interleave", (c, h, w), 8.0 * c * h * w, "byte", lambda: _lib.load().drba_pair_interleave(
             _p(f), _p(fp), c, h, w, _stream())), "drba_pair_interleave")
-        f._drba_pair = fp
+        _set_copy(f, "_drba_pair", fp, versioned=False)
     return fp
 
 
@@ -1036,19 +1049,18 @@ def _x4_of(img):
     """The [H,W,4] copy a frame carries (ops.to_inp writes it with the frame; rgbx() makes it on demand), or None: then the
     kernels read the planes.  A frame that did not come from to_inp (tests, a caller's own tensors) is NOT converted behind the
     caller's back per call -- rgbx(frame) once is the caller's choice."""
-    x = getattr(img, "_drba_x4", None) if IMG_X4 else None
-    return x[0] if x is not None and x[1] == img._version else None  # (a frame written in place since: the copy is stale)
+    return _copy_of(img, "_drba_x4") if IMG_X4 else None
 
 
 def rgbx(img):
     """A frame [1,3,H,W] -> its [H,W,4] copy (c0, c1, c2, 0), made once per tensor (to_inp writes it with the frame) and kept on it."""
-    x = getattr(img, "_drba_x4", None)
-    if x is None or x[1] != img._version:
+    x4 = _copy_of(img, "_drba_x4")
+    if x4 is None:
         _, _, h, w = img.shape
         x4 = torch.empty((h, w, 4), dtype=torch.float32, device=img.device)
         _lib.check(_timed("rgbx", (h, w), 28.0 * h * w, "byte", lambda: _lib.load().drba_rgbx(_p(img), _p(x4), h, w, _stream())), "drba_rgbx")
-        x = img._drba_x4 = (x4, img._version)
-    return x[0]
+        _set_copy(img, "_drba_x4", x4)
+    return x4
 
 
 def _stage_geometry(H, W, scale):

@@ -129,8 +129,8 @@ def test_lookahead_flow_matches_inline(hip_backend, mode):
                 nxt = (nxt, np.array([0.8, 1.2]) if mode == "frame+other ts" else ts)
             o, reuse = m.inference_ts_drba(fr[k], fr[k + 1], fr[k + 2], ts, reuse, True, lookahead=nxt)
             if look and k == 0:
-                assert m._look.pending is not None and m._look.pending[0] is fr[2] and m._look.pending[1] is fr[3]
-                staged = m._look.pending[2][1]
+                assert m._look.pending is not None and m._look.pending.key[0] is fr[2] and m._look.pending.key[1] is fr[3]
+                staged = m._look.pending.value[1]
                 assert (staged is not None) == (mode != "frame")
             outs += o
         torch.cuda.synchronize()
@@ -170,8 +170,8 @@ def test_prefetched_encoder_matches_inline(hip_backend):
             outs += o
         torch.cuda.synchronize()
         if prefetch:
-            assert getattr(frames[3], "_drba_enc", None) is not None and frames[3]._drba_enc[0] is reuse[2]  # f of the last I2
-            assert frames[3]._drba_pairflow[1][1] is reuse[0]  # flow21 of the last call came from prefetch_pair
+            assert getattr(frames[3], "_drba_enc", None) is not None and frames[3]._drba_enc.value is reuse[2]  # f of the last I2
+            assert frames[3]._drba_pairflow.value[1] is reuse[0]  # flow21 of the last call came from prefetch_pair
         return outs, reuse
 
     a, ra = run(True)
@@ -506,6 +506,31 @@ def test_prefetch_does_not_retain_frames(hip_backend):
             gc.collect()
             marks[k] = torch.cuda.memory_allocated(dev)
     assert marks[59] <= marks[19] + (1 << 20), marks  # 40 more steps: not one frame's worth (0.3 MB + 3.1 MB features) each
+
+
+def test_collected_value_is_ordered_behind_its_producer(hip_backend):
+    """handoff.collect makes the consumer's stream wait for the event publish recorded: a value filled on the prefetch
+    stream behind tens of milliseconds of other work reads complete on the default stream, in both layouts (without the wait
+    both sums would be 0: the zeros the tensors start from)."""
+    from drba_amd import handoff, ops
+    from drba_amd.models.lookahead import shared_stream
+    dev = hip_backend.dev
+    side, main = shared_stream(dev, "prefetch"), torch.cuda.current_stream(dev)
+    assert side != main
+    holder = torch.zeros(1, device=dev)
+    x = torch.zeros(1, 16, 64, 64, device=dev)
+    fp = ops.pair_interleaved(x)  # of the zeros
+    assert x._drba_pair is fp
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        torch.cuda._sleep(4_000_000)  # 40 ms of a 100 MHz counter
+        x.fill_(1)
+        fp.fill_(1)
+        handoff.publish(holder, "_drba_test", x, "key", side)
+    got = handoff.collect(holder, "_drba_test", "key")
+    assert got is x
+    assert x.sum().item() == x.numel() and fp.sum().item() == x.numel()
+    torch.cuda.synchronize()
 
 
 def test_gmfss_union_lookahead_matches_inline(hip_backend):
