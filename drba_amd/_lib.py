@@ -79,12 +79,18 @@ SIGNATURES = {
     "drba_to_inp": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _p]),
     "drba_to_inp_x4": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _p]),
     "drba_to_out": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _i, _p]),
+    "drba_u16hwc_to_f32nchw": (_i, [_p, _p, _i, _i, _f, _p]),
+    "drba_f32nchw_to_u16hwc": (_i, [_p, _p, _i, _i, _f, _p]),
+    "drba_to_inp16_x4": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _p]),
+    "drba_to_out16": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _i, _f, _p]),
     "drba_ssim3d_32": (_i, [_p, _p, _p, _p]),
     "drba_ssim3d_ws_floats": (_z, [_i, _i, _i]),
     "drba_ssim3d": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _d, _p]),
     "drba_frame_error_ws_floats": (_z, [_i, _z]),
     "drba_frame_error_u8": (_i, [_p, _p, _p, _p, _i, _z, _p]),
     "drba_frame_error_f32": (_i, [_p, _p, _p, _p, _i, _z, _p]),
+    "drba_frame_error_u16_ws_floats": (_z, [_i, _z]),
+    "drba_frame_error_u16": (_i, [_p, _p, _p, _p, _i, _z, _p]),
     "drba_conv3x3_pick_cfg": (_i, [_i, _i, _i, _i, _i]),
     "drba_conv3x3_num_cfgs": (_i, []),
     "drba_conv3x3_cfg_stride": (_i, [_i]),

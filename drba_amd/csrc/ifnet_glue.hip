@@ -172,6 +172,141 @@ __global__ void __launch_bounds__(256) f32_to_u8_kernel(const float *__restrict_
   }
 }
 
+// ---- 16-bit frames: uint16 HWC with samples in [0, maxval] (1023: 10-bit data, 65535: full range) ------------------------------
+// The way in is the 8-bit one with the divisor exchanged (a true fp32 division, then the same ATen-order lerp).  The way out is
+// NOT the 8-bit one: bytes keep the reference's trunc(x * 255) and its wrap-around because they must equal the reference's; a
+// 16-bit frame has no reference to equal, so it is rounded to nearest even and saturated, NaN -> 0.  v / maxval * maxval lies
+// within 65535 * 2^-23 of v, so an unresized frame comes back bit for bit.
+__device__ __forceinline__ uint32_t round_sat_u16(float scaled, float maxval) {
+  float r = rintf(scaled);  // half to even (torch.round)
+  if (!(r >= 0.f)) r = 0.f;  // negative values and NaN
+  if (r > maxval) r = maxval;
+  return (uint32_t)(int)r;
+}
+
+// ATen takes BOTH taps of an axis whose size does not change from the pixel itself, weights (1, 0) ("scale_factor = 1, simply
+// copy"); lerp_src_aten's (x, x + 1) with the same weights gives the same value for finite data only: 1 * inf + 0 * inf is NaN,
+// and the right neighbour's inf must not reach this pixel.  The frames on the way out may hold anything, so the rule is kept.
+__device__ __forceinline__ Lerp lerp_src_aten_sized(int dst, float scale, int in_size, int out_size) {
+  if (in_size == out_size) {
+    Lerp l;
+    l.i0 = l.i1 = dst;
+    l.w0 = 1.f;
+    l.w1 = 0.f;
+    return l;
+  }
+  return lerp_src_aten(dst, scale, in_size);
+}
+
+__global__ void __launch_bounds__(256) to_inp16_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4,
+                                                       int Hin, int Win, int Hout, int Wout, float sy, float sx, float maxval) {
+  const Tile2D p = tile_pixel(Wout, Hout);
+  if (!p.valid) return;
+  const Lerp ly = lerp_src_aten(p.y, sy, Hin), lx = lerp_src_aten(p.x, sx, Win);
+  const uint16_t *r0 = in + (size_t)ly.i0 * Win * 3, *r1 = in + (size_t)ly.i1 * Win * 3;
+  const size_t P = (size_t)Hout * Wout, o = (size_t)p.y * Wout + p.x;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float a = __fdiv_rn((float)r0[lx.i0 * 3 + c], maxval), b = __fdiv_rn((float)r0[lx.i1 * 3 + c], maxval);
+    const float cc = __fdiv_rn((float)r1[lx.i0 * 3 + c], maxval), d = __fdiv_rn((float)r1[lx.i1 * 3 + c], maxval);
+    const float v = lerp2_aten(ly, lx, a, b, cc, d);
+    out[c * P + o] = v;
+    if (out_x4) out_x4[4 * o + c] = v;
+  }
+  if (out_x4) out_x4[4 * o + 3] = 0.f;
+}
+
+__global__ void __launch_bounds__(256) to_out16_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int Hin, int Win,
+                                                       int Hout, int Wout, float sy, float sx, int rev, float maxval) {
+  const Tile2D p = tile_pixel(Wout, Hout);
+  if (!p.valid) return;
+  const Lerp ly = lerp_src_aten_sized(p.y, sy, Hin, Hout), lx = lerp_src_aten_sized(p.x, sx, Win, Wout);
+  const size_t P = (size_t)Hin * Win;
+  uint16_t *o = out + ((size_t)p.y * Wout + p.x) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float *r0 = in + c * P + (size_t)ly.i0 * Win, *r1 = in + c * P + (size_t)ly.i1 * Win;
+    const float v = __fmul_rn(lerp2_aten(ly, lx, r0[lx.i0], r0[lx.i1], r1[lx.i0], r1[lx.i1]), maxval);
+    o[rev ? 2 - c : c] = (uint16_t)round_sat_u16(v, maxval);
+  }
+}
+
+// The height-only frame sizes (to_inp_rows_kernel above): four pixels of a row are 12 samples = 24 bytes, 8-byte aligned
+// (W % 4 == 0), taken as three 8-byte loads per source row instead of twelve 2-byte ones.
+__global__ void __launch_bounds__(256) to_inp16_rows_kernel(const uint16_t *__restrict__ in, float *__restrict__ out,
+                                                            float *__restrict__ out_x4, int Hin, int W, int Hout, float sy, float maxval) {
+  const int W4 = W >> 2;
+  const size_t total = (size_t)W4 * Hout, P = (size_t)Hout * W;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int y = (int)(i / W4), x = (int)(i - (size_t)y * W4) * 4;
+    const Lerp ly = lerp_src_aten(y, sy, Hin);
+    const uint2 *r0 = reinterpret_cast<const uint2 *>(in + ((size_t)ly.i0 * W + x) * 3);
+    const uint2 *r1 = reinterpret_cast<const uint2 *>(in + ((size_t)ly.i1 * W + x) * 3);
+    const uint2 a0 = r0[0], a1 = r0[1], a2 = r0[2], b0 = r1[0], b1 = r1[1], b2 = r1[2];
+    const uint32_t a[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y}, b[6] = {b0.x, b0.y, b1.x, b1.y, b2.x, b2.y};
+    f32x4g o[3];
+#pragma unroll
+    for (int px = 0; px < 4; ++px)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int k = px * 3 + c;
+        const float top = __fdiv_rn((float)((a[k >> 1] >> (16 * (k & 1))) & 0xffffu), maxval);
+        const float bot = __fdiv_rn((float)((b[k >> 1] >> (16 * (k & 1))) & 0xffffu), maxval);
+        o[c][px] = __fmaf_rn(ly.w0, top, __fmul_rn(ly.w1, bot));
+      }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4g *>(out + (size_t)c * P + (size_t)y * W + x) = o[c];
+    if (out_x4) {
+#pragma unroll
+      for (int px = 0; px < 4; ++px)
+        *reinterpret_cast<f32x4g *>(out_x4 + ((size_t)y * W + x + px) * 4) = (f32x4g){o[0][px], o[1][px], o[2][px], 0.f};
+    }
+  }
+}
+// ... and 24 contiguous bytes stored per lane.  The horizontal pass is ATen's copy, fma(1, a, 0 * a): a for finite a, NaN otherwise.
+__global__ void __launch_bounds__(256) to_out16_rows_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int Hin, int W,
+                                                            int Hout, float sy, int rev, float maxval) {
+  const int W4 = W >> 2;
+  const size_t total = (size_t)W4 * Hout, P = (size_t)Hin * W;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int y = (int)(i / W4), x = (int)(i - (size_t)y * W4) * 4;
+    const Lerp ly = lerp_src_aten_sized(y, sy, Hin, Hout);
+    uint32_t s[12];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const f32x4g t = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)ly.i0 * W + x);
+      const f32x4g u = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)ly.i1 * W + x);
+#pragma unroll
+      for (int px = 0; px < 4; ++px) {
+        const float top = __fmaf_rn(1.f, t[px], __fmul_rn(0.f, t[px])), bot = __fmaf_rn(1.f, u[px], __fmul_rn(0.f, u[px]));
+        const float v = __fmul_rn(__fmaf_rn(ly.w0, top, __fmul_rn(ly.w1, bot)), maxval);
+        s[px * 3 + (rev ? 2 - c : c)] = round_sat_u16(v, maxval);
+      }
+    }
+    uint2 *o = reinterpret_cast<uint2 *>(out + ((size_t)y * W + x) * 3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] = make_uint2(s[4 * k] | (s[4 * k + 1] << 16), s[4 * k + 2] | (s[4 * k + 3] << 16));
+  }
+}
+
+// the no-resize pair: HWC uint16 -> [1,3,H,W] fp32 / maxval, and back with the rounding rule above
+__global__ void __launch_bounds__(256) u16_to_f32_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, int H, int W, float maxval) {
+  const size_t P = (size_t)H * W;
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (size_t)gridDim.x * blockDim.x) {
+    const uint16_t *s = in + p * 3;
+    out[p] = __fdiv_rn((float)s[0], maxval);
+    out[P + p] = __fdiv_rn((float)s[1], maxval);
+    out[2 * P + p] = __fdiv_rn((float)s[2], maxval);
+  }
+}
+__global__ void __launch_bounds__(256) f32_to_u16_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int H, int W, float maxval) {
+  const size_t P = (size_t)H * W;
+  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (size_t)gridDim.x * blockDim.x) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[p * 3 + c] = (uint16_t)round_sat_u16(__fmul_rn(in[(size_t)c * P + p], maxval), maxval);
+  }
+}
+
 // The interpolations of one step (`-t 2`: two frames) are independent until their convolutions are stacked along N: the
 // stage-input and flow-update kernels of ALL items of a stage are one launch (blockIdx.y = item).  On the small maps of
 // the first stages these kernels are latency-bound, and every launch also costs the ~5.5 us a dependent dispatch waits
@@ -1012,6 +1147,54 @@ int drba_to_out(const float *in, uint8_t *out_hwc, int Hin, int Win, int Hout, i
   }
   DRBA_LAUNCH(to_out_kernel, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Win, Hout,
               Wout, scale_y, scale_x, reverse_channels);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+static bool maxval_ok(float maxval) { return maxval > 255.f && maxval <= 65535.f; }  // (NaN fails both)
+
+int drba_u16hwc_to_f32nchw(const uint16_t *in, float *out, int H, int W, float maxval, void *stream) {
+  if (!in || !out || H <= 0 || W <= 0 || !maxval_ok(maxval) || ((uintptr_t)in & 1) != 0) return DRBA_EINVAL;
+  DRBA_LAUNCH(u16_to_f32_kernel, dim3(grid_for((size_t)H * W)), dim3(kBlock), 0, (hipStream_t)stream, in, out, H, W, maxval);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+int drba_f32nchw_to_u16hwc(const float *in, uint16_t *out, int H, int W, float maxval, void *stream) {
+  if (!in || !out || H <= 0 || W <= 0 || !maxval_ok(maxval) || ((uintptr_t)out & 1) != 0) return DRBA_EINVAL;
+  DRBA_LAUNCH(f32_to_u16_kernel, dim3(grid_for((size_t)H * W)), dim3(kBlock), 0, (hipStream_t)stream, in, out, H, W, maxval);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+int drba_to_inp16_x4(const uint16_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y,
+                     float scale_x, float maxval, void *stream) {
+  if (!img_hwc || !out || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || ((uintptr_t)out_x4 & 15) != 0) return DRBA_EINVAL;
+  if (!maxval_ok(maxval) || ((uintptr_t)img_hwc & 1) != 0) return DRBA_EINVAL;
+  if (Win == Wout && scale_x == 1.f && (Wout & 3) == 0 && (((uintptr_t)img_hwc & 7) | ((uintptr_t)out & 15)) == 0) {
+    DRBA_LAUNCH(to_inp16_rows_kernel, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out,
+                out_x4, Hin, Wout, Hout, scale_y, maxval);
+    DRBA_CHECK_LAUNCH();
+    return DRBA_OK;
+  }
+  DRBA_LAUNCH(to_inp16_kernel, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4, Hin, Win, Hout,
+              Wout, scale_y, scale_x, maxval);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+int drba_to_out16(const float *in, uint16_t *out_hwc, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
+                  int reverse_channels, float maxval, void *stream) {
+  if (!in || !out_hwc || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0) return DRBA_EINVAL;
+  if (!maxval_ok(maxval) || ((uintptr_t)out_hwc & 1) != 0) return DRBA_EINVAL;
+  if (Win == Wout && scale_x == 1.f && (Wout & 3) == 0 && (((uintptr_t)out_hwc & 7) | ((uintptr_t)in & 15)) == 0) {
+    DRBA_LAUNCH(to_out16_rows_kernel, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin,
+                Wout, Hout, scale_y, reverse_channels, maxval);
+    DRBA_CHECK_LAUNCH();
+    return DRBA_OK;
+  }
+  DRBA_LAUNCH(to_out16_kernel, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Win, Hout,
+              Wout, scale_y, scale_x, reverse_channels, maxval);
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }

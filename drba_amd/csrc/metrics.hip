@@ -9,8 +9,8 @@
 // (x pass into LDS, y pass + channel mix into registers).  Tile sums go to the workspace, a second kernel adds them in a fixed
 // order: no floating-point atomics, the same bits on every run and for an item alone or in a batch.
 //
-// drba_frame_error_u8 / _f32: sum d^2, sum |d|, max |d| and a count per item, integers for bytes and fp64 for floats, through
-// the same two-stage reduction.
+// drba_frame_error_u8 / _u16 / _f32: sum d^2, sum |d|, max |d| and a count per item, integers for bytes and 16-bit samples and
+// fp64 for floats, through the same two-stage reduction.
 #include "common.hpp"
 
 #include <math.h>
@@ -286,6 +286,71 @@ __global__ void __launch_bounds__(256) frame_error_u8_kernel(const uint8_t *__re
   }
 }
 
+// uint16 samples: the same walk in samples -- head up to a's next 16-byte boundary (a is 2-byte aligned: fewer than 8), chunks of
+// 8, tail.  One d^2 fits 32 bits (65535^2 < 2^32), two do not: the squares are added in 64 bits; the partials have the byte
+// kernel's layout and go through frame_error_u8_final.
+__device__ __forceinline__ void acc_u16(unsigned a, unsigned b, u64 &sq, unsigned &ab, unsigned &mx, unsigned &nz) {
+  const unsigned d = a > b ? a - b : b - a;
+  sq += (u64)(d * d);
+  ab += d;
+  mx = max(mx, d);
+  nz += d != 0u;
+}
+
+__global__ void __launch_bounds__(256) frame_error_u16_kernel(const uint16_t *__restrict__ a, const uint16_t *__restrict__ b,
+                                                              size_t n, int parts, u64 *__restrict__ partial) {
+  __shared__ u64 red[4][4];
+  const uint16_t *pa = a + (size_t)blockIdx.y * n, *pb = b + (size_t)blockIdx.y * n;
+  size_t head = (size_t)(((16u - (unsigned)((uintptr_t)pa & 15u)) & 15u) >> 1);
+  if (head > n) head = n;
+  const size_t chunks = (n - head) >> 3, tail0 = head + (chunks << 3);
+  const bool same_phase = (((uintptr_t)pa ^ (uintptr_t)pb) & 15u) == 0;
+  u64 sq = 0, ab = 0;
+  unsigned mx = 0, nz = 0;
+  const size_t gtid = (size_t)blockIdx.x * 256 + threadIdx.x, gstride = (size_t)parts * 256;
+  for (size_t i = gtid; i < chunks; i += gstride) {
+    const u32x4 va = *reinterpret_cast<const u32x4 *>(pa + head + (i << 3));
+    u32x4 vb;
+    if (same_phase)
+      vb = *reinterpret_cast<const u32x4 *>(pb + head + (i << 3));
+    else
+      vb = *reinterpret_cast<const u32x4u *>(pb + head + (i << 3));
+    unsigned cab = 0;  // 8 samples: at most 8 * 65535
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) acc_u16((va[w] >> (16 * k)) & 0xffffu, (vb[w] >> (16 * k)) & 0xffffu, sq, cab, mx, nz);
+    ab += cab;
+  }
+  if (blockIdx.x == 0) {  // head and tail: fewer than 16 samples per item, taken by the first workgroup
+    const size_t edge = head + (n - tail0);
+    if (threadIdx.x < edge) {
+      const size_t e = threadIdx.x < head ? threadIdx.x : tail0 + (threadIdx.x - head);
+      unsigned cab = 0;
+      acc_u16(pa[e], pb[e], sq, cab, mx, nz);
+      ab += cab;
+    }
+  }
+  sq = wave_sum_u64(sq);
+  ab = wave_sum_u64(ab);
+  const u64 m = wave_max_u64(mx), z = wave_sum_u64(nz);
+  if ((threadIdx.x & 63) == 0) {
+    const int w = threadIdx.x >> 6;
+    red[w][0] = sq;
+    red[w][1] = ab;
+    red[w][2] = m;
+    red[w][3] = z;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 *o = partial + ((size_t)blockIdx.y * parts + blockIdx.x) * 4;
+    o[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+    o[1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+    o[2] = max(max(red[0][2], red[1][2]), max(red[2][2], red[3][2]));
+    o[3] = red[0][3] + red[1][3] + red[2][3] + red[3][3];
+  }
+}
+
 __global__ void __launch_bounds__(256) frame_error_u8_final(const u64 *__restrict__ partial, int parts, u64 *__restrict__ out) {
   __shared__ u64 red[4][4];
   const u64 *p = partial + (size_t)blockIdx.x * parts * 4;
@@ -452,6 +517,22 @@ extern "C" int drba_frame_error_u8(const uint8_t *a, const uint8_t *b, unsigned 
   const int parts = err_parts(n_per_item, 16 * 8);
   hipStream_t s = (hipStream_t)stream;
   DRBA_LAUNCH(frame_error_u8_kernel, dim3(parts, N), dim3(256), 0, s, a, b, n_per_item, parts, reinterpret_cast<u64 *>(ws));
+  DRBA_CHECK_LAUNCH();
+  DRBA_LAUNCH(frame_error_u8_final, dim3(N), dim3(256), 0, s, reinterpret_cast<const u64 *>(ws), parts, reinterpret_cast<u64 *>(out));
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+extern "C" size_t drba_frame_error_u16_ws_floats(int N, size_t n_per_item) { return drba_frame_error_ws_floats(N, n_per_item); }
+
+extern "C" int drba_frame_error_u16(const uint16_t *a, const uint16_t *b, unsigned long long *out, float *ws, int N,
+                                    size_t n_per_item, void *stream) {
+  if (!a || !b || !out || !ws || N < 1 || n_per_item < 1) return DRBA_EINVAL;
+  if (((uintptr_t)ws & 7u) || ((uintptr_t)out & 7u) || (((uintptr_t)a | (uintptr_t)b) & 1u)) return DRBA_EINVAL;
+  if (N > 65535 || n_per_item > 0xffffffffull) return DRBA_EUNSUPPORTED;  // sum d^2 < 2^32 * 2^32
+  const int parts = err_parts(n_per_item, 8 * 8);
+  hipStream_t s = (hipStream_t)stream;
+  DRBA_LAUNCH(frame_error_u16_kernel, dim3(parts, N), dim3(256), 0, s, a, b, n_per_item, parts, reinterpret_cast<u64 *>(ws));
   DRBA_CHECK_LAUNCH();
   DRBA_LAUNCH(frame_error_u8_final, dim3(N), dim3(256), 0, s, reinterpret_cast<const u64 *>(ws), parts, reinterpret_cast<u64 *>(out));
   DRBA_CHECK_LAUNCH();

@@ -13,6 +13,10 @@ builds agree within 1 LSB" is `compare a.npz b.npz --max-lsb 1`.
 position.  K is odd: an even K puts every emission half-way between two original frames.  `--plain` replaces each DRBA step by
 plain inference_ts on the pair the timestep lies in -- the baseline DRBA's "preserves the original pace" is a claim against.
 
+16-bit clips (uint16 frames; `maxval` from the .npz entry or the .json sidecar, 65535 when absent) are measured in their own
+steps: the reports carry "depth": 16 and "maxval", the PSNR peak is maxval, `--max-lsb` counts 16-bit steps, and `holdout` emits
+at 16 bits.  Two clips of different depth or maxval are refused.
+
 Non-finite JSON numbers are written as the strings "inf" / "-inf" / "nan" (float() reads them back).
 """
 import argparse
@@ -33,16 +37,21 @@ class ClipSource:
 
     def __init__(self, path):
         self.path, self._frames, self._cap = path, None, None
+        self.depth, self.maxval = 8, 255
         if not os.path.exists(path):
             raise FileNotFoundError(f"can't find the clip {path}")
         ext = os.path.splitext(path)[1].lower()
+        maxval = None
         if ext == ".npz":
             z = np.load(path)
             self._frames, self.fps = z["frames"], (float(z["fps"]) if "fps" in z.files else 24.0)
+            maxval = int(z["maxval"]) if "maxval" in z.files else None
         elif ext == ".npy":
             self._frames = np.load(path, mmap_mode="r")
             side = os.path.splitext(path)[0] + ".json"
-            self.fps = float(json.load(open(side))["fps"]) if os.path.exists(side) else 24.0
+            meta = json.load(open(side)) if os.path.exists(side) else {}
+            self.fps = float(meta["fps"]) if "fps" in meta else 24.0
+            maxval = int(meta["maxval"]) if "maxval" in meta else None
         else:
             try:
                 import cv2  # noqa: WPS433 (optional dependency)
@@ -50,8 +59,13 @@ class ClipSource:
                 raise RuntimeError(f"decoding {ext or 'this input'} needs OpenCV, which is not installed; use a .npz/.npy clip") from e
             self._cap = cv2.VideoCapture(path)
             self.fps = float(self._cap.get(cv2.CAP_PROP_FPS))
-        if self._frames is not None and (self._frames.ndim != 4 or self._frames.shape[3] != 3 or self._frames.dtype != np.uint8):
-            raise ValueError(f"{path}: frames must be uint8 [N,H,W,3], got {self._frames.dtype} {self._frames.shape}")
+        if self._frames is not None and (self._frames.ndim != 4 or self._frames.shape[3] != 3 or
+                                         self._frames.dtype not in (np.uint8, np.uint16)):
+            raise ValueError(f"{path}: frames must be uint8 or uint16 [N,H,W,3], got {self._frames.dtype} {self._frames.shape}")
+        if self._frames is not None and self._frames.dtype == np.uint16:  # samples in [0, maxval], 65535 unless the clip says
+            if maxval is not None and not 255 < maxval <= 65535:
+                raise ValueError(f"{path}: maxval of a 16-bit clip must satisfy 255 < maxval <= 65535, got {maxval}")
+            self.depth, self.maxval = 16, (65535 if maxval is None else maxval)
 
     def __len__(self):
         if self._frames is None:
@@ -88,10 +102,15 @@ def _jsonable(v):
 # ----------------------------------------------------------------------------------------------------------------- compare
 def compare(a, b, backend=None):
     """The metrics of clip `b` against clip `a` (two ClipSources, or anything that iterates uint8 [H,W,3] frames).
-    ValueError when the frame counts or the frame sizes differ (both values are named)."""
+    ValueError when the frame counts or the frame sizes differ (both values are named).  Two uint16 clips (ClipSource.depth 16)
+    are compared in their own steps, the peak being their maxval; clips of different depth or maxval are refused, both named."""
+    da, db = getattr(a, "depth", None), getattr(b, "depth", None)
+    if da is not None and db is not None and (da, getattr(a, "maxval", None)) != (db, getattr(b, "maxval", None)):
+        raise ValueError(f"the clips differ in depth: {da}-bit frames with maxval {getattr(a, 'maxval', None)} against {db}-bit "
+                         f"frames with maxval {getattr(b, 'maxval', None)}; convert one of them first")
     if getattr(a, "random_access", True) and getattr(b, "random_access", True) and hasattr(a, "__len__") and len(a) != len(b):
         raise ValueError(f"the clips differ in length: {len(a)} frames against {len(b)}")
-    cm = metrics.ClipMetrics(backend=backend)
+    cm = metrics.ClipMetrics(backend=backend, maxval=getattr(a, "maxval", None) if da == 16 else None)
     ia, ib = iter(a), iter(b)
     na = nb = 0
     size = None
@@ -110,6 +129,8 @@ def compare(a, b, backend=None):
         cm.add(fa, fb)
     res = cm.result()
     res["size"] = size
+    if da == 16:  # (the report of two 8-bit clips is what it was)
+        res["depth"], res["maxval"] = 16, int(a.maxval)
     return res
 
 
@@ -138,6 +159,8 @@ def compare_report(res, limits, a_name=None, b_name=None):
     ok = all(g["ok"] for g in gates.values())
     rep = {"command": "compare", "a": a_name, "b": b_name, "frames": res["frames"], "size": res.get("size"), "peak": res["peak"]}
     rep.update(summary)
+    if "depth" in res:  # 16-bit clips: max_lsb (and its gate) and total_differing are in the clips' own steps and samples
+        rep.update({"depth": res["depth"], "maxval": res["maxval"]})
     rep.update({"gates": gates, "ok": ok})
     return rep, ok
 
@@ -204,20 +227,32 @@ class _HoldoutIO:
 
 
 def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.3, plain=False, backend=None, to_inp=None,
-            to_out=None, check_scene=None):
+            to_out=None, check_scene=None, maxval=None):
     """Keep every k-th frame of `frames` (uint8 [N,H,W,3], indexable), let interpolate_stream fill the gaps at `times = k`
     and compare every emission with the original frame at its position.  -> {"k", "m", "frames_used", "emissions",
     "pairs": [(emission, original)], "kept": ClipMetrics.result() + "positions", "held_out": the same}.
     to_inp / to_out / check_scene / backend: the hooks of interpolate_stream and of drba_amd.metrics (defaults: the device
-    ones, with the emitted frames staying on the device)."""
+    ones, with the emitted frames staying on the device).
+    uint16 frames (samples in [0, maxval], 65535 unless given): the default hooks read and emit 16 bits at that maxval and the
+    emissions are compared with the 16-bit originals in their own steps; the result carries "depth": 16 and "maxval"."""
     from drba_amd import infer as drv
     m, half = holdout_plan(len(frames), k)
+    deep = getattr(frames, "dtype", None) == np.uint16
+    if maxval is not None and not deep:
+        raise ValueError("maxval belongs to uint16 frames")
+    mv = (65535 if maxval is None else int(maxval)) if deep else None
     device_out = to_out is None
     if device_out:
         from drba_amd import ops
-        to_out = lambda x, size: ops.to_out(x, size)  # noqa: E731  (uint8 on the device: compared there)
+        if deep:
+            to_out = lambda x, size: ops.to_out(x, size, depth=16, maxval=mv)  # noqa: E731  (uint16 on the device: compared there)
+        else:
+            to_out = lambda x, size: ops.to_out(x, size)  # noqa: E731  (uint8 on the device: compared there)
+    if to_inp is None and deep:
+        from drba_amd.models.utils import tools
+        to_inp = lambda fr, size: tools.to_inp(fr, size, maxval=mv)  # noqa: E731
     backend = backend or metrics.default_backend()
-    kept, held = metrics.ClipMetrics(backend=backend), metrics.ClipMetrics(backend=backend)
+    kept, held = metrics.ClipMetrics(backend=backend, maxval=mv), metrics.ClipMetrics(backend=backend, maxval=mv)
     io = _HoldoutIO(frames, int(k), m, half, fps, kept, held)
     run = PlainSteps(model) if plain else model
     written = drv.interpolate_stream(run, io, float(fps) * int(k), times=int(k), enable_scdet=enable_scdet,
@@ -226,6 +261,8 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
         raise RuntimeError(f"hold-out at k = {k}: the run emitted {written} frames ({len(io.skipped)} without an original), "
                            f"expected {int(k) * (m + 1)} ({2 * half})")
     out = {"k": int(k), "m": m, "frames_used": m * int(k) + 1, "emissions": written, "plain": bool(plain), "pairs": io.pairs}
+    if deep:
+        out.update({"depth": 16, "maxval": mv})
     for name, cm in (("kept", kept), ("held_out", held)):
         res = cm.result()  # (has waited for every kernel behind the frames)
         res["positions"] = [p for _, p in io.pairs if (p % int(k) == 0) == (name == "kept")]
@@ -239,6 +276,8 @@ def holdout_report(res):
     """The JSON object of `holdout` without the per-frame lists."""
     rep = {"command": "holdout", "k": res["k"], "m": res["m"], "frames_used": res["frames_used"], "emissions": res["emissions"],
            "plain": res["plain"]}
+    if "depth" in res:
+        rep.update({"depth": res["depth"], "maxval": res["maxval"]})
     for name in ("kept", "held_out"):
         r = res[name]
         s = dict(r["summary"])
@@ -255,7 +294,7 @@ def parse_args(argv=None):
     c.add_argument("a")
     c.add_argument("b")
     c.add_argument("--json", dest="json_path", type=str, default=None, help="also write the report with the per-frame lists here")
-    c.add_argument("--max-lsb", dest="max_lsb", type=float, default=None, help="gate: the largest byte difference allowed")
+    c.add_argument("--max-lsb", dest="max_lsb", type=float, default=None, help="gate: the largest difference allowed, in the clips' own steps (bytes, or 16-bit samples)")
     c.add_argument("--min-psnr", dest="min_psnr", type=float, default=None, help="gate: the lowest per-frame PSNR allowed")
     c.add_argument("--min-ssim", dest="min_ssim", type=float, default=None, help="gate: the lowest per-frame SSIM allowed")
     h = sub.add_parser("holdout", help="hold frames out of a clip and compare what the driver loop puts in their place")
@@ -301,7 +340,8 @@ def main(argv=None, backend=None):
         model = drv.load_model(args.model_type, scale=args.scale,
                                weights=tune._synthetic_weights(args.model_type) if synthetic else wdir)
         res = holdout(model, src._frames, args.k, fps=src.fps, enable_scdet=args.enable_scdet,
-                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend)
+                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend,
+                      **({"maxval": src.maxval} if src.depth == 16 else {}))
         rep = holdout_report(res)
         rep.update({"model": args.model_type, "scale": args.scale, "input": args.input,
                     "weights": "synthetic (drba_amd.utils.synth): the figures say nothing about quality" if synthetic else wdir})

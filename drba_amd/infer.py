@@ -1,6 +1,9 @@
 """DRBA command line and per-frame driver loop (same CLI as the reference's infer.py).
 
-    python infer.py -m rife -i in.npz -o out.npz [-fps 60 | -t 2] [-s] [-st 0.3] [-hw] [-scale 1.0]
+    python infer.py -m rife -i in.npz -o out.npz [-fps 60 | -t 2] [-s] [-st 0.3] [-hw] [-scale 1.0] [--out-depth source|8|16]
+
+`--out-depth` is not in the reference: a .npz / .npy clip may hold uint16 frames, and the written frames are 8 or 16 bits deep
+(default: as the source, so an 8-bit clip is handled exactly as before).
 
 The driver logic is host-side Python like the reference; the model calls it makes run on
 the HIP library.  `interpolate_stream` is the loop of reference infer.py:58-174 (drba_amd/driver.py) with the
@@ -31,7 +34,20 @@ def parse_args(argv=None):
                    help="enable hardware acceleration encode")
     p.add_argument("-scale", "--scale", dest="scale", type=float, default=1.0,
                    help="flow scale, generally use 1.0 with 1080P and 0.5 with 4K resolution")
+    p.add_argument("--out-depth", dest="out_depth", type=str, default="source", choices=("source", "8", "16"),
+                   help="bits per sample of the written frames: the source's (default), 8, or 16 (uint16 .npz / .npy, rgb48le raw, "
+                        "libx264 yuv420p10le; not with -hw, not in the frame-sharded run)")
     return p.parse_args(argv)
+
+
+def out_depth_of(args):
+    """--out-depth as VideoFI_IO takes it: None (the source's depth), 8 or 16.  A namespace built without the flag means None."""
+    v = getattr(args, "out_depth", "source")
+    if v in (None, "source"):
+        return None
+    if str(v) not in ("8", "16"):
+        raise ValueError(f"--out-depth must be source, 8 or 16, got {v!r}")
+    return int(v)
 
 
 def load_model(model_type, scale=1.0, device=None, weights=None):
@@ -77,19 +93,26 @@ def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, s
 
 
 def inference(model, args):
-    video_io = _tools.VideoFI_IO(args.input, args.output, dst_fps=args.dst_fps, times=args.times, hwaccel=args.hwaccel)
+    depth_kw = {} if out_depth_of(args) is None else {"out_depth": out_depth_of(args)}
+    video_io = _tools.VideoFI_IO(args.input, args.output, dst_fps=args.dst_fps, times=args.times, hwaccel=args.hwaccel, **depth_kw)
     try:
         from tqdm import tqdm
         bar = tqdm(total=video_io.total_frames_count)
         step = lambda _i: bar.update(1)  # noqa: E731
     except ImportError:
         bar, step = None, None
-    to_out = None
-    if getattr(video_io, "wants_rgb", False):  # encoder pipe / raw sink: BGR -> RGB inside the to_out kernel, not on the host
+    to_inp = to_out = None
+    rgb = bool(getattr(video_io, "wants_rgb", False))
+    if rgb:  # encoder pipe / raw sink: BGR -> RGB inside the to_out kernel, not on the host
         video_io.frames_are_rgb = True
         to_out = lambda x, size: _tools.to_out(x, size, rgb=True)  # noqa: E731
+    # 16-bit frames at either end: the hooks carry the depth and the clip's maxval, the loop between them never looks at a frame
+    if getattr(video_io, "depth", 8) == 16:
+        to_inp = lambda fr, size: _tools.to_inp(fr, size, maxval=video_io.maxval)  # noqa: E731
+    if getattr(video_io, "out_depth", 8) == 16:
+        to_out = lambda x, size: _tools.to_out(x, size, rgb=rgb, depth=16, maxval=video_io.out_maxval)  # noqa: E731
     n = interpolate_stream(model, video_io, args.dst_fps, times=args.times, enable_scdet=args.enable_scdet,
-                           scdet_threshold=args.scdet_threshold, to_out=to_out, on_step=step)
+                           scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, on_step=step)
     while not video_io.finish_writing():
         time.sleep(0.01)
     video_io.close()
@@ -120,6 +143,10 @@ def inference_sharded(model, args, rank, world, to_inp=None, to_out=None, check_
             fps = float(json.load(open(side))["fps"])
     else:
         raise RuntimeError("the frame-sharded run needs random access to the clip: use a .npz / .npy source")
+    # every rank sees the same clip and the same flag: all of them refuse here, before the gather exists and before any collective
+    if frames.dtype == np.uint16 or out_depth_of(args) == 16:
+        raise ValueError(f"the frame-sharded run carries 8-bit frames only (the gather to the writer moves uint8): {args.input} holds "
+                         f"{frames.dtype} frames, --out-depth is {getattr(args, 'out_depth', 'source')}; run 16-bit clips on one GPU")
     counts = parallel.emission_counts(len(frames), fps, args.dst_fps, args.times, world)
     sg = parallel.StreamedGather(rank, world, counts, chunk=chunk, device=device, frame_shape=tuple(frames[0].shape))
     if to_out is None and world > 1 and device is not None and device.type == "cuda":

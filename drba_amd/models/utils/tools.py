@@ -52,14 +52,33 @@ def load_weights(path):
     return torch.load(path, map_location="cpu", weights_only=True)
 
 
-def to_tensor(img, device=None):
-    """uint8 HWC -> fp32 [1,3,H,W] in [0,1] on the GPU (tools.py:33-34).  Channel order is kept."""
+def _is_u16(img):
+    return img.dtype == (torch.uint16 if torch.is_tensor(img) else np.uint16)
+
+
+def _check_depth(depth, maxval):
+    if depth not in (8, 16):
+        raise ValueError(f"depth must be 8 or 16, got {depth!r}")
+    if depth == 8 and maxval is not None:
+        raise ValueError("maxval belongs to 16-bit frames (depth=16)")
+
+
+def to_tensor(img, device=None, maxval=None):
+    """uint8 HWC -> fp32 [1,3,H,W] in [0,1] on the GPU (tools.py:33-34).  Channel order is kept.  A uint16 frame is divided by
+    `maxval` (65535 unless given) instead of 255."""
     device = _ops.default_device() if device is None else device
-    return _ops.u8hwc_to_f32nchw(torch.from_numpy(np.ascontiguousarray(img)).to(device, non_blocking=True))
+    t = torch.from_numpy(np.ascontiguousarray(img)).to(device, non_blocking=True)
+    if _is_u16(t):
+        return _ops.u16hwc_to_f32nchw(t, maxval)
+    return _ops.u8hwc_to_f32nchw(t)
 
 
-def to_cv2(img):
-    """fp32 [1,3,H,W] -> uint8 HWC with (x*255.) truncation, no clamp/round (tools.py:37-38)."""
+def to_cv2(img, depth=8, maxval=None):
+    """fp32 [1,3,H,W] -> uint8 HWC with (x*255.) truncation, no clamp/round (tools.py:37-38).  depth=16: uint16 HWC, x * maxval
+    rounded to nearest even and saturated (ops.to_out)."""
+    _check_depth(depth, maxval)
+    if depth == 16:
+        return _ops.f32nchw_to_u16hwc(img, maxval).cpu().numpy()
     return _ops.f32nchw_to_u8hwc(img).cpu().numpy()
 
 
@@ -68,21 +87,31 @@ def resize(tensor, size):
     return _ops.resize_bilinear(tensor, size)
 
 
-def to_inp(npInp, dst_size, device=None):
+def to_inp(npInp, dst_size, device=None, maxval=None):
     """resize(to_tensor(npInp), dst_size) (tools.py:59-60) as one kernel on the uploaded uint8 frame (the full-size
-    fp32 frame of the reference is never materialised); bit-exact with the two-step form."""
+    fp32 frame of the reference is never materialised); bit-exact with the two-step form.  A uint16 frame goes through the
+    16-bit kernel with its `maxval` (65535 unless given)."""
     device = _ops.default_device() if device is None else device
     if torch.is_tensor(npInp):
         u8 = npInp.to(device, non_blocking=True)
     else:
         u8 = torch.from_numpy(np.ascontiguousarray(npInp)).to(device, non_blocking=True)
+    if _is_u16(u8):
+        return _ops.to_inp(u8, dst_size, maxval=maxval)
+    if maxval is not None:
+        raise ValueError("maxval belongs to 16-bit frames (uint16)")
     return _ops.to_inp(u8, dst_size)
 
 
-def to_out(tenInp, src_size, rgb=False):
+def to_out(tenInp, src_size, rgb=False, depth=8, maxval=None):
     """to_cv2(resize(tenInp, src_size)) (tools.py:63-64) as one kernel + the D2H copy.  rgb=True returns the frame in RGB
-    order (the flip the reference's writer thread does on the host, tools.py:202, done on the device instead)."""
-    frame = _ops.to_out(tenInp, src_size, rgb=rgb).cpu().numpy()
+    order (the flip the reference's writer thread does on the host, tools.py:202, done on the device instead).  depth=16
+    returns a uint16 frame scaled to `maxval` (65535 unless given), rounded and saturated (ops.to_out)."""
+    _check_depth(depth, maxval)
+    if depth == 16:
+        frame = _ops.to_out(tenInp, src_size, rgb=rgb, depth=16, maxval=maxval).cpu().numpy()
+    else:
+        frame = _ops.to_out(tenInp, src_size, rgb=rgb).cpu().numpy()
     # the copy has waited for every kernel behind this frame: had one of the two-term fp16 kernels overflowed on the way, its
     # status byte is set by now -- raise here rather than hand the frame to the writer (ops.check_overflow: a host memory read)
     _ops.check_overflow(tenInp.device)
@@ -190,21 +219,35 @@ class VideoFI_IO:
       output: .npz  {frames, fps}  or .npy;  anything else -> raw rgb24 bytes (ffmpeg's pipe format)
     `hwaccel` selects a hardware encoder when ffmpeg is present (h264_vaapi/h264_amf on AMD
     instead of the reference's h264_nvenc).
+
+    16-bit frames (not in the reference): a .npz / .npy source may hold uint16 [N,H,W,3] frames with samples in [0, maxval]
+    (.npz entry `maxval` / .json {"maxval"}, 65535 when absent; 1023 for 10-bit data); a container source stays 8-bit.
+    .depth (8 | 16) and .maxval describe the source, .out_depth / .out_maxval what the sink takes: `out_depth` 8 or 16, or None
+    for the source's depth (a 16-bit sink of an 8-bit source is scaled to 65535, otherwise to the source's maxval).  At depth 16
+    the .npz / .npy sink stores uint16 frames (.npz: with `maxval`), the raw sink and the encoder pipe take rgb48le bytes --
+    little-endian, RGB order, always scaled to 65535 -- and the encoder is libx264 at yuv420p10le; `hwaccel` is refused there
+    (h264_vaapi encodes 8 bits).
     """
 
-    def __init__(self, input_path, output_path, dst_fps=60, times=-1, hwaccel=False, src_fps=None):
+    def __init__(self, input_path, output_path, dst_fps=60, times=-1, hwaccel=False, src_fps=None, out_depth=None):
         self.input_path, self.output_path = input_path, output_path
         self._cv2 = None
+        self.depth, self.maxval = 8, 255
         ext = os.path.splitext(input_path)[1].lower()
         if ext in (".npz", ".npy"):
             if ext == ".npz":
                 z = np.load(input_path)
                 self._frames = z["frames"]
                 fps = float(z["fps"]) if "fps" in z.files else None
+                maxval = int(z["maxval"]) if "maxval" in z.files else None
             else:
                 self._frames = np.load(input_path, mmap_mode="r")
                 side = os.path.splitext(input_path)[0] + ".json"
-                fps = float(json.load(open(side))["fps"]) if os.path.exists(side) else None
+                meta = json.load(open(side)) if os.path.exists(side) else {}
+                fps = float(meta["fps"]) if "fps" in meta else None
+                maxval = int(meta["maxval"]) if "maxval" in meta else None
+            if self._frames.dtype == np.uint16:
+                self.depth, self.maxval = 16, _ops._maxval(maxval)
             self.src_fps = float(src_fps if src_fps is not None else (fps if fps is not None else 24.0))
             self.total_frames_count = float(len(self._frames))
             self.height, self.width = int(self._frames.shape[1]), int(self._frames.shape[2])
@@ -220,6 +263,13 @@ class VideoFI_IO:
             self.width = int(self._cv2.get(cv2.CAP_PROP_FRAME_WIDTH))
             self.height = int(self._cv2.get(cv2.CAP_PROP_FRAME_HEIGHT))
         self.dst_fps = times * self.src_fps if times != -1 else dst_fps
+        if out_depth not in (None, 8, 16):
+            raise ValueError(f"out_depth must be 8, 16 or None (the source's depth), got {out_depth!r}")
+        self.out_depth = self.depth if out_depth is None else int(out_depth)
+        self.out_maxval = 255 if self.out_depth == 8 else (self.maxval if self.depth == 16 else 65535)
+        if hwaccel and self.out_depth == 16:  # before a frame is read or an encoder is started
+            raise ValueError("-hw at 16-bit output: the hardware encoder (h264_vaapi) takes 8-bit frames, there is no 10-bit "
+                             "hardware encode here; drop -hw (libx264 at yuv420p10le) or write 8 bits (--out-depth 8)")
 
         oext = os.path.splitext(output_path)[1].lower()
         self._sink_frames = [] if oext in (".npz", ".npy") else None
@@ -251,13 +301,13 @@ class VideoFI_IO:
         cmd = ["ffmpeg", "-y"]
         if hwaccel:
             cmd += ["-vaapi_device", "/dev/dri/renderD128"]
-        cmd += ["-f", "rawvideo", "-pix_fmt", "rgb24", "-r", f"{self.dst_fps}", "-s", f"{self.width}x{self.height}", "-i", "pipe:0"]
+        cmd += ["-f", "rawvideo", "-pix_fmt", "rgb24" if self.out_depth == 8 else "rgb48le", "-r", f"{self.dst_fps}", "-s", f"{self.width}x{self.height}", "-i", "pipe:0"]
         if container:
             cmd += ["-i", self.input_path, "-map", "0:v", "-map", "1:a?"]
         if hwaccel:
             cmd += ["-vf", "format=nv12,hwupload", "-c:v", "h264_vaapi", "-qp", "16"]
         else:
-            cmd += ["-c:v", "libx264", "-pix_fmt", "yuv420p", "-qp", "16", "-preset", "medium"]
+            cmd += ["-c:v", "libx264", "-pix_fmt", "yuv420p" if self.out_depth == 8 else "yuv420p10le", "-qp", "16", "-preset", "medium"]
         cmd += ["-movflags", "+faststart"]
         if container:
             cmd += ["-c:a", "aac", "-b:a", "320k"]
@@ -288,15 +338,21 @@ class VideoFI_IO:
                 # BGR -> RGB as the reference's pipe, unless the driver already flipped on the device
                 rgb = np.ascontiguousarray(item if self.frames_are_rgb else item[:, :, ::-1])
                 try:
+                    if self.out_depth == 16:
+                        rgb = self._rgb48le(rgb)
                     if self._ffmpeg is not None and self._ffmpeg.poll() is not None:
                         raise BrokenPipeError(f"ffmpeg exited with code {self._ffmpeg.returncode}")
                     (self._ffmpeg.stdin if self._ffmpeg is not None else self._raw).write(rgb)
-                except (BrokenPipeError, OSError) as e:  # keep draining the queue; close() re-raises
+                except (BrokenPipeError, OSError, TypeError) as e:  # keep draining the queue; close() re-raises
                     self._sink_error = e
         if self._sink_frames is not None:
-            arr = np.stack(self._sink_frames) if self._sink_frames else np.zeros((0, self.height, self.width, 3), np.uint8)
-            if self.output_path.lower().endswith(".npz"):
-                np.savez(self.output_path, frames=arr, fps=np.float64(self.dst_fps))
+            dtype = np.uint8 if self.out_depth == 8 else np.uint16
+            arr = np.stack(self._sink_frames) if self._sink_frames else np.zeros((0, self.height, self.width, 3), dtype)
+            if self.out_depth == 16 and arr.dtype != dtype:
+                self._sink_error = TypeError(f"the sink takes {np.dtype(dtype).name} frames (out_depth {self.out_depth}), got {arr.dtype}")
+            elif self.output_path.lower().endswith(".npz"):
+                extra = {} if self.out_depth == 8 else {"maxval": np.int64(self.out_maxval)}
+                np.savez(self.output_path, frames=arr, fps=np.float64(self.dst_fps), **extra)
             else:
                 np.save(self.output_path, arr)
         elif self._ffmpeg is not None:
@@ -309,6 +365,15 @@ class VideoFI_IO:
         else:
             self._raw.close()
         self._closed.set()
+
+    def _rgb48le(self, rgb):
+        """uint16 RGB frame with samples in [0, out_maxval] -> rgb48le: full range (v * 65535 / maxval, rounded), little-endian."""
+        if rgb.dtype != np.uint16:
+            raise TypeError(f"the 16-bit sink takes uint16 frames, got {rgb.dtype}")
+        if self.out_maxval != 65535:
+            mv = np.uint32(self.out_maxval)
+            rgb = (np.minimum(rgb, self.out_maxval).astype(np.uint32) * np.uint32(65535) + mv // np.uint32(2)) // mv
+        return np.ascontiguousarray(rgb.astype("<u2"))
 
     def write_frame(self, x):
         self.write_buffer.put(x)

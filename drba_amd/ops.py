@@ -451,10 +451,67 @@ def f32nchw_to_u8hwc(x):
     return out
 
 
-def to_inp(img_u8, dst_size):
-    """tools.to_inp on a device-resident frame: uint8 [H,W,3] -> fp32 [1,3,*dst_size] in [0,1], one kernel."""
+def _maxval(maxval):
+    """The largest sample of a 16-bit frame: 65535 unless given (1023: 10-bit data); an integer in (255, 65535]."""
+    if maxval is None:
+        return 65535
+    if int(maxval) != maxval or not 255 < int(maxval) <= 65535:
+        raise ValueError(f"maxval of a 16-bit frame must be an integer with 255 < maxval <= 65535, got {maxval!r}")
+    return int(maxval)
+
+
+def _is_u16_frame(t):
+    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint16 and t.dim() == 3 and t.shape[2] == 3
+
+
+def u16hwc_to_f32nchw(img_u16, maxval=None):
+    """u8hwc_to_f32nchw for a uint16 frame: / maxval."""
+    if not _is_u16_frame(img_u16):
+        raise _lib.DrbaHipError("expected a CUDA uint16 [H,W,3] tensor")
+    mv = float(_maxval(maxval))
+    img_u16 = img_u16.contiguous()
+    h, w = img_u16.shape[:2]
+    out = torch.empty((1, 3, h, w), dtype=torch.float32, device=img_u16.device)
+    _lib.check(_timed("u16hwc_to_f32nchw", (h, w), 18.0 * h * w, "byte", lambda: _lib.load().drba_u16hwc_to_f32nchw(
+        _p(img_u16), _p(out), h, w, mv, _stream())), "drba_u16hwc_to_f32nchw")
+    return out
+
+
+def f32nchw_to_u16hwc(x, maxval=None):
+    """fp32 [1,3,H,W] -> uint16 [H,W,3]: x * maxval rounded to nearest even and saturated to [0, maxval], NaN -> 0."""
+    mv = float(_maxval(maxval))
+    x = _f32(x)
+    assert x.shape[0] == 1 and x.shape[1] == 3
+    h, w = x.shape[2:]
+    out = torch.empty((h, w, 3), dtype=torch.uint16, device=x.device)
+    _lib.check(_timed("f32nchw_to_u16hwc", (h, w), 18.0 * h * w, "byte", lambda: _lib.load().drba_f32nchw_to_u16hwc(
+        _p(x), _p(out), h, w, mv, _stream())), "drba_f32nchw_to_u16hwc")
+    return out
+
+
+def _to_inp16(img_u16, dst_size, maxval):
+    mv = float(_maxval(maxval))
+    img_u16 = img_u16.contiguous()
+    h, w = img_u16.shape[:2]
+    ho, wo = int(dst_size[0]), int(dst_size[1])
+    out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=img_u16.device)
+    x4 = torch.empty((ho, wo, 4), dtype=torch.float32, device=img_u16.device) if IMG_X4 else None
+    sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))  # ATen: static_cast<float>(in) / out
+    _lib.check(_timed("to_inp16", (h, w, ho, wo), 6.0 * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
+                      lambda: _lib.load().drba_to_inp16_x4(_p(img_u16), _p(out), _p(x4), h, w, ho, wo, sy, sx, mv, _stream())),
+               "drba_to_inp16_x4")
+    if x4 is not None:
+        _set_copy(out, "_drba_x4", x4)
+    return out
+
+
+def to_inp(img_u8, dst_size, maxval=None):
+    """tools.to_inp on a device-resident frame: uint8 [H,W,3] -> fp32 [1,3,*dst_size] in [0,1], one kernel.  A uint16 [H,W,3]
+    frame takes the 16-bit kernel: its samples are divided by `maxval` (65535 unless given; 255 < maxval <= 65535)."""
+    if _is_u16_frame(img_u8):
+        return _to_inp16(img_u8, dst_size, maxval)
     if not (torch.is_tensor(img_u8) and img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 3 and img_u8.shape[2] == 3):
-        raise _lib.DrbaHipError("expected a CUDA uint8 [H,W,3] tensor")
+        raise _lib.DrbaHipError("expected a CUDA uint8 or uint16 [H,W,3] tensor")
     img_u8 = img_u8.contiguous()
     h, w = img_u8.shape[:2]
     ho, wo = int(dst_size[0]), int(dst_size[1])
@@ -469,15 +526,28 @@ def to_inp(img_u8, dst_size):
     return out
 
 
-def to_out(x, src_size, rgb=False):
+def to_out(x, src_size, rgb=False, depth=8, maxval=None):
     """tools.to_out without the D2H copy: fp32 [1,3,h,w] -> uint8 [*src_size,3] on the device, one kernel
-    (resize + *255. truncation; rgb=True also flips BGR -> RGB for the encoder pipe)."""
+    (resize + *255. truncation; rgb=True also flips BGR -> RGB for the encoder pipe).
+    depth=16: a torch.uint16 [*src_size,3] frame instead -- resize, * maxval (65535 unless given), rounded to nearest even and
+    saturated to [0, maxval], NaN -> 0: the 8-bit path keeps the reference's truncation because its bytes must equal the
+    reference's, a 16-bit frame has no reference to equal."""
+    if depth not in (8, 16):
+        raise ValueError(f"depth must be 8 or 16, got {depth!r}")
+    if depth == 8 and maxval is not None:
+        raise ValueError("maxval belongs to 16-bit frames (depth=16)")
     x = _f32(x)
     assert x.shape[0] == 1 and x.shape[1] == 3
     h, w = x.shape[2:]
     ho, wo = int(src_size[0]), int(src_size[1])
-    out = torch.empty((ho, wo, 3), dtype=torch.uint8, device=x.device)
     sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))
+    if depth == 16:
+        mv = float(_maxval(maxval))
+        out = torch.empty((ho, wo, 3), dtype=torch.uint16, device=x.device)
+        _lib.check(_timed("to_out16", (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 6.0 * ho * wo, "byte", lambda: _lib.load().drba_to_out16(
+            _p(x), _p(out), h, w, ho, wo, sy, sx, 1 if rgb else 0, mv, _stream())), "drba_to_out16")
+        return out
+    out = torch.empty((ho, wo, 3), dtype=torch.uint8, device=x.device)
     _lib.check(_timed("to_out", (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 3.0 * ho * wo, "byte", lambda: _lib.load().drba_to_out(
         _p(x), _p(out), h, w, ho, wo, sy, sx, 1 if rgb else 0, _stream())), "drba_to_out")
     return out

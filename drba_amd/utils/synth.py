@@ -278,6 +278,21 @@ def make_clip(n_frames, height, width, seed=1234, cut_at=None, offsets=None):
     return frames
 
 
+def make_clip16(n_frames, height, width, seed=1234, cut_at=None, maxval=65535):
+    """make_clip's frames as uint16 with samples in [0, maxval] (65535, or 1023 for 10-bit data): the byte of make_clip in the
+    high bits -- at maxval 65535, frame >> 8 IS make_clip's frame -- and seeded uniform noise in the bits below it, so every
+    bit of a sample is populated (a 16-bit path that drops to 8 bits anywhere shows).  Returns a list of np.uint16 [H, W, 3]."""
+    if not 255 < int(maxval) <= 65535:
+        raise ValueError(f"maxval must satisfy 255 < maxval <= 65535, got {maxval}")
+    step = (int(maxval) + 1) // 256  # 256 * step - 1 <= maxval
+    rng = np.random.default_rng(seed)
+    frames = []
+    for f in make_clip(n_frames, height, width, seed=seed, cut_at=cut_at):
+        low = rng.integers(0, step, size=f.shape, dtype=np.uint16)
+        frames.append((f.astype(np.uint16) * np.uint16(step) + low).astype(np.uint16))
+    return frames
+
+
 def make_triplet_tensors(height, width, seed=1234, device="cpu"):
     """Three consecutive fp32 NCHW frames in [0,1] already at network size."""
     fr = make_clip(3, height, width, seed=seed)

@@ -32,7 +32,9 @@ extern "C" {
 #define DRBA_EUNSUPPORTED (-2) /* shape/config outside what the kernels were built for */
 #define DRBA_ELAUNCH (-3)  /* hipGetLastError() reported a launch failure */
 
-/* ABI version.  10: drba_ssim3d / drba_ssim3d_ws_floats (ssim_matlab at full size, fp64 accumulation) and drba_frame_error_u8 /
+/* ABI version.  11: 16-bit frames -- drba_to_inp16_x4 / drba_to_out16 / drba_u16hwc_to_f32nchw / drba_f32nchw_to_u16hwc (uint16 HWC frames
+ * with an explicit maxval; the way out rounds to nearest even and saturates) and drba_frame_error_u16 / drba_frame_error_u16_ws_floats:
+ * additions only, no earlier entry changes.  10: drba_ssim3d / drba_ssim3d_ws_floats (ssim_matlab at full size, fp64 accumulation) and drba_frame_error_u8 /
  * drba_frame_error_f32 / drba_frame_error_ws_floats (exact frame differences): additions only, no earlier entry changes.
  * 9: drba_conv3x3_shuffle (a 3x3 convolution storing through PixelShuffle(2): GridNet's tail); drba_quad_interleave / drba_softsplat_index / drba_softsplat_gather_quad (drba_softsplat in pieces: the interleaved copy of a feature tensor kept by the caller).  8: configuration ids appended behind every earlier id of drba_conv3x3 (three, family 4: the waves of a workgroup split rows and
  * cout tiles) and drba_deconv4x4s2 (four: rows and couts split across the waves, both row phases per work item); drba_status_word / drba_status_clear (the always-on, synchronisation-free overflow report of kernel family 4); the
@@ -49,7 +51,7 @@ extern "C" {
  * workspace that must be ZERO on entry (they leave it zero on return: self-cleaning accumulator) instead of clearing it
  * themselves; batched stage entry points added; drba_conv3x3_cfg_family added and configuration ids 19 (LDS-DMA, 32
  * channels) / 20 (K split across waves) behind drba_conv3x3; the allocation exception above.  1: the first release. */
-#define DRBA_ABI_VERSION 10  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
+#define DRBA_ABI_VERSION 11  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
 int drba_abi_version(void);
 const char *drba_error_string(int code);
 /* ABI 6, debug: with the range check on, every entry point that ran a kernel of family 4 (two fp16 terms per operand:
@@ -205,6 +207,20 @@ int drba_to_inp_x4(const uint8_t *img_hwc, float *out, float *out_x4, int Hin, i
                    float scale_x, void *stream);
 int drba_to_out(const float *in, uint8_t *out_hwc, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
                 int reverse_channels, void *stream);
+/* ABI 11: the same four conversions for 16-bit frames, uint16 HWC with samples in [0, maxval] (255 < maxval <= 65535: 1023 for
+ * 10-bit data, 65535 for full-range 16-bit; anything else is DRBA_EINVAL).
+ * The way in is the 8-bit one with the divisor exchanged: (float)v / maxval, a true fp32 division, then the same ATen-order lerp;
+ * drba_to_inp16_x4 writes the planar frame and (out_x4 != NULL, 16-byte aligned) the pixel-major [Hout][Wout][4] copy.
+ * The way out DIFFERS from the 8-bit one on purpose.  Bytes keep the reference's trunc(x * 255) and its wrap-around because they
+ * must equal the reference's bytes; there is no 16-bit reference to equal, so: resize, fmul(v, maxval), round to nearest EVEN
+ * (rintf), saturate to [0, maxval], NaN -> 0.  v / maxval * maxval rounds back to v for every integer v <= 65535, so a frame that
+ * passes through unresized comes back bit-identical.  reverse_channels as drba_to_out. */
+int drba_u16hwc_to_f32nchw(const uint16_t *in, float *out, int H, int W, float maxval, void *stream);
+int drba_f32nchw_to_u16hwc(const float *in, uint16_t *out, int H, int W, float maxval, void *stream);
+int drba_to_inp16_x4(const uint16_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y,
+                     float scale_x, float maxval, void *stream);
+int drba_to_out16(const float *in, uint16_t *out_hwc, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
+                  int reverse_channels, float maxval, void *stream);
 
 /* ---- scene-cut metric: tools.py:27-30 + pytorch_msssim/__init__.py:83-136 (ssim_matlab)
  * x1, x2: [1,3,32,32] thumbnails (already resized); out: 1 float on device. */
@@ -236,6 +252,14 @@ size_t drba_frame_error_ws_floats(int N, size_t n_per_item);
 int drba_frame_error_u8(const uint8_t *a, const uint8_t *b, unsigned long long *out, float *ws, int N, size_t n_per_item,
                         void *stream);
 int drba_frame_error_f32(const float *a, const float *b, double *out, float *ws, int N, size_t n_per_item, void *stream);
+/* ABI 11: drba_frame_error_u8 for uint16 samples (n_per_item counts SAMPLES; a and b 2-byte aligned): sum d^2, sum |d|, max |d| and
+ * the number of d != 0 per item as unsigned long long, integer accumulation through the same fixed-order two-stage reduction, no
+ * floating-point atomics: the same bits on every run.  A 4K frame is 2160 * 3840 * 3 < 2^25 samples of d^2 <= 65535^2 < 2^32: the
+ * sum stays below 2^57, far inside 64 bits (items of 2^32 samples and more are DRBA_EUNSUPPORTED).
+ * ws: drba_frame_error_u16_ws_floats(N, n_per_item) floats, 8-byte aligned, any content. */
+size_t drba_frame_error_u16_ws_floats(int N, size_t n_per_item);
+int drba_frame_error_u16(const uint16_t *a, const uint16_t *b, unsigned long long *out, float *ws, int N, size_t n_per_item,
+                         void *stream);
 
 /* ---- convolutions (models/rife_426_heavy/IFNet_HDv3.py:11-16, :28-47, :50-59, :65-82) ------
  * fp32 implicit GEMM on v_mfma_f32_16x16x4_f32.  Weights must be pre-packed by the matching
