@@ -127,6 +127,7 @@ SIGNATURES = {
     "drba_head_fused16": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "drba_ifblock_input_lazy_batch": (_i, [_p, _i, _p, _i, _i, _f, _i, _i, _i, _i, _f, _p]),
     "drba_warp_blend_lazy_batch": (_i, [_p, _i, _p, _i, _i, _f, _i, _i, _p]),
+    "drba_tile_item_order": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "drba_ifblock_update_batch": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "drba_warp_blend_fold": (_i, [_p, _p, _p, _p, _i, _i, _f, _p, _i, _i, _p]),
     "drba_pair_interleave": (_i, [_p, _p, _i, _i, _i, _p]),

@@ -150,6 +150,15 @@ extern "C" {
 
 int drba_abi_version(void) { return DRBA_ABI_VERSION; }
 
+// host only: the function the kernels call (common.hpp tile_item_order), evaluated here for one workgroup id
+int drba_tile_item_order(int block, int tiles_x, int tiles_y, int n_items, int strip_w, int *tx, int *ty, int *item) {
+  if (!tx || !ty || !item || tiles_x <= 0 || tiles_y <= 0 || n_items <= 0 || strip_w <= 0) return DRBA_EINVAL;
+  const long long total = (long long)tiles_x * tiles_y * n_items;
+  if (total > 0x7fffffffLL || block < 0 || block >= total) return DRBA_EINVAL;
+  drba::tile_item_order(block, tiles_x, tiles_y, n_items, strip_w, *tx, *ty, *item);
+  return DRBA_OK;
+}
+
 int drba_set_range_check(int on) {
   const int was = drba::g_range_check ? 1 : 0;
   drba::g_range_check = on != 0;

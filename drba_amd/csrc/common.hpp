@@ -98,55 +98,66 @@ static inline int grid_for(size_t n, int per_block = kBlock) {
 // used for speed only): remap so that each XCD owns a contiguous band of tiles and the source rows a
 // bilinear gather shares between neighbouring tiles are fetched into ONE private L2 instead of up to
 // eight (PMC: 4x the algorithmic read traffic with the linear block order).  Bijective for any count.
-__device__ __forceinline__ int xcd_band(int b, int nblocks) {
+// The order functions below are plain integer arithmetic, compiled for the host as well: drba_tile_item_order (api_misc.hip)
+// hands the (tile, item) of a workgroup out so that the mapping is tested without a GPU.
+__host__ __device__ __forceinline__ int xcd_band(int b, int nblocks) {
   const int q = nblocks >> 3, r = nblocks & 7, xcd = b & 7, k = b >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
 }
-// ... and inside its band an XCD walks the tiles in STRIPS of kStripW columns, top to bottom, instead of whole rows: a
+// ... and inside its band an XCD walks the tiles in STRIPS of strip_w columns, top to bottom, instead of whole rows: a
 // row of tiles of the 1080p stage-input gather moves 2.6 MB of sources and 3.2 MB of output through the XCD's 4 MB L2, so
 // the halo rows a tile shares with the one below it were gone by the time that one ran (PMC, row-major walk: reads
 // 1.34x / 1.70x algorithmic on the scale-1 / scale-2 gathers -- exactly the tiles' halo ratio).  With 8 tiles between
-// vertical neighbours the shared rows are still resident.  nblocks == tiles_x * tiles_y; bijective for any shape.
+// vertical neighbours the shared rows are still resident.  The width is a parameter of the walk (a kernel whose tiles have a
+// larger footprint may want a narrower strip: profiles/tile_item_order.md); every kernel runs kStripW.
 constexpr int kStripW = 8;
-__device__ __forceinline__ void xcd_strip_tile(int b, int nblocks, int tiles_x, int &tx, int &ty) {
-  const int i = xcd_band(b, nblocks);  // position in the global order: XCD b % 8 owns a contiguous range of it
-  const int tiles_y = nblocks / tiles_x;
+// position i of the walk (0 <= i < tiles_x * tiles_y; positions are handed to the XCDs in contiguous ranges) -> tile.
+// Bijective for any shape and any strip_w >= 1.
+__host__ __device__ __forceinline__ void strip_walk_tile(int i, int tiles_x, int tiles_y, int strip_w, int &tx, int &ty) {
   const int RB = (tiles_y + 7) >> 3;   // tile rows per band (the last band may be shorter)
   const int per_band = RB * tiles_x;
   const int j = i / per_band, k = i - j * per_band;
-  const int nrows = min(RB, tiles_y - j * RB);
-  const int nfull = tiles_x / kStripW, full = nfull * kStripW * nrows;
+  const int rest = tiles_y - j * RB, nrows = RB < rest ? RB : rest;
+  const int nfull = tiles_x / strip_w, full = nfull * strip_w * nrows;
   int row, col;
   if (k < full) {
-    const int s = k / (kStripW * nrows), r = k - s * kStripW * nrows;
-    row = r / kStripW;
-    col = s * kStripW + (r - row * kStripW);
+    const int s = k / (strip_w * nrows), r = k - s * strip_w * nrows;
+    row = r / strip_w;
+    col = s * strip_w + (r - row * strip_w);
   } else {  // the narrower last strip
-    const int wl = max(tiles_x - nfull * kStripW, 1), r = k - full;
+    const int wrest = tiles_x - nfull * strip_w, wl = wrest > 1 ? wrest : 1, r = k - full;
     row = r / wl;
-    col = nfull * kStripW + (r - row * wl);
+    col = nfull * strip_w + (r - row * wl);
   }
   tx = col;
   ty = j * RB + row;
 }
+// nblocks == tiles_x * tiles_y
+__host__ __device__ __forceinline__ void xcd_strip_tile(int b, int nblocks, int tiles_x, int &tx, int &ty, int strip_w = kStripW) {
+  // xcd_band: the position in the global order -- XCD b % 8 owns a contiguous range of it
+  strip_walk_tile(xcd_band(b, nblocks), tiles_x, nblocks / tiles_x, strip_w, tx, ty);
+}
 // A launch over (tiles x items) as ONE grid dimension with the items of a tile back to back on ONE XCD (round 4).  The items of
 // a group of DRBA steps read the same six source frames -- frame I(k) is img0 of two items and img1 of up to two more, at
 // sample points a few pixels apart --, but launched as blockIdx.y = item the whole frame of item 0 was gathered before
-// item 1 started: every item fetched its 159 MB per source from HBM again.  XCD x (= linear workgroup id % 8) walks its band
-// of tiles and runs all n items of a tile consecutively, so the later items find the neighbourhood in the XCD's L2.
-// vb = the block id xcd_strip_tile() expects (over `ntiles`), item = which item.  Falls back to item-major order when the
-// tile count is not a multiple of 8 (the XCD bands would not be equal).
-__device__ __forceinline__ void tile_item_block(int n_items, int &vb, int &item, int &ntiles) {
-  const int b = blockIdx.x;
-  ntiles = gridDim.x / n_items;
-  if ((ntiles & 7) == 0 && n_items > 1) {
-    const int xcd = b & 7, k = b >> 3;
-    item = k % n_items;
-    vb = (k / n_items) * 8 + xcd;
-  } else {
-    item = b / ntiles;
-    vb = b - item * ntiles;
-  }
+// item 1 started: every item fetched its 159 MB per source from HBM again.  Here workgroup b of the ntiles * n_items takes
+// position p = xcd_band(b, ntiles * n_items) of the XCD-major order and runs item p % n_items of the tile at position
+// p / n_items of the strip walk: the workgroups that follow each other on one XCD run all n items of a tile consecutively, so
+// the later items find the neighbourhood in that XCD's L2.  This holds for ANY tile count and item count -- the ranges of the
+// XCDs need not hold whole tiles: where a range ends inside a tile (at most 7 tiles of a launch) that tile's items are
+// shared by two neighbouring XCDs.  With ntiles a multiple of 8, p = xcd * total / 8 + k, i.e. tile position
+// xcd * ntiles / 8 + k / n_items and item k % n_items: what the round-4 form computed (which fell back to item-major order
+// for every other tile count: 1080p's scale-2 and scale-8 stages, every fused stage at 480p).
+__host__ __device__ __forceinline__ void tile_item_order(int b, int tiles_x, int tiles_y, int n_items, int strip_w, int &tx, int &ty,
+                                                         int &item) {
+  const int p = xcd_band(b, tiles_x * tiles_y * n_items);
+  const int i = p / n_items;
+  item = p - i * n_items;
+  strip_walk_tile(i, tiles_x, tiles_y, strip_w, tx, ty);
+}
+// the same for a kernel that knows its grid: gridDim.x == tiles_x * tiles_y * n_items
+__device__ __forceinline__ void tile_item_block(int n_items, int tiles_x, int &tx, int &ty, int &item, int strip_w = kStripW) {
+  tile_item_order(blockIdx.x, tiles_x, gridDim.x / n_items / tiles_x, n_items, strip_w, tx, ty, item);
 }
 
 constexpr int kTileW = 32, kTileH = 8;  // pixels per 256-thread workgroup: a wave covers 32 x 2

@@ -640,8 +640,9 @@ __global__ void __launch_bounds__(256)
 ifblock_input_lds(const StageItems items, const FlowTermsArg T, int hp, int wp, float inv_prev_scale, float prev_scale, int H, int W,
                   int h, int w, float scale, int n_items) {
   constexpr bool FOLD = FMODE != 0, WRITES = FMODE == 1, LAZY = FMODE == 2;
-  int vb_, vitem_, ntiles_;
-  tile_item_block(n_items, vb_, vitem_, ntiles_);  // one grid dimension: the items of a tile back to back on one XCD
+  constexpr int TWo = SINGLE ? 32 : 16, THo = SINGLE ? 8 : 4;
+  int tx, ty, vitem_;
+  tile_item_block(n_items, (w + TWo - 1) / TWo, tx, ty, vitem_);  // one grid dimension: the items of a tile back to back on one XCD
   DRBA_UNPACK_STAGE_ITEM_AT(items, vitem_);
   float *__restrict__ flow_out = item_.flow_out;
   // [row][column][16]: the 13 channels of a footprint pixel (padded to 16) are four 16-byte LDS words, so a sample point
@@ -652,12 +653,8 @@ ifblock_input_lds(const StageItems items, const FlowTermsArg T, int hp, int wp, 
   constexpr int STG = VS ? (SINGLE ? 4 * 64 : 52 * 16 + 4 * 64) : 1;  // floats per wave
   __shared__ __attribute__((aligned(16))) float stg_all[4 * STG];
   constexpr int LPO = SINGLE ? 1 : 4;
-  constexpr int TWo = SINGLE ? 32 : 16, THo = SINGLE ? 8 : 4;
   constexpr int C0 = FOLD ? 0 : 4;  // first channel of tmp_prev that is needed
   const size_t P = (size_t)H * W, p_lo = (size_t)h * w, p_prev = (size_t)hp * wp;
-  const int tiles_x = (w + TWo - 1) / TWo;
-  int tx, ty;
-  xcd_strip_tile(vb_, ntiles_, tiles_x, tx, ty);
   // footprint of this workgroup's sample points in tmp_prev (same for every lane: computed from the tile corners)
   const int ox_a = tx * TWo, oy_a = ty * THo;
   const int ox_b = min(ox_a + TWo - 1, w - 1), oy_b = min(oy_a + THo - 1, h - 1);
@@ -932,8 +929,8 @@ struct BlendItems {
 template <bool LAZY, bool S1 = false>
 __global__ void __launch_bounds__(256)
 warp_blend_fold_kernel(const BlendItems items, const FlowTermsArg T, int h, int w, float inv_scale, float scale, int H, int W, int n_items) {
-  int vb_, vitem_, ntiles_;
-  tile_item_block(n_items, vb_, vitem_, ntiles_);  // one grid dimension: the items of a tile back to back on one XCD
+  int tx, ty, vitem_;
+  tile_item_block(n_items, (W + kTileW - 1) / kTileW, tx, ty, vitem_); // one grid dimension: the items of a tile back to back on one XCD, for any tile count (common.hpp)
   const float *__restrict__ img0 = items.img0[vitem_], *__restrict__ img1 = items.img1[vitem_];
   const float *__restrict__ flow = items.flow[vitem_], *__restrict__ tmp = items.tmp[vitem_];
   const float *__restrict__ img0x = items.img0x[vitem_], *__restrict__ img1x = items.img1x[vitem_];
@@ -942,9 +939,6 @@ warp_blend_fold_kernel(const BlendItems items, const FlowTermsArg T, int h, int 
   __shared__ __attribute__((aligned(16))) float tl[LAZY ? kMaxTerms * 4 * kWbTermR * kWbTermC : 4];
   int trx0[kMaxTerms], try0[kMaxTerms];
   const size_t P = (size_t)H * W, p_lo = (size_t)h * w;
-  const int tiles_x = (W + kTileW - 1) / kTileW;
-  int tx, ty;
-  xcd_strip_tile(vb_, ntiles_, tiles_x, tx, ty);
   const int Xa = tx * kTileW, Ya = ty * kTileH, Xb = min(Xa + kTileW - 1, W - 1), Yb = min(Ya + kTileH - 1, H - 1);
   const int x = Xa + (threadIdx.x & (kTileW - 1)), y = Ya + (threadIdx.x >> 5);
   const size_t p = (size_t)min(y, H - 1) * W + min(x, W - 1);

@@ -102,8 +102,8 @@ stage_conv0(const StageItems items, const FlowTermsArg T, const float *__restric
   float *win = lds + G_::WL;               // [2][4][CS]
   float *prev = win + 2 * 4 * CS;          // [PR][PC][16]: a footprint pixel's 13 channels as four 16-byte words (flow | mask | feat 0..3 | feat 4..7)
   float *tl = prev + 16 * PR * PC;         // [kMaxTerms][TR * TC][4]
-  int vb_, vitem_, ntiles_;
-  tile_item_block(n_items, vb_, vitem_, ntiles_);  // one grid dimension: the items of a tile back to back on one XCD (common.hpp)
+  int tx, ty, vitem_;
+  tile_item_block(n_items, tiles_x, tx, ty, vitem_); // one grid dimension: the items of a tile back to back on one XCD, for any tile count (common.hpp)
   // the item is picked by the block id out of the by-value argument: the compiler does not see that its fields are
   // wave-uniform (it would address every load per lane and wrap every buffer load in a waterfall loop) -- state it
   typedef __attribute__((address_space(1))) float *gptr;
@@ -130,8 +130,6 @@ stage_conv0(const StageItems items, const FlowTermsArg T, const float *__restric
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t P = (size_t)H * W, p_prev = (size_t)hp * wp;
-  int tx, ty;
-  xcd_strip_tile(vb_, ntiles_, tiles_x, tx, ty);
   const int ox0 = tx * TOW, oy0 = ty * TOH;
   const int X0 = 2 * ox0 - 1, Y0 = 2 * oy0 - 1;  // full-resolution coordinates of window (row 0, column 0)
 

@@ -121,8 +121,8 @@ stage_conv16(const StageItems items, const FlowTermsArg T, const u32x4 *__restri
   u32x4 *wl = lds16 + G_::U_W;                                  // [K step][plane][n tile][64]
   float *prev = reinterpret_cast<float *>(lds16 + G_::U_PREV);  // [PR][PC][16]: flow | mask, - | feat 0..3 | feat 4..7
   float *tl = reinterpret_cast<float *>(lds16 + G_::U_TERM);    // [kMaxTerms][TR * TC][4]
-  int vb_, vitem_, ntiles_;
-  tile_item_block(n_items, vb_, vitem_, ntiles_);  // one grid dimension: the items of a tile back to back on one XCD (common.hpp)
+  int tx, ty, vitem_;
+  tile_item_block(n_items, tiles_x, tx, ty, vitem_); // one grid dimension: the items of a tile back to back on one XCD, for any tile count (common.hpp)
   typedef __attribute__((address_space(1))) float *gptr;
   typedef __attribute__((address_space(1))) const float *cgptr;
   auto uniform = [](const float *p) -> gptr {  // the item is picked by the block id: state that its fields are wave-uniform
@@ -151,8 +151,6 @@ stage_conv16(const StageItems items, const FlowTermsArg T, const u32x4 *__restri
 #endif
   SC16_CLK(0);
   const size_t P = (size_t)H * W, p_prev = (size_t)hp * wp;
-  int tx, ty;
-  xcd_strip_tile(vb_, ntiles_, tiles_x, tx, ty);
   const int ox0 = tx * TOW, oy0 = ty * TOH;
   const int X0 = 2 * ox0 - 1, Y0 = 2 * oy0 - 1;  // full-resolution coordinates of window (row 0, column 0)
 
@@ -527,6 +525,12 @@ stage_conv16(const StageItems items, const FlowTermsArg T, const u32x4 *__restri
 // (point, frame) at a time -- 8 x 16 bytes in flight -- and averaged into the group's 16 values, which are then split and
 // parked exactly as at scale 1.  The flow is given as terms (the lazy form) and the frames as [H][W][4]; anything else takes
 // the unfused pair.  NT = Cout / 16 output tiles per wave (1080p: block 3, 32 channels; 4K scale 0.5: block 4, 16).
+// Strip width of this kernel's tile walk (common.hpp): a tile's sample points cover 30 x 66 full-resolution pixels, four times
+// the scale-1 tile's footprint, so a narrower strip was a candidate.  A build-time constant for same-box A/B of two libraries
+// (`make S2_STRIP_W=4`, tools/ab_lib.sh); the measurements are in profiles/tile_item_order.md.
+#ifndef DRBA_S2_STRIP_W
+#define DRBA_S2_STRIP_W kStripW
+#endif
 template <class G_>
 __global__ void __launch_bounds__(G_::THREADS, 4)
 stage_conv16_s2(const StageItems items, const FlowTermsArg T, const u32x4 *__restrict__ wpk, const float *__restrict__ bias, int hp, int wp,
@@ -539,8 +543,8 @@ stage_conv16_s2(const StageItems items, const FlowTermsArg T, const u32x4 *__res
   u32x4 *wl = lds16 + G_::U_W;
   float *prev = reinterpret_cast<float *>(lds16 + G_::U_PREV);
   float *tl = reinterpret_cast<float *>(lds16 + G_::U_TERM);
-  int vb_, vitem_, ntiles_;
-  tile_item_block(n_items, vb_, vitem_, ntiles_);
+  int tx, ty, vitem_;
+  tile_item_block(n_items, tiles_x, tx, ty, vitem_, DRBA_S2_STRIP_W);
   typedef __attribute__((address_space(1))) float *gptr;
   typedef __attribute__((address_space(1))) const float *cgptr;
   auto uniform = [](const float *p) -> gptr {
@@ -564,8 +568,6 @@ stage_conv16_s2(const StageItems items, const FlowTermsArg T, const u32x4 *__res
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const size_t P = (size_t)H * W, p_prev = (size_t)hp * wp;
-  int tx, ty;
-  xcd_strip_tile(vb_, ntiles_, tiles_x, tx, ty);
   const int ox0 = tx * TOW, oy0 = ty * TOH;
   const int xs0 = 2 * ox0 - 1, ys0 = 2 * oy0 - 1;  // stage (half-resolution) coordinates of window (row 0, column 0)
 

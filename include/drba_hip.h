@@ -32,7 +32,8 @@ extern "C" {
 #define DRBA_EUNSUPPORTED (-2) /* shape/config outside what the kernels were built for */
 #define DRBA_ELAUNCH (-3)  /* hipGetLastError() reported a launch failure */
 
-/* ABI version.  11: 16-bit frames -- drba_to_inp16_x4 / drba_to_out16 / drba_u16hwc_to_f32nchw / drba_f32nchw_to_u16hwc (uint16 HWC frames
+/* ABI version.  12: drba_tile_item_order (host function: the workgroup -> (tile, item) order of the batched stage launches): an
+ * addition only, no earlier entry changes.  11: 16-bit frames -- drba_to_inp16_x4 / drba_to_out16 / drba_u16hwc_to_f32nchw / drba_f32nchw_to_u16hwc (uint16 HWC frames
  * with an explicit maxval; the way out rounds to nearest even and saturates) and drba_frame_error_u16 / drba_frame_error_u16_ws_floats:
  * additions only, no earlier entry changes.  10: drba_ssim3d / drba_ssim3d_ws_floats (ssim_matlab at full size, fp64 accumulation) and drba_frame_error_u8 /
  * drba_frame_error_f32 / drba_frame_error_ws_floats (exact frame differences): additions only, no earlier entry changes.
@@ -51,7 +52,7 @@ extern "C" {
  * workspace that must be ZERO on entry (they leave it zero on return: self-cleaning accumulator) instead of clearing it
  * themselves; batched stage entry points added; drba_conv3x3_cfg_family added and configuration ids 19 (LDS-DMA, 32
  * channels) / 20 (K split across waves) behind drba_conv3x3; the allocation exception above.  1: the first release. */
-#define DRBA_ABI_VERSION 11  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
+#define DRBA_ABI_VERSION 12  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
 int drba_abi_version(void);
 const char *drba_error_string(int code);
 /* ABI 6, debug: with the range check on, every entry point that ran a kernel of family 4 (two fp16 terms per operand:
@@ -428,6 +429,12 @@ int drba_stage_conv16_pack(const float *w, int Cout, float *packed);
 int drba_stage_conv16_supported(int H, int W, float scale, float prev_scale, int Cout);
 int drba_stage_conv16_batch(const drba_stage_item_t *items, int n_items, const drba_flow_terms_t *terms, int hp, int wp, float prev_scale,
                             int H, int W, float scale, int Cout, const float *packed_w, const float *bias, void *stream);
+/* ABI 12, HOST function (no GPU, no stream), for tests and tools: which output tile (*tx, *ty) and which item workgroup `block`
+ * of the tiles_x * tiles_y * n_items of a batched stage launch computes (drba_stage_conv16_batch, drba_stage_conv0_batch,
+ * drba_ifblock_input_lds_batch / _lazy_batch, drba_warp_blend_lazy_batch).  Workgroup b runs on XCD b % 8; the order hands
+ * every XCD a contiguous range of (tile, item) pairs in which the items of a tile follow each other, for any tile count and
+ * any item count, the tiles walked in strips of strip_w columns (the kernels run 8).  A bijection of [0, total). */
+int drba_tile_item_order(int block, int tiles_x, int tiles_y, int n_items, int strip_w, int *tx, int *ty, int *item);
 /* drba_ifblock_update for several items (arrays of n_items device pointers; flow_in may be NULL or hold NULLs). */
 int drba_ifblock_update_batch(const float *const *tmp, const float *const *flow_in, float *const *flow_out, int n_items,
                               int h, int w, int H, int W, float scale, void *stream);
