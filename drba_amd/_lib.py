@@ -68,6 +68,9 @@ SIGNATURES = {
     "drba_flow_reverse": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "drba_drm_rife_linear": (_i, [_p, _p, _f, _p, _f, _p, _p, _i, _i, _i, _p]),
     "drba_drm_rife_linear_batch": (_i, [_p, _i, _f, _p, _i, _i, _p]),
+    "drba_drm_walk": (_i, [_d, _d, C.POINTER(C.c_uint32), C.POINTER(_i)]),
+    "drba_drm_rife_nonlinear": (_i, [_p, _p, _d, _d, _f, _p, _p, _i, _i, _i, _p]),
+    "drba_drm_rife_nonlinear_batch": (_i, [_p, _i, _d, _f, _p, _i, _i, _p]),
     "drba_drm_ratio": (_i, [_p, _p, _f, _p, _p, _i, _i, _i, _p]),
     "drba_affine": (_i, [_p, _f, _f, _p, _z, _p]),
     "drba_mul_map": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
@@ -174,6 +177,11 @@ class StageItem(C.Structure):
 class DrmJob(C.Structure):
     """include/drba_hip.h: drba_drm_job_t"""
     _fields_ = [("flow_self", C.c_void_p), ("flow_other", C.c_void_p), ("t", C.c_float), ("out", C.c_void_p)]
+
+
+class DrmNonlinearJob(C.Structure):
+    """include/drba_hip.h: drba_drm_nonlinear_job_t"""
+    _fields_ = [("flow_self", C.c_void_p), ("flow_other", C.c_void_p), ("t", C.c_double), ("out", C.c_void_p)]
 
 
 MAX_FLOW_TERMS = 4  # DRBA_MAX_FLOW_TERMS

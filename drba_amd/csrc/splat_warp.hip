@@ -95,6 +95,8 @@ __device__ __forceinline__ void scatter_avg(float *__restrict__ acc, int x, int 
 //                             out = 2 * (hole ? max(H,W) : -avg)
 //   MODE 1 (drm.py:65-107)  : value = u = d_other/(d_self+d_other)*t*2, splat flow = self*u;
 //                             out = hole ? u : avg
+//   MODE 2 (drm.py:65-107, linear=False): r = d_other/(d_self+d_other), value = u = get_drm_t(r, t) (drm.py:10-62),
+//                             splat flow = self*u; out = hole ? u : avg -- everything after u is MODE 1's code
 // A workgroup owns a TX x TY output tile whose accumulators live in LDS.  It visits every source
 // pixel within R of the tile and adds the corners that land inside the tile with ds_add_f32 --
 // no global atomics for "short" flows (all four corners within R of the source).  The rare
@@ -104,6 +106,34 @@ __device__ __forceinline__ void scatter_avg(float *__restrict__ acc, int x, int 
 #define DRBA_SPLAT_R 16
 #endif
 constexpr int kRMax = DRBA_SPLAT_R;  // largest tile halo: sources with longer flows take the global-atomic pre-pass
+
+// |flow| as drm_ratio_kernel rounds it: one product, then one fused multiply-add.  Written out (and shared with that kernel) because
+// the non-linear DRM's u must equal drm_retime(drm_ratio(...)) bit for bit, and left to the compiler `u * u + v * v` becomes this in
+// one kernel and two packed products and an add in another.
+__device__ __forceinline__ float flow_length(float u, float v) {
+#pragma clang fp contract(off)
+  return sqrtf(__builtin_fmaf(u, u, v * v));
+}
+
+// get_drm_t's map updates for one element (drm.py:44-59).  The scalar bracket walk is data independent: the host runs it once, in
+// double (drba_drm_walk), and hands the kernel its moves -- bit k of `moves` set: move k is the `_x < t` update, clear: the `_x > t`
+// update -- and their number.  Both are uniform over a job, so the loop and its branches are scalar; a lane pays one multiply and two
+// subtractions per move (at most 9 at the model's precision).  Product and difference round separately, as the reference's tensor
+// expressions and drm_retime_kernel do: the result equals drm_retime_kernel's bit for bit.
+__device__ __forceinline__ float drm_walk_apply(float fm, unsigned moves, int n_moves) {
+#pragma clang fp contract(off)
+  float xm = fm, lom = xm * 0.f, him = xm * 0.f + 1.f;
+  for (int k = 0; k < n_moves; ++k) {
+    if ((moves >> k) & 1u) {
+      lom = xm;
+      xm = xm + (him - xm) * fm;
+    } else {
+      him = xm;
+      xm = xm - (xm - lom) * fm;
+    }
+  }
+  return xm;
+}
 
 template <int MODE>
 struct SplatSrc {
@@ -115,7 +145,7 @@ struct SplatSrc {
 // value and splat flow of a source from its raw flow vectors (su, sv) [and (ou, ov) of the other direction]
 template <int MODE>
 __device__ __forceinline__ SplatSrc<MODE> splat_source_from(float su, float sv, float ou, float ov, int x, int y, float t,
-                                                            float eps) {
+                                                            float eps, unsigned moves, int n_moves) {
   SplatSrc<MODE> s;
   if (MODE == 0) {
     s.v[0] = su;
@@ -123,8 +153,9 @@ __device__ __forceinline__ SplatSrc<MODE> splat_source_from(float su, float sv, 
     s.fx = su;
     s.fy = sv;
   } else {
-    const float ds = sqrtf(su * su + sv * sv) + eps, d_o = sqrtf(ou * ou + ov * ov) + eps;
-    const float u = (d_o / (ds + d_o)) * t * 2.f;
+    const float ds = (MODE == 2 ? flow_length(su, sv) : sqrtf(su * su + sv * sv)) + eps;
+    const float d_o = (MODE == 2 ? flow_length(ou, ov) : sqrtf(ou * ou + ov * ov)) + eps;
+    const float u = MODE == 1 ? (d_o / (ds + d_o)) * t * 2.f : drm_walk_apply(d_o / (ds + d_o), moves, n_moves);
     s.v[0] = u;
     s.v[1] = 0.f;
     s.fx = su * u;
@@ -139,25 +170,39 @@ __device__ __forceinline__ SplatSrc<MODE> splat_source_from(float su, float sv, 
 
 template <int MODE>
 __device__ __forceinline__ SplatSrc<MODE> splat_source(const float *__restrict__ fs, const float *__restrict__ fo,
-                                                       size_t P, size_t p, int x, int y, float t, float eps) {
+                                                       size_t P, size_t p, int x, int y, float t, float eps, unsigned moves,
+                                                       int n_moves) {
   const float su = fs[p], sv = fs[P + p];
   float ou = 0.f, ov = 0.f;
   if (MODE != 0) {
     ou = fo[p];
     ov = fo[P + p];
   }
-  return splat_source_from<MODE>(su, sv, ou, ov, x, y, t, eps);
+  return splat_source_from<MODE>(su, sv, ou, ov, x, y, t, eps, moves, n_moves);
 }
 
 // Several (flow_self, flow_other, t) -> out jobs of ONE geometry in one launch (drba_drm_rife_linear_batch): the DRM maps of a
 // group of steps were 2 launches each, 16 dependent launches of 20-55 us per group with ~6.5 us between them.  n == 0: the
-// single-tensor form (items contiguous along N).
+// single-tensor form (items contiguous along N).  MODE 2: moves / n_moves are job k's retime walk (drm_walk_apply); the single-tensor
+// form carries its one walk in entry 0.
 struct SplatJobs {
   int n;
   const float *fs[DRBA_MAX_STAGE_ITEMS], *fo[DRBA_MAX_STAGE_ITEMS];
   float t[DRBA_MAX_STAGE_ITEMS];
   float *out[DRBA_MAX_STAGE_ITEMS];
+  unsigned moves[DRBA_MAX_STAGE_ITEMS];
+  int n_moves[DRBA_MAX_STAGE_ITEMS];
 };
+
+// the walk of item n of a launch: kernel arguments indexed by the workgroup's z, i.e. scalar registers
+template <int MODE>
+__device__ __forceinline__ void splat_walk_of(const SplatJobs &jobs, int n, unsigned &moves, int &n_moves) {
+  moves = 0, n_moves = 0;
+  if (MODE == 2) {
+    const int k = jobs.n ? n : 0;
+    moves = jobs.moves[k], n_moves = jobs.n_moves[k];
+  }
+}
 
 // Workspace of the two fused splats (drba_rife_splat_ws_floats): [kReachWords ints: the reach map, scratch -- any content on entry
 // and on return][accumulators [N][P][NV + 1], zero on entry and on return][one dirty flag per (item, tile), zero on entry and on return].
@@ -177,6 +222,9 @@ __global__ void __launch_bounds__(256) splat_long_prepass(const float *__restric
   if (t_dev) t = *t_dev;  // timestep from device memory: lets one captured HIP graph serve every t
   const int n = blockIdx.z;
   const size_t P = (size_t)H * W;
+  unsigned moves;
+  int n_moves;
+  splat_walk_of<MODE>(jobs, n, moves, n_moves);
   if (jobs.n) {
     fs = jobs.fs[n], fo = jobs.fo[n], t = jobs.t[n];
   } else {
@@ -195,7 +243,7 @@ __global__ void __launch_bounds__(256) splat_long_prepass(const float *__restric
     const int x = blockIdx.x * 32 + (tid & 31), y = blockIdx.y * 16 + (tid >> 5) + 8 * i;
     if (x >= W || y >= H) continue;
     const size_t p = (size_t)y * W + x;
-    const SplatSrc<MODE> s = splat_source<MODE>(fs, fo, P, p, x, y, t, eps);
+    const SplatSrc<MODE> s = splat_source<MODE>(fs, fo, P, p, x, y, t, eps, moves, n_moves);
     if (!s.finite) continue;
     if (s.is_short) {
       // fx in [-R, R - 1)  <=>  R >= -fx and R > fx + 1
@@ -236,8 +284,8 @@ constexpr int kCAP = 1536;                              // records held in LDS (
 // R: the halo this tile scans (kR, or less where the reach map allows it)
 template <int MODE, int R>
 __device__ __forceinline__ void splat_tile_body(const float *__restrict__ fs, const float *__restrict__ fo, float t, float eps,
-                                                float *gacc, int *dirty, float *__restrict__ out, int H, int W, int *cnt,
-                                                int *wsum, float4 *rec, int *spilled_) {
+                                                unsigned moves, int n_moves, float *gacc, int *dirty, float *__restrict__ out,
+                                                int H, int W, int *cnt, int *wsum, float4 *rec, int *spilled_) {
   constexpr int NV = MODE == 0 ? 2 : 1;
   constexpr int kSWX = kSX + 2 * R, kSWY = kSY + 2 * R;  // source window
   constexpr int kSPT = (kSWX * kSWY + 255) / 256;        // window sources per thread
@@ -277,7 +325,7 @@ __device__ __forceinline__ void splat_tile_body(const float *__restrict__ fs, co
     const int y = ty0 - kR + ry, x = tx0 - kR + rx;
     if (e >= kSWX * kSWY || x < 0 || x >= W || y < 0 || y >= H) continue;
     const SplatSrc<MODE> sp = splat_source_from<MODE>(raw[i][0], raw[i][1], MODE == 0 ? 0.f : raw[i][2],
-                                                      MODE == 0 ? 0.f : raw[i][3], x, y, t, eps);
+                                                      MODE == 0 ? 0.f : raw[i][3], x, y, t, eps, moves, n_moves);
     if (!sp.finite || !sp.is_short) continue;
     const float X = (float)x + sp.fx, Y = (float)y + sp.fy;
     const int kx = (int)floorf(X) - tx0 + 1, ky = (int)floorf(Y) - ty0 + 1;
@@ -399,7 +447,7 @@ __device__ __forceinline__ void splat_tile_body(const float *__restrict__ fs, co
     } else {
       a0 += g0;
       float o = a0 / nrm;
-      if (gap) o = splat_source<MODE>(fs, fo, P, p, x, y, t, eps).v[0];  // the unaligned value for holes (rare: not loaded otherwise)
+      if (gap) o = splat_source<MODE>(fs, fo, P, p, x, y, t, eps, moves, n_moves).v[0];  // the unaligned value for holes (rare: not loaded otherwise)
       out[p] = o;
     }
   }
@@ -418,6 +466,9 @@ __global__ void __launch_bounds__(256) splat_tiled(const float *__restrict__ fs,
   static_assert(kSX == 32 && kSY == 16, "scatter_avg and the pre-pass work on 32 x 16 tiles");
   const int n = blockIdx.z;
   const size_t P = (size_t)H * W;
+  unsigned moves;
+  int n_moves;
+  splat_walk_of<MODE>(jobs, n, moves, n_moves);
   if (jobs.n) {
     fs = jobs.fs[n], fo = jobs.fo[n], t = jobs.t[n], out = jobs.out[n];
   } else {
@@ -446,9 +497,9 @@ __global__ void __launch_bounds__(256) splat_tiled(const float *__restrict__ fs,
       }
     r = __builtin_amdgcn_readfirstlane(r);
   }
-  if (r <= 4) splat_tile_body<MODE, 4>(fs, fo, t, eps, gacc, dirty, out, H, W, cnt, wsum, rec, &spilled);
-  else if (r <= 8) splat_tile_body<MODE, 8>(fs, fo, t, eps, gacc, dirty, out, H, W, cnt, wsum, rec, &spilled);
-  else splat_tile_body<MODE, kRMax>(fs, fo, t, eps, gacc, dirty, out, H, W, cnt, wsum, rec, &spilled);
+  if (r <= 4) splat_tile_body<MODE, 4>(fs, fo, t, eps, moves, n_moves, gacc, dirty, out, H, W, cnt, wsum, rec, &spilled);
+  else if (r <= 8) splat_tile_body<MODE, 8>(fs, fo, t, eps, moves, n_moves, gacc, dirty, out, H, W, cnt, wsum, rec, &spilled);
+  else splat_tile_body<MODE, kRMax>(fs, fo, t, eps, moves, n_moves, gacc, dirty, out, H, W, cnt, wsum, rec, &spilled);
 }
 
 
@@ -680,8 +731,8 @@ __global__ void __launch_bounds__(256) drm_ratio_kernel(const float *__restrict_
   f10 += (size_t)n * 2 * P;
   f12 += (size_t)n * 2 * P;
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (size_t)gridDim.x * blockDim.x) {
-    float a = sqrtf(f10[p] * f10[p] + f10[P + p] * f10[P + p]);
-    float b = sqrtf(f12[p] * f12[p] + f12[P + p] * f12[P + p]);
+    float a = flow_length(f10[p], f10[P + p]);
+    float b = flow_length(f12[p], f12[P + p]);
     if (eps != 0.f) {
       a += eps;
       b += eps;
@@ -924,6 +975,70 @@ int drba_drm_rife_linear_batch(const drba_drm_job_t *jobs, int n_jobs, float eps
   DRBA_LAUNCH(splat_long_prepass<1>, g, dim3(kBlock), 0, s, J.fs[0], J.fo[0], 0.f, (const float *)nullptr, eps, ws,
               H, W, J);
   DRBA_LAUNCH(splat_tiled<1>, g, dim3(kBlock), 0, s, J.fs[0], J.fo[0], 0.f, (const float *)nullptr, eps, ws, J.out[0], H, W, J);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+// get_drm_t's scalar walk (drm.py:36-37, :43-56), run literally in double: `_x > t` moves the upper bracket down (bit clear), `_x < t`
+// the lower one up (bit set); both may fire in one iteration, the precision test is made at the top of an iteration only.
+int drba_drm_walk(double t, double precision, uint32_t *moves, int *n_moves) {
+#pragma clang fp contract(off)
+  if (!moves || !n_moves || !(precision > 0)) return DRBA_EINVAL;
+  double x = 0.5, l = 0.0, r = 1.0;
+  const double b = 0.5;
+  uint32_t m = 0;
+  int n = 0;
+  while (fabs(x - t) > precision) {
+    if (x > t) {
+      if (n == 32) return DRBA_EUNSUPPORTED;
+      r = x;
+      x = x - (x - l) * b;
+      ++n;
+    }
+    if (x < t) {
+      if (n == 32) return DRBA_EUNSUPPORTED;
+      l = x;
+      x = x + (r - x) * b;
+      m |= 1u << n;
+      ++n;
+    }
+  }
+  *moves = m;
+  *n_moves = n;
+  return DRBA_OK;
+}
+
+int drba_drm_rife_nonlinear(const float *flow_self, const float *flow_other, double t, double precision, float eps, float *out,
+                            float *ws, int N, int H, int W, void *stream) {
+  if (!flow_self || !flow_other || !out || !ws || N <= 0 || H <= 0 || W <= 0 || !(precision > 0)) return DRBA_EINVAL;
+  SplatJobs one;
+  memset(&one, 0, sizeof(one));  // n == 0: the single-tensor form, its walk in entry 0
+  const int rc = drba_drm_walk(t, precision, &one.moves[0], &one.n_moves[0]);
+  if (rc != DRBA_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 g((W + kSX - 1) / kSX, (H + kSY - 1) / kSY, N);
+  DRBA_LAUNCH(splat_long_prepass<2>, g, dim3(kBlock), 0, s, flow_self, flow_other, 0.f, (const float *)nullptr, eps, ws, H, W, one);
+  DRBA_LAUNCH(splat_tiled<2>, g, dim3(kBlock), 0, s, flow_self, flow_other, 0.f, (const float *)nullptr, eps, ws, out, H, W, one);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+int drba_drm_rife_nonlinear_batch(const drba_drm_nonlinear_job_t *jobs, int n_jobs, double precision, float eps, float *ws, int H,
+                                  int W, void *stream) {
+  if (!jobs || n_jobs <= 0 || n_jobs > DRBA_MAX_STAGE_ITEMS || !ws || H <= 0 || W <= 0 || !(precision > 0)) return DRBA_EINVAL;
+  SplatJobs J;
+  memset(&J, 0, sizeof(J));
+  J.n = n_jobs;
+  for (int k = 0; k < n_jobs; ++k) {
+    if (!jobs[k].flow_self || !jobs[k].flow_other || !jobs[k].out) return DRBA_EINVAL;
+    J.fs[k] = jobs[k].flow_self, J.fo[k] = jobs[k].flow_other, J.out[k] = jobs[k].out;
+    const int rc = drba_drm_walk(jobs[k].t, precision, &J.moves[k], &J.n_moves[k]);
+    if (rc != DRBA_OK) return rc;  // (nothing launched yet)
+  }
+  hipStream_t s = (hipStream_t)stream;
+  dim3 g((W + kSX - 1) / kSX, (H + kSY - 1) / kSY, n_jobs);
+  DRBA_LAUNCH(splat_long_prepass<2>, g, dim3(kBlock), 0, s, J.fs[0], J.fo[0], 0.f, (const float *)nullptr, eps, ws, H, W, J);
+  DRBA_LAUNCH(splat_tiled<2>, g, dim3(kBlock), 0, s, J.fs[0], J.fo[0], 0.f, (const float *)nullptr, eps, ws, J.out[0], H, W, J);
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }

@@ -35,7 +35,7 @@ class SceneCuts:
 
 
 def run(model, get, pair, first, to_inp, emit, cuts, ts_of, state=(False, None), head=True, tail=True, on_step=None,
-        announce_ungrouped=False):
+        announce_ungrouped=False, linear=True):
     """Drive the model from loop iteration `first` until the frame source ends.
 
     get(k): raw source frame k, or None past the end (not asked again after that).  pair: [I0, I1], the network inputs of
@@ -45,6 +45,9 @@ def run(model, get, pair, first, to_inp, emit, cuts, ts_of, state=(False, None),
     ts_of(idx) -> tools.calc_t of iteration idx.  state: (cut_left, reuse) entering iteration `first` when there is no head
     (the head is a cold start and tests the first pair itself).  on_step(idx) fires after the head (idx = first), after
     every iteration and after the tail.  announce_ungrouped: name the following iterations to a GROUP = 1 model too.
+    linear: the `linear` of every inference_ts_drba call -- True, the reference driver's (infer.py:143); False runs the clip
+    through the non-linear DistanceRatioMap (get_drm_t), which the reference's model entry point defaults to but its driver never
+    asks for.
 
     Schedule quirks kept from the reference: calc_t is evaluated at an index one behind the centre frame
     in the loop and tail (infer.py:118,159); the left/right split uses `ts < 1` when the left pair is unusable and `ts <= 1`
@@ -149,9 +152,9 @@ def run(model, get, pair, first, to_inp, emit, cuts, ts_of, state=(False, None),
                     prev = x
                 if len(entries) >= 4:
                     look = tuple(entries)
-            out, reuse = model.inference_ts_drba(I0, I1, I2, ts, reuse, linear=True, lookahead=look)
+            out, reuse = model.inference_ts_drba(I0, I1, I2, ts, reuse, linear=linear, lookahead=look)
         else:
-            out, reuse = model.inference_ts_drba(I0, I1, I2, ts, reuse, linear=True)
+            out, reuse = model.inference_ts_drba(I0, I1, I2, ts, reuse, linear=linear)
         emit(out)
         I0, I1, cut_left = I1, I2, cut_right
         I2 = ahead.pop(0) if ahead else (read() if depth == 0 else None)

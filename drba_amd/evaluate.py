@@ -227,15 +227,19 @@ class _HoldoutIO:
 
 
 def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.3, plain=False, backend=None, to_inp=None,
-            to_out=None, check_scene=None, maxval=None):
+            to_out=None, check_scene=None, maxval=None, linear=True):
     """Keep every k-th frame of `frames` (uint8 [N,H,W,3], indexable), let interpolate_stream fill the gaps at `times = k`
     and compare every emission with the original frame at its position.  -> {"k", "m", "frames_used", "emissions",
     "pairs": [(emission, original)], "kept": ClipMetrics.result() + "positions", "held_out": the same}.
     to_inp / to_out / check_scene / backend: the hooks of interpolate_stream and of drba_amd.metrics (defaults: the device
     ones, with the emitted frames staying on the device).
     uint16 frames (samples in [0, maxval], 65535 unless given): the default hooks read and emit 16 bits at that maxval and the
-    emissions are compared with the 16-bit originals in their own steps; the result carries "depth": 16 and "maxval"."""
+    emissions are compared with the 16-bit originals in their own steps; the result carries "depth": 16 and "maxval".
+    linear=False: every DRBA step of the run with the non-linear DistanceRatioMap (infer.py --nonlinear); not together with
+    `plain`, whose steps have no DistanceRatioMap at all.  The result carries "linear"."""
     from drba_amd import infer as drv
+    if plain and not linear:
+        raise ValueError("--nonlinear and --plain exclude each other: a plain step is inference_ts, it has no DistanceRatioMap to retime")
     m, half = holdout_plan(len(frames), k)
     deep = getattr(frames, "dtype", None) == np.uint16
     if maxval is not None and not deep:
@@ -256,11 +260,13 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
     io = _HoldoutIO(frames, int(k), m, half, fps, kept, held)
     run = PlainSteps(model) if plain else model
     written = drv.interpolate_stream(run, io, float(fps) * int(k), times=int(k), enable_scdet=enable_scdet,
-                                     scdet_threshold=scdet_threshold, to_inp=to_inp, to_out=to_out, check_scene=check_scene)
+                                     scdet_threshold=scdet_threshold, to_inp=to_inp, to_out=to_out, check_scene=check_scene,
+                                     linear=bool(linear))
     if written != int(k) * (m + 1) or len(io.skipped) != 2 * half:
         raise RuntimeError(f"hold-out at k = {k}: the run emitted {written} frames ({len(io.skipped)} without an original), "
                            f"expected {int(k) * (m + 1)} ({2 * half})")
-    out = {"k": int(k), "m": m, "frames_used": m * int(k) + 1, "emissions": written, "plain": bool(plain), "pairs": io.pairs}
+    out = {"k": int(k), "m": m, "frames_used": m * int(k) + 1, "emissions": written, "plain": bool(plain), "linear": bool(linear),
+           "pairs": io.pairs}
     if deep:
         out.update({"depth": 16, "maxval": mv})
     for name, cm in (("kept", kept), ("held_out", held)):
@@ -275,7 +281,7 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
 def holdout_report(res):
     """The JSON object of `holdout` without the per-frame lists."""
     rep = {"command": "holdout", "k": res["k"], "m": res["m"], "frames_used": res["frames_used"], "emissions": res["emissions"],
-           "plain": res["plain"]}
+           "plain": res["plain"], "linear": res["linear"]}
     if "depth" in res:
         rep.update({"depth": res["depth"], "maxval": res["maxval"]})
     for name in ("kept", "held_out"):
@@ -305,6 +311,7 @@ def parse_args(argv=None):
     h.add_argument("-s", "--enable_scdet", dest="enable_scdet", action="store_true", default=False)
     h.add_argument("-st", "--scdet_threshold", dest="scdet_threshold", type=float, default=0.3)
     h.add_argument("--plain", action="store_true", help="plain inference_ts in place of every DRBA step (the baseline)")
+    h.add_argument("--nonlinear", action="store_true", help="every DRBA step with the non-linear DistanceRatioMap (linear=False); not with --plain")
     h.add_argument("--weights", type=str, default=None, help="weight directory (default: the model's, synthetic if absent)")
     h.add_argument("--json", dest="json_path", type=str, default=None)
     return p.parse_args(argv)
@@ -332,6 +339,8 @@ def main(argv=None, backend=None):
         if not src.random_access:
             raise ValueError("a hold-out needs random access to the clip: use a .npz / .npy source")
         holdout_plan(len(src), args.k)  # refuse before a model is loaded
+        if args.plain and args.nonlinear:
+            raise ValueError("--nonlinear and --plain exclude each other: a plain step is inference_ts, it has no DistanceRatioMap to retime")
         from drba_amd import infer as drv
         from drba_amd import tune, tunecache
         tunecache.default_on()  # a command line: the conv autotuner's winners are kept across runs unless DRBA_TUNE_CACHE=0
@@ -340,7 +349,7 @@ def main(argv=None, backend=None):
         model = drv.load_model(args.model_type, scale=args.scale,
                                weights=tune._synthetic_weights(args.model_type) if synthetic else wdir)
         res = holdout(model, src._frames, args.k, fps=src.fps, enable_scdet=args.enable_scdet,
-                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend,
+                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend, linear=not args.nonlinear,
                       **({"maxval": src.maxval} if src.depth == 16 else {}))
         rep = holdout_report(res)
         rep.update({"model": args.model_type, "scale": args.scale, "input": args.input,

@@ -1,9 +1,12 @@
 """DRBA command line and per-frame driver loop (same CLI as the reference's infer.py).
 
     python infer.py -m rife -i in.npz -o out.npz [-fps 60 | -t 2] [-s] [-st 0.3] [-hw] [-scale 1.0] [--out-depth source|8|16]
+                    [--nonlinear]
 
 `--out-depth` is not in the reference: a .npz / .npy clip may hold uint16 frames, and the written frames are 8 or 16 bits deep
-(default: as the source, so an 8-bit clip is handled exactly as before).
+(default: as the source, so an 8-bit clip is handled exactly as before).  `--nonlinear` is not in the reference either: its driver
+always asks the model for linear=True (infer.py:143) although the model entry point defaults to the non-linear DistanceRatioMap
+(get_drm_t); with the flag every DRBA step of the clip runs with linear=False.
 
 The driver logic is host-side Python like the reference; the model calls it makes run on
 the HIP library.  `interpolate_stream` is the loop of reference infer.py:58-174 (drba_amd/driver.py) with the
@@ -37,6 +40,8 @@ def parse_args(argv=None):
     p.add_argument("--out-depth", dest="out_depth", type=str, default="source", choices=("source", "8", "16"),
                    help="bits per sample of the written frames: the source's (default), 8, or 16 (uint16 .npz / .npy, rgb48le raw, "
                         "libx264 yuv420p10le; not with -hw, not in the frame-sharded run)")
+    p.add_argument("--nonlinear", dest="nonlinear", action="store_true", default=False,
+                   help="run every DRBA step with the non-linear DistanceRatioMap (inference_ts_drba(..., linear=False))")
     return p.parse_args(argv)
 
 
@@ -66,8 +71,9 @@ def load_model(model_type, scale=1.0, device=None, weights=None):
 
 
 def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, scdet_threshold=0.3,
-                       to_inp=None, to_out=None, check_scene=None, on_step=None):
-    """Run the whole clip: drba_amd.driver.run from a cold start, head and tail included.  Returns the number of frames written."""
+                       to_inp=None, to_out=None, check_scene=None, on_step=None, linear=True):
+    """Run the whole clip: drba_amd.driver.run from a cold start, head and tail included.  Returns the number of frames written.
+    linear=False: every DRBA step with the non-linear DistanceRatioMap (--nonlinear)."""
     to_inp = to_inp or _tools.to_inp
     to_out = to_out or _tools.to_out
     src_fps = video_io.src_fps
@@ -88,7 +94,7 @@ def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, s
     mapper = _tools.TMapper(src_fps, dst_fps, times)
     driver.run(model, lambda k: video_io.read_frame(), [to_inp(i0, dst_size), to_inp(i1, dst_size)], 0,
                to_inp=lambda raw: to_inp(raw, dst_size), emit=emit, cuts=driver.SceneCuts(enable_scdet, scdet_threshold, check_scene),
-               ts_of=lambda idx: _tools.calc_t(idx, times, mapper), on_step=on_step)
+               ts_of=lambda idx: _tools.calc_t(idx, times, mapper), on_step=on_step, linear=linear)
     return written
 
 
@@ -112,7 +118,8 @@ def inference(model, args):
     if getattr(video_io, "out_depth", 8) == 16:
         to_out = lambda x, size: _tools.to_out(x, size, rgb=rgb, depth=16, maxval=video_io.out_maxval)  # noqa: E731
     n = interpolate_stream(model, video_io, args.dst_fps, times=args.times, enable_scdet=args.enable_scdet,
-                           scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, on_step=step)
+                           scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, on_step=step,
+                           linear=not getattr(args, "nonlinear", False))
     while not video_io.finish_writing():
         time.sleep(0.01)
     video_io.close()
@@ -156,7 +163,7 @@ def inference_sharded(model, args, rank, world, to_inp=None, to_out=None, check_
         to_out = lambda x, size: _ops.to_out(x, size)  # noqa: E731
     parallel.interpolate_shard(model, frames, fps, args.dst_fps, rank, world, times=args.times, enable_scdet=args.enable_scdet,
                                scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, check_scene=check_scene,
-                               sink=sg.push)
+                               sink=sg.push, linear=not getattr(args, "nonlinear", False))
     allf = sg.finish()
     if rank != 0:
         return 0

@@ -1,8 +1,12 @@
 """DistanceRatioMap (DRM) operators on the HIP library; names/arguments as the reference's models/drm.py.
 
-calc_drm_rife with linear=True (the only form the driver uses, infer.py:143) runs as two
+calc_drm_rife with linear=True (what the driver asks for by default, infer.py:143) runs as two
 fused kernels per direction (distance + ratio + scale + splat scatter, then normalise +
 hole fill).  The remaining variants compose the generic HIP operators.
+
+calc_drm_rife with linear=False stays that composition on purpose: it is the public operator
+and the second implementation the fused non-linear kernel (ops.drm_rife_nonlinear, the form
+RIFE.inference_ts_drba(..., linear=False) runs for flows on the device) is tested against.
 """
 import torch
 

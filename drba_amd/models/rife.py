@@ -211,16 +211,17 @@ class RIFE:
 
     def _items(self, I0, I1, I2, ts, linear, flow10, flow12, f0, f1, f2, defer=None):
         """DRM maps and the (img0, img1, timestep, f0, f1) work items of one step; output holds pass-through frames
-        and, for the frames to synthesise, their index into items.  defer (a list, linear DRM only): the maps are not computed here --
+        and, for the frames to synthesise, their index into items.  defer (a list): the maps are not computed here --
         (flow_self, flow_other, t) is appended and the item carries its index into `defer` as the timestep; the caller computes
-        the maps of all its steps in one launch (_ops.drm_rife_linear_many) and calls _fill_drm."""
+        the maps of all its steps in one launch (_drm_many) and puts them in.  Flows on the device take the fused kernels in
+        either mode; a non-linear step on host tensors keeps the composition of the generic operators (calc_drm_rife)."""
         output, items = [], []
 
         def drm_of(fs, fo, t, key):
-            if not linear:
+            if not linear and not fs.is_cuda:
                 return calc_drm_rife(t, flow10, flow12, False)[key]
             if defer is None:
-                return _ops.drm_rife_linear(fs, fo, t, 1e-4)
+                return _ops.drm_rife_linear(fs, fo, t, 1e-4) if linear else _ops.drm_rife_nonlinear(fs, fo, t, 1e-4)
             defer.append((fs, fo, t))
             return len(defer) - 1
 
@@ -267,26 +268,31 @@ class RIFE:
 
     BATCH_COARSE = True  # with GROUP > 1: calc_flow of a group's new frame pairs in one batched pass (A/B runs)
     GROUP = 4          # consecutive steps per stacked IFNet pass when the driver announces enough frames (class attribute: A/B runs; 1: off)
-    _group_out = ()    # the later steps of a group, computed by an earlier call: [(I0, I1, I2, ts, reuse_in, outputs, reuse_out)]
+    _group_out = ()    # the later steps of a group, computed by an earlier call: [(I0, I1, I2, ts, reuse_in, outputs, reuse_out, linear)]
     _look2 = None      # side-stream staging of the NEXT group of steps
 
-    def _group_items(self, F, ts_list, reuse0, P):
+    @staticmethod
+    def _drm_many(jobs, linear):
+        """The DRM maps of a group of steps, one launch pair in either mode."""
+        return _ops.drm_rife_linear_many(jobs, 1e-4) if linear else _ops.drm_rife_nonlinear_many(jobs, 1e-4)
+
+    def _group_items(self, F, ts_list, reuse0, P, linear):
         """Work items of the steps (F[j], F[j+1], F[j+2]; ts_list[j]), j = 0 .. len(ts_list) - 1: P[j] = calc_flow(F[j+1], F[j+2]),
         reuse0 what the step before the first one handed on.  -> (per-step outputs with placeholders, per-step item counts,
         all items, per-step reuse: reuses[j] enters step j, reuses[j + 1] leaves it)."""
         outs, counts, items, reuses, jobs = [], [], [], [reuse0], []
         for j, ts in enumerate(ts_list):
             r, p = reuses[j], P[j]
-            o, it = self._items(F[j], F[j + 1], F[j + 2], ts, True, r[0], p[0], r[3], r[2], p[3], defer=jobs)
+            o, it = self._items(F[j], F[j + 1], F[j + 2], ts, linear, r[0], p[0], r[3], r[2], p[3], defer=jobs)
             outs.append(o)
             counts.append(len(it))
             items += it
             reuses.append((p[1], p[0], p[3], p[2]))  # (flow21, flow12, f2, f1), reference rife.py:109
-        maps = _ops.drm_rife_linear_many(jobs, 1e-4)  # the group's DRM maps: one launch pair (they were 2 launches per map)
+        maps = self._drm_many(jobs, linear)  # the group's DRM maps: one launch pair (they were 2 launches per map)
         items = [(a, b, maps[t], fa, fb) for (a, b, t, fa, fb) in items]
         return outs, counts, items, reuses
 
-    def _stage_group(self, F, ts_list, reuse0):
+    def _stage_group(self, F, ts_list, reuse0, linear):
         """Side stream: the group of steps after the one being computed -- steps (F[j], F[j+1], F[j+2]; ts_list[j]).  Coarse
         flows of the new frame pairs (from prefetch_pair where the driver started them), the DRM maps and the first
         SIDE_STAGES IFNet stages of all their frames stacked."""
@@ -296,20 +302,24 @@ class RIFE:
 
         def work():
             P = self._group_flows(F, n, reuse0[2])
-            outs, counts, items, reuses = self._group_items(F, ts_list, reuse0, P)
+            outs, counts, items, reuses = self._group_items(F, ts_list, reuse0, P, linear)
             state = self.ifnet.forward_pairs(items, self.scale_list, 0, self.SIDE_STAGES) if items else None
-            return {"F": tuple(F), "ts": ts_list, "flow10": reuse0[0], "P": P, "outs": outs, "counts": counts, "items": items,
+            return {"F": tuple(F), "ts": ts_list, "linear": linear, "flow10": reuse0[0], "P": P, "outs": outs, "counts": counts, "items": items,
                     "reuses": reuses, "state": state}
         self._look2.start(F[n], F[n + 1], work, inputs=tuple(t for t in tuple(F[:n]) + tuple(reuse0) if t is not None))
 
-    def _drba_group(self, F, ts_list, reuse, more):
+    def _drba_group(self, F, ts_list, reuse, more, linear):
         """Steps (F[j], F[j+1], F[j+2]; ts_list[j]), j = 0 .. g - 1, in ONE stacked IFNet pass: the frames of g steps are 2 g instead
         of 2 samples per launch -- at 1080p 11 % less kernel time per frame for g = 2 and 17 % for g = 4 (the low-resolution
         stages are latency-bound: 18 % / 31 %), and 1 / g of the launches.  Returns the first step's result and keeps the others
         for the next calls.  `more` = ([frames], [ts]) of the group after this one (its frames continue F), whose
-        low-resolution stages start on the side stream now, or None."""
+        low-resolution stages start on the side stream now, or None.  `linear`: the mode of every step of the group, of the group
+        staged here and part of every match: a group staged or computed ahead in the other mode is not taken."""
         g = len(ts_list)
         staged = self._look2.take(F[g], F[g + 1]) if self._look2 is not None else None
+        if staged is not None and staged["linear"] is not linear:
+            self._count("groups_dropped")  # staged by a call in the other mode
+            staged = None
         if not (staged is not None and len(staged["ts"]) == g and all(a is b for a, b in zip(staged["F"], F))
                 and staged["flow10"] is reuse[0] and all(np.array_equal(a, b) for a, b in zip(staged["ts"], ts_list))):
             staged = None
@@ -320,9 +330,9 @@ class RIFE:
         else:
             got = self._look.take(F[1], F[2]) if self._look is not None else None  # a one-step lookahead of the call before
             P = [got[0]] + self._group_flows(F[1:], g - 1, got[0][3]) if got is not None else self._group_flows(F, g, reuse[2])
-            outs, counts, items, reuses = self._group_items(F, ts_list, reuse, P)
+            outs, counts, items, reuses = self._group_items(F, ts_list, reuse, P, linear)
         if more is not None:
-            self._stage_group(list(F[g:]) + list(more[0]), list(more[1]), reuses[g])
+            self._stage_group(list(F[g:]) + list(more[0]), list(more[1]), reuses[g], linear)
         if staged is not None:
             frames = self.ifnet.forward_pairs(items, self.scale_list, self.SIDE_STAGES, 5, staged["state"]) if items else []
         else:
@@ -331,7 +341,7 @@ class RIFE:
         for j in range(g):
             res.append([frames[base + o] if isinstance(o, int) else o for o in outs[j]])
             base += counts[j]
-        self._group_out = [(F[j], F[j + 1], F[j + 2], ts_list[j], reuses[j], res[j], reuses[j + 1]) for j in range(1, g)]
+        self._group_out = [(F[j], F[j + 1], F[j + 2], ts_list[j], reuses[j], res[j], reuses[j + 1], linear) for j in range(1, g)]
         return res[0], reuses[1]
 
     def reset_stream_state(self):
@@ -349,17 +359,21 @@ class RIFE:
         call's full-resolution stages; the next call resumes from there if its arguments match.
         (next, ts1, next2, ts2, ...) -- the driver reading further ahead and vouching that the calls it announces are plain DRBA
         steps -- lets this call compute the next GROUP - 1 steps together with this one (_drba_group): the following calls
-        then only collect their results."""
+        then only collect their results.
+        `linear` selects the DistanceRatioMap (False: get_drm_t's non-linear retiming); groups, staging and collection work the
+        same in both modes, and a step computed ahead in one mode is never handed to a call in the other: that call drops it
+        (`groups_dropped`) and computes its own."""
+        linear = bool(linear)
         _ops.check_overflow(self.device)  # raises if a family-4 kernel of an earlier call stored inf / NaN (no synchronisation)
         if self._group_out:
             po, self._group_out = self._group_out[0], self._group_out[1:]
-            if (reuse and po[0] is I0 and po[1] is I1 and po[2] is I2 and po[4][0] is reuse[0]
+            if (reuse and po[7] is linear and po[0] is I0 and po[1] is I1 and po[2] is I2 and po[4][0] is reuse[0]
                     and np.array_equal(po[3], np.asarray(ts, dtype=np.float64))):
                 self._count("group_collects")
                 return po[5], po[6]  # a later step of the group an earlier call computed
             self._group_out = ()     # another call pattern than announced: what was computed ahead is dropped
             self._count("groups_dropped")
-        if self.GROUP > 1 and linear and reuse and isinstance(lookahead, (tuple, list)) and len(lookahead) >= 4 and I0.is_cuda:
+        if self.GROUP > 1 and reuse and isinstance(lookahead, (tuple, list)) and len(lookahead) >= 4 and I0.is_cuda:
             # (frame, ts) of the following calls; two or more entries = the driver vouches that all of them are plain DRBA steps
             # (no scene cut up to the last frame it names); one entry alone is the one-step lookahead below
             ahead = []
@@ -373,22 +387,25 @@ class RIFE:
                 ts_list = [np.asarray(ts, dtype=np.float64)] + [a[1] for a in ahead[:g - 1]]
                 rest = ahead[g - 1:]
                 more = ([a[0] for a in rest[:g]], [a[1] for a in rest[:g]]) if len(rest) >= g else None
-                return self._drba_group(F, ts_list, reuse, more)
+                return self._drba_group(F, ts_list, reuse, more, linear)
         self._count("single_steps")
         flow10, flow01, f1, f0 = self.calc_flow(I1, I0) if not reuse else reuse
         (flow12, flow21, f1, f2), staged = self._flow_pair(I1, I2, None if reuse is None else reuse[2])
         nxt, ts_nxt = split_lookahead(lookahead)
         if nxt is not None:
             then = None
-            if ts_nxt is not None and linear and 0 < self.SIDE_STAGES < 5:
+            if ts_nxt is not None and (linear or I1.is_cuda) and 0 < self.SIDE_STAGES < 5:  # (host tensors, non-linear: the composition, unstaged)
                 ts_nxt = np.array(ts_nxt, dtype=np.float64)
 
                 def then(res):  # the next step: (I0, I1, I2) = (I1, I2, nxt), its reuse = (flow21, flow12, f2, f1)
-                    out_n, items_n = self._items(I1, I2, nxt, ts_nxt, True, flow21, res[0], f1, f2, res[3])
+                    out_n, items_n = self._items(I1, I2, nxt, ts_nxt, linear, flow21, res[0], f1, f2, res[3])
                     state = self.ifnet.forward_pairs(items_n, self.scale_list, 0, self.SIDE_STAGES) if items_n else None
-                    return {"I0": I1, "flow10": flow21, "ts": ts_nxt, "output": out_n, "items": items_n, "state": state}
+                    return {"I0": I1, "flow10": flow21, "ts": ts_nxt, "linear": linear, "output": out_n, "items": items_n, "state": state}
             self.prefetch_flow(I2, nxt, f2, then, also_reads=(I1, flow21, f1))
-        if (staged is not None and linear and staged["I0"] is I0 and staged["flow10"] is flow10
+        if staged is not None and staged["linear"] is not linear:
+            self._count("groups_dropped")  # the step was staged by a call in the other mode: not collected
+            staged = None
+        if (staged is not None and staged["I0"] is I0 and staged["flow10"] is flow10
                 and np.array_equal(staged["ts"], np.asarray(ts, dtype=np.float64))):
             output, items = staged["output"], staged["items"]
             if items:

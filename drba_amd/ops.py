@@ -365,6 +365,73 @@ def drm_rife_linear_many(jobs, eps=1e-4):
     return res
 
 
+def drm_walk(t, precision=1e-3):
+    """get_drm_t's scalar walk (reference drm.py:43-56) as the library makes it on the host -> (moves, n_moves): bit k of moves
+    set = move k is the `_x < t` update, clear = the `_x > t` update.  None: longer than the 32-bit mask (DRBA_EUNSUPPORTED)."""
+    moves, n = C.c_uint32(), C.c_int()
+    rc = _lib.load().drba_drm_walk(float(t), float(precision), C.byref(moves), C.byref(n))
+    if rc == _EUNSUPPORTED:
+        return None
+    _lib.check(rc, "drba_drm_walk")
+    return moves.value, n.value
+
+
+def _drm_rife_composed(flow_self, flow_other, t, eps, precision):
+    """One direction of calc_drm_rife(linear=False) from the generic operators (what models/drm.py composes): the form for a
+    walk the fused kernel's move mask cannot hold."""
+    u = drm_retime(drm_ratio(flow_self, flow_other, eps)[1], t, precision)
+    both = softsplat(torch.cat((u, affine(u, 0.0, 1.0)), 1), mul_map(flow_self, u), None, "avg")
+    return fill_holes(both[:, 0:1].contiguous(), both[:, 1:2].contiguous(), u)
+
+
+def drm_rife_nonlinear(flow_self, flow_other, t, eps=1e-4, precision=1e-3):
+    """One direction of calc_drm_rife(linear=False) (reference drm.py:65-107) as one fused launch pair: the retimed ratio
+    u = get_drm_t(d_other / (d_self + d_other), t), avg-splatted along flow_self * u, holes keeping u."""
+    a, b = _f32(flow_self, "flow_self"), _f32(flow_other, "flow_other")
+    n, _, h, w = a.shape
+    out = torch.empty((n, 1, h, w), dtype=torch.float32, device=a.device)
+    ws = _zero_workspace(a.device, _lib.load().drba_rife_splat_ws_floats(n, h, w, 1))
+    first = _trace_pos()
+    rc = _lib.load().drba_drm_rife_nonlinear(_p(a), _p(b), float(t), float(precision), float(eps), _p(out), _p(ws), n, h, w,
+                                             _stream())
+    if rc == _EUNSUPPORTED:  # a walk longer than the move mask (nothing was launched): the composition
+        return _drm_rife_composed(a, b, t, eps, precision)
+    _lib.check(rc, "drba_drm_rife_nonlinear")
+    _tag(first, [None, (20.0 * n * h * w, "byte", f"drm_rife_nonlinear {(n, h, w)}")])  # long-flow prepass, then the tiled splat
+    return out
+
+
+def drm_rife_nonlinear_many(jobs, eps=1e-4, precision=1e-3):
+    """drm_rife_nonlinear(flow_self, flow_other, t, eps, precision) for every (flow_self, flow_other, t) of `jobs` ([1,2,H,W] flows
+    of one size) in ONE launch pair (drba_drm_rife_nonlinear_batch; chunks of MAX_STAGE_ITEMS) -> list of [1,1,H,W] maps."""
+    if not jobs:
+        return []
+    flows = [(_f32(a, "flow_self"), _f32(b, "flow_other"), float(t)) for a, b, t in jobs]
+    _, _, h, w = flows[0][0].shape
+    dev = flows[0][0].device
+    res = []
+    for c0 in range(0, len(flows), _lib.MAX_STAGE_ITEMS):
+        chunk = flows[c0:c0 + _lib.MAX_STAGE_ITEMS]
+        n = len(chunk)
+        out = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev)
+        arr = (_lib.DrmNonlinearJob * n)()
+        for k, (a, b, t) in enumerate(chunk):
+            if tuple(a.shape) != (1, 2, h, w) or tuple(b.shape) != (1, 2, h, w):
+                raise _lib.DrbaHipError("drm_rife_nonlinear_many: every flow must be [1,2,H,W] of one size")
+            arr[k].flow_self, arr[k].flow_other, arr[k].t, arr[k].out = a.data_ptr(), b.data_ptr(), t, out[k].data_ptr()
+        ws = _zero_workspace(dev, _lib.load().drba_rife_splat_ws_floats(n, h, w, 1))
+        first = _trace_pos()
+        rc = _lib.load().drba_drm_rife_nonlinear_batch(C.cast(arr, C.c_void_p), n, float(precision), float(eps), _p(ws), h, w,
+                                                       _stream())
+        if rc == _EUNSUPPORTED:  # some walk of the chunk is longer than the move mask (nothing was launched)
+            res += [drm_rife_nonlinear(a, b, t, eps, precision) for a, b, t in chunk]
+            continue
+        _lib.check(rc, "drba_drm_rife_nonlinear_batch")
+        _tag(first, [None, (20.0 * n * h * w, "byte", f"drm_rife_nonlinear {(n, h, w)}")])
+        res += [out[k:k + 1] for k in range(n)]
+    return res
+
+
 def drm_ratio(flow10, flow12, eps):
     a, b = _f32(flow10), _f32(flow12)
     n, _, h, w = a.shape

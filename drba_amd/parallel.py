@@ -59,14 +59,14 @@ def emission_counts(n_frames, src_fps, dst_fps, times, world):
 
 
 def interpolate_shard(model, frames, src_fps, dst_fps, rank, world, times=-1, enable_scdet=False, scdet_threshold=0.3,
-                      to_inp=None, to_out=None, check_scene=None, sink=None):
+                      to_inp=None, to_out=None, check_scene=None, sink=None, linear=True):
     """Run this rank's share of the clip.  `frames` is a random-access sequence of uint8 HWC frames
     (every rank can index it; only its own range plus the halo is touched).
     Returns the list of output frames (whatever to_out returns) this rank is responsible for, in order.
     Concatenating the lists of ranks 0..world-1 gives exactly the sequential driver's output.
     `sink(list_of_frames)`, if given, receives each emission (head / one loop iteration / tail) as it is produced
     instead (StreamedGather.push: the frames travel to the writer rank while the next steps compute) and the
-    function returns []."""
+    function returns [].  `linear`: see drba_amd.driver.run."""
     to_inp = to_inp or _tools.to_inp
     to_out = to_out or _tools.to_out
     if dst_fps <= src_fps:
@@ -104,7 +104,7 @@ def interpolate_shard(model, frames, src_fps, dst_fps, rank, world, times=-1, en
     hi = min(b + 1, n - 1)
     driver.run(model, lambda k: frames[k] if k <= hi else None, pair, a, to_inp=lambda raw: to_inp(raw, dst_size), emit=emit,
                cuts=cuts, ts_of=lambda idx: _tools.calc_t(idx, times, mapper), state=(cut_left, reuse), head=head, tail=tail,
-               announce_ungrouped=True)
+               announce_ungrouped=True, linear=linear)
     return out
 
 

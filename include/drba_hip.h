@@ -32,7 +32,9 @@ extern "C" {
 #define DRBA_EUNSUPPORTED (-2) /* shape/config outside what the kernels were built for */
 #define DRBA_ELAUNCH (-3)  /* hipGetLastError() reported a launch failure */
 
-/* ABI version.  12: drba_tile_item_order (host function: the workgroup -> (tile, item) order of the batched stage launches): an
+/* ABI version.  13: the fused non-linear DRM of the RIFE path -- drba_drm_walk (host function: get_drm_t's scalar walk as a move
+ * mask), drba_drm_rife_nonlinear and drba_drm_rife_nonlinear_batch with drba_drm_nonlinear_job_t: additions only, no earlier entry
+ * changes.  12: drba_tile_item_order (host function: the workgroup -> (tile, item) order of the batched stage launches): an
  * addition only, no earlier entry changes.  11: 16-bit frames -- drba_to_inp16_x4 / drba_to_out16 / drba_u16hwc_to_f32nchw / drba_f32nchw_to_u16hwc (uint16 HWC frames
  * with an explicit maxval; the way out rounds to nearest even and saturates) and drba_frame_error_u16 / drba_frame_error_u16_ws_floats:
  * additions only, no earlier entry changes.  10: drba_ssim3d / drba_ssim3d_ws_floats (ssim_matlab at full size, fp64 accumulation) and drba_frame_error_u8 /
@@ -52,7 +54,7 @@ extern "C" {
  * workspace that must be ZERO on entry (they leave it zero on return: self-cleaning accumulator) instead of clearing it
  * themselves; batched stage entry points added; drba_conv3x3_cfg_family added and configuration ids 19 (LDS-DMA, 32
  * channels) / 20 (K split across waves) behind drba_conv3x3; the allocation exception above.  1: the first release. */
-#define DRBA_ABI_VERSION 12  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
+#define DRBA_ABI_VERSION 13  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
 int drba_abi_version(void);
 const char *drba_error_string(int code);
 /* ABI 6, debug: with the range check on, every entry point that ran a kernel of family 4 (two fp16 terms per operand:
@@ -174,6 +176,30 @@ typedef struct drba_drm_job {
   float *out; /* [1,H,W] */
 } drba_drm_job_t;
 int drba_drm_rife_linear_batch(const drba_drm_job_t *jobs, int n_jobs, float eps, float *ws, int H, int W, void *stream);
+
+/* ---- fused non-linear DRM, one direction (ABI 13): models/drm.py:65-107 with linear=False
+ * r = d_other/(d_self+d_other) with d = |flow| + eps, u = get_drm_t(r, t, precision) (drm.py:10-62); out = splat_avg(u, self*u) with
+ * uncovered pixels keeping u: drba_drm_rife_linear with the retimed ratio in place of r * t * 2, same (self, other) convention, same
+ * workspace (drba_rife_splat_ws_floats(N, H, W, 1) floats, zero on entry and on return), same kernels after u.  u equals
+ * drba_drm_retime(drba_drm_ratio(...)) bit for bit.
+ *
+ * get_drm_t's bisection on the scalar is data independent.  drba_drm_walk -- a HOST function (no GPU, no stream) -- runs the reference's
+ * loop in double and returns its moves: *n_moves of them, bit k of *moves set where move k is the `_x < t` update, clear where it is the
+ * `_x > t` update (both may happen in one iteration).  The kernels replay the moves on every source pixel in fp32.  A walk of more than
+ * 32 moves (a precision far finer than the model's 1e-3, or a t outside [0, 1]) returns DRBA_EUNSUPPORTED, from all three entry points
+ * and before anything is launched: compose drba_drm_ratio / drba_drm_retime / drba_softsplat / drba_fill_holes then. */
+int drba_drm_walk(double t, double precision, uint32_t *moves, int *n_moves);
+int drba_drm_rife_nonlinear(const float *flow_self, const float *flow_other, double t, double precision, float eps, float *out,
+                            float *ws, int N, int H, int W, void *stream);
+/* n_jobs (<= DRBA_MAX_STAGE_ITEMS) maps of one geometry, each with its own t, in one launch pair (the maps of a group of DRBA steps).
+ * t is a double here: the walk is made in double, as Python makes it.  ws: drba_rife_splat_ws_floats(n_jobs, H, W, 1) floats. */
+typedef struct drba_drm_nonlinear_job {
+  const float *flow_self, *flow_other; /* [2,H,W] each */
+  double t;
+  float *out; /* [1,H,W] */
+} drba_drm_nonlinear_job_t;
+int drba_drm_rife_nonlinear_batch(const drba_drm_nonlinear_job_t *jobs, int n_jobs, double precision, float eps, float *ws, int H,
+                                  int W, void *stream);
 
 /* ---- DRM building blocks for the non-fused variants (drm.py:110-195, :10-62) */
 /* ratio maps: a = d10/(d10+d12), b = d12/(d10+d12), d = |flow| + eps; either output may be NULL */
