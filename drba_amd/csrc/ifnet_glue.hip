@@ -3,7 +3,6 @@
 //   ifblock_input : warp x4 + concat + bilinear downsample  -> the stage's conv input
 //   ifblock_update: PixelShuffle'd head output -> bilinear upsample + flow accumulate
 //   warp_blend    : final two warps + sigmoid blend
-// plus bilinear resize and the uint8<->fp32 frame conversions used by to_inp/to_out.
 #include "common.hpp"
 #include "flow_terms.hpp"
 
@@ -14,298 +13,6 @@
 using namespace drba;
 
 namespace {
-
-// ---- frame source / sink (tools.py:33-38,59-72): bit-exact with ATen's CPU upsample_bilinear2d --------------------
-// ATen evaluates the source coordinate as fma(scale, dst + 0.5, -0.5) and each 1-D interpolation as
-// fma(w0, a, w1 * b) (its vectorised kernels are compiled with contraction; established by comparing every
-// contraction variant against F.interpolate on the 480p/1080p/4K frame sizes: only this one matches in every bit).
-// hipcc would pick its own contraction, so the operations are spelled out.
-__device__ __forceinline__ Lerp lerp_src_aten(int dst, float scale, int size) {
-  float s = __fmaf_rn(scale, (float)dst + 0.5f, -0.5f);
-  if (s < 0.f) s = 0.f;
-  Lerp l;
-  l.i0 = min((int)s, size - 1);
-  l.i1 = l.i0 + (l.i0 < size - 1 ? 1 : 0);
-  l.w1 = __fsub_rn(s, (float)l.i0);
-  l.w0 = __fsub_rn(1.f, l.w1);
-  return l;
-}
-__device__ __forceinline__ float lerp2_aten(const Lerp &ly, const Lerp &lx, float a, float b, float c, float d) {
-  const float top = __fmaf_rn(lx.w0, a, __fmul_rn(lx.w1, b));
-  const float bot = __fmaf_rn(lx.w0, c, __fmul_rn(lx.w1, d));
-  return __fmaf_rn(ly.w0, top, __fmul_rn(ly.w1, bot));
-}
-
-// F.interpolate(bilinear, align_corners=False): out = wy0*(wx0*a + wx1*b) + wy1*(wx0*c + wx1*d)
-// (ATen's separable evaluation order: innermost axis first).
-__global__ void __launch_bounds__(256) resize_bilinear_kernel(const float *__restrict__ in, float *__restrict__ out, int NC, int Hin,
-                                       int Win, int Hout, int Wout, float sy, float sx) {
-  const size_t total = (size_t)NC * Hout * Wout;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int ox = (int)(i % Wout);
-    const int oy = (int)((i / Wout) % Hout);
-    const int c = (int)(i / ((size_t)Wout * Hout));
-    const Lerp ly = lerp_src_aten(oy, sy, Hin), lx = lerp_src_aten(ox, sx, Win);
-    const float *p = in + (size_t)c * Hin * Win;
-    const float *r0 = p + (size_t)ly.i0 * Win, *r1 = p + (size_t)ly.i1 * Win;
-    out[i] = lerp2_aten(ly, lx, r0[lx.i0], r0[lx.i1], r1[lx.i0], r1[lx.i1]);
-  }
-}
-
-// to_inp = resize(to_tensor(img), dst_size) in ONE pass: uint8 HWC -> /255. -> bilinear -> fp32 [1,3,Hout,Wout].
-// (the reference materialises the full-size fp32 frame in between, tools.py:33-34,59-60)
-__global__ void __launch_bounds__(256) to_inp_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4,
-                                                     int Hin, int Win, int Hout, int Wout, float sy, float sx) {
-  const Tile2D p = tile_pixel(Wout, Hout);
-  if (!p.valid) return;
-  const Lerp ly = lerp_src_aten(p.y, sy, Hin), lx = lerp_src_aten(p.x, sx, Win);
-  const uint8_t *r0 = in + (size_t)ly.i0 * Win * 3, *r1 = in + (size_t)ly.i1 * Win * 3;
-  const size_t P = (size_t)Hout * Wout, o = (size_t)p.y * Wout + p.x;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float a = (float)r0[lx.i0 * 3 + c] / 255.f, b = (float)r0[lx.i1 * 3 + c] / 255.f;
-    const float cc = (float)r1[lx.i0 * 3 + c] / 255.f, d = (float)r1[lx.i1 * 3 + c] / 255.f;
-    const float v = lerp2_aten(ly, lx, a, b, cc, d);
-    out[c * P + o] = v;
-    if (out_x4) out_x4[4 * o + c] = v;
-  }
-  if (out_x4) out_x4[4 * o + 3] = 0.f;
-}
-
-// to_out = to_cv2(resize(x, src_size)) in ONE pass: fp32 [1,3,Hin,Win] -> bilinear -> *255. truncated -> uint8 HWC,
-// channels reversed when `rev` (the BGR -> RGB flip of the encoder pipe, tools.py:202, otherwise a host-side copy).
-__global__ void __launch_bounds__(256) to_out_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int Win,
-                                                     int Hout, int Wout, float sy, float sx, int rev) {
-  const Tile2D p = tile_pixel(Wout, Hout);
-  if (!p.valid) return;
-  const Lerp ly = lerp_src_aten(p.y, sy, Hin), lx = lerp_src_aten(p.x, sx, Win);
-  const size_t P = (size_t)Hin * Win;
-  uint8_t *o = out + ((size_t)p.y * Wout + p.x) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float *r0 = in + c * P + (size_t)ly.i0 * Win, *r1 = in + c * P + (size_t)ly.i1 * Win;
-    const float v = __fmul_rn(lerp2_aten(ly, lx, r0[lx.i0], r0[lx.i1], r1[lx.i0], r1[lx.i1]), 255.f);
-    o[rev ? 2 - c : c] = (uint8_t)(int)v;
-  }
-}
-
-// The frame sizes of the 1080p / 4K configurations change the HEIGHT only (1080 -> 1088, 2160 -> 2176: the width is already a
-// multiple of the padding): the horizontal interpolation is the identity -- scale_x == 1 gives s = x, weights (1, 0), and
-// fma(1, a, 0 * b) == a for finite b -- so a lane takes FOUR consecutive pixels of a row with 16-byte loads / stores instead of
-// one pixel with 12 scalar loads and 3 byte (or 3 dword) stores: same values bit for bit, a third of the time (round 4: the
-// one-pixel kernels were 46 + 2 x 34 us of a 2.43 ms 1080p step at 0.9 TB/s).
-typedef float f32x4g __attribute__((ext_vector_type(4)));
-__global__ void __launch_bounds__(256) to_inp_rows_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4,
-                                                          int Hin, int W, int Hout, float sy) {
-  const int W4 = W >> 2;
-  const size_t total = (size_t)W4 * Hout, P = (size_t)Hout * W;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int y = (int)(i / W4), x = (int)(i - (size_t)y * W4) * 4;
-    const Lerp ly = lerp_src_aten(y, sy, Hin);
-    // 4 pixels x 3 channels = 12 bytes per row, 4-byte aligned (W % 4 == 0)
-    const uint32_t *r0 = reinterpret_cast<const uint32_t *>(in + ((size_t)ly.i0 * W + x) * 3);
-    const uint32_t *r1 = reinterpret_cast<const uint32_t *>(in + ((size_t)ly.i1 * W + x) * 3);
-    const uint32_t a[3] = {r0[0], r0[1], r0[2]}, b[3] = {r1[0], r1[1], r1[2]};
-    f32x4g o[3];
-#pragma unroll
-    for (int px = 0; px < 4; ++px)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int k = px * 3 + c;
-        const float top = (float)((a[k >> 2] >> (8 * (k & 3))) & 0xffu) / 255.f, bot = (float)((b[k >> 2] >> (8 * (k & 3))) & 0xffu) / 255.f;
-        o[c][px] = __fmaf_rn(ly.w0, top, __fmul_rn(ly.w1, bot));
-      }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4g *>(out + (size_t)c * P + (size_t)y * W + x) = o[c];
-    if (out_x4) {  // the same values pixel-major, (c0, c1, c2, 0): 64 contiguous bytes per lane
-#pragma unroll
-      for (int px = 0; px < 4; ++px)
-        *reinterpret_cast<f32x4g *>(out_x4 + ((size_t)y * W + x + px) * 4) = (f32x4g){o[0][px], o[1][px], o[2][px], 0.f};
-    }
-  }
-}
-__global__ void __launch_bounds__(256) to_out_rows_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int W, int Hout,
-                                                          float sy, int rev) {
-  const int W4 = W >> 2;
-  const size_t total = (size_t)W4 * Hout, P = (size_t)Hin * W;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int y = (int)(i / W4), x = (int)(i - (size_t)y * W4) * 4;
-    const Lerp ly = lerp_src_aten(y, sy, Hin);
-    uint32_t bytes[12];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const f32x4g t = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)ly.i0 * W + x);
-      const f32x4g u = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)ly.i1 * W + x);
-#pragma unroll
-      for (int px = 0; px < 4; ++px) {
-        const float v = __fmul_rn(__fmaf_rn(ly.w0, t[px], __fmul_rn(ly.w1, u[px])), 255.f);
-        bytes[px * 3 + (rev ? 2 - c : c)] = (uint32_t)(uint8_t)(int)v;
-      }
-    }
-    uint32_t *o = reinterpret_cast<uint32_t *>(out + ((size_t)y * W + x) * 3);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = bytes[4 * k] | (bytes[4 * k + 1] << 8) | (bytes[4 * k + 2] << 16) | (bytes[4 * k + 3] << 24);
-  }
-}
-
-// tools.py:33-34: HWC uint8 -> [1,3,H,W] fp32 / 255.
-__global__ void __launch_bounds__(256) u8_to_f32_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, int H, int W) {
-  const size_t P = (size_t)H * W;
-  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (size_t)gridDim.x * blockDim.x) {
-    const uint8_t *s = in + p * 3;
-    out[p] = (float)s[0] / 255.f;
-    out[P + p] = (float)s[1] / 255.f;
-    out[2 * P + p] = (float)s[2] / 255.f;
-  }
-}
-
-// tools.py:37-38: (x*255.).astype(uint8): truncation toward zero, no clamp, no rounding
-// (out-of-range values wrap modulo 256 like the x86 float->int32->uint8 conversion numpy performs).
-__global__ void __launch_bounds__(256) f32_to_u8_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int H, int W) {
-  const size_t P = (size_t)H * W;
-  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (size_t)gridDim.x * blockDim.x) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float v = in[(size_t)c * P + p] * 255.f;
-      out[p * 3 + c] = (uint8_t)(int)v;
-    }
-  }
-}
-
-// ---- 16-bit frames: uint16 HWC with samples in [0, maxval] (1023: 10-bit data, 65535: full range) ------------------------------
-// The way in is the 8-bit one with the divisor exchanged (a true fp32 division, then the same ATen-order lerp).  The way out is
-// NOT the 8-bit one: bytes keep the reference's trunc(x * 255) and its wrap-around because they must equal the reference's; a
-// 16-bit frame has no reference to equal, so it is rounded to nearest even and saturated, NaN -> 0.  v / maxval * maxval lies
-// within 65535 * 2^-23 of v, so an unresized frame comes back bit for bit.
-__device__ __forceinline__ uint32_t round_sat_u16(float scaled, float maxval) {
-  float r = rintf(scaled);  // half to even (torch.round)
-  if (!(r >= 0.f)) r = 0.f;  // negative values and NaN
-  if (r > maxval) r = maxval;
-  return (uint32_t)(int)r;
-}
-
-// ATen takes BOTH taps of an axis whose size does not change from the pixel itself, weights (1, 0) ("scale_factor = 1, simply
-// copy"); lerp_src_aten's (x, x + 1) with the same weights gives the same value for finite data only: 1 * inf + 0 * inf is NaN,
-// and the right neighbour's inf must not reach this pixel.  The frames on the way out may hold anything, so the rule is kept.
-__device__ __forceinline__ Lerp lerp_src_aten_sized(int dst, float scale, int in_size, int out_size) {
-  if (in_size == out_size) {
-    Lerp l;
-    l.i0 = l.i1 = dst;
-    l.w0 = 1.f;
-    l.w1 = 0.f;
-    return l;
-  }
-  return lerp_src_aten(dst, scale, in_size);
-}
-
-__global__ void __launch_bounds__(256) to_inp16_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4,
-                                                       int Hin, int Win, int Hout, int Wout, float sy, float sx, float maxval) {
-  const Tile2D p = tile_pixel(Wout, Hout);
-  if (!p.valid) return;
-  const Lerp ly = lerp_src_aten(p.y, sy, Hin), lx = lerp_src_aten(p.x, sx, Win);
-  const uint16_t *r0 = in + (size_t)ly.i0 * Win * 3, *r1 = in + (size_t)ly.i1 * Win * 3;
-  const size_t P = (size_t)Hout * Wout, o = (size_t)p.y * Wout + p.x;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float a = __fdiv_rn((float)r0[lx.i0 * 3 + c], maxval), b = __fdiv_rn((float)r0[lx.i1 * 3 + c], maxval);
-    const float cc = __fdiv_rn((float)r1[lx.i0 * 3 + c], maxval), d = __fdiv_rn((float)r1[lx.i1 * 3 + c], maxval);
-    const float v = lerp2_aten(ly, lx, a, b, cc, d);
-    out[c * P + o] = v;
-    if (out_x4) out_x4[4 * o + c] = v;
-  }
-  if (out_x4) out_x4[4 * o + 3] = 0.f;
-}
-
-__global__ void __launch_bounds__(256) to_out16_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int Hin, int Win,
-                                                       int Hout, int Wout, float sy, float sx, int rev, float maxval) {
-  const Tile2D p = tile_pixel(Wout, Hout);
-  if (!p.valid) return;
-  const Lerp ly = lerp_src_aten_sized(p.y, sy, Hin, Hout), lx = lerp_src_aten_sized(p.x, sx, Win, Wout);
-  const size_t P = (size_t)Hin * Win;
-  uint16_t *o = out + ((size_t)p.y * Wout + p.x) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float *r0 = in + c * P + (size_t)ly.i0 * Win, *r1 = in + c * P + (size_t)ly.i1 * Win;
-    const float v = __fmul_rn(lerp2_aten(ly, lx, r0[lx.i0], r0[lx.i1], r1[lx.i0], r1[lx.i1]), maxval);
-    o[rev ? 2 - c : c] = (uint16_t)round_sat_u16(v, maxval);
-  }
-}
-
-// The height-only frame sizes (to_inp_rows_kernel above): four pixels of a row are 12 samples = 24 bytes, 8-byte aligned
-// (W % 4 == 0), taken as three 8-byte loads per source row instead of twelve 2-byte ones.
-__global__ void __launch_bounds__(256) to_inp16_rows_kernel(const uint16_t *__restrict__ in, float *__restrict__ out,
-                                                            float *__restrict__ out_x4, int Hin, int W, int Hout, float sy, float maxval) {
-  const int W4 = W >> 2;
-  const size_t total = (size_t)W4 * Hout, P = (size_t)Hout * W;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int y = (int)(i / W4), x = (int)(i - (size_t)y * W4) * 4;
-    const Lerp ly = lerp_src_aten(y, sy, Hin);
-    const uint2 *r0 = reinterpret_cast<const uint2 *>(in + ((size_t)ly.i0 * W + x) * 3);
-    const uint2 *r1 = reinterpret_cast<const uint2 *>(in + ((size_t)ly.i1 * W + x) * 3);
-    const uint2 a0 = r0[0], a1 = r0[1], a2 = r0[2], b0 = r1[0], b1 = r1[1], b2 = r1[2];
-    const uint32_t a[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y}, b[6] = {b0.x, b0.y, b1.x, b1.y, b2.x, b2.y};
-    f32x4g o[3];
-#pragma unroll
-    for (int px = 0; px < 4; ++px)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int k = px * 3 + c;
-        const float top = __fdiv_rn((float)((a[k >> 1] >> (16 * (k & 1))) & 0xffffu), maxval);
-        const float bot = __fdiv_rn((float)((b[k >> 1] >> (16 * (k & 1))) & 0xffffu), maxval);
-        o[c][px] = __fmaf_rn(ly.w0, top, __fmul_rn(ly.w1, bot));
-      }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4g *>(out + (size_t)c * P + (size_t)y * W + x) = o[c];
-    if (out_x4) {
-#pragma unroll
-      for (int px = 0; px < 4; ++px)
-        *reinterpret_cast<f32x4g *>(out_x4 + ((size_t)y * W + x + px) * 4) = (f32x4g){o[0][px], o[1][px], o[2][px], 0.f};
-    }
-  }
-}
-// ... and 24 contiguous bytes stored per lane.  The horizontal pass is ATen's copy, fma(1, a, 0 * a): a for finite a, NaN otherwise.
-__global__ void __launch_bounds__(256) to_out16_rows_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int Hin, int W,
-                                                            int Hout, float sy, int rev, float maxval) {
-  const int W4 = W >> 2;
-  const size_t total = (size_t)W4 * Hout, P = (size_t)Hin * W;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int y = (int)(i / W4), x = (int)(i - (size_t)y * W4) * 4;
-    const Lerp ly = lerp_src_aten_sized(y, sy, Hin, Hout);
-    uint32_t s[12];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const f32x4g t = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)ly.i0 * W + x);
-      const f32x4g u = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)ly.i1 * W + x);
-#pragma unroll
-      for (int px = 0; px < 4; ++px) {
-        const float top = __fmaf_rn(1.f, t[px], __fmul_rn(0.f, t[px])), bot = __fmaf_rn(1.f, u[px], __fmul_rn(0.f, u[px]));
-        const float v = __fmul_rn(__fmaf_rn(ly.w0, top, __fmul_rn(ly.w1, bot)), maxval);
-        s[px * 3 + (rev ? 2 - c : c)] = round_sat_u16(v, maxval);
-      }
-    }
-    uint2 *o = reinterpret_cast<uint2 *>(out + ((size_t)y * W + x) * 3);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = make_uint2(s[4 * k] | (s[4 * k + 1] << 16), s[4 * k + 2] | (s[4 * k + 3] << 16));
-  }
-}
-
-// the no-resize pair: HWC uint16 -> [1,3,H,W] fp32 / maxval, and back with the rounding rule above
-__global__ void __launch_bounds__(256) u16_to_f32_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, int H, int W, float maxval) {
-  const size_t P = (size_t)H * W;
-  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (size_t)gridDim.x * blockDim.x) {
-    const uint16_t *s = in + p * 3;
-    out[p] = __fdiv_rn((float)s[0], maxval);
-    out[P + p] = __fdiv_rn((float)s[1], maxval);
-    out[2 * P + p] = __fdiv_rn((float)s[2], maxval);
-  }
-}
-__global__ void __launch_bounds__(256) f32_to_u16_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int H, int W, float maxval) {
-  const size_t P = (size_t)H * W;
-  for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (size_t)gridDim.x * blockDim.x) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[p * 3 + c] = (uint16_t)round_sat_u16(__fmul_rn(in[(size_t)c * P + p], maxval), maxval);
-  }
-}
 
 // The interpolations of one step (`-t 2`: two frames) are independent until their convolutions are stacked along N: the
 // stage-input and flow-update kernels of ALL items of a stage are one launch (blockIdx.y = item).  On the small maps of
@@ -1070,15 +777,6 @@ warp_blend_kernel(const float *__restrict__ img0, const float *__restrict__ img1
 
 extern "C" {
 
-int drba_resize_bilinear(const float *in, float *out, int NC, int Hin, int Win, int Hout, int Wout, float scale_y,
-                         float scale_x, void *stream) {
-  if (!in || !out || NC <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0) return DRBA_EINVAL;
-  DRBA_LAUNCH(resize_bilinear_kernel, dim3(grid_for((size_t)NC * Hout * Wout)), dim3(kBlock), 0,
-                     (hipStream_t)stream, in, out, NC, Hin, Win, Hout, Wout, scale_y, scale_x);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
-}
-
 int drba_pair_interleave(const float *in, float *out, int C, int H, int W, void *stream) {
   if (!in || !out || C <= 0 || (C & 1) || H <= 0 || W <= 0) return DRBA_EINVAL;
   const size_t P = (size_t)H * W;
@@ -1092,103 +790,6 @@ int drba_rgbx(const float *img, float *out, int H, int W, void *stream) {
   if (!img || !out || H <= 0 || W <= 0 || ((uintptr_t)out & 15) != 0) return DRBA_EINVAL;
   const size_t P = (size_t)H * W;
   DRBA_LAUNCH(rgbx_kernel, dim3(grid_for(P)), dim3(kBlock), 0, (hipStream_t)stream, img, out, P);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
-}
-
-int drba_u8hwc_to_f32nchw(const uint8_t *in, float *out, int H, int W, void *stream) {
-  if (!in || !out || H <= 0 || W <= 0) return DRBA_EINVAL;
-  DRBA_LAUNCH(u8_to_f32_kernel, dim3(grid_for((size_t)H * W)), dim3(kBlock), 0, (hipStream_t)stream, in, out, H, W);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
-}
-
-int drba_f32nchw_to_u8hwc(const float *in, uint8_t *out, int H, int W, void *stream) {
-  if (!in || !out || H <= 0 || W <= 0) return DRBA_EINVAL;
-  DRBA_LAUNCH(f32_to_u8_kernel, dim3(grid_for((size_t)H * W)), dim3(kBlock), 0, (hipStream_t)stream, in, out, H, W);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
-}
-
-int drba_to_inp_x4(const uint8_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
-                   void *stream) {
-  if (!img_hwc || !out || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || ((uintptr_t)out_x4 & 15) != 0) return DRBA_EINVAL;
-  if (Win == Wout && scale_x == 1.f && (Wout & 3) == 0 && (((uintptr_t)img_hwc & 3) | ((uintptr_t)out & 15)) == 0) {
-    DRBA_LAUNCH(to_inp_rows_kernel, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4,
-                Hin, Wout, Hout, scale_y);
-    DRBA_CHECK_LAUNCH();
-    return DRBA_OK;
-  }
-  DRBA_LAUNCH(to_inp_kernel, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4, Hin, Win, Hout,
-              Wout, scale_y, scale_x);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
-}
-
-int drba_to_inp(const uint8_t *img_hwc, float *out, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
-                void *stream) {
-  return drba_to_inp_x4(img_hwc, out, nullptr, Hin, Win, Hout, Wout, scale_y, scale_x, stream);
-}
-
-int drba_to_out(const float *in, uint8_t *out_hwc, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
-                int reverse_channels, void *stream) {
-  if (!in || !out_hwc || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0) return DRBA_EINVAL;
-  if (Win == Wout && scale_x == 1.f && (Wout & 3) == 0 && (((uintptr_t)out_hwc & 3) | ((uintptr_t)in & 15)) == 0) {
-    DRBA_LAUNCH(to_out_rows_kernel, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin,
-                Wout, Hout, scale_y, reverse_channels);
-    DRBA_CHECK_LAUNCH();
-    return DRBA_OK;
-  }
-  DRBA_LAUNCH(to_out_kernel, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Win, Hout,
-              Wout, scale_y, scale_x, reverse_channels);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
-}
-
-static bool maxval_ok(float maxval) { return maxval > 255.f && maxval <= 65535.f; }  // (NaN fails both)
-
-int drba_u16hwc_to_f32nchw(const uint16_t *in, float *out, int H, int W, float maxval, void *stream) {
-  if (!in || !out || H <= 0 || W <= 0 || !maxval_ok(maxval) || ((uintptr_t)in & 1) != 0) return DRBA_EINVAL;
-  DRBA_LAUNCH(u16_to_f32_kernel, dim3(grid_for((size_t)H * W)), dim3(kBlock), 0, (hipStream_t)stream, in, out, H, W, maxval);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
-}
-
-int drba_f32nchw_to_u16hwc(const float *in, uint16_t *out, int H, int W, float maxval, void *stream) {
-  if (!in || !out || H <= 0 || W <= 0 || !maxval_ok(maxval) || ((uintptr_t)out & 1) != 0) return DRBA_EINVAL;
-  DRBA_LAUNCH(f32_to_u16_kernel, dim3(grid_for((size_t)H * W)), dim3(kBlock), 0, (hipStream_t)stream, in, out, H, W, maxval);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
-}
-
-int drba_to_inp16_x4(const uint16_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y,
-                     float scale_x, float maxval, void *stream) {
-  if (!img_hwc || !out || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || ((uintptr_t)out_x4 & 15) != 0) return DRBA_EINVAL;
-  if (!maxval_ok(maxval) || ((uintptr_t)img_hwc & 1) != 0) return DRBA_EINVAL;
-  if (Win == Wout && scale_x == 1.f && (Wout & 3) == 0 && (((uintptr_t)img_hwc & 7) | ((uintptr_t)out & 15)) == 0) {
-    DRBA_LAUNCH(to_inp16_rows_kernel, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out,
-                out_x4, Hin, Wout, Hout, scale_y, maxval);
-    DRBA_CHECK_LAUNCH();
-    return DRBA_OK;
-  }
-  DRBA_LAUNCH(to_inp16_kernel, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4, Hin, Win, Hout,
-              Wout, scale_y, scale_x, maxval);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
-}
-
-int drba_to_out16(const float *in, uint16_t *out_hwc, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
-                  int reverse_channels, float maxval, void *stream) {
-  if (!in || !out_hwc || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0) return DRBA_EINVAL;
-  if (!maxval_ok(maxval) || ((uintptr_t)out_hwc & 1) != 0) return DRBA_EINVAL;
-  if (Win == Wout && scale_x == 1.f && (Wout & 3) == 0 && (((uintptr_t)out_hwc & 7) | ((uintptr_t)in & 15)) == 0) {
-    DRBA_LAUNCH(to_out16_rows_kernel, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin,
-                Wout, Hout, scale_y, reverse_channels, maxval);
-    DRBA_CHECK_LAUNCH();
-    return DRBA_OK;
-  }
-  DRBA_LAUNCH(to_out16_kernel, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Win, Hout,
-              Wout, scale_y, scale_x, reverse_channels, maxval);
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }

@@ -204,18 +204,6 @@ typedef unsigned long long u64;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4u __attribute__((ext_vector_type(4), aligned(1)));
 
-struct ErrU8 {
-  u64 sq, ab, mx, nz;
-};
-
-__device__ __forceinline__ void acc_byte(unsigned a, unsigned b, unsigned &sq, unsigned &ab, unsigned &mx, unsigned &nz) {
-  const unsigned d = a > b ? a - b : b - a;
-  sq += d * d;
-  ab += d;
-  mx = max(mx, d);
-  nz += d != 0u;
-}
-
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   return v;
@@ -228,106 +216,68 @@ __device__ __forceinline__ u64 wave_max_u64(u64 v) {
   return v;
 }
 
-// per item: head bytes up to a's next 16-byte boundary, 16-byte chunks (b's loads unaligned when its phase differs), tail bytes
-__global__ void __launch_bounds__(256) frame_error_u8_kernel(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b,
-                                                             size_t n, int parts, u64 *__restrict__ partial) {
-  __shared__ u64 red[4][4];
-  const uint8_t *pa = a + (size_t)blockIdx.y * n, *pb = b + (size_t)blockIdx.y * n;
-  size_t head = (size_t)((16u - (unsigned)((uintptr_t)pa & 15u)) & 15u);
-  if (head > n) head = n;
-  const size_t chunks = (n - head) >> 4, tail0 = head + (chunks << 4);
-  const bool same_phase = (((uintptr_t)pa ^ (uintptr_t)pb) & 15u) == 0;
-  u64 sq = 0, ab = 0;
-  unsigned mx = 0, nz = 0;
-  const size_t gtid = (size_t)blockIdx.x * 256 + threadIdx.x, gstride = (size_t)parts * 256;
-  for (size_t i = gtid; i < chunks; i += gstride) {
-    const u32x4 va = *reinterpret_cast<const u32x4 *>(pa + head + (i << 4));
-    u32x4 vb;
-    if (same_phase)
-      vb = *reinterpret_cast<const u32x4 *>(pb + head + (i << 4));
-    else
-      vb = *reinterpret_cast<const u32x4u *>(pb + head + (i << 4));
-    unsigned csq = 0, cab = 0;  // 16 bytes: at most 16 * 255^2, far inside 32 bits
-#pragma unroll
-    for (int w = 0; w < 4; ++w)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) acc_byte((va[w] >> (8 * k)) & 0xffu, (vb[w] >> (8 * k)) & 0xffu, csq, cab, mx, nz);
-    sq += csq;
-    ab += cab;
-  }
-  // head and tail: fewer than 32 bytes per item, taken by the first workgroup
-  if (blockIdx.x == 0) {
-    const size_t edge = head + (n - tail0);
-    if (threadIdx.x < edge) {
-      const size_t e = threadIdx.x < head ? threadIdx.x : tail0 + (threadIdx.x - head);
-      unsigned csq = 0, cab = 0;
-      acc_byte(pa[e], pb[e], csq, cab, mx, nz);
-      sq += csq;
-      ab += cab;
-    }
-  }
-  sq = wave_sum_u64(sq);
-  ab = wave_sum_u64(ab);
-  const u64 m = wave_max_u64(mx), z = wave_sum_u64(nz);
-  if ((threadIdx.x & 63) == 0) {
-    const int w = threadIdx.x >> 6;
-    red[w][0] = sq;
-    red[w][1] = ab;
-    red[w][2] = m;
-    red[w][3] = z;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 *o = partial + ((size_t)blockIdx.y * parts + blockIdx.x) * 4;
-    o[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-    o[1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-    o[2] = max(max(red[0][2], red[1][2]), max(red[2][2], red[3][2]));
-    o[3] = red[0][3] + red[1][3] + red[2][3] + red[3][3];
-  }
-}
-
-// uint16 samples: the same walk in samples -- head up to a's next 16-byte boundary (a is 2-byte aligned: fewer than 8), chunks of
-// 8, tail.  One d^2 fits 32 bits (65535^2 < 2^32), two do not: the squares are added in 64 bits; the partials have the byte
-// kernel's layout and go through frame_error_u8_final.
-__device__ __forceinline__ void acc_u16(unsigned a, unsigned b, u64 &sq, unsigned &ab, unsigned &mx, unsigned &nz) {
+// One difference into the sums.  SQ is what the squares are added in, and why each width is exact:
+// bytes: unsigned, one per 16-byte chunk -- 16 * 255^2 is far inside 32 bits -- that is then added to the 64-bit sum;
+// uint16: the 64-bit sum itself -- one d^2 fits 32 bits (65535^2 < 2^32), two do not.
+template <class SQ>
+__device__ __forceinline__ void acc_sample(unsigned a, unsigned b, SQ &sq, unsigned &ab, unsigned &mx, unsigned &nz) {
   const unsigned d = a > b ? a - b : b - a;
-  sq += (u64)(d * d);
+  sq += (SQ)(d * d);
   ab += d;
   mx = max(mx, d);
   nz += d != 0u;
 }
 
-__global__ void __launch_bounds__(256) frame_error_u16_kernel(const uint16_t *__restrict__ a, const uint16_t *__restrict__ b,
-                                                              size_t n, int parts, u64 *__restrict__ partial) {
+// T = uint8_t / uint16_t.  Per item: head samples up to a's next 16-byte boundary (a is aligned to its samples), 16-byte chunks
+// (b's loads unaligned when its phase differs), tail samples; the wave and workgroup reduction; one partial
+// (sum d^2, sum |d|, max |d|, differing) per workgroup for frame_error_u8_final.
+template <class T>
+__device__ __forceinline__ void frame_error_body(const T *__restrict__ a, const T *__restrict__ b, size_t n, int parts,
+                                                 u64 *__restrict__ partial) {
+  constexpr int kBits = 8 * (int)sizeof(T), kPerWord = 32 / kBits;
+  constexpr size_t kPerChunk = 16 / sizeof(T);
   __shared__ u64 red[4][4];
-  const uint16_t *pa = a + (size_t)blockIdx.y * n, *pb = b + (size_t)blockIdx.y * n;
-  size_t head = (size_t)(((16u - (unsigned)((uintptr_t)pa & 15u)) & 15u) >> 1);
+  const T *pa = a + (size_t)blockIdx.y * n, *pb = b + (size_t)blockIdx.y * n;
+  size_t head = (size_t)(((16u - (unsigned)((uintptr_t)pa & 15u)) & 15u) / (unsigned)sizeof(T));
   if (head > n) head = n;
-  const size_t chunks = (n - head) >> 3, tail0 = head + (chunks << 3);
+  const size_t chunks = (n - head) / kPerChunk, tail0 = head + chunks * kPerChunk;
   const bool same_phase = (((uintptr_t)pa ^ (uintptr_t)pb) & 15u) == 0;
   u64 sq = 0, ab = 0;
   unsigned mx = 0, nz = 0;
+  auto with_sq = [&](auto &&step) {  // step(what the squares of one chunk, or of one edge sample, are added in)
+    if constexpr (sizeof(T) == 1) {
+      unsigned csq = 0;
+      step(csq);
+      sq += csq;
+    } else {
+      step(sq);
+    }
+  };
   const size_t gtid = (size_t)blockIdx.x * 256 + threadIdx.x, gstride = (size_t)parts * 256;
   for (size_t i = gtid; i < chunks; i += gstride) {
-    const u32x4 va = *reinterpret_cast<const u32x4 *>(pa + head + (i << 3));
+    const u32x4 va = *reinterpret_cast<const u32x4 *>(pa + head + i * kPerChunk);
     u32x4 vb;
     if (same_phase)
-      vb = *reinterpret_cast<const u32x4 *>(pb + head + (i << 3));
+      vb = *reinterpret_cast<const u32x4 *>(pb + head + i * kPerChunk);
     else
-      vb = *reinterpret_cast<const u32x4u *>(pb + head + (i << 3));
-    unsigned cab = 0;  // 8 samples: at most 8 * 65535
+      vb = *reinterpret_cast<const u32x4u *>(pb + head + i * kPerChunk);
+    unsigned cab = 0;  // at most 16 * 255 or 8 * 65535
+    with_sq([&](auto &csq) {
 #pragma unroll
-    for (int w = 0; w < 4; ++w)
+      for (int w = 0; w < 4; ++w)
 #pragma unroll
-      for (int k = 0; k < 2; ++k) acc_u16((va[w] >> (16 * k)) & 0xffffu, (vb[w] >> (16 * k)) & 0xffffu, sq, cab, mx, nz);
+        for (int k = 0; k < kPerWord; ++k)
+          acc_sample((va[w] >> (kBits * k)) & ((1u << kBits) - 1u), (vb[w] >> (kBits * k)) & ((1u << kBits) - 1u), csq, cab, mx, nz);
+    });
     ab += cab;
   }
-  if (blockIdx.x == 0) {  // head and tail: fewer than 16 samples per item, taken by the first workgroup
+  // head and tail: fewer than two chunks of samples per item, taken by the first workgroup
+  if (blockIdx.x == 0) {
     const size_t edge = head + (n - tail0);
     if (threadIdx.x < edge) {
       const size_t e = threadIdx.x < head ? threadIdx.x : tail0 + (threadIdx.x - head);
       unsigned cab = 0;
-      acc_u16(pa[e], pb[e], sq, cab, mx, nz);
+      with_sq([&](auto &csq) { acc_sample(pa[e], pb[e], csq, cab, mx, nz); });
       ab += cab;
     }
   }
@@ -349,6 +299,15 @@ __global__ void __launch_bounds__(256) frame_error_u16_kernel(const uint16_t *__
     o[2] = max(max(red[0][2], red[1][2]), max(red[2][2], red[3][2]));
     o[3] = red[0][3] + red[1][3] + red[2][3] + red[3][3];
   }
+}
+
+__global__ void __launch_bounds__(256) frame_error_u8_kernel(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b,
+                                                             size_t n, int parts, u64 *__restrict__ partial) {
+  frame_error_body(a, b, n, parts, partial);
+}
+__global__ void __launch_bounds__(256) frame_error_u16_kernel(const uint16_t *__restrict__ a, const uint16_t *__restrict__ b,
+                                                              size_t n, int parts, u64 *__restrict__ partial) {
+  frame_error_body(a, b, n, parts, partial);
 }
 
 __global__ void __launch_bounds__(256) frame_error_u8_final(const u64 *__restrict__ partial, int parts, u64 *__restrict__ out) {
@@ -509,34 +468,33 @@ extern "C" size_t drba_frame_error_ws_floats(int N, size_t n_per_item) {
   return (size_t)N * kErrParts * 4 * 2;  // 4 x 8 bytes per workgroup
 }
 
-extern "C" int drba_frame_error_u8(const uint8_t *a, const uint8_t *b, unsigned long long *out, float *ws, int N,
-                                   size_t n_per_item, void *stream) {
+// the integer kinds: a partial per workgroup, then frame_error_u8_final; a thread takes 8 chunks of 16 bytes
+template <class T>
+static int frame_error_int(void (*kernel)(const T *, const T *, size_t, int, u64 *), const T *a, const T *b, unsigned long long *out,
+                           float *ws, int N, size_t n_per_item, size_t n_max, void *stream) {
   if (!a || !b || !out || !ws || N < 1 || n_per_item < 1) return DRBA_EINVAL;
   if (((uintptr_t)ws & 7u) || ((uintptr_t)out & 7u)) return DRBA_EINVAL;
-  if (N > 65535) return DRBA_EUNSUPPORTED;
-  const int parts = err_parts(n_per_item, 16 * 8);
+  if (N > 65535 || n_per_item > n_max) return DRBA_EUNSUPPORTED;
+  const int parts = err_parts(n_per_item, (16 / sizeof(T)) * 8);
   hipStream_t s = (hipStream_t)stream;
-  DRBA_LAUNCH(frame_error_u8_kernel, dim3(parts, N), dim3(256), 0, s, a, b, n_per_item, parts, reinterpret_cast<u64 *>(ws));
+  DRBA_LAUNCH(kernel, dim3(parts, N), dim3(256), 0, s, a, b, n_per_item, parts, reinterpret_cast<u64 *>(ws));
   DRBA_CHECK_LAUNCH();
   DRBA_LAUNCH(frame_error_u8_final, dim3(N), dim3(256), 0, s, reinterpret_cast<const u64 *>(ws), parts, reinterpret_cast<u64 *>(out));
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }
 
+extern "C" int drba_frame_error_u8(const uint8_t *a, const uint8_t *b, unsigned long long *out, float *ws, int N,
+                                   size_t n_per_item, void *stream) {
+  return frame_error_int(frame_error_u8_kernel, a, b, out, ws, N, n_per_item, SIZE_MAX, stream);
+}
+
 extern "C" size_t drba_frame_error_u16_ws_floats(int N, size_t n_per_item) { return drba_frame_error_ws_floats(N, n_per_item); }
 
 extern "C" int drba_frame_error_u16(const uint16_t *a, const uint16_t *b, unsigned long long *out, float *ws, int N,
                                     size_t n_per_item, void *stream) {
-  if (!a || !b || !out || !ws || N < 1 || n_per_item < 1) return DRBA_EINVAL;
-  if (((uintptr_t)ws & 7u) || ((uintptr_t)out & 7u) || (((uintptr_t)a | (uintptr_t)b) & 1u)) return DRBA_EINVAL;
-  if (N > 65535 || n_per_item > 0xffffffffull) return DRBA_EUNSUPPORTED;  // sum d^2 < 2^32 * 2^32
-  const int parts = err_parts(n_per_item, 8 * 8);
-  hipStream_t s = (hipStream_t)stream;
-  DRBA_LAUNCH(frame_error_u16_kernel, dim3(parts, N), dim3(256), 0, s, a, b, n_per_item, parts, reinterpret_cast<u64 *>(ws));
-  DRBA_CHECK_LAUNCH();
-  DRBA_LAUNCH(frame_error_u8_final, dim3(N), dim3(256), 0, s, reinterpret_cast<const u64 *>(ws), parts, reinterpret_cast<u64 *>(out));
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
+  if ((((uintptr_t)a | (uintptr_t)b) & 1u)) return DRBA_EINVAL;
+  return frame_error_int(frame_error_u16_kernel, a, b, out, ws, N, n_per_item, (size_t)0xffffffffull, stream);  // sum d^2 < 2^32 * 2^32
 }
 
 extern "C" int drba_frame_error_f32(const float *a, const float *b, double *out, float *ws, int N, size_t n_per_item,

@@ -497,27 +497,6 @@ def resize_bilinear_scale(x, size, src_scale):
     return out
 
 
-def u8hwc_to_f32nchw(img_u8):
-    if not (img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 3 and img_u8.shape[2] == 3):
-        raise _lib.DrbaHipError("expected a CUDA uint8 [H,W,3] tensor")
-    img_u8 = img_u8.contiguous()
-    h, w = img_u8.shape[:2]
-    out = torch.empty((1, 3, h, w), dtype=torch.float32, device=img_u8.device)
-    _lib.check(_timed("u8hwc_to_f32nchw", (h, w), 15.0 * h * w, "byte", lambda: _lib.load().drba_u8hwc_to_f32nchw(
-        _p(img_u8), _p(out), h, w, _stream())), "drba_u8hwc_to_f32nchw")
-    return out
-
-
-def f32nchw_to_u8hwc(x):
-    x = _f32(x)
-    assert x.shape[0] == 1 and x.shape[1] == 3
-    h, w = x.shape[2:]
-    out = torch.empty((h, w, 3), dtype=torch.uint8, device=x.device)
-    _lib.check(_timed("f32nchw_to_u8hwc", (h, w), 15.0 * h * w, "byte", lambda: _lib.load().drba_f32nchw_to_u8hwc(
-        _p(x), _p(out), h, w, _stream())), "drba_f32nchw_to_u8hwc")
-    return out
-
-
 def _maxval(maxval):
     """The largest sample of a 16-bit frame: 65535 unless given (1023: 10-bit data); an integer in (255, 65535]."""
     if maxval is None:
@@ -527,67 +506,77 @@ def _maxval(maxval):
     return int(maxval)
 
 
-def _is_u16_frame(t):
-    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint16 and t.dim() == 3 and t.shape[2] == 3
+def _is_frame(t, dtype):
+    return torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.dim() == 3 and t.shape[2] == 3
+
+
+def _sample_kind(dtype, maxval):
+    """What the frame paths of the two sample types differ in -> (bytes per sample, the tag of their trace kinds and library
+    entries, the maxval argument the 16-bit entries take in front of the stream)."""
+    if dtype == torch.uint16:
+        return 2, "16", (float(_maxval(maxval)),)
+    return 1, "", ()
+
+
+def _hwc_to_f32nchw(img, dtype, maxval=None):
+    if not _is_frame(img, dtype):
+        raise _lib.DrbaHipError(f"expected a CUDA {str(dtype)[6:]} [H,W,3] tensor")
+    size, _, mv = _sample_kind(dtype, maxval)
+    img = img.contiguous()
+    h, w = img.shape[:2]
+    out = torch.empty((1, 3, h, w), dtype=torch.float32, device=img.device)
+    name = f"u{8 * size}hwc_to_f32nchw"
+    _lib.check(_timed(name, (h, w), (12.0 + 3.0 * size) * h * w, "byte", lambda: getattr(_lib.load(), "drba_" + name)(
+        _p(img), _p(out), h, w, *mv, _stream())), "drba_" + name)
+    return out
+
+
+def _f32nchw_to_hwc(x, dtype, maxval=None):
+    size, _, mv = _sample_kind(dtype, maxval)
+    x = _f32(x)
+    assert x.shape[0] == 1 and x.shape[1] == 3
+    h, w = x.shape[2:]
+    out = torch.empty((h, w, 3), dtype=dtype, device=x.device)
+    name = f"f32nchw_to_u{8 * size}hwc"
+    _lib.check(_timed(name, (h, w), (12.0 + 3.0 * size) * h * w, "byte", lambda: getattr(_lib.load(), "drba_" + name)(
+        _p(x), _p(out), h, w, *mv, _stream())), "drba_" + name)
+    return out
+
+
+def u8hwc_to_f32nchw(img_u8):
+    return _hwc_to_f32nchw(img_u8, torch.uint8)
+
+
+def f32nchw_to_u8hwc(x):
+    return _f32nchw_to_hwc(x, torch.uint8)
 
 
 def u16hwc_to_f32nchw(img_u16, maxval=None):
     """u8hwc_to_f32nchw for a uint16 frame: / maxval."""
-    if not _is_u16_frame(img_u16):
-        raise _lib.DrbaHipError("expected a CUDA uint16 [H,W,3] tensor")
-    mv = float(_maxval(maxval))
-    img_u16 = img_u16.contiguous()
-    h, w = img_u16.shape[:2]
-    out = torch.empty((1, 3, h, w), dtype=torch.float32, device=img_u16.device)
-    _lib.check(_timed("u16hwc_to_f32nchw", (h, w), 18.0 * h * w, "byte", lambda: _lib.load().drba_u16hwc_to_f32nchw(
-        _p(img_u16), _p(out), h, w, mv, _stream())), "drba_u16hwc_to_f32nchw")
-    return out
+    return _hwc_to_f32nchw(img_u16, torch.uint16, maxval)
 
 
 def f32nchw_to_u16hwc(x, maxval=None):
     """fp32 [1,3,H,W] -> uint16 [H,W,3]: x * maxval rounded to nearest even and saturated to [0, maxval], NaN -> 0."""
-    mv = float(_maxval(maxval))
-    x = _f32(x)
-    assert x.shape[0] == 1 and x.shape[1] == 3
-    h, w = x.shape[2:]
-    out = torch.empty((h, w, 3), dtype=torch.uint16, device=x.device)
-    _lib.check(_timed("f32nchw_to_u16hwc", (h, w), 18.0 * h * w, "byte", lambda: _lib.load().drba_f32nchw_to_u16hwc(
-        _p(x), _p(out), h, w, mv, _stream())), "drba_f32nchw_to_u16hwc")
-    return out
-
-
-def _to_inp16(img_u16, dst_size, maxval):
-    mv = float(_maxval(maxval))
-    img_u16 = img_u16.contiguous()
-    h, w = img_u16.shape[:2]
-    ho, wo = int(dst_size[0]), int(dst_size[1])
-    out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=img_u16.device)
-    x4 = torch.empty((ho, wo, 4), dtype=torch.float32, device=img_u16.device) if IMG_X4 else None
-    sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))  # ATen: static_cast<float>(in) / out
-    _lib.check(_timed("to_inp16", (h, w, ho, wo), 6.0 * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
-                      lambda: _lib.load().drba_to_inp16_x4(_p(img_u16), _p(out), _p(x4), h, w, ho, wo, sy, sx, mv, _stream())),
-               "drba_to_inp16_x4")
-    if x4 is not None:
-        _set_copy(out, "_drba_x4", x4)
-    return out
+    return _f32nchw_to_hwc(x, torch.uint16, maxval)
 
 
 def to_inp(img_u8, dst_size, maxval=None):
     """tools.to_inp on a device-resident frame: uint8 [H,W,3] -> fp32 [1,3,*dst_size] in [0,1], one kernel.  A uint16 [H,W,3]
     frame takes the 16-bit kernel: its samples are divided by `maxval` (65535 unless given; 255 < maxval <= 65535)."""
-    if _is_u16_frame(img_u8):
-        return _to_inp16(img_u8, dst_size, maxval)
-    if not (torch.is_tensor(img_u8) and img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 3 and img_u8.shape[2] == 3):
+    if not (_is_frame(img_u8, torch.uint8) or _is_frame(img_u8, torch.uint16)):
         raise _lib.DrbaHipError("expected a CUDA uint8 or uint16 [H,W,3] tensor")
-    img_u8 = img_u8.contiguous()
-    h, w = img_u8.shape[:2]
+    size, tag, mv = _sample_kind(img_u8.dtype, maxval)
+    img = img_u8.contiguous()
+    h, w = img.shape[:2]
     ho, wo = int(dst_size[0]), int(dst_size[1])
-    out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=img_u8.device)
+    out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=img.device)
     # ... and the same frame pixel-major, [H,W,4]: what the gathers read their image taps from (IMG_X4), written in the same pass
-    x4 = torch.empty((ho, wo, 4), dtype=torch.float32, device=img_u8.device) if IMG_X4 else None
+    x4 = torch.empty((ho, wo, 4), dtype=torch.float32, device=img.device) if IMG_X4 else None
     sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))  # ATen: static_cast<float>(in) / out
-    _lib.check(_timed("to_inp", (h, w, ho, wo), 3.0 * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
-                      lambda: _lib.load().drba_to_inp_x4(_p(img_u8), _p(out), _p(x4), h, w, ho, wo, sy, sx, _stream())), "drba_to_inp_x4")
+    entry = f"drba_to_inp{tag}_x4"
+    _lib.check(_timed("to_inp" + tag, (h, w, ho, wo), 3.0 * size * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
+                      lambda: getattr(_lib.load(), entry)(_p(img), _p(out), _p(x4), h, w, ho, wo, sy, sx, *mv, _stream())), entry)
     if x4 is not None:
         _set_copy(out, "_drba_x4", x4)
     return out
@@ -608,15 +597,12 @@ def to_out(x, src_size, rgb=False, depth=8, maxval=None):
     h, w = x.shape[2:]
     ho, wo = int(src_size[0]), int(src_size[1])
     sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))
-    if depth == 16:
-        mv = float(_maxval(maxval))
-        out = torch.empty((ho, wo, 3), dtype=torch.uint16, device=x.device)
-        _lib.check(_timed("to_out16", (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 6.0 * ho * wo, "byte", lambda: _lib.load().drba_to_out16(
-            _p(x), _p(out), h, w, ho, wo, sy, sx, 1 if rgb else 0, mv, _stream())), "drba_to_out16")
-        return out
-    out = torch.empty((ho, wo, 3), dtype=torch.uint8, device=x.device)
-    _lib.check(_timed("to_out", (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 3.0 * ho * wo, "byte", lambda: _lib.load().drba_to_out(
-        _p(x), _p(out), h, w, ho, wo, sy, sx, 1 if rgb else 0, _stream())), "drba_to_out")
+    dtype = torch.uint16 if depth == 16 else torch.uint8
+    size, tag, mv = _sample_kind(dtype, maxval)
+    out = torch.empty((ho, wo, 3), dtype=dtype, device=x.device)
+    entry = "drba_to_out" + tag
+    _lib.check(_timed("to_out" + tag, (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 3.0 * size * ho * wo, "byte",
+                      lambda: getattr(_lib.load(), entry)(_p(x), _p(out), h, w, ho, wo, sy, sx, 1 if rgb else 0, *mv, _stream())), entry)
     return out
 
 

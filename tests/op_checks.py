@@ -1,6 +1,6 @@
 """Per-operator fp64 parity checks of the GMFlow / GMFSS glue kernels (gmflow.hip, gmfss_glue.hip, the small kernels of
-splat_warp.hip and the layout kernels of ifnet_glue.hip), shared by tests/test_gpu_op_parity.py, tests/test_op_checks_cpu.py and
-the diagnostic report (python -m tests.gpu_report).
+splat_warp.hip and the layout kernels of ifnet_glue.hip and frame_io.hip), shared by tests/test_gpu_op_parity.py,
+tests/test_op_checks_cpu.py and the diagnostic report (python -m tests.gpu_report).
 
 Every check takes the device the inputs go to and the `ops` namespace under test (default: drba_amd.ops; the CPU test hands
 in a torch stand-in, with and without a planted defect) and returns rows (name, err, tol, extra) with the pass rule of every

@@ -1,5 +1,6 @@
-"""GPU: 16-bit frames -- the conversion kernels (ifnet_glue.hip: drba_to_inp16_x4, drba_to_out16 and the no-resize pair) bit for
-bit against the CPU restatement of tests/depth16_common.py, the identity of the round trip, drba_frame_error_u16 against numpy
+"""GPU: 16-bit frames -- the conversion kernels (frame_io.hip: drba_to_inp16_x4, drba_to_out16 and the no-resize pair) bit for
+bit against the CPU restatement of tests/depth16_common.py (and their 8-bit siblings, which share their bodies, at the same
+shapes against the same resize), the identity of the round trip, drba_frame_error_u16 against numpy
 int64, the "u16" kind of drba_amd.metrics, a whole clip through interpolate_stream against the CPU oracle driver, and the command
 lines.  Shapes are the smallest that reach each kernel form (the form a call took is read from the launch trace)."""
 import ctypes as C
@@ -88,6 +89,33 @@ def test_to_inp16_to_out16_bit_exact_against_the_cpu_restatement(dev, src, net, 
     if src == (45, 70):  # output (17, 26) reads rows 24, 25 and columns 47, 48; output (31, 26) rows 44, 45: inside the blocks
         b = ops.to_out(x.to(dev), src, depth=16, maxval=maxval).cpu().numpy()
         assert b[17, 26].tolist() == [0, maxval, 0] and b[31, 26, 0] == maxval
+
+
+@pytest.mark.parametrize("src,net,form", GEOMETRIES)
+def test_to_inp_to_out_8bit_bit_exact_in_both_forms(dev, src, net, form):
+    """The byte kernels at the shapes of the 16-bit test, in every bit: to_inp against resize(frame / 255) with the loop ATen runs
+    on frames (d16.resize), its [H,W,4] copy against its own planar result, and to_out of a finite frame slightly outside [0, 1]
+    -- truncation and wrap-around -- with rgb off and on against (resize(x) * 255.).astype(uint8), the form read from the trace."""
+    g = torch.Generator().manual_seed(src[0] * 1000 + src[1])
+    f = torch.randint(0, 256, (src[0], src[1], 3), dtype=torch.uint8, generator=g)
+    want = d16.resize(f.permute(2, 0, 1).unsqueeze(0).float() / 255, net)
+    got, names = _traced(lambda: ops.to_inp(f.to(dev), net))
+    assert [("rows" if "rows" in n else "one-pixel") for n in names if "to_inp_" in n] == [form] and not [n for n in names if "16" in n], names
+    assert torch.equal(got.cpu(), want), float((got.cpu() - want).abs().max())
+    x4 = ops._x4_of(got)
+    assert x4 is not None and tuple(x4.shape) == (net[0], net[1], 4)
+    assert torch.equal(x4[:, :, :3], got[0].permute(1, 2, 0)) and not bool(x4[:, :, 3].any())
+
+    x = torch.rand(1, 3, net[0], net[1], generator=g) * 1.02 - 0.01
+    assert bool(torch.isfinite(x).all()) and float(x.min()) < 0.0 and float(x.max()) > 1.0
+    ref = (d16.resize(x, src)[0].numpy().transpose(1, 2, 0) * 255.).astype(np.uint8)
+    for rev in (False, True):
+        back, names = _traced(lambda: ops.to_out(x.to(dev), src, rgb=rev))
+        assert [("rows" if "rows" in n else "one-pixel") for n in names if "to_out_" in n] == [form] and not [n for n in names if "16" in n], names
+        assert back.dtype == torch.uint8 and tuple(back.shape) == (src[0], src[1], 3)
+        du = np.abs(back.cpu().numpy().astype(np.int32) - (ref[:, :, ::-1] if rev else ref).astype(np.int32))
+        du = np.minimum(du, 256 - du)  # uint8 wrap-around of slightly negative / > 1 values
+        assert int(du.max()) == 0, (rev, int(du.max()), int((du != 0).sum()))
 
 
 @pytest.mark.parametrize("maxval", [65535, 1023])
