@@ -301,6 +301,332 @@ DRBA_FRAME_KERNEL f32_to_u8_kernel(const float *__restrict__ in, uint8_t *__rest
 DRBA_FRAME_KERNEL f32_to_u16_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int H, int W, float maxval) {
   f32_to_samples_body(Samples16{maxval}, in, out, H, W);
 }
+
+// ---- planar YCbCr 4:2:0 frames (include/drba_hip.h, ABI 14) -------------------------------------------------------------------
+// Three planes instead of HWC samples: Y [H][W], U and V [ceil(H/2)][ceil(W/2)].  The colour conversion and the chroma
+// resampling happen inside the conversion kernels, on the taps the resize reads (way in) or on the pixels it produced (way
+// out): the full-size RGB frame is never formed.  The network tensor keeps the BGR channel order.  The constants are worked
+// out on the host in double (yuv_in_consts / yuv_out_consts below); everything here is fp32.
+struct YuvIn {
+  float y_off, y_mul, c_off, c_mul;  // Y' = (y - y_off) * y_mul, Cb = (u - c_off) * c_mul
+  float r_cr, b_cb, kr, kb, inv_kg;  // R = Y' + r_cr Cr, B = Y' + b_cb Cb, G = (Y' - kr R - kb B) * inv_kg
+};
+struct YuvOut {
+  float kr, kg, kb, cb_mul, cr_mul;  // Y' = kr R + kg G + kb B, Cb = (B - Y') * cb_mul, Cr = (R - Y') * cr_mul
+  float y_off, y_mul, c_off, c_mul;  // y = y_off + y_mul Y', u = c_off + c_mul Cb
+  float maxval;
+};
+
+// The two chroma taps of luma coordinate p along one axis of nc chroma samples: the bilinear taps at s = p / 2 - 0.25 clamped
+// to [0, nc - 1].  Even p: (p/2 - 1, p/2) with weights (1/4, 3/4); odd p: ((p-1)/2, (p+1)/2) with (3/4, 1/4).  At the two ends
+// the clamp of s makes the weights (1, 0) on the edge sample; clamping the INDEX instead gives both taps the edge sample, and
+// a / 4 + 3 a / 4 == a exactly for a sample of at most 20 bits, so no case is told apart.  Sums of samples weighted by
+// sixteenths are exact in fp32 too: the interpolated chroma carries no rounding at all.
+struct CTap {
+  int i0, i1;
+  float w0, w1;
+};
+__device__ __forceinline__ CTap chroma_tap(int p, int nc) {
+  CTap t;
+  const int h = p >> 1;
+  if (p & 1) {
+    t.i0 = h, t.i1 = min(h + 1, nc - 1);
+    t.w0 = 0.75f, t.w1 = 0.25f;
+  } else {
+    t.i0 = max(h - 1, 0), t.i1 = h;
+    t.w0 = 0.25f, t.w1 = 0.75f;
+  }
+  return t;
+}
+__device__ __forceinline__ float clamp01(float v) {  // NaN -> 0
+  v = v >= 0.f ? v : 0.f;
+  return v > 1.f ? 1.f : v;
+}
+// one pixel: raw luma sample, raw chroma interpolated to its position -> (B, G, R) clamped to [0, 1]
+__device__ __forceinline__ void yuv_to_bgr(const YuvIn &k, float y, float u, float v, float (&bgr)[3]) {
+  const float Y = (y - k.y_off) * k.y_mul, Cb = (u - k.c_off) * k.c_mul, Cr = (v - k.c_off) * k.c_mul;
+  const float R = Y + k.r_cr * Cr, B = Y + k.b_cb * Cb;
+  const float G = (Y - k.kr * R - k.kb * B) * k.inv_kg;
+  bgr[0] = clamp01(B), bgr[1] = clamp01(G), bgr[2] = clamp01(R);
+}
+// (B, G, R) as the resize left them -> clamped, Y' and the two colour differences
+__device__ __forceinline__ void bgr_to_ycc(const YuvOut &k, float b, float g, float r, float &Y, float &Cb, float &Cr) {
+  b = clamp01(b), g = clamp01(g), r = clamp01(r);
+  Y = k.kr * r + k.kg * g + k.kb * b;
+  Cb = (b - Y) * k.cb_mul;
+  Cr = (r - Y) * k.cr_mul;
+}
+
+// the general form of the way in: one output pixel per lane, any size.  Each of the four taps of the resize is a source PIXEL,
+// converted from its luma sample and the 2 x 2 chroma taps of either plane.
+template <class T>
+__device__ __forceinline__ void yuv_pixel(const YuvIn &k, const T *__restrict__ yp, const T *__restrict__ up, const T *__restrict__ vp,
+                                          int ys, int cs, int Hc, int Wc, int sy, int sx, float (&bgr)[3]) {
+  const CTap ty = chroma_tap(sy, Hc), tx = chroma_tap(sx, Wc);
+  const size_t r0 = (size_t)ty.i0 * cs, r1 = (size_t)ty.i1 * cs;
+  const float u = ty.w0 * (tx.w0 * (float)up[r0 + tx.i0] + tx.w1 * (float)up[r0 + tx.i1]) +
+                  ty.w1 * (tx.w0 * (float)up[r1 + tx.i0] + tx.w1 * (float)up[r1 + tx.i1]);
+  const float v = ty.w0 * (tx.w0 * (float)vp[r0 + tx.i0] + tx.w1 * (float)vp[r0 + tx.i1]) +
+                  ty.w1 * (tx.w0 * (float)vp[r1 + tx.i0] + tx.w1 * (float)vp[r1 + tx.i1]);
+  yuv_to_bgr(k, (float)yp[(size_t)sy * ys + sx], u, v, bgr);
+}
+template <class T>
+__device__ __forceinline__ void to_inp_yuv_body(const YuvIn k, const T *__restrict__ yp, const T *__restrict__ up, const T *__restrict__ vp,
+                                                int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,
+                                                int Hout, int Wout, float sy, float sx) {
+  const Tile2D p = tile_pixel(Wout, Hout);
+  if (!p.valid) return;
+  const Lerp ly = lerp_src_aten(p.y, sy, Hin), lx = lerp_src_aten(p.x, sx, Win);
+  const int Hc = (Hin + 1) >> 1, Wc = (Win + 1) >> 1;
+  float a[3], b[3], c[3], d[3];
+  yuv_pixel(k, yp, up, vp, ys, cs, Hc, Wc, ly.i0, lx.i0, a);
+  yuv_pixel(k, yp, up, vp, ys, cs, Hc, Wc, ly.i0, lx.i1, b);
+  yuv_pixel(k, yp, up, vp, ys, cs, Hc, Wc, ly.i1, lx.i0, c);
+  yuv_pixel(k, yp, up, vp, ys, cs, Hc, Wc, ly.i1, lx.i1, d);
+  const size_t P = (size_t)Hout * Wout, o = (size_t)p.y * Wout + p.x;
+  float v[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    v[ch] = lerp2_aten(ly, lx, a[ch], b[ch], c[ch], d[ch]);
+    out[ch * P + o] = v[ch];
+  }
+  if (out_x4) *reinterpret_cast<f32x4g *>(out_x4 + 4 * o) = (f32x4g){v[0], v[1], v[2], 0.f};
+}
+
+// N consecutive samples of a plane row with one aligned load: 4 bytes (N = 4) or 8 (N = 8) for bytes, 8 or 16 for 16-bit samples
+template <class T, int N>
+struct SampleRow {
+  static constexpr int kBits = 8 * (int)sizeof(T), kPerWord = 32 / kBits, kWords = N / kPerWord;
+  uint32_t w[kWords];
+  __device__ __forceinline__ void load(const T *p) {
+    if constexpr (kWords == 1) {
+      w[0] = *reinterpret_cast<const uint32_t *>(p);
+    } else if constexpr (kWords == 2) {
+      const uint2 r = *reinterpret_cast<const uint2 *>(p);
+      w[0] = r.x, w[1] = r.y;
+    } else {
+      const uint4 r = *reinterpret_cast<const uint4 *>(p);
+      w[0] = r.x, w[1] = r.y, w[2] = r.z, w[3] = r.w;
+    }
+  }
+  __device__ __forceinline__ float sample(int j) const { return (float)((w[j / kPerWord] >> (kBits * (j % kPerWord))) & ((1u << kBits) - 1u)); }
+  // ... and N quantised samples (one per element of q) stored the same way
+  static __device__ __forceinline__ void store(T *p, const uint32_t (&q)[N]) {
+    uint32_t o[kWords];
+#pragma unroll
+    for (int j = 0; j < kWords; ++j) {
+      o[j] = 0;
+#pragma unroll
+      for (int e = 0; e < kPerWord; ++e) o[j] |= q[j * kPerWord + e] << (kBits * e);
+    }
+    if constexpr (kWords == 1)
+      *reinterpret_cast<uint32_t *>(p) = o[0];
+    else if constexpr (kWords == 2)
+      *reinterpret_cast<uint2 *>(p) = make_uint2(o[0], o[1]);
+    else
+      *reinterpret_cast<uint4 *>(p) = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+};
+
+// The rows form of the way in (an unchanged width that is a multiple of 8: only the height is resized).  A lane takes EIGHT
+// consecutive pixels of an output row: per source row one aligned load of 8 luma samples and, per chroma plane and chroma row,
+// one aligned load of the 4 samples under them plus their two neighbours (index clamped: see chroma_tap), then 2 x 3 16-byte
+// stores of the planes and 8 of the pixel-major copy.  The horizontal pass of the resize is the identity as in to_inp_rows_body.
+template <class T>
+__device__ __forceinline__ void chroma_raw6(const T *__restrict__ row, int Wc, int xc, float (&c)[6]) {
+  SampleRow<T, 4> a;
+  a.load(row + xc);
+  c[0] = (float)row[max(xc - 1, 0)];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) c[1 + j] = a.sample(j);
+  c[5] = (float)row[min(xc + 4, Wc - 1)];
+}
+// The two source rows of an output row are neighbours (i1 == i0 + 1, or i0 itself at the bottom), and so are their chroma taps:
+// rows (h-1, h) and (h, h+1) for i0 = 2h, the one pair (h, h+1) with the weights exchanged for i0 = 2h + 1.  So at most THREE
+// chroma rows per plane are loaded, base .. base + 2 with base = floor((i0 - 1) / 2), each index clamped (a clamped duplicate
+// holds the samples its tap asks for), and the third only where the second source row reaches it.
+template <class T>
+__device__ __forceinline__ void to_inp_yuv_rows_body(const YuvIn k, const T *__restrict__ yp, const T *__restrict__ up,
+                                                     const T *__restrict__ vp, int ys, int cs, float *__restrict__ out,
+                                                     float *__restrict__ out_x4, int Hin, int W, int Hout, float sy) {
+  const int W8 = W >> 3, Hc = (Hin + 1) >> 1, Wc = W >> 1;
+  const size_t total = (size_t)W8 * Hout, P = (size_t)Hout * W;
+  for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
+    const int y = (int)(i / W8), x = (int)(i - (size_t)y * W8) * 8, xc = x >> 1;
+    const Lerp ly = lerp_src_aten(y, sy, Hin);
+    const CTap t0 = chroma_tap(ly.i0, Hc), t1 = chroma_tap(ly.i1, Hc);
+    const int base = (ly.i0 - 1) >> 1;
+    const int rk0 = min(max(base, 0), Hc - 1), rk1 = min(max(base + 1, 0), Hc - 1), rk2 = min(base + 2, Hc - 1);
+    float ru[3][6], rv[3][6];
+    chroma_raw6(up + (size_t)rk0 * cs, Wc, xc, ru[0]), chroma_raw6(vp + (size_t)rk0 * cs, Wc, xc, rv[0]);
+    chroma_raw6(up + (size_t)rk1 * cs, Wc, xc, ru[1]), chroma_raw6(vp + (size_t)rk1 * cs, Wc, xc, rv[1]);
+    if (t1.i1 != rk0 && t1.i1 != rk1) {
+      chroma_raw6(up + (size_t)rk2 * cs, Wc, xc, ru[2]), chroma_raw6(vp + (size_t)rk2 * cs, Wc, xc, rv[2]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) ru[2][j] = ru[1][j], rv[2][j] = rv[1][j];
+    }
+    float px[2][8][3];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      SampleRow<T, 8> luma;
+      luma.load(yp + (size_t)(r ? ly.i1 : ly.i0) * ys + x);
+      const CTap ty = r ? t1 : t0;
+      const int sa = ty.i0 == rk0 ? 0 : (ty.i0 == rk1 ? 1 : 2), sb = ty.i1 == rk0 ? 0 : (ty.i1 == rk1 ? 1 : 2);
+      float cu[6], cv[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const float ua = sa == 0 ? ru[0][j] : (sa == 1 ? ru[1][j] : ru[2][j]), ub = sb == 0 ? ru[0][j] : (sb == 1 ? ru[1][j] : ru[2][j]);
+        const float va = sa == 0 ? rv[0][j] : (sa == 1 ? rv[1][j] : rv[2][j]), vb = sb == 0 ? rv[0][j] : (sb == 1 ? rv[1][j] : rv[2][j]);
+        cu[j] = ty.w0 * ua + ty.w1 * ub;
+        cv[j] = ty.w0 * va + ty.w1 * vb;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {  // pixel x + j: taps (j/2, j/2 + 1) of the six for even j, ((j+1)/2, (j+1)/2 + 1) for odd j
+        const int c0 = (j + 1) >> 1;
+        const float w0 = (j & 1) ? 0.75f : 0.25f, w1 = (j & 1) ? 0.25f : 0.75f;
+        yuv_to_bgr(k, luma.sample(j), w0 * cu[c0] + w1 * cu[c0 + 1], w0 * cv[c0] + w1 * cv[c0 + 1], px[r][j]);
+      }
+    }
+    f32x4g o[3][2];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c][j >> 2][j & 3] = __fmaf_rn(ly.w0, px[0][j][c], __fmul_rn(ly.w1, px[1][j][c]));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      f32x4g *dst = reinterpret_cast<f32x4g *>(out + (size_t)c * P + (size_t)y * W + x);
+      dst[0] = o[c][0], dst[1] = o[c][1];
+    }
+    if (out_x4) {
+      f32x4g *dst = reinterpret_cast<f32x4g *>(out_x4 + ((size_t)y * W + x) * 4);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dst[j] = (f32x4g){o[0][j >> 2][j & 3], o[1][j >> 2][j & 3], o[2][j >> 2][j & 3], 0.f};
+    }
+  }
+}
+
+// The general form of the way out: one 2 x 2 luma block per lane, so the chroma mean stays in the lane.  A pixel past an odd
+// edge repeats the edge pixel in the mean and is not stored.  The resize follows to_out16's rules (lerp_out<Samples16>).
+template <class T>
+__device__ __forceinline__ void to_out_yuv_body(const YuvOut k, const float *__restrict__ in, T *__restrict__ yp, T *__restrict__ up,
+                                                T *__restrict__ vp, int ys, int cs, int Hin, int Win, int Hout, int Wout, float sy,
+                                                float sx) {
+  const int Hc = (Hout + 1) >> 1, Wc = (Wout + 1) >> 1;
+  const Tile2D p = tile_pixel(Wc, Hc);
+  if (!p.valid) return;
+  const size_t P = (size_t)Hin * Win;
+  float cb = 0.f, cr = 0.f;
+#pragma unroll
+  for (int dy = 0; dy < 2; ++dy) {
+    const int oy = min(2 * p.y + dy, Hout - 1);
+    const Lerp ly = lerp_out<Samples16>(oy, sy, Hin, Hout);
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx) {
+      const int ox = min(2 * p.x + dx, Wout - 1);
+      const Lerp lx = lerp_out<Samples16>(ox, sx, Win, Wout);
+      float ch[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float *r0 = in + c * P + (size_t)ly.i0 * Win, *r1 = in + c * P + (size_t)ly.i1 * Win;
+        ch[c] = lerp2_aten(ly, lx, r0[lx.i0], r0[lx.i1], r1[lx.i0], r1[lx.i1]);
+      }
+      float Y, Cb, Cr;
+      bgr_to_ycc(k, ch[0], ch[1], ch[2], Y, Cb, Cr);
+      cb += Cb, cr += Cr;
+      if (2 * p.y + dy < Hout && 2 * p.x + dx < Wout) yp[(size_t)oy * ys + ox] = (T)round_sat_u16(k.y_off + k.y_mul * Y, k.maxval);
+    }
+  }
+  const size_t o = (size_t)p.y * cs + p.x;
+  up[o] = (T)round_sat_u16(k.c_off + k.c_mul * (cb * 0.25f), k.maxval);
+  vp[o] = (T)round_sat_u16(k.c_off + k.c_mul * (cr * 0.25f), k.maxval);
+}
+
+// The rows form of the way out (an unchanged width that is a multiple of 8): a lane takes two output rows of four blocks,
+// 2 x 8 pixels, with 16-byte loads of the fp32 planes, and stores 8 luma samples per row and 4 of either chroma plane with one
+// store each.  With an odd height the last lane row repeats the last output row in the mean and stores it once.
+template <class T>
+__device__ __forceinline__ void to_out_yuv_rows_body(const YuvOut k, const float *__restrict__ in, T *__restrict__ yp, T *__restrict__ up,
+                                                     T *__restrict__ vp, int ys, int cs, int Hin, int W, int Hout, float sy) {
+  const int W8 = W >> 3, Hc = (Hout + 1) >> 1;
+  const size_t total = (size_t)W8 * Hc, P = (size_t)Hin * W;
+  for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
+    const int j = (int)(i / W8), x = (int)(i - (size_t)j * W8) * 8;
+    float cb[4] = {0.f, 0.f, 0.f, 0.f}, cr[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int oy = min(2 * j + r, Hout - 1);
+      const Lerp ly = lerp_out<Samples16>(oy, sy, Hin, Hout);
+      uint32_t q[8];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        f32x4g ch[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const f32x4g t = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)ly.i0 * W + x + 4 * h);
+          const f32x4g u = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)ly.i1 * W + x + 4 * h);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {  // the horizontal pass is ATen's copy, fma(1, a, 0 * a): a for finite a, NaN otherwise
+            const float top = __fmaf_rn(1.f, t[e], __fmul_rn(0.f, t[e])), bot = __fmaf_rn(1.f, u[e], __fmul_rn(0.f, u[e]));
+            ch[c][e] = __fmaf_rn(ly.w0, top, __fmul_rn(ly.w1, bot));
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float Y, Cb, Cr;
+          bgr_to_ycc(k, ch[0][e], ch[1][e], ch[2][e], Y, Cb, Cr);
+          q[4 * h + e] = round_sat_u16(k.y_off + k.y_mul * Y, k.maxval);
+          cb[2 * h + (e >> 1)] += Cb, cr[2 * h + (e >> 1)] += Cr;
+        }
+      }
+      if (2 * j + r < Hout) SampleRow<T, 8>::store(yp + (size_t)oy * ys + x, q);
+    }
+    uint32_t qu[4], qv[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      qu[b] = round_sat_u16(k.c_off + k.c_mul * (cb[b] * 0.25f), k.maxval);
+      qv[b] = round_sat_u16(k.c_off + k.c_mul * (cr[b] * 0.25f), k.maxval);
+    }
+    SampleRow<T, 4>::store(up + (size_t)j * cs + (x >> 1), qu);
+    SampleRow<T, 4>::store(vp + (size_t)j * cs + (x >> 1), qv);
+  }
+}
+
+DRBA_FRAME_KERNEL to_inp_yuv_kernel(YuvIn k, const uint8_t *__restrict__ y, const uint8_t *__restrict__ u, const uint8_t *__restrict__ v, int ys,
+                                    int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win, int Hout, int Wout, float sy,
+                                    float sx) {
+  to_inp_yuv_body(k, y, u, v, ys, cs, out, out_x4, Hin, Win, Hout, Wout, sy, sx);
+}
+DRBA_FRAME_KERNEL to_inp16_yuv_kernel(YuvIn k, const uint16_t *__restrict__ y, const uint16_t *__restrict__ u, const uint16_t *__restrict__ v,
+                                      int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win, int Hout, int Wout,
+                                      float sy, float sx) {
+  to_inp_yuv_body(k, y, u, v, ys, cs, out, out_x4, Hin, Win, Hout, Wout, sy, sx);
+}
+DRBA_FRAME_KERNEL to_inp_yuv_rows_kernel(YuvIn k, const uint8_t *__restrict__ y, const uint8_t *__restrict__ u, const uint8_t *__restrict__ v,
+                                         int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int W, int Hout, float sy) {
+  to_inp_yuv_rows_body(k, y, u, v, ys, cs, out, out_x4, Hin, W, Hout, sy);
+}
+DRBA_FRAME_KERNEL to_inp16_yuv_rows_kernel(YuvIn k, const uint16_t *__restrict__ y, const uint16_t *__restrict__ u,
+                                           const uint16_t *__restrict__ v, int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4,
+                                           int Hin, int W, int Hout, float sy) {
+  to_inp_yuv_rows_body(k, y, u, v, ys, cs, out, out_x4, Hin, W, Hout, sy);
+}
+DRBA_FRAME_KERNEL to_out_yuv_kernel(YuvOut k, const float *__restrict__ in, uint8_t *__restrict__ y, uint8_t *__restrict__ u,
+                                    uint8_t *__restrict__ v, int ys, int cs, int Hin, int Win, int Hout, int Wout, float sy, float sx) {
+  to_out_yuv_body(k, in, y, u, v, ys, cs, Hin, Win, Hout, Wout, sy, sx);
+}
+DRBA_FRAME_KERNEL to_out16_yuv_kernel(YuvOut k, const float *__restrict__ in, uint16_t *__restrict__ y, uint16_t *__restrict__ u,
+                                      uint16_t *__restrict__ v, int ys, int cs, int Hin, int Win, int Hout, int Wout, float sy, float sx) {
+  to_out_yuv_body(k, in, y, u, v, ys, cs, Hin, Win, Hout, Wout, sy, sx);
+}
+DRBA_FRAME_KERNEL to_out_yuv_rows_kernel(YuvOut k, const float *__restrict__ in, uint8_t *__restrict__ y, uint8_t *__restrict__ u,
+                                         uint8_t *__restrict__ v, int ys, int cs, int Hin, int W, int Hout, float sy) {
+  to_out_yuv_rows_body(k, in, y, u, v, ys, cs, Hin, W, Hout, sy);
+}
+DRBA_FRAME_KERNEL to_out16_yuv_rows_kernel(YuvOut k, const float *__restrict__ in, uint16_t *__restrict__ y, uint16_t *__restrict__ u,
+                                           uint16_t *__restrict__ v, int ys, int cs, int Hin, int W, int Hout, float sy) {
+  to_out_yuv_rows_body(k, in, y, u, v, ys, cs, Hin, W, Hout, sy);
+}
 #undef DRBA_FRAME_KERNEL
 
 // ---- launch helpers: one per operation; M... is empty for bytes and (float maxval) for 16-bit samples ---------------------------
@@ -354,6 +680,87 @@ int plane_launch(void (*kernel)(const Tin *, Tout *, int, int, M...), const Tin 
 
 // the 16-bit entries check this and the 2-byte alignment of their samples in front
 bool maxval_ok(float maxval) { return maxval > 255.f && maxval <= 65535.f; }  // (NaN fails both)
+
+// ---- planar 4:2:0: constants and launch helpers -----------------------------------------------------------------------------------
+// m = maxval (255 | 1023 | ...), k = (m + 1) / 256: limited range is Y in [16k, 235k], chroma 128k +- 112k; full range divides
+// by m.  matrix 0 = bt709, 1 = bt601.
+bool yuv_coeffs(int matrix, double &kr, double &kb) {
+  if (matrix == 0) kr = 0.2126, kb = 0.0722;
+  else if (matrix == 1) kr = 0.299, kb = 0.114;
+  else return false;
+  return true;
+}
+YuvIn yuv_in_consts(double kr, double kb, int full_range, double m) {
+  const double k = (m + 1.0) / 256.0, kg = 1.0 - kr - kb;
+  YuvIn c;
+  c.y_off = (float)(full_range ? 0.0 : 16.0 * k), c.y_mul = (float)(1.0 / (full_range ? m : 219.0 * k));
+  c.c_off = (float)(128.0 * k), c.c_mul = (float)(1.0 / (full_range ? m : 224.0 * k));
+  c.r_cr = (float)(2.0 * (1.0 - kr)), c.b_cb = (float)(2.0 * (1.0 - kb));
+  c.kr = (float)kr, c.kb = (float)kb, c.inv_kg = (float)(1.0 / kg);
+  return c;
+}
+YuvOut yuv_out_consts(double kr, double kb, int full_range, double m) {
+  const double k = (m + 1.0) / 256.0;
+  YuvOut c;
+  c.kr = (float)kr, c.kg = (float)(1.0 - kr - kb), c.kb = (float)kb;
+  c.cb_mul = (float)(1.0 / (2.0 * (1.0 - kb))), c.cr_mul = (float)(1.0 / (2.0 * (1.0 - kr)));
+  c.y_off = (float)(full_range ? 0.0 : 16.0 * k), c.y_mul = (float)(full_range ? m : 219.0 * k);
+  c.c_off = (float)(128.0 * k), c.c_mul = (float)(full_range ? m : 224.0 * k);
+  c.maxval = (float)m;
+  return c;
+}
+// The rows form: an unchanged width that is a multiple of 8, luma rows aligned to 8 samples and chroma rows to 4 (pointers and
+// strides), 16-byte aligned fp32 rows.
+template <class T>
+bool yuv_rows_form_ok(int Win, int Wout, float scale_x, const T *y, const T *u, const T *v, int ys, int cs, const float *planes) {
+  return Win == Wout && scale_x == 1.f && (Wout & 7) == 0 && (ys & 7) == 0 && (cs & 3) == 0 &&
+         (((uintptr_t)y & (8 * sizeof(T) - 1)) | (((uintptr_t)u | (uintptr_t)v) & (4 * sizeof(T) - 1)) | ((uintptr_t)planes & 15)) == 0;
+}
+template <class T>
+bool yuv_args_ok(const T *y, const T *u, const T *v, int ys, int cs, const float *planes, int Hin, int Win, int Hout, int Wout, int H, int W,
+                 float maxval) {
+  // (H, W): the size of the planar frame, which the strides must hold; every plane aligned to its sample
+  return y && u && v && planes && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && ys >= W && cs >= (W + 1) / 2 && H > 0 &&
+         (((uintptr_t)y | (uintptr_t)u | (uintptr_t)v) & (sizeof(T) - 1)) == 0 && (sizeof(T) == 1 || maxval_ok(maxval));
+}
+
+template <class T>
+int to_inp_yuv_launch(void (*one)(YuvIn, const T *, const T *, const T *, int, int, float *, float *, int, int, int, int, float, float),
+                      void (*rows)(YuvIn, const T *, const T *, const T *, int, int, float *, float *, int, int, int, float), const T *y,
+                      const T *u, const T *v, int ys, int cs, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y,
+                      float scale_x, int matrix, int full_range, float maxval, void *stream) {
+  double kr, kb;
+  if (!yuv_args_ok(y, u, v, ys, cs, out, Hin, Win, Hout, Wout, Hin, Win, maxval) || ((uintptr_t)out_x4 & 15) != 0 || !yuv_coeffs(matrix, kr, kb))
+    return DRBA_EINVAL;
+  const YuvIn k = yuv_in_consts(kr, kb, full_range, maxval);
+  if (yuv_rows_form_ok(Win, Wout, scale_x, y, u, v, ys, cs, out))
+    DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 3) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, k, y, u, v, ys, cs, out, out_x4, Hin,
+                Wout, Hout, scale_y);
+  else
+    DRBA_LAUNCH(one, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, k, y, u, v, ys, cs, out, out_x4, Hin, Win, Hout, Wout,
+                scale_y, scale_x);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+template <class T>
+int to_out_yuv_launch(void (*one)(YuvOut, const float *, T *, T *, T *, int, int, int, int, int, int, float, float),
+                      void (*rows)(YuvOut, const float *, T *, T *, T *, int, int, int, int, int, float), const float *in, T *y, T *u, T *v,
+                      int ys, int cs, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range,
+                      float maxval, void *stream) {
+  double kr, kb;
+  if (!yuv_args_ok(y, u, v, ys, cs, in, Hin, Win, Hout, Wout, Hout, Wout, maxval) || !yuv_coeffs(matrix, kr, kb)) return DRBA_EINVAL;
+  const YuvOut k = yuv_out_consts(kr, kb, full_range, maxval);
+  const int Hc = (Hout + 1) / 2, Wc = (Wout + 1) / 2;
+  if (yuv_rows_form_ok(Win, Wout, scale_x, y, u, v, ys, cs, in))
+    DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 3) * Hc)), dim3(kBlock), 0, (hipStream_t)stream, k, in, y, u, v, ys, cs, Hin, Wout, Hout,
+                scale_y);
+  else
+    DRBA_LAUNCH(one, dim3(tiles_for(Wc, Hc)), dim3(kBlock), 0, (hipStream_t)stream, k, in, y, u, v, ys, cs, Hin, Win, Hout, Wout, scale_y,
+                scale_x);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
 
 }  // namespace
 
@@ -412,6 +819,31 @@ int drba_to_out16(const float *in, uint16_t *out_hwc, int Hin, int Win, int Hout
   if (!maxval_ok(maxval) || ((uintptr_t)out_hwc & 1) != 0) return DRBA_EINVAL;
   return to_out_launch(to_out16_kernel, to_out16_rows_kernel, in, out_hwc, Hin, Win, Hout, Wout, scale_y, scale_x, reverse_channels, stream,
                        maxval);
+}
+
+int drba_to_inp_yuv420_x4(const uint8_t *y, const uint8_t *u, const uint8_t *v, int y_stride, int c_stride, float *out, float *out_x4, int Hin,
+                          int Win, int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range, void *stream) {
+  return to_inp_yuv_launch(to_inp_yuv_kernel, to_inp_yuv_rows_kernel, y, u, v, y_stride, c_stride, out, out_x4, Hin, Win, Hout, Wout, scale_y,
+                           scale_x, matrix, full_range, 255.f, stream);
+}
+
+int drba_to_inp16_yuv420_x4(const uint16_t *y, const uint16_t *u, const uint16_t *v, int y_stride, int c_stride, float *out, float *out_x4,
+                            int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range, float maxval,
+                            void *stream) {
+  return to_inp_yuv_launch(to_inp16_yuv_kernel, to_inp16_yuv_rows_kernel, y, u, v, y_stride, c_stride, out, out_x4, Hin, Win, Hout, Wout,
+                           scale_y, scale_x, matrix, full_range, maxval, stream);
+}
+
+int drba_to_out_yuv420(const float *in, uint8_t *y, uint8_t *u, uint8_t *v, int y_stride, int c_stride, int Hin, int Win, int Hout, int Wout,
+                       float scale_y, float scale_x, int matrix, int full_range, void *stream) {
+  return to_out_yuv_launch(to_out_yuv_kernel, to_out_yuv_rows_kernel, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout, scale_y, scale_x,
+                           matrix, full_range, 255.f, stream);
+}
+
+int drba_to_out16_yuv420(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win, int Hout,
+                         int Wout, float scale_y, float scale_x, int matrix, int full_range, float maxval, void *stream) {
+  return to_out_yuv_launch(to_out16_yuv_kernel, to_out16_yuv_rows_kernel, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout, scale_y,
+                           scale_x, matrix, full_range, maxval, stream);
 }
 
 }  // extern "C"

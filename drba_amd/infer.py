@@ -1,12 +1,17 @@
 """DRBA command line and per-frame driver loop (same CLI as the reference's infer.py).
 
     python infer.py -m rife -i in.npz -o out.npz [-fps 60 | -t 2] [-s] [-st 0.3] [-hw] [-scale 1.0] [--out-depth source|8|16]
-                    [--nonlinear]
+                    [--nonlinear] [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full]
 
 `--out-depth` is not in the reference: a .npz / .npy clip may hold uint16 frames, and the written frames are 8 or 16 bits deep
 (default: as the source, so an 8-bit clip is handled exactly as before).  `--nonlinear` is not in the reference either: its driver
 always asks the model for linear=True (infer.py:143) although the model entry point defaults to the non-linear DistanceRatioMap
 (get_drm_t); with the flag every DRBA step of the clip runs with linear=False.
+
+A `.y4m` path, or `-` for stdin / stdout, at either end selects the YUV4MPEG2 source or sink (drba_amd/y4m.py; planar 4:2:0 at 8
+or 10 bits, converted inside the to_inp / to_out kernels): `ffmpeg -i a.mkv -f yuv4mpegpipe - | python infer.py -m rife -i - -o - -t 2
+| x264 --demuxer y4m -o b.264 -`.  `--yuv-matrix` and `--yuv-range` name the conversion; on a Y4M sink `--out-depth 16` writes
+C420p10.  Nothing is printed to stdout.
 
 The driver logic is host-side Python like the reference; the model calls it makes run on
 the HIP library.  `interpolate_stream` is the loop of reference infer.py:58-174 (drba_amd/driver.py) with the
@@ -42,6 +47,11 @@ def parse_args(argv=None):
                         "libx264 yuv420p10le; not with -hw, not in the frame-sharded run)")
     p.add_argument("--nonlinear", dest="nonlinear", action="store_true", default=False,
                    help="run every DRBA step with the non-linear DistanceRatioMap (inference_ts_drba(..., linear=False))")
+    p.add_argument("--yuv-matrix", dest="yuv_matrix", type=str, default="bt709", choices=("bt709", "bt601"),
+                   help="YCbCr matrix of a .y4m source / sink (default bt709)")
+    p.add_argument("--yuv-range", dest="yuv_range", type=str, default="source", choices=("source", "limited", "full"),
+                   help="sample range of a .y4m source / sink: the source header's XCOLORRANGE (default; limited when it has none or "
+                        "the source is not Y4M), limited or full; a Y4M source that carries the tag is always read by it")
     return p.parse_args(argv)
 
 
@@ -100,6 +110,9 @@ def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, s
 
 def inference(model, args):
     depth_kw = {} if out_depth_of(args) is None else {"out_depth": out_depth_of(args)}
+    for flag, dflt in (("yuv_matrix", "bt709"), ("yuv_range", "source")):  # a namespace built without the flags means the defaults
+        if getattr(args, flag, dflt) != dflt:
+            depth_kw[flag] = getattr(args, flag)
     video_io = _tools.VideoFI_IO(args.input, args.output, dst_fps=args.dst_fps, times=args.times, hwaccel=args.hwaccel, **depth_kw)
     try:
         from tqdm import tqdm
@@ -117,6 +130,13 @@ def inference(model, args):
         to_inp = lambda fr, size: _tools.to_inp(fr, size, maxval=video_io.maxval)  # noqa: E731
     if getattr(video_io, "out_depth", 8) == 16:
         to_out = lambda x, size: _tools.to_out(x, size, rgb=rgb, depth=16, maxval=video_io.out_maxval)  # noqa: E731
+    # planar 4:2:0 at either end, each on its own: a YuvFrame knows its depth, the planar sink takes the 1-D Y, U, V array
+    if getattr(video_io, "pixfmt", "bgr") == "yuv420":
+        to_inp = lambda fr, size: _tools.to_inp(fr, size, matrix=video_io.yuv_matrix, full_range=video_io.yuv_full_range)  # noqa: E731
+    if getattr(video_io, "out_pixfmt", "bgr") == "yuv420":
+        mv = video_io.out_maxval if video_io.out_depth == 16 else None
+        to_out = lambda x, size: _tools.to_out(x, size, depth=video_io.out_depth, maxval=mv, pixfmt="yuv420",  # noqa: E731
+                                               matrix=video_io.yuv_matrix, full_range=video_io.out_full_range)
     n = interpolate_stream(model, video_io, args.dst_fps, times=args.times, enable_scdet=args.enable_scdet,
                            scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, on_step=step,
                            linear=not getattr(args, "nonlinear", False))
@@ -180,7 +200,7 @@ def main(argv=None):
     """`python infer.py ...` = the reference CLI.  Under torch.distributed.run (WORLD_SIZE > 1, one rank per GPU) the same
     command line shards the clip over the ranks: `python -m torch.distributed.run --nproc-per-node 8 infer.py -m rife ...`."""
     args = parse_args(argv)
-    if not os.path.exists(args.input):
+    if args.input != "-" and not os.path.exists(args.input):
         raise FileNotFoundError(f"can't find the video file {args.input}")
     # the command line keeps the conv autotuner's winners across runs unless DRBA_TUNE_CACHE=0 (drba_amd/tunecache.py; the library
     # alone leaves the store off); nothing is written before the first winner is stored

@@ -10,6 +10,7 @@ import math
 import weakref
 import os
 import subprocess
+import sys
 import threading
 from queue import Queue
 
@@ -17,6 +18,7 @@ import numpy as np
 import torch
 
 from drba_amd import ops as _ops
+from drba_amd import y4m as _y4m
 
 
 def check_cupy_env():
@@ -87,11 +89,19 @@ def resize(tensor, size):
     return _ops.resize_bilinear(tensor, size)
 
 
-def to_inp(npInp, dst_size, device=None, maxval=None):
+def to_inp(npInp, dst_size, device=None, maxval=None, matrix="bt709", full_range=False):
     """resize(to_tensor(npInp), dst_size) (tools.py:59-60) as one kernel on the uploaded uint8 frame (the full-size
     fp32 frame of the reference is never materialised); bit-exact with the two-step form.  A uint16 frame goes through the
-    16-bit kernel with its `maxval` (65535 unless given)."""
+    16-bit kernel with its `maxval` (65535 unless given).  A planar 4:2:0 frame (y4m.YuvFrame) is uploaded as it stands -- half
+    the bytes of a BGR frame -- and converted with `matrix` / `full_range` inside the kernel (ops.to_inp_yuv); the frame knows its
+    own depth."""
     device = _ops.default_device() if device is None else device
+    if isinstance(npInp, _y4m.YuvFrame):
+        if maxval not in (None, npInp.maxval):
+            raise ValueError(f"a {npInp.depth}-bit 4:2:0 frame has maxval {npInp.maxval}, got {maxval}")
+        planes = torch.from_numpy(npInp.data if npInp.data.flags.writeable else npInp.data.copy()).to(device, non_blocking=True)
+        return _ops.to_inp_yuv(planes, npInp.shape[:2], dst_size, matrix=matrix, full_range=full_range,
+                               maxval=None if npInp.depth == 8 else npInp.maxval)
     if torch.is_tensor(npInp):
         u8 = npInp.to(device, non_blocking=True)
     else:
@@ -103,12 +113,19 @@ def to_inp(npInp, dst_size, device=None, maxval=None):
     return _ops.to_inp(u8, dst_size)
 
 
-def to_out(tenInp, src_size, rgb=False, depth=8, maxval=None):
+def to_out(tenInp, src_size, rgb=False, depth=8, maxval=None, pixfmt="bgr", matrix="bt709", full_range=False):
     """to_cv2(resize(tenInp, src_size)) (tools.py:63-64) as one kernel + the D2H copy.  rgb=True returns the frame in RGB
     order (the flip the reference's writer thread does on the host, tools.py:202, done on the device instead).  depth=16
-    returns a uint16 frame scaled to `maxval` (65535 unless given), rounded and saturated (ops.to_out)."""
+    returns a uint16 frame scaled to `maxval` (65535 unless given), rounded and saturated (ops.to_out).  pixfmt="yuv420" returns
+    the frame as planar 4:2:0 instead, one 1-D array holding Y, U, V (ops.to_out_yuv; at depth 16 scaled to 1023 unless given)."""
     _check_depth(depth, maxval)
-    if depth == 16:
+    if pixfmt not in ("bgr", "yuv420"):
+        raise ValueError(f"pixfmt must be bgr or yuv420, got {pixfmt!r}")
+    if pixfmt == "yuv420":
+        if rgb:
+            raise ValueError("rgb=True belongs to packed frames (pixfmt='bgr')")
+        frame = _ops.to_out_yuv(tenInp, src_size, matrix=matrix, full_range=full_range, depth=depth, maxval=maxval).cpu().numpy()
+    elif depth == 16:
         frame = _ops.to_out(tenInp, src_size, rgb=rgb, depth=16, maxval=maxval).cpu().numpy()
     else:
         frame = _ops.to_out(tenInp, src_size, rgb=rgb).cpu().numpy()
@@ -227,14 +244,45 @@ class VideoFI_IO:
     the .npz / .npy sink stores uint16 frames (.npz: with `maxval`), the raw sink and the encoder pipe take rgb48le bytes --
     little-endian, RGB order, always scaled to 65535 -- and the encoder is libx264 at yuv420p10le; `hwaccel` is refused there
     (h264_vaapi encodes 8 bits).
+
+    YUV4MPEG2 (not in the reference; drba_amd/y4m.py): a `.y4m` path, or `-` for stdin / stdout, selects the Y4M source or sink,
+    each independently of the other end.  The source reads one planar 4:2:0 frame at a time behind the bounded read queue (frames
+    are y4m.YuvFrame objects; .pixfmt is "yuv420", .depth 8, or 16 with .maxval 1023 for C420p10) and the sink writes each frame
+    as it arrives (.out_pixfmt "yuv420": frames are the 1-D Y, U, V arrays of to_out(..., pixfmt="yuv420"); out_depth 16 writes
+    C420p10, .out_maxval 1023).  `yuv_matrix` (bt709 | bt601) and `yuv_range` (source | limited | full) describe the conversion the
+    hooks perform: .yuv_full_range for the way in (the header's XCOLORRANGE; without one, what `yuv_range` says, limited by
+    default), .out_full_range for the way out (`yuv_range`, or the way in's when it is `source`).  The sink's header carries the
+    source's C tag, A, I and X tags through and the exact frame rate (y4m.output_fps).
     """
 
-    def __init__(self, input_path, output_path, dst_fps=60, times=-1, hwaccel=False, src_fps=None, out_depth=None):
+    def __init__(self, input_path, output_path, dst_fps=60, times=-1, hwaccel=False, src_fps=None, out_depth=None,
+                 yuv_matrix="bt709", yuv_range="source"):
         self.input_path, self.output_path = input_path, output_path
         self._cv2 = None
+        self._y4m_in = self._y4m_out = None
         self.depth, self.maxval = 8, 255
+        self.pixfmt = "bgr"
+        if yuv_matrix not in _ops.YUV_MATRICES:
+            raise ValueError(f"yuv_matrix must be one of {sorted(_ops.YUV_MATRICES)}, got {yuv_matrix!r}")
+        if yuv_range not in ("source", "limited", "full"):
+            raise ValueError(f"yuv_range must be source, limited or full, got {yuv_range!r}")
+        self.yuv_matrix = yuv_matrix
+        self.yuv_full_range = yuv_range == "full"
+        src_ratio = None
         ext = os.path.splitext(input_path)[1].lower()
-        if ext in (".npz", ".npy"):
+        if input_path == "-" or ext == ".y4m":
+            self._y4m_in = _y4m.Reader(sys.stdin.buffer if input_path == "-" else open(input_path, "rb"))
+            hdr = self._y4m_in.header
+            self.pixfmt = "yuv420"
+            if hdr.depth > 8:
+                self.depth, self.maxval = 16, hdr.maxval
+            if hdr.color_range is not None:
+                self.yuv_full_range = hdr.color_range == "FULL"
+            src_ratio = (hdr.fps_num, hdr.fps_den)
+            self.src_fps = float(src_fps if src_fps is not None else hdr.fps)
+            self.total_frames_count = float(self._y4m_in.frame_count_estimate())
+            self.height, self.width = hdr.height, hdr.width
+        elif ext in (".npz", ".npy"):
             if ext == ".npz":
                 z = np.load(input_path)
                 self._frames = z["frames"]
@@ -275,22 +323,51 @@ class VideoFI_IO:
         self._sink_frames = [] if oext in (".npz", ".npy") else None
         self._ffmpeg = None
         self._raw = None
-        if self._sink_frames is None:
+        self.out_pixfmt = "bgr"
+        self.out_full_range = self.yuv_full_range if yuv_range == "source" else yuv_range == "full"
+        if output_path == "-" or oext == ".y4m":
+            self.out_pixfmt = "yuv420"
+            if self.out_depth == 16:
+                self.out_maxval = 1023  # 10 bits is what the format and the encoders carry
+            self._y4m_out = _y4m.Writer(sys.stdout.buffer if output_path == "-" else open(output_path, "wb"),
+                                        self._y4m_header(src_ratio, src_fps, dst_fps, times, yuv_range))
+        elif self._sink_frames is None:
             if _have_ffmpeg() and oext not in (".raw", ".rgb"):
                 self._ffmpeg = self._spawn_ffmpeg(hwaccel)
             else:
                 self._raw = open(output_path, "wb")
         # sinks that want RGB bytes (the ffmpeg pipe and the raw file, tools.py:202): the driver can hand over frames that
         # are already RGB (to_out(..., rgb=True) flips on the device) by setting frames_are_rgb
-        self.wants_rgb = self._sink_frames is None
+        self.wants_rgb = self._sink_frames is None and self._y4m_out is None
         self.frames_are_rgb = False
         self._sink_error = None
         self.read_buffer = Queue(maxsize=100)
-        self.write_buffer = Queue(maxsize=-1)
+        # the Y4M sink writes each frame as it arrives and may be a pipe into an encoder that is slower than this pipeline: its
+        # queue is bounded like the read queue, so that memory does not grow with the clip (write_frame then waits for the sink)
+        self.write_buffer = Queue(maxsize=100 if self._y4m_out is not None else -1)
         self._closed = threading.Event()
         threading.Thread(target=self._reader, daemon=True).start()
         self._writer_thread = threading.Thread(target=self._writer, daemon=True)
         self._writer_thread.start()
+
+    def _y4m_header(self, src_ratio, src_fps, dst_fps, times, yuv_range):
+        """The sink's header: the source's tags where it is a Y4M stream (its C tag unchanged while the depth class stays, A, I, the
+        other X tags), C420p10 at 16-bit output, C420jpeg for any other source; the exact frame rate; XCOLORRANGE when the source
+        carried one or `yuv_range` names one."""
+        src = self._y4m_in.header if self._y4m_in is not None else None
+        if src_fps is not None or src_ratio is None:
+            src_ratio = self.src_fps
+        num, den = _y4m.output_fps(src_ratio, dst_fps, times)
+        if self.out_depth == 16:
+            chroma = "420p10"
+        else:
+            chroma = src.chroma if src is not None and src.depth == 8 and src.chroma is not None else "420jpeg"
+        color_range = None
+        if yuv_range != "source" or (src is not None and src.color_range is not None):
+            color_range = "FULL" if self.out_full_range else "LIMITED"
+        return _y4m.Header(self.width, self.height, (num, den), interlace=src.interlace if src is not None else "p",
+                           aspect=src.aspect if src is not None else None, chroma=chroma, color_range=color_range,
+                           extra=src.extra if src is not None else ())
 
     def _ffmpeg_cmd(self, hwaccel):
         """The reference's pipe (tools.py:176-186): rawvideo rgb24 in, libx264 -qp 16 -preset medium, audio copied from the
@@ -317,7 +394,16 @@ class VideoFI_IO:
         return subprocess.Popen(self._ffmpeg_cmd(hwaccel), stdin=subprocess.PIPE)
 
     def _reader(self):
-        if self._cv2 is not None:
+        if self._y4m_in is not None:
+            try:
+                fr = self._y4m_in.read_frame()  # one frame ahead of the bounded queue, never more
+                while fr is not None:
+                    self.read_buffer.put(fr)
+                    fr = self._y4m_in.read_frame()
+            except Exception as e:  # a truncated stream: hand the error to the reading side instead of dying silently
+                self.read_buffer.put(e)
+                return
+        elif self._cv2 is not None:
             ok, fr = self._cv2.read()
             while ok:
                 self.read_buffer.put(fr)
@@ -334,6 +420,12 @@ class VideoFI_IO:
                 break
             if self._sink_frames is not None:
                 self._sink_frames.append(item)
+            elif self._y4m_out is not None:
+                if self._sink_error is None:
+                    try:
+                        self._y4m_out.write_frame(item)  # each frame as it arrives: nothing is kept
+                    except (BrokenPipeError, OSError, TypeError, ValueError) as e:
+                        self._sink_error = e
             elif self._sink_error is None:
                 # BGR -> RGB as the reference's pipe, unless the driver already flipped on the device
                 rgb = np.ascontiguousarray(item if self.frames_are_rgb else item[:, :, ::-1])
@@ -355,6 +447,13 @@ class VideoFI_IO:
                 np.savez(self.output_path, frames=arr, fps=np.float64(self.dst_fps), **extra)
             else:
                 np.save(self.output_path, arr)
+        elif self._y4m_out is not None:
+            try:
+                self._y4m_out.flush()
+                if self.output_path != "-":
+                    self._y4m_out.f.close()
+            except OSError as e:
+                self._sink_error = self._sink_error or e
         elif self._ffmpeg is not None:
             try:
                 self._ffmpeg.stdin.close()
@@ -379,7 +478,10 @@ class VideoFI_IO:
         self.write_buffer.put(x)
 
     def read_frame(self):
-        return self.read_buffer.get()
+        fr = self.read_buffer.get()
+        if isinstance(fr, Exception):
+            raise fr
+        return fr
 
     def finish_writing(self):
         return self.write_buffer.empty() or self._closed.is_set()

@@ -606,6 +606,81 @@ def to_out(x, src_size, rgb=False, depth=8, maxval=None):
     return out
 
 
+YUV_MATRICES = {"bt709": 0, "bt601": 1}
+
+
+def _yuv_args(matrix, depth, maxval):
+    """-> (matrix id, sample dtype, tag of the library entries, the maxval argument).  depth 8: bytes; 16: uint16 samples in
+    [0, maxval], 1023 (10-bit, what YUV4MPEG2 carries) unless given."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"matrix must be one of {sorted(YUV_MATRICES)}, got {matrix!r}")
+    if depth not in (8, 16):
+        raise ValueError(f"depth must be 8 or 16, got {depth!r}")
+    if depth == 8:
+        if maxval not in (None, 255):
+            raise ValueError("maxval belongs to 16-bit samples (depth=16)")
+        return YUV_MATRICES[matrix], torch.uint8, "", ()
+    return YUV_MATRICES[matrix], torch.uint16, "16", (float(_maxval(1023 if maxval is None else maxval)),)
+
+
+def yuv420_layout(size):
+    """(H, W) -> (samples of Y, of U (= of V), Hc, Wc) of a packed planar 4:2:0 frame: Y, then U, then V, rows without padding"""
+    h, w = int(size[0]), int(size[1])
+    hc, wc = (h + 1) // 2, (w + 1) // 2
+    return h * w, hc * wc, hc, wc
+
+
+def to_inp_yuv(planes, size, dst_size, matrix="bt709", full_range=False, maxval=None):
+    """to_inp for a planar YCbCr 4:2:0 frame on the device: `planes` is one contiguous 1-D tensor holding Y [H,W], then U, then V
+    [ceil(H/2),ceil(W/2)] of a frame of `size` = (H, W) -- uint8 samples, or uint16 ones in [0, maxval] (1023 unless given) --
+    -> fp32 [1,3,*dst_size] in [0,1], BGR channel order, one kernel: chroma interpolation, colour conversion and the resize
+    (include/drba_hip.h, ABI 14).  The [H,W,4] copy is written in the same pass, as in to_inp."""
+    if not (torch.is_tensor(planes) and planes.is_cuda and planes.dim() == 1 and planes.dtype in (torch.uint8, torch.uint16)):
+        raise _lib.DrbaHipError("expected a CUDA uint8 or uint16 1-D tensor of packed Y, U, V planes")
+    mid, dtype, tag, mv = _yuv_args(matrix, 8 if planes.dtype == torch.uint8 else 16, maxval)
+    h, w = int(size[0]), int(size[1])
+    ny, nc, _, wc = yuv420_layout((h, w))
+    planes = planes.contiguous()
+    if planes.numel() != ny + 2 * nc:
+        raise _lib.DrbaHipError(f"a {w}x{h} 4:2:0 frame is {ny + 2 * nc} samples, got {planes.numel()}")
+    ho, wo = int(dst_size[0]), int(dst_size[1])
+    out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=planes.device)
+    x4 = torch.empty((ho, wo, 4), dtype=torch.float32, device=planes.device) if IMG_X4 else None
+    sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))
+    es = planes.element_size()
+    base = planes.data_ptr()
+    y, u, v = C.c_void_p(base), C.c_void_p(base + ny * es), C.c_void_p(base + (ny + nc) * es)
+    entry = f"drba_to_inp{tag}_yuv420_x4"
+    _lib.check(_timed("to_inp_yuv" + tag, (h, w, ho, wo), 1.5 * es * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
+                      lambda: getattr(_lib.load(), entry)(y, u, v, w, wc, _p(out), _p(x4), h, w, ho, wo, sy, sx, mid, 1 if full_range else 0,
+                                                          *mv, _stream())), entry)
+    if x4 is not None:
+        _set_copy(out, "_drba_x4", x4)
+    return out
+
+
+def to_out_yuv(x, src_size, matrix="bt709", full_range=False, depth=8, maxval=None):
+    """to_out to a planar YCbCr 4:2:0 frame on the device: fp32 [1,3,h,w] (BGR) -> ONE contiguous 1-D tensor holding Y [*src_size],
+    then U, then V [ceil(H/2),ceil(W/2)], uint8 (depth 8) or uint16 scaled to `maxval` (depth 16; 1023 unless given): resize, clamp,
+    colour conversion, 2 x 2 chroma mean, round to nearest even, in one kernel.  One D2H copy and one write per frame."""
+    mid, dtype, tag, mv = _yuv_args(matrix, depth, maxval)
+    x = _f32(x)
+    assert x.shape[0] == 1 and x.shape[1] == 3
+    h, w = x.shape[2:]
+    ho, wo = int(src_size[0]), int(src_size[1])
+    ny, nc, _, wc = yuv420_layout((ho, wo))
+    sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))
+    out = torch.empty(ny + 2 * nc, dtype=dtype, device=x.device)
+    es = out.element_size()
+    base = out.data_ptr()
+    y, u, v = C.c_void_p(base), C.c_void_p(base + ny * es), C.c_void_p(base + (ny + nc) * es)
+    entry = f"drba_to_out{tag}_yuv420"
+    _lib.check(_timed("to_out_yuv" + tag, (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 1.5 * es * ho * wo, "byte",
+                      lambda: getattr(_lib.load(), entry)(_p(x), y, u, v, wo, wc, h, w, ho, wo, sy, sx, mid, 1 if full_range else 0, *mv,
+                                                          _stream())), entry)
+    return out
+
+
 def _ssim_thumb32_enqueue(x1, x2):
     """The two thumbnails and the SSIM kernel on the current stream -> the device tensor [1] the value lands in."""
     a, b = resize_bilinear(x1, (32, 32)), resize_bilinear(x2, (32, 32))

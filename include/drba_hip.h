@@ -32,7 +32,9 @@ extern "C" {
 #define DRBA_EUNSUPPORTED (-2) /* shape/config outside what the kernels were built for */
 #define DRBA_ELAUNCH (-3)  /* hipGetLastError() reported a launch failure */
 
-/* ABI version.  13: the fused non-linear DRM of the RIFE path -- drba_drm_walk (host function: get_drm_t's scalar walk as a move
+/* ABI version.  14: planar YCbCr 4:2:0 frames -- drba_to_inp_yuv420_x4 / drba_to_inp16_yuv420_x4 / drba_to_out_yuv420 /
+ * drba_to_out16_yuv420 (three planes with row strides, bt709 / bt601, limited / full range; colour conversion and chroma
+ * resampling inside the conversion kernels): additions only, no earlier entry changes.  13: the fused non-linear DRM of the RIFE path -- drba_drm_walk (host function: get_drm_t's scalar walk as a move
  * mask), drba_drm_rife_nonlinear and drba_drm_rife_nonlinear_batch with drba_drm_nonlinear_job_t: additions only, no earlier entry
  * changes.  12: drba_tile_item_order (host function: the workgroup -> (tile, item) order of the batched stage launches): an
  * addition only, no earlier entry changes.  11: 16-bit frames -- drba_to_inp16_x4 / drba_to_out16 / drba_u16hwc_to_f32nchw / drba_f32nchw_to_u16hwc (uint16 HWC frames
@@ -54,7 +56,7 @@ extern "C" {
  * workspace that must be ZERO on entry (they leave it zero on return: self-cleaning accumulator) instead of clearing it
  * themselves; batched stage entry points added; drba_conv3x3_cfg_family added and configuration ids 19 (LDS-DMA, 32
  * channels) / 20 (K split across waves) behind drba_conv3x3; the allocation exception above.  1: the first release. */
-#define DRBA_ABI_VERSION 13  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
+#define DRBA_ABI_VERSION 14  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
 int drba_abi_version(void);
 const char *drba_error_string(int code);
 /* ABI 6, debug: with the range check on, every entry point that ran a kernel of family 4 (two fp16 terms per operand:
@@ -248,6 +250,28 @@ int drba_to_inp16_x4(const uint16_t *img_hwc, float *out, float *out_x4, int Hin
                      float scale_x, float maxval, void *stream);
 int drba_to_out16(const float *in, uint16_t *out_hwc, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
                   int reverse_channels, float maxval, void *stream);
+/* ABI 14: the same two conversions for planar YCbCr 4:2:0 frames (YUV4MPEG2's C420 family).  y: [H][y_stride] samples, u and v:
+ * [ceil(H/2)][c_stride] samples, strides in SAMPLES (y_stride >= W, c_stride >= ceil(W/2)); bytes, or uint16 with samples in
+ * [0, maxval] (1023: 10-bit).  matrix: 0 = bt709, 1 = bt601 (anything else is DRBA_EINVAL); full_range != 0: Y' = y / m and
+ * Cb = (u - 128k) / m, otherwise Y' = (y - 16k) / 219k and Cb = (u - 128k) / 224k, with m = maxval (255 for bytes), k = (m + 1) / 256.
+ * The network tensor keeps the BGR channel order (channel 0 = B).
+ * Way in: chroma is brought to luma resolution with the centre-sited bilinear taps at s = x / 2 - 0.25 (clamped; weights 3/4, 1/4)
+ * on both axes, R = Y' + 2(1 - Kr) Cr, B = Y' + 2(1 - Kb) Cb, G = (Y' - Kr R - Kb B) / Kg, each clamped to [0, 1], then the bilinear
+ * resize of drba_to_inp_x4 in the same ATen order; out_x4 as there.  No 8-bit RGB is formed in between.
+ * Way out: the resize of drba_to_out16 (an axis whose size does not change copies), clamp to [0, 1] with NaN -> 0, Y' = Kr R + Kg G +
+ * Kb B, Cb = (B - Y') / (2(1 - Kb)), Cr = (R - Y') / (2(1 - Kr)); a chroma sample is the mean over its 2 x 2 luma block (pixels past
+ * an odd edge repeat the edge pixel); samples are rounded to nearest even and saturated to [0, m].
+ * Both have a general form (any size) and a rows form taken when the width is unchanged and a multiple of 8, the luma rows are
+ * aligned to 8 samples and the chroma rows to 4 (pointers and strides) and the fp32 planes to 16 bytes. */
+int drba_to_inp_yuv420_x4(const uint8_t *y, const uint8_t *u, const uint8_t *v, int y_stride, int c_stride, float *out, float *out_x4,
+                          int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range, void *stream);
+int drba_to_inp16_yuv420_x4(const uint16_t *y, const uint16_t *u, const uint16_t *v, int y_stride, int c_stride, float *out,
+                            float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x, int matrix,
+                            int full_range, float maxval, void *stream);
+int drba_to_out_yuv420(const float *in, uint8_t *y, uint8_t *u, uint8_t *v, int y_stride, int c_stride, int Hin, int Win, int Hout,
+                       int Wout, float scale_y, float scale_x, int matrix, int full_range, void *stream);
+int drba_to_out16_yuv420(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win,
+                         int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range, float maxval, void *stream);
 
 /* ---- scene-cut metric: tools.py:27-30 + pytorch_msssim/__init__.py:83-136 (ssim_matlab)
  * x1, x2: [1,3,32,32] thumbnails (already resized); out: 1 float on device. */
