@@ -45,6 +45,8 @@ SIGNATURES = {
     "drba_abi_version": (_i, []),
     "drba_rife_splat_ws_floats": (_z, [_i, _i, _i, _i]),
     "drba_set_range_check": (_i, [_i]),
+    "drba_set_deterministic": (_i, [_i]),
+    "drba_get_deterministic": (_i, []),
     "drba_status_word": (_i, [C.POINTER(C.c_void_p)]),
     "drba_status_clear": (_i, []),
     "drba_stream_create_cu_mask": (_i, [C.POINTER(C.c_uint32), _i, C.POINTER(C.c_void_p)]),
@@ -236,6 +238,8 @@ def load():
                            "stale build, run `make -C drba_amd/csrc`")
     if os.environ.get("DRBA_CHECK_RANGE", "0") not in ("", "0"):  # debug: family-4 outputs are scanned for inf / NaN (drba_hip.h)
         lib.drba_set_range_check(1)
+    if os.environ.get("DRBA_DETERMINISTIC", "0") not in ("", "0"):  # bit-reproducible outputs (drba_hip.h; ops.set_deterministic)
+        lib.drba_set_deterministic(1)
     _lib = lib
     return lib
 

@@ -93,6 +93,7 @@ hipError_t max_dynamic_lds(const void *kernel, int bytes) {
   return e;
 }
 bool g_range_check = false;
+bool g_deterministic = false;
 
 // Status words (drba_status_word): one 8-byte host-mapped allocation per device, made on request, never freed.  The table is
 // read on every family-4 launch (an atomic pointer load indexed by the current device) and written once per device.
@@ -164,6 +165,14 @@ int drba_set_range_check(int on) {
   drba::g_range_check = on != 0;
   return was;
 }
+
+int drba_set_deterministic(int on) {
+  const int was = drba::g_deterministic ? 1 : 0;
+  drba::g_deterministic = on != 0;
+  return was;
+}
+
+int drba_get_deterministic(void) { return drba::g_deterministic ? 1 : 0; }
 
 int drba_status_word(volatile unsigned long long **host_word) {
   if (!host_word) return DRBA_EINVAL;

@@ -53,6 +53,10 @@ static inline int range_checked(int rc, const float *out, size_t n, void *stream
   return (rc != DRBA_OK || !g_range_check) ? rc : range_scan(out, n, stream);
 }
 
+// Deterministic mode (drba_set_deterministic, include/drba_hip.h): read at launch by the splat entry points (splat_warp.hip), which
+// then run the kernels whose sums are taken in an order fixed by the data.  Off by default.
+extern bool g_deterministic;
+
 // Always-on overflow report of the same family (drba_status_word, include/drba_hip.h; ABI 8): every family-4 kernel takes the
 // device address of the current device's status bytes (null until the caller asked for the word: then nothing is reported),
 // folds each value it stores into a NaN accumulator (v * 0 + nf: NaN as soon as one v is inf / NaN, one VALU operation per stored

@@ -63,12 +63,45 @@ __global__ void __launch_bounds__(256) distance_kernel(const float *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------
+// Deterministic mode (drba_set_deterministic): what the fused splats put through global memory is summed as 64-bit
+// fixed-point integers -- integer addition is associative, so the total does not depend on the order the atomics arrive in,
+// which a float atomic sum does.  A contribution v * w is rounded ONCE to a multiple of 2^-S, added with one 64-bit integer
+// atomic (two's complement in an unsigned word), and the total goes back to fp32 when the owning tile collects it.
+// S (splat_fx, host) from the code's own bounds, b = ceil(log2(bound on |v * w|)), c = ceil(log2(H * W)):
+//   * a corner is added only inside the image, so the target of a MODE 0 source lies in [-1, W) x [-1, H) and its value, the
+//     flow itself, has |v| <= max(H, W); weights are <= 1: |v * w| <= max(H, W) < 2^b with b = ceil(log2(max(H, W) + 1)).
+//     The DRM modes splat u = r * t * 2 or the retimed ratio, both in [0, 2): b = 1 -- and the weight itself: <= 1;
+//   * every source pixel adds to a given output pixel at most once: at most H * W <= 2^c contributions meet;
+//   * |sum| * 2^S <= 2^(b + c + S) must stay below 2^63: S = 62 - b - c, and no more than 40 (2^-40 ~ 1e-12 is already far
+//     below fp32's own rounding of any sum the hole test can pass).  1088 x 1920: S = 30 / 40; 4320 x 7680: S = 24 / 36 --
+//     steps of 1e-9 and 6e-8 against the 1e-4 scale of the `cover < 0.999` hole test.  Below S = 16 (more than 2^31 pixels) the
+//     entry points refuse the geometry;
+//   * a value outside the derived range (it cannot come from the kernels' own sources) saturates at +-2^(b + S) instead of
+//     wrapping.
+struct SplatFx {
+  double scale, inv, limit;  // 2^S, 2^-S, 2^(b + S)
+};
+typedef unsigned long long fx_t;
+__device__ __forceinline__ void fx_add(fx_t *p, float v, const SplatFx &fx) {
+  const double q = fmin(fmax((double)v * fx.scale, -fx.limit), fx.limit);  // (the product is exact: a power of two)
+  atomicAdd(p, (fx_t)__double2ll_rn(q));
+}
+__device__ __forceinline__ float fx_value(fx_t a, const SplatFx &fx) { return (float)((double)(long long)a * fx.inv); }
+
+// one accumulator word: fp32 (arrival-order sum) or, DET, fixed point (order-free sum); `acc` counts words of either kind
+template <bool DET>
+__device__ __forceinline__ void gacc_add(float *acc, size_t word, float v, const SplatFx &fx) {
+  if (DET) fx_add(reinterpret_cast<fx_t *>(acc) + word, v, fx);
+  else atomic_add_f32(acc + word, v);
+}
+
+// ------------------------------------------------------------------------------------------
 // Generic "value + ones" avg-splat scatter shared by the fused pipelines: accumulates
 // [v0*w, (v1*w,) w] at (x+fx, y+fy).  NV = number of value channels (1 or 2).
-template <int NV>
+template <int NV, bool DET = false>
 __device__ __forceinline__ void scatter_avg(float *__restrict__ acc, int x, int y, float fx_, float fy_,
                                             const float (&v)[NV], int H, int W, int *__restrict__ dirty = nullptr,
-                                            int tiles_x = 0) {
+                                            int tiles_x = 0, const SplatFx &fxp = SplatFx()) {
   const float X = (float)x + fx_, Y = (float)y + fy_;
   if (!(isfinite(X) && isfinite(Y))) return;
   const float fx = floorf(X), fy = floorf(Y);
@@ -80,10 +113,10 @@ __device__ __forceinline__ void scatter_avg(float *__restrict__ acc, int x, int 
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     if (!(okx[k & 1] && oky[k >> 1])) continue;
-    float *d = acc + ((long long)(y0 + (k >> 1)) * W + (x0 + (k & 1))) * (NV + 1);
+    const size_t d = ((size_t)(y0 + (k >> 1)) * W + (x0 + (k & 1))) * (NV + 1);
 #pragma unroll
-    for (int c = 0; c < NV; ++c) atomic_add_f32(d + c, v[c] * wgt[k]);
-    atomic_add_f32(d + NV, wgt[k]);
+    for (int c = 0; c < NV; ++c) gacc_add<DET>(acc, d + c, v[c] * wgt[k], fxp);
+    gacc_add<DET>(acc, d + NV, wgt[k], fxp);
     // the 32 x 16 output tile this corner lies in has something to collect from the accumulator (kSX, kSY below)
     if (dirty) atomicOr(dirty + ((y0 + (k >> 1)) >> 4) * tiles_x + ((x0 + (k & 1)) >> 5), 1);
   }
@@ -214,11 +247,13 @@ constexpr int kReachWords = 1 << 18;  // 1 MB: 8 items of a 4K map are 130 560 t
 // short ones -> the tile's reach, the smallest halo R with all four corners of each within R of its source (what
 // splat_source_from's is_short tests against kR): an output tile whose 3 x 3 neighbourhood of source tiles has reach <= R
 // receives nothing from beyond R pixels and scans a (32 + 2R) x (16 + 2R) window instead of 64 x 48.
-template <int MODE>
-__global__ void __launch_bounds__(256) splat_long_prepass(const float *__restrict__ fs, const float *__restrict__ fo,
-                                                          float t, const float *__restrict__ t_dev, float eps,
-                                                          float *__restrict__ ws, int H, int W, const SplatJobs jobs) {
+// DET: the accumulator words are fixed point (twice the room, SplatFx); the kernel of that form is splat_long_prepass_det.
+template <int MODE, bool DET>
+__device__ __forceinline__ void splat_prepass_body(const float *__restrict__ fs, const float *__restrict__ fo, float t,
+                                                   const float *__restrict__ t_dev, float eps, float *__restrict__ ws, int H, int W,
+                                                   const SplatJobs &jobs, const SplatFx &fx) {
   constexpr int NV = MODE == 0 ? 2 : 1;
+  constexpr int kAccF = (NV + 1) * (DET ? 2 : 1);  // floats of workspace per pixel
   if (t_dev) t = *t_dev;  // timestep from device memory: lets one captured HIP graph serve every t
   const int n = blockIdx.z;
   const size_t P = (size_t)H * W;
@@ -234,8 +269,8 @@ __global__ void __launch_bounds__(256) splat_long_prepass(const float *__restric
   const int tiles_x = gridDim.x, tiles = tiles_x * gridDim.y;
   int *reach = reinterpret_cast<int *>(ws);
   float *gacc = ws + kReachWords;
-  int *dirty = reinterpret_cast<int *>(gacc + (size_t)gridDim.z * P * (NV + 1)) + (size_t)n * tiles;
-  gacc += (size_t)n * P * (NV + 1);
+  int *dirty = reinterpret_cast<int *>(gacc + (size_t)gridDim.z * P * kAccF) + (size_t)n * tiles;
+  gacc += (size_t)n * P * kAccF;
   const int tid = threadIdx.x;
   int r = 0;
 #pragma unroll
@@ -254,10 +289,10 @@ __global__ void __launch_bounds__(256) splat_long_prepass(const float *__restric
     }
     if (MODE == 0) {
       const float v[2] = {s.v[0], s.v[1]};
-      scatter_avg<2>(gacc, x, y, s.fx, s.fy, v, H, W, dirty, tiles_x);
+      scatter_avg<2, DET>(gacc, x, y, s.fx, s.fy, v, H, W, dirty, tiles_x, fx);
     } else {
       const float v[1] = {s.v[0]};
-      scatter_avg<1>(gacc, x, y, s.fx, s.fy, v, H, W, dirty, tiles_x);
+      scatter_avg<1, DET>(gacc, x, y, s.fx, s.fy, v, H, W, dirty, tiles_x, fx);
     }
   }
   if ((size_t)gridDim.z * tiles > (size_t)kReachWords) return;  // (no room for the map: the tiles scan the full halo)
@@ -267,6 +302,21 @@ __global__ void __launch_bounds__(256) splat_long_prepass(const float *__restric
   if ((tid & 63) == 0) wr[tid >> 6] = r;
   __syncthreads();
   if (tid == 0) reach[(size_t)n * tiles + blockIdx.y * tiles_x + blockIdx.x] = max(max(wr[0], wr[1]), max(wr[2], wr[3]));
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) splat_long_prepass(const float *__restrict__ fs, const float *__restrict__ fo,
+                                                          float t, const float *__restrict__ t_dev, float eps,
+                                                          float *__restrict__ ws, int H, int W, const SplatJobs jobs) {
+  splat_prepass_body<MODE, false>(fs, fo, t, t_dev, eps, ws, H, W, jobs, SplatFx());
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) splat_long_prepass_det(const float *__restrict__ fs, const float *__restrict__ fo,
+                                                              float t, const float *__restrict__ t_dev, float eps,
+                                                              float *__restrict__ ws, int H, int W, const SplatJobs jobs,
+                                                              const SplatFx fx) {
+  splat_prepass_body<MODE, true>(fs, fo, t, t_dev, eps, ws, H, W, jobs, fx);
 }
 
 // Tile kernel.  On gfx950 ds_add_f32 retires ~0.33 lane-adds per clock per CU while integer LDS atomics retire ~13
@@ -281,11 +331,64 @@ constexpr int kKX = kSX + 1, kKY = kSY + 1;             // key grid: footprint o
 constexpr int kNKEY = kKX * kKY;
 constexpr int kCAP = 1536;                              // records held in LDS (3 per output pixel)
 
-// R: the halo this tile scans (kR, or less where the reach map allows it)
-template <int MODE, int R>
+// Deterministic mode: one lane puts the records [lo, hi) of a key segment into ascending order of their source pixel index
+// (unique within a segment, so the result is a function of the segment's CONTENT, whatever order the slots were handed out in).
+// A: key(i) -> the index of record i, swap(i, j).  Segments are a handful of records: insertion sort; a long one (strong
+// convergence) is heap-sorted so that the worst case stays n log n.
+template <class A>
+__device__ __forceinline__ void sort_segment(A a, int lo, int hi) {
+  const int n = hi - lo;
+  if (n < 2) return;
+  if (n <= 16) {
+    for (int i = 1; i < n; ++i)
+      for (int j = i; j > 0 && a.key(lo + j - 1) > a.key(lo + j); --j) a.swap(lo + j - 1, lo + j);
+    return;
+  }
+  auto sift = [&](int root, int end) {  // max-heap on [0, end)
+    for (;;) {
+      int c = 2 * root + 1;
+      if (c >= end) return;
+      if (c + 1 < end && a.key(lo + c + 1) > a.key(lo + c)) ++c;
+      if (a.key(lo + root) >= a.key(lo + c)) return;
+      a.swap(lo + root, lo + c);
+      root = c;
+    }
+  };
+  for (int i = n / 2 - 1; i >= 0; --i) sift(i, n);
+  for (int end = n - 1; end > 0; --end) {
+    a.swap(lo, lo + end);
+    sift(0, end);
+  }
+}
+
+// the records of a tile in LDS: the source index rides in the free y lane of a one-value record, in `sidx` beside a two-value one
+template <int NV>
+struct LdsSegment {
+  float4 *rec;
+  unsigned *sidx;
+  __device__ __forceinline__ unsigned key(int i) const { return NV == 2 ? sidx[i] : __float_as_uint(rec[i].y); }
+  __device__ __forceinline__ void swap(int i, int j) const {
+    const float4 t = rec[i];
+    rec[i] = rec[j];
+    rec[j] = t;
+    if (NV == 2) {
+      const unsigned u = sidx[i];
+      sidx[i] = sidx[j];
+      sidx[j] = u;
+    }
+  }
+};
+
+// R: the halo this tile scans (kR, or less where the reach map allows it).
+// DET (splat_tiled_det): every key segment is summed in ascending order of the GLOBAL source pixel index y * W + x -- not the
+// window-relative one: which halo variant a tile takes follows the reach map, which large launches run without --, a tile whose
+// records do not ALL fit in LDS (the scanned total, a function of the data; not which record came last) sends all of its
+// in-tile corners through the global accumulator, and that accumulator is fixed point (SplatFx).
+template <int MODE, int R, bool DET>
 __device__ __forceinline__ void splat_tile_body(const float *__restrict__ fs, const float *__restrict__ fo, float t, float eps,
                                                 unsigned moves, int n_moves, float *gacc, int *dirty, float *__restrict__ out,
-                                                int H, int W, int *cnt, int *wsum, float4 *rec, int *spilled_) {
+                                                int H, int W, int *cnt, int *wsum, float4 *rec, int *spilled_, unsigned *sidx,
+                                                const SplatFx &fx) {
   constexpr int NV = MODE == 0 ? 2 : 1;
   constexpr int kSWX = kSX + 2 * R, kSWY = kSY + 2 * R;  // source window
   constexpr int kSPT = (kSWX * kSWY + 255) / 256;        // window sources per thread
@@ -367,11 +470,19 @@ __device__ __forceinline__ void splat_tile_body(const float *__restrict__ fs, co
   __syncthreads();
 
   // pass 2: place the records
+  const bool all_global = DET && cnt[kNKEY] > kCAP;  // uniform over the workgroup, decided by the data alone
 #pragma unroll
   for (int i = 0; i < kSPT; ++i) {
     if (kr[i] < 0) continue;
     const int slot = cnt[kr[i] >> 16] + (kr[i] & 0xFFFF);
-    if (slot < kCAP) {
+    if (DET ? !all_global : slot < kCAP) {
+      if (DET) {  // the record carries its global source index (the same arithmetic as pass 1: e -> (x, y))
+        const int e = tid + i * 256;
+        const int ry = e / kSWX, rx = e - ry * kSWX;
+        const unsigned src = (unsigned)(ty0 - kR + ry) * (unsigned)W + (unsigned)(tx0 - kR + rx);
+        if (NV == 2) sidx[slot] = src;
+        else val[i].y = __uint_as_float(src);
+      }
       rec[slot] = val[i];
     } else {  // LDS record space exhausted: the corners of this source that lie in THIS tile go through the global
               // accumulator (a neighbouring tile handles its own corners of the same source)
@@ -384,10 +495,10 @@ __device__ __forceinline__ void splat_tile_body(const float *__restrict__ fs, co
         const int cx = x0 + (k & 1), cy = y0 + (k >> 1);
         if (cx < tx0 || cx >= tx0 + kSX || cy < ty0 || cy >= ty0 + kSY || cx >= W || cy >= H) continue;
         const float w = ((k & 1) ? X - fl_x : (fl_x + 1.f) - X) * ((k >> 1) ? Y - fl_y : (fl_y + 1.f) - Y);
-        float *d = gacc + ((size_t)cy * W + cx) * (NV + 1);
-        atomic_add_f32(d, val[i].x * w);
-        if (NV == 2) atomic_add_f32(d + 1, val[i].y * w);
-        atomic_add_f32(d + NV, w);
+        const size_t d = ((size_t)cy * W + cx) * (NV + 1);
+        gacc_add<DET>(gacc, d, val[i].x * w, fx);
+        if (NV == 2) gacc_add<DET>(gacc, d + 1, val[i].y * w, fx);
+        gacc_add<DET>(gacc, d + NV, w, fx);
       }
     }
   }
@@ -395,6 +506,11 @@ __device__ __forceinline__ void splat_tile_body(const float *__restrict__ fs, co
   // is enough (same CU, lines not yet in L1) -- an agent-scope fence writes the XCD's L2 back from every workgroup
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   __syncthreads();
+  if (DET) {  // one lane per key: the segment into source order
+    if (!all_global)
+      for (int k = tid; k < kNKEY; k += 256) sort_segment(LdsSegment<NV>{rec, sidx}, cnt[k], cnt[k + 1]);
+    __syncthreads();
+  }
 
 #ifndef DRBA_SPLAT_ALWAYS_COLLECT  // A/B builds: every tile reads its accumulator entries, as before ABI 7
 #define DRBA_SPLAT_ALWAYS_COLLECT 0
@@ -411,7 +527,7 @@ __device__ __forceinline__ void splat_tile_body(const float *__restrict__ fs, co
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy) {
       const int k1 = (ly - dy + 1) * kKX + lx;
-      const int s0 = cnt[k1], s1 = cnt[k1 + 1], s2 = min(cnt[k1 + 2], kCAP);
+      const int s0 = cnt[k1], s1 = cnt[k1 + 1], s2 = DET ? (all_global ? s0 : cnt[k1 + 2]) : min(cnt[k1 + 2], kCAP);
       for (int s_ = s0; s_ < s2; ++s_) {
         const float4 r = rec[s_];
         const int dx = s_ < s1 ? 1 : 0;
@@ -427,7 +543,20 @@ __device__ __forceinline__ void splat_tile_body(const float *__restrict__ fs, co
     }
     const size_t p = (size_t)y * W + x;
     float g0 = 0.f, g1 = 0.f, gw = 0.f;
-    if (collect) {
+    if (collect && DET) {
+      fx_t *g = reinterpret_cast<fx_t *>(gacc) + p * (NV + 1);
+      // agent-scope loads: they read what the atomics left in L2 even where a workgroup that ran on this CU before pulled a
+      // line shared with the neighbouring tile into L1 (far more tiles take the global path here than in the default mode)
+      const fx_t q0 = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const fx_t q1 = NV == 2 ? __hip_atomic_load(g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+      const fx_t qw = __hip_atomic_load(g + NV, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if ((q0 | q1 | qw) != 0) {  // self-cleaning, as below
+        g[0] = 0;
+        if (NV == 2) g[1] = 0;
+        g[NV] = 0;
+      }
+      g0 = fx_value(q0, fx), g1 = fx_value(q1, fx), gw = fx_value(qw, fx);
+    } else if (collect) {
       float *g = gacc + p * (NV + 1);
       g0 = g[0], g1 = NV == 2 ? g[1] : 0.f, gw = g[NV];
       if (g0 != 0.f || g1 != 0.f || gw != 0.f) {  // self-cleaning accumulator: zero on entry, zero again on return
@@ -453,16 +582,15 @@ __device__ __forceinline__ void splat_tile_body(const float *__restrict__ fs, co
   }
 }
 
-template <int MODE>
-__global__ void __launch_bounds__(256) splat_tiled(const float *__restrict__ fs, const float *__restrict__ fo, float t,
-                                                   const float *__restrict__ t_dev, float eps, float *ws,
-                                                   float *__restrict__ out, int H, int W, const SplatJobs jobs) {
+// what splat_tiled and splat_tiled_det share: the item's pointers, its place in the workspace, the halo variant
+template <int MODE, bool DET>
+__device__ __forceinline__ void splat_tiled_body(const float *__restrict__ fs, const float *__restrict__ fo, float t,
+                                                 const float *__restrict__ t_dev, float eps, float *ws, float *__restrict__ out,
+                                                 int H, int W, const SplatJobs &jobs, int *cnt, int *wsum, float4 *rec,
+                                                 int *spilled, unsigned *sidx, const SplatFx &fx) {
   constexpr int NV = MODE == 0 ? 2 : 1;
+  constexpr int kAccF = (NV + 1) * (DET ? 2 : 1);  // floats of workspace per pixel
   if (t_dev) t = *t_dev;
-  __shared__ int cnt[kNKEY + 1];   // per key: count, then (after the scan) segment start; [kNKEY] = total
-  __shared__ int wsum[4];
-  __shared__ float4 rec[kCAP];     // (v0, v1, X - tx0, Y - ty0) of a source, grouped by key
-  __shared__ int spilled;          // this tile put records beyond kCAP into the global accumulator
   static_assert(kSX == 32 && kSY == 16, "scatter_avg and the pre-pass work on 32 x 16 tiles");
   const int n = blockIdx.z;
   const size_t P = (size_t)H * W;
@@ -481,8 +609,8 @@ __global__ void __launch_bounds__(256) splat_tiled(const float *__restrict__ fs,
   float *gacc = ws + kReachWords;
   // dirty[tile] != 0: the long-flow pre-pass scattered into this tile.  Only then (or after a spill of its own) does the
   // tile read its accumulator entries -- 8-12 bytes per output pixel that are zero in all but a few tiles of a frame.
-  int *dirty = reinterpret_cast<int *>(gacc + (size_t)gridDim.z * P * (NV + 1)) + ((size_t)n * tiles_y + blockIdx.y) * tiles_x + blockIdx.x;
-  gacc += (size_t)n * P * (NV + 1);
+  int *dirty = reinterpret_cast<int *>(gacc + (size_t)gridDim.z * P * kAccF) + ((size_t)n * tiles_y + blockIdx.y) * tiles_x + blockIdx.x;
+  gacc += (size_t)n * P * kAccF;
   // the halo: what the source tiles around this one reach (all of them lie within kRMax = 16 <= a tile's smaller side)
   int r = kRMax;
   if ((size_t)gridDim.z * tiles <= (size_t)kReachWords) {
@@ -497,9 +625,34 @@ __global__ void __launch_bounds__(256) splat_tiled(const float *__restrict__ fs,
       }
     r = __builtin_amdgcn_readfirstlane(r);
   }
-  if (r <= 4) splat_tile_body<MODE, 4>(fs, fo, t, eps, moves, n_moves, gacc, dirty, out, H, W, cnt, wsum, rec, &spilled);
-  else if (r <= 8) splat_tile_body<MODE, 8>(fs, fo, t, eps, moves, n_moves, gacc, dirty, out, H, W, cnt, wsum, rec, &spilled);
-  else splat_tile_body<MODE, kRMax>(fs, fo, t, eps, moves, n_moves, gacc, dirty, out, H, W, cnt, wsum, rec, &spilled);
+  if (r <= 4) splat_tile_body<MODE, 4, DET>(fs, fo, t, eps, moves, n_moves, gacc, dirty, out, H, W, cnt, wsum, rec, spilled, sidx, fx);
+  else if (r <= 8) splat_tile_body<MODE, 8, DET>(fs, fo, t, eps, moves, n_moves, gacc, dirty, out, H, W, cnt, wsum, rec, spilled, sidx, fx);
+  else splat_tile_body<MODE, kRMax, DET>(fs, fo, t, eps, moves, n_moves, gacc, dirty, out, H, W, cnt, wsum, rec, spilled, sidx, fx);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) splat_tiled(const float *__restrict__ fs, const float *__restrict__ fo, float t,
+                                                   const float *__restrict__ t_dev, float eps, float *ws,
+                                                   float *__restrict__ out, int H, int W, const SplatJobs jobs) {
+  __shared__ int cnt[kNKEY + 1];   // per key: count, then (after the scan) segment start; [kNKEY] = total
+  __shared__ int wsum[4];
+  __shared__ float4 rec[kCAP];     // (v0, v1, X - tx0, Y - ty0) of a source, grouped by key
+  __shared__ int spilled;          // this tile put records beyond kCAP into the global accumulator
+  splat_tiled_body<MODE, false>(fs, fo, t, t_dev, eps, ws, out, H, W, jobs, cnt, wsum, rec, &spilled, nullptr, SplatFx());
+}
+
+// the deterministic form (drba_set_deterministic): same LDS, plus the source indices of MODE 0's two-value records
+template <int MODE>
+__global__ void __launch_bounds__(256) splat_tiled_det(const float *__restrict__ fs, const float *__restrict__ fo, float t,
+                                                       const float *__restrict__ t_dev, float eps, float *ws,
+                                                       float *__restrict__ out, int H, int W, const SplatJobs jobs,
+                                                       const SplatFx fx) {
+  __shared__ int cnt[kNKEY + 1];
+  __shared__ int wsum[4];
+  __shared__ float4 rec[kCAP];
+  __shared__ int spilled;          // this tile put its records into the global accumulator
+  __shared__ unsigned sidx[MODE == 0 ? kCAP : 1];
+  splat_tiled_body<MODE, true>(fs, fo, t, t_dev, eps, ws, out, H, W, jobs, cnt, wsum, rec, &spilled, sidx, fx);
 }
 
 
@@ -624,6 +777,24 @@ splat_sort_fill(const float *__restrict__ flow, const float *__restrict__ metric
     const int slot = start[k] + atomicSub(&cnt[k], 1) - 1;
     rec[slot] = r;
   }
+}
+
+// Deterministic mode only (drba_set_deterministic): splat_sort_fill hands a record its slot in arrival order and the gathers
+// sum a segment in slot order, so one lane per key of the [N](H+1) x (W+1) grid puts its segment into ascending source order
+// first.  A segment holds sources of one image only, each once: the order is a function of the flow alone.
+struct RecSegment {
+  int4 *rec;  // a SplatRec as one 16-byte word: .x = src
+  __device__ __forceinline__ int key(int i) const { return rec[i].x; }
+  __device__ __forceinline__ void swap(int i, int j) const {
+    const int4 t = rec[i];
+    rec[i] = rec[j];
+    rec[j] = t;
+  }
+};
+static_assert(sizeof(SplatRec) == sizeof(int4) && offsetof(SplatRec, src) == 0, "RecSegment reads a record as an int4");
+__global__ void __launch_bounds__(256) splat_sort_segments(const int *__restrict__ start, SplatRec *rec, size_t L) {
+  for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < L; k += (size_t)gridDim.x * blockDim.x)
+    sort_segment(RecSegment{reinterpret_cast<int4 *>(rec)}, start[k], start[k + 1]);
 }
 
 __global__ void __launch_bounds__(256)
@@ -798,6 +969,40 @@ __global__ void __launch_bounds__(256) drm_retime_kernel(const float *__restrict
 
 }  // namespace
 
+static int ceil_log2(size_t v) {
+  int b = 0;
+  while (((size_t)1 << b) < v) ++b;
+  return b;
+}
+// the fixed-point format of a geometry (see SplatFx): false when 63 bits leave fewer than 16 fraction bits
+static bool splat_fx(int mode, int H, int W, SplatFx *fx) {
+  const int b = mode == 0 ? ceil_log2((size_t)(H > W ? H : W) + 1) : 1, c = ceil_log2((size_t)H * W);
+  int S = 62 - b - c;
+  if (S > 40) S = 40;
+  if (S < 16) return false;
+  fx->scale = ldexp(1.0, S), fx->inv = ldexp(1.0, -S), fx->limit = ldexp(1.0, b + S);
+  return true;
+}
+
+// the launch pair of every fused entry point: the long-flow pre-pass, then the tiles -- in the mode read here, at launch
+template <int MODE>
+static int splat_launch(const float *fs, const float *fo, float t, const float *t_dev, float eps, float *ws, float *out, int n_items,
+                        int H, int W, const SplatJobs &J, hipStream_t s) {
+  dim3 g((W + kSX - 1) / kSX, (H + kSY - 1) / kSY, n_items);  // source tiles of the pre-pass = output tiles of the splat
+  if (g_deterministic) {
+    SplatFx fx;
+    if (!splat_fx(MODE, H, W, &fx) || (size_t)H * W > 0xffffffffu) return DRBA_EUNSUPPORTED;  // (source indices are 32 bits)
+    if ((uintptr_t)ws & 7) return DRBA_EINVAL;  // 64-bit accumulator words
+    DRBA_LAUNCH(splat_long_prepass_det<MODE>, g, dim3(kBlock), 0, s, fs, fo, t, t_dev, eps, ws, H, W, J, fx);
+    DRBA_LAUNCH(splat_tiled_det<MODE>, g, dim3(kBlock), 0, s, fs, fo, t, t_dev, eps, ws, out, H, W, J, fx);
+  } else {
+    DRBA_LAUNCH(splat_long_prepass<MODE>, g, dim3(kBlock), 0, s, fs, fo, t, t_dev, eps, ws, H, W, J);
+    DRBA_LAUNCH(splat_tiled<MODE>, g, dim3(kBlock), 0, s, fs, fo, t, t_dev, eps, ws, out, H, W, J);
+  }
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
 // ============================================================================================ C ABI
 extern "C" {
 
@@ -884,6 +1089,8 @@ int drba_softsplat_index(const float *flow, const float *metric, float *ws, int 
   DRBA_LAUNCH(scan_sums, dim3(1), dim3(kBlock), 0, s, w.bsum, w.nb, w.start + w.L);
   DRBA_LAUNCH(scan_add, dim3((unsigned)((w.L + 255) / 256)), dim3(kBlock), 0, s, w.start, w.bsum, w.L);
   DRBA_LAUNCH(splat_sort_fill, dim3(grid_for(P), N), dim3(kBlock), 0, s, flow, metric, w.start, w.cnt, w.rec, H, W, mode);
+  // every gather of this index (drba_softsplat, _again, _gather_quad) then sums in source order
+  if (g_deterministic) DRBA_LAUNCH(splat_sort_segments, dim3(grid_for(w.L)), dim3(kBlock), 0, s, w.start, w.rec, w.L);
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }
@@ -929,36 +1136,26 @@ int drba_flow_distance(const float *flow, float *out, int N, int H, int W, void 
 
 size_t drba_rife_splat_ws_floats(int N, int H, int W, int values) {
   if (N <= 0 || H <= 0 || W <= 0 || values < 1 || values > 2) return 0;
-  // the reach map (fixed size, scratch), accumulators [N][H*W][values + 1], then one flag per (item, 32 x 16 output tile)
-  return (size_t)kReachWords + (size_t)N * H * W * (values + 1) + (size_t)N * ((W + kSX - 1) / kSX) * ((H + kSY - 1) / kSY);
+  // the reach map (fixed size, scratch), accumulators [N][H*W][values + 1], then one flag per (item, 32 x 16 output tile).
+  // Deterministic mode (drba_set_deterministic): the accumulator words are 64-bit fixed point, i.e. twice the floats; the same
+  // zero-on-entry, zero-on-return contract, so one zeroed buffer of the larger size serves calls of either mode in any order
+  const size_t acc = (size_t)N * H * W * (values + 1) * (g_deterministic ? 2 : 1);
+  return (size_t)kReachWords + acc + (size_t)N * ((W + kSX - 1) / kSX) * ((H + kSY - 1) / kSY);
 }
 
 int drba_flow_reverse(const float *flow, float *out, float *ws, int N, int H, int W, void *stream) {
   if (!flow || !out || !ws || N <= 0 || H <= 0 || W <= 0) return DRBA_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
   SplatJobs none;
   none.n = 0;
-  dim3 g((W + kSX - 1) / kSX, (H + kSY - 1) / kSY, N);  // source tiles of the pre-pass = output tiles of the splat
-  DRBA_LAUNCH(splat_long_prepass<0>, g, dim3(kBlock), 0, s, flow, (const float *)nullptr, 0.f,
-                     (const float *)nullptr, 0.f, ws, H, W, none);
-  DRBA_LAUNCH(splat_tiled<0>, g, dim3(kBlock), 0, s, flow, (const float *)nullptr, 0.f, (const float *)nullptr,
-                     0.f, ws, out, H, W, none);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
+  return splat_launch<0>(flow, nullptr, 0.f, nullptr, 0.f, ws, out, N, H, W, none, (hipStream_t)stream);
 }
 
 int drba_drm_rife_linear(const float *flow_self, const float *flow_other, float t, const float *t_dev, float eps,
                          float *out, float *ws, int N, int H, int W, void *stream) {
   if (!flow_self || !flow_other || !out || !ws || N <= 0 || H <= 0 || W <= 0) return DRBA_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
   SplatJobs none;
   none.n = 0;
-  dim3 g((W + kSX - 1) / kSX, (H + kSY - 1) / kSY, N);
-  DRBA_LAUNCH(splat_long_prepass<1>, g, dim3(kBlock), 0, s, flow_self, flow_other, t, t_dev,
-                     eps, ws, H, W, none);
-  DRBA_LAUNCH(splat_tiled<1>, g, dim3(kBlock), 0, s, flow_self, flow_other, t, t_dev, eps, ws, out, H, W, none);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
+  return splat_launch<1>(flow_self, flow_other, t, t_dev, eps, ws, out, N, H, W, none, (hipStream_t)stream);
 }
 
 int drba_drm_rife_linear_batch(const drba_drm_job_t *jobs, int n_jobs, float eps, float *ws, int H, int W, void *stream) {
@@ -970,13 +1167,7 @@ int drba_drm_rife_linear_batch(const drba_drm_job_t *jobs, int n_jobs, float eps
     if (!jobs[k].flow_self || !jobs[k].flow_other || !jobs[k].out) return DRBA_EINVAL;
     J.fs[k] = jobs[k].flow_self, J.fo[k] = jobs[k].flow_other, J.t[k] = jobs[k].t, J.out[k] = jobs[k].out;
   }
-  hipStream_t s = (hipStream_t)stream;
-  dim3 g((W + kSX - 1) / kSX, (H + kSY - 1) / kSY, n_jobs);
-  DRBA_LAUNCH(splat_long_prepass<1>, g, dim3(kBlock), 0, s, J.fs[0], J.fo[0], 0.f, (const float *)nullptr, eps, ws,
-              H, W, J);
-  DRBA_LAUNCH(splat_tiled<1>, g, dim3(kBlock), 0, s, J.fs[0], J.fo[0], 0.f, (const float *)nullptr, eps, ws, J.out[0], H, W, J);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
+  return splat_launch<1>(J.fs[0], J.fo[0], 0.f, nullptr, eps, ws, J.out[0], n_jobs, H, W, J, (hipStream_t)stream);
 }
 
 // get_drm_t's scalar walk (drm.py:36-37, :43-56), run literally in double: `_x > t` moves the upper bracket down (bit clear), `_x < t`
@@ -1015,12 +1206,7 @@ int drba_drm_rife_nonlinear(const float *flow_self, const float *flow_other, dou
   memset(&one, 0, sizeof(one));  // n == 0: the single-tensor form, its walk in entry 0
   const int rc = drba_drm_walk(t, precision, &one.moves[0], &one.n_moves[0]);
   if (rc != DRBA_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  dim3 g((W + kSX - 1) / kSX, (H + kSY - 1) / kSY, N);
-  DRBA_LAUNCH(splat_long_prepass<2>, g, dim3(kBlock), 0, s, flow_self, flow_other, 0.f, (const float *)nullptr, eps, ws, H, W, one);
-  DRBA_LAUNCH(splat_tiled<2>, g, dim3(kBlock), 0, s, flow_self, flow_other, 0.f, (const float *)nullptr, eps, ws, out, H, W, one);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
+  return splat_launch<2>(flow_self, flow_other, 0.f, nullptr, eps, ws, out, N, H, W, one, (hipStream_t)stream);
 }
 
 int drba_drm_rife_nonlinear_batch(const drba_drm_nonlinear_job_t *jobs, int n_jobs, double precision, float eps, float *ws, int H,
@@ -1035,12 +1221,7 @@ int drba_drm_rife_nonlinear_batch(const drba_drm_nonlinear_job_t *jobs, int n_jo
     const int rc = drba_drm_walk(jobs[k].t, precision, &J.moves[k], &J.n_moves[k]);
     if (rc != DRBA_OK) return rc;  // (nothing launched yet)
   }
-  hipStream_t s = (hipStream_t)stream;
-  dim3 g((W + kSX - 1) / kSX, (H + kSY - 1) / kSY, n_jobs);
-  DRBA_LAUNCH(splat_long_prepass<2>, g, dim3(kBlock), 0, s, J.fs[0], J.fo[0], 0.f, (const float *)nullptr, eps, ws, H, W, J);
-  DRBA_LAUNCH(splat_tiled<2>, g, dim3(kBlock), 0, s, J.fs[0], J.fo[0], 0.f, (const float *)nullptr, eps, ws, J.out[0], H, W, J);
-  DRBA_CHECK_LAUNCH();
-  return DRBA_OK;
+  return splat_launch<2>(J.fs[0], J.fo[0], 0.f, nullptr, eps, ws, J.out[0], n_jobs, H, W, J, (hipStream_t)stream);
 }
 
 int drba_drm_ratio(const float *flow10, const float *flow12, float eps, float *drm10, float *drm12, int N, int H,

@@ -312,6 +312,7 @@ def parse_args(argv=None):
     h.add_argument("-st", "--scdet_threshold", dest="scdet_threshold", type=float, default=0.3)
     h.add_argument("--plain", action="store_true", help="plain inference_ts in place of every DRBA step (the baseline)")
     h.add_argument("--nonlinear", action="store_true", help="every DRBA step with the non-linear DistanceRatioMap (linear=False); not with --plain")
+    h.add_argument("--deterministic", action="store_true", help="bit-reproducible run (infer.py --deterministic): the same clip and command give the same figures")
     h.add_argument("--weights", type=str, default=None, help="weight directory (default: the model's, synthetic if absent)")
     h.add_argument("--json", dest="json_path", type=str, default=None)
     return p.parse_args(argv)
@@ -344,6 +345,7 @@ def main(argv=None, backend=None):
         from drba_amd import infer as drv
         from drba_amd import tune, tunecache
         tunecache.default_on()  # a command line: the conv autotuner's winners are kept across runs unless DRBA_TUNE_CACHE=0
+        drv.apply_deterministic(args)
         wdir = args.weights or tune._default_weights(args.model_type)
         synthetic = args.weights is None and not (wdir and os.path.isdir(wdir))
         model = drv.load_model(args.model_type, scale=args.scale,

@@ -1,12 +1,16 @@
 """DRBA command line and per-frame driver loop (same CLI as the reference's infer.py).
 
     python infer.py -m rife -i in.npz -o out.npz [-fps 60 | -t 2] [-s] [-st 0.3] [-hw] [-scale 1.0] [--out-depth source|8|16]
-                    [--nonlinear] [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full]
+                    [--nonlinear] [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--deterministic]
 
 `--out-depth` is not in the reference: a .npz / .npy clip may hold uint16 frames, and the written frames are 8 or 16 bits deep
 (default: as the source, so an 8-bit clip is handled exactly as before).  `--nonlinear` is not in the reference either: its driver
 always asks the model for linear=True (infer.py:143) although the model entry point defaults to the non-linear DistanceRatioMap
 (get_drm_t); with the flag every DRBA step of the clip runs with linear=False.
+
+`--deterministic` (not in the reference): the written bytes depend on the clip, the command, the build, the device model and the
+stored kernel configurations only -- two runs write the same file (drba_amd.ops.set_deterministic).  A frame-sharded
+run is reproducible too, but not promised to equal the sequential one.
 
 A `.y4m` path, or `-` for stdin / stdout, at either end selects the YUV4MPEG2 source or sink (drba_amd/y4m.py; planar 4:2:0 at 8
 or 10 bits, converted inside the to_inp / to_out kernels): `ffmpeg -i a.mkv -f yuv4mpegpipe - | python infer.py -m rife -i - -o - -t 2
@@ -52,7 +56,17 @@ def parse_args(argv=None):
     p.add_argument("--yuv-range", dest="yuv_range", type=str, default="source", choices=("source", "limited", "full"),
                    help="sample range of a .y4m source / sink: the source header's XCOLORRANGE (default; limited when it has none or "
                         "the source is not Y4M), limited or full; a Y4M source that carries the tag is always read by it")
+    p.add_argument("--deterministic", dest="deterministic", action="store_true", default=False,
+                   help="bit-reproducible output: the splats sum in an order fixed by the data and no timing picks a kernel "
+                        "configuration (stored winners of `python -m drba_amd.tune` are still used)")
     return p.parse_args(argv)
+
+
+def apply_deterministic(args):
+    """--deterministic: switch the mode on (process wide) before anything runs.  A namespace built without the flag leaves it alone."""
+    if getattr(args, "deterministic", False):
+        from drba_amd import ops
+        ops.set_deterministic(True)
 
 
 def out_depth_of(args):
@@ -109,6 +123,7 @@ def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, s
 
 
 def inference(model, args):
+    apply_deterministic(args)
     depth_kw = {} if out_depth_of(args) is None else {"out_depth": out_depth_of(args)}
     for flag, dflt in (("yuv_matrix", "bt709"), ("yuv_range", "source")):  # a namespace built without the flags means the defaults
         if getattr(args, flag, dflt) != dflt:
@@ -157,6 +172,7 @@ def inference_sharded(model, args, rank, world, to_inp=None, to_out=None, check_
     import numpy as np
 
     from drba_amd import parallel
+    apply_deterministic(args)
     ext = os.path.splitext(args.input)[1].lower()
     if ext == ".npz":
         z = np.load(args.input)
@@ -206,6 +222,7 @@ def main(argv=None):
     # alone leaves the store off); nothing is written before the first winner is stored
     from drba_amd import tunecache
     tunecache.default_on()
+    apply_deterministic(args)  # before the model is built: nothing it does at load is timed in this mode
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1:
         model = load_model(args.model_type, scale=args.scale)

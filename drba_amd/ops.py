@@ -195,6 +195,27 @@ def check_overflow(device=None):
             "previous step are not to be trusted.  drba_amd.ops.set_precision({0, 1, 2, 3}) keeps every operand at 24 bits")
 
 
+# ----------------------------------------------------------------------------- deterministic mode
+# The library's switch (drba_set_deterministic) mirrored here, so that the per-call questions of this module cost no library call:
+# DRBA_DETERMINISTIC=1 turns both on -- this one at import, the library's when it is loaded (_lib.load) --, which lets an unmodified
+# bench.py time the mode.
+_deterministic = os.environ.get("DRBA_DETERMINISTIC", "0") not in ("", "0")
+
+
+def set_deterministic(on):
+    """Bit-reproducible outputs (include/drba_hip.h, drba_set_deterministic): the splats sum in an order fixed
+    by the data, and no timing decides a kernel configuration (_tune).  Process wide, off by default; switch it before the first
+    frame -- kernel configurations are kept per mode.  -> the previous setting."""
+    global _deterministic
+    was = bool(_lib.load().drba_set_deterministic(1 if on else 0))
+    _deterministic = bool(on)
+    return was
+
+
+def deterministic():
+    return _deterministic
+
+
 # ----------------------------------------------------------------------------- splat / warp / drm
 def softsplat(tenIn, tenFlow, tenMetric, strMode, out=None, keep_quad=False):
     """`out` (not in the reference): a contiguous [N,C,H,W] destination, e.g. a channel slice of a concatenation buffer.
@@ -719,6 +740,11 @@ AUTOTUNE = True
 # CONV_FAMILIES = {0, 1, 2, 3} before the first call keeps every operand at 24 bits
 CONV_FAMILIES = {0, 1, 2, 3, 4}
 _tuned = {}
+_tuned_det = {}  # the choices of the deterministic mode (shape-only or stored; never timed here): kept apart from the timed winners
+
+
+def _tuned_table():
+    return _tuned_det if deterministic() else _tuned
 
 
 def set_precision(families):
@@ -759,7 +785,7 @@ def _candidates(lib, kind, stride, families, cin, cout):
 
 
 def _tuned_get(shape_key, families=None):
-    return _tuned.get((shape_key, tuple(sorted(CONV_FAMILIES if families is None else families))))
+    return _tuned_table().get((shape_key, tuple(sorted(CONV_FAMILIES if families is None else families))))
 
 
 class NoKernelConfig(_lib.DrbaHipError):
@@ -782,15 +808,21 @@ def tune_stats():
 _EUNSUPPORTED = -2  # DRBA_EUNSUPPORTED (include/drba_hip.h): the shape is outside what the configuration was built for
 
 
-def _tune(shape_key, candidates, run, reps=3, families=None, persist=False, device=None):
+def _tune(shape_key, candidates, run, reps=3, families=None, persist=False, device=None, pick=None):
     """persist: the winner is looked up in / written to the store of drba_amd.tunecache when DRBA_TUNE_CACHE turns it on (the
     three convolution wrappers below pass it, with the index of the device the layer runs on; keys of any other caller are never
-    stored)."""
+    stored).
+    Deterministic mode (set_deterministic): no timing decides anything.  A stored winner is taken as always (that path never timed);
+    otherwise the choice follows from the shape alone -- `pick()`, the library's *_pick_cfg answer, when it is a candidate and its
+    warm launch accepts the shape, else the first candidate that does -- with no timing pass, no synchronisation and nothing
+    written to the store: two runs agree given the same build, device model, store contents and command."""
     # a winner of one family set is not offered to another
     fams = tuple(sorted(CONV_FAMILIES if families is None else families))
     kind_key, shape_key = shape_key, (shape_key, fams)
-    if shape_key in _tuned:
-        return _tuned[shape_key]
+    det = deterministic()
+    table = _tuned_det if det else _tuned
+    if shape_key in table:
+        return table[shape_key]
     if shape_key in _no_config:
         raise NoKernelConfig(f"no kernel configuration accepts {shape_key}")
     # (with the library's debug range check armed a launch can return DRBA_EUNSUPPORTED for what is in the DATA: nothing such a
@@ -807,11 +839,23 @@ def _tune(shape_key, candidates, run, reps=3, families=None, persist=False, devi
             code = run(hit["cfg"]) if hit["cfg"] in candidates else _EUNSUPPORTED
             if code == 0:
                 _tune_stats["cache_hits"] += 1
-                _tuned[shape_key] = hit["cfg"]
+                table[shape_key] = hit["cfg"]
                 return hit["cfg"]
             if code != _EUNSUPPORTED:  # a launch failure / bad argument says nothing about the entry: not rejected, not re-tuned over
                 raise _lib.DrbaHipError(f"warm launch of the stored configuration {hit['cfg']} for {shape_key} failed ({code})")
             _tune_stats["rejected"] += 1
+
+    if det:
+        first = pick() if callable(pick) else pick
+        for cfg in ([first] if first in candidates else []) + [c for c in candidates if c != first]:
+            code = run(cfg)  # the one warm launch: does the configuration accept the shape?
+            if code == 0:
+                table[shape_key] = cfg
+                return cfg
+            if code != _EUNSUPPORTED:
+                raise _lib.DrbaHipError(f"warm launch of configuration {cfg} for {shape_key} failed ({code})")
+        _no_config.add(shape_key)  # (a property of the shape; remembered in the process, not in the store)
+        raise NoKernelConfig(f"no kernel configuration accepts {shape_key}")
 
     def timed(cfg):
         # the candidates are timed on an otherwise idle device: the first call for a shape usually comes from inside the
@@ -916,7 +960,8 @@ class _ConvLayer:
         elif AUTOTUNE and x.is_cuda:
             fam = _families(self.two_term_ok)
             cands = _candidates(_lib.load(), self.KIND, self._tune_stride(), fam, self.cin, self.cout)
-            cfg = _tune(self._tune_key(n, h, w), cands, run, families=fam, persist=True, device=x.device.index)
+            cfg = _tune(self._tune_key(n, h, w), cands, run, families=fam, persist=True, device=x.device.index,
+                        pick=lambda: self._pick_cfg(h, w))
             self._keep.add(cfg)  # a layer can have one winner per batch size (block0: N=1 in calc_flow, N=2 stacked)
             _prune(self._packed, self._keep)
         else:
@@ -996,7 +1041,8 @@ def conv3x3_shuffle(layer, x):
     run = lambda c: lib.drba_conv3x3_shuffle(_p(x), _p(layer._pack(c)), _p(layer.bias), _p(out), n, cin, h, w, layer.cout,  # noqa: E731
                                              layer.act, layer.post_slope, c, _stream())
     try:
-        cfg = _tune(("conv3x3_shuffle", n, cin, layer.cout, h, w), cands, run, families=(4,), persist=True, device=x.device.index)
+        cfg = _tune(("conv3x3_shuffle", n, cin, layer.cout, h, w), cands, run, families=(4,), persist=True, device=x.device.index,
+                    pick=lambda: layer._pick_cfg(h, w))
     except NoKernelConfig:  # remembered per shape (in the process and in the store): the next call comes here without a launch
         _prune(layer._packed, layer._keep)
         return pixel_shuffle2(layer(x))
@@ -1101,7 +1147,7 @@ class ConvChain:
         """out (optional): a contiguous float32 destination of the chain's output shape (a batch slice of a larger tensor)."""
         x = _f32(x)
         n, _, h, w = x.shape
-        key = (n, h, w)
+        key = (n, h, w, "det") if deterministic() else (n, h, w)  # a plan holds configurations: one per mode
         plan = self._plans.get(key)
         if plan is None and key in self._plans:  # known: not chainable
             return self._eager(x, out)

@@ -183,6 +183,9 @@ def rehearse(model, frame_hw, src_fps=24.0, dst_fps=60.0, times=-1, enable_scdet
         return x
 
     ops.TUNE_IGNORE_HITS = bool(retune) or ignore0
+    det0 = ops.deterministic()  # a rehearsal IS the timing: it runs with the deterministic mode off and puts it back
+    if det0:
+        ops.set_deterministic(False)
     try:
         with torch.cuda.device(device):
             drv.interpolate_stream(rec, io, dst_fps, times=times, enable_scdet=enable_scdet, scdet_threshold=scdet_threshold,
@@ -191,6 +194,8 @@ def rehearse(model, frame_hw, src_fps=24.0, dst_fps=60.0, times=-1, enable_scdet
             torch.cuda.synchronize(device)
     finally:
         ops.TUNE_IGNORE_HITS = ignore0
+        if det0:
+            ops.set_deterministic(True)
         stats1 = dict(model.stats) if stats0 is not None else {}
         _model_state_reset(model, stats0)
     segments = [rec.calls[a:b] for a, b in zip([0] + marks, marks)]

@@ -32,7 +32,10 @@ extern "C" {
 #define DRBA_EUNSUPPORTED (-2) /* shape/config outside what the kernels were built for */
 #define DRBA_ELAUNCH (-3)  /* hipGetLastError() reported a launch failure */
 
-/* ABI version.  14: planar YCbCr 4:2:0 frames -- drba_to_inp_yuv420_x4 / drba_to_inp16_yuv420_x4 / drba_to_out_yuv420 /
+/* ABI version.  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
+ * the splat entry points: drba_flow_reverse, drba_drm_rife_linear(_batch), drba_drm_rife_nonlinear(_batch), drba_softsplat and
+ * drba_softsplat_index; while it is on, drba_rife_splat_ws_floats reports the larger workspace of the fixed-point accumulator):
+ * additions only, nothing changes while the switch is off.  14: planar YCbCr 4:2:0 frames -- drba_to_inp_yuv420_x4 / drba_to_inp16_yuv420_x4 / drba_to_out_yuv420 /
  * drba_to_out16_yuv420 (three planes with row strides, bt709 / bt601, limited / full range; colour conversion and chroma
  * resampling inside the conversion kernels): additions only, no earlier entry changes.  13: the fused non-linear DRM of the RIFE path -- drba_drm_walk (host function: get_drm_t's scalar walk as a move
  * mask), drba_drm_rife_nonlinear and drba_drm_rife_nonlinear_batch with drba_drm_nonlinear_job_t: additions only, no earlier entry
@@ -56,7 +59,7 @@ extern "C" {
  * workspace that must be ZERO on entry (they leave it zero on return: self-cleaning accumulator) instead of clearing it
  * themselves; batched stage entry points added; drba_conv3x3_cfg_family added and configuration ids 19 (LDS-DMA, 32
  * channels) / 20 (K split across waves) behind drba_conv3x3; the allocation exception above.  1: the first release. */
-#define DRBA_ABI_VERSION 14  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
+#define DRBA_ABI_VERSION 15  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
 int drba_abi_version(void);
 const char *drba_error_string(int code);
 /* ABI 6, debug: with the range check on, every entry point that ran a kernel of family 4 (two fp16 terms per operand:
@@ -67,6 +70,23 @@ const char *drba_error_string(int code);
  * where families 0 - 3 keep fp32's range; a non-finite INPUT reads the same.  Returns the previous setting.  The Python
  * layer switches it on when DRBA_CHECK_RANGE=1 is set (drba_amd/_lib.py). */
 int drba_set_range_check(int on);
+/* ABI 15: the deterministic mode.  Off (the default) nothing changes.  On, the bits of every output of the library depend on the
+ * bits of the inputs, the geometry and the scalar arguments only -- not on timing, the stream, other work on the device, the other
+ * items of a batch or what the workspace held before.  The entry points whose sums followed wave-arrival order read the switch when
+ * they LAUNCH and run kernels of their own names (splat_tiled_det<MODE>, splat_long_prepass_det<MODE>, splat_sort_segments):
+ *   - drba_flow_reverse, drba_drm_rife_linear(_batch), drba_drm_rife_nonlinear(_batch): a key segment is summed in ascending order of
+ *     the global source pixel index y * W + x; a tile whose records do not all fit in LDS sends every one of its in-tile corners
+ *     through the global accumulator; that accumulator (long flows and those tiles) is 64-bit fixed point, added with integer
+ *     atomics.  Its workspace: drba_rife_splat_ws_floats is mode aware -- it returns what it always returned while the switch is
+ *     off and the room of the wider accumulator while it is on; `ws` must then be 8-byte aligned; same contract (zero on entry,
+ *     zero on return, the reach map in its fixed place in front), so ONE zeroed buffer of the larger size serves calls of both
+ *     modes in any order.  More than 2^32 - 1 pixels per map: DRBA_EUNSUPPORTED;
+ *   - drba_softsplat / drba_softsplat_index: one more kernel sorts each key's segment of the index by source pixel, and every gather
+ *     through that index (drba_softsplat_again, drba_softsplat_gather_quad included) sums in that order.
+ * Every other entry point is deterministic as it is.  drba_set_deterministic returns the previous setting.  Not covered: equality
+ * across builds, device models or -- for the Python layer's tuned convolutions -- different kernel configurations. */
+int drba_set_deterministic(int on);
+int drba_get_deterministic(void);
 /* ABI 8, always on once requested, no synchronisation: every kernel of family 4 (the list above) tests the values it STORES and,
  * when one is inf / NaN, writes 1 into its byte of the current device's status word -- 8 bytes of host-mapped memory, one byte
  * per kernel group (DRBA_STATUS_*), sticky until drba_status_clear().  The family's operands overflow fp16 where families 0 - 3
