@@ -95,6 +95,8 @@ SIGNATURES = {
     "drba_ssim3d_32": (_i, [_p, _p, _p, _p]),
     "drba_ssim3d_ws_floats": (_z, [_i, _i, _i]),
     "drba_ssim3d": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _d, _p]),
+    "drba_ssim2d_ws_floats": (_z, [_i, _i, _i]),
+    "drba_ssim2d": (_i, [_p, _p, _p, _p, _i, _i, _i, _z, _z, _i, _d, _p]),
     "drba_frame_error_ws_floats": (_z, [_i, _z]),
     "drba_frame_error_u8": (_i, [_p, _p, _p, _p, _i, _z, _p]),
     "drba_frame_error_f32": (_i, [_p, _p, _p, _p, _i, _z, _p]),

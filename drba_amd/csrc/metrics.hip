@@ -9,6 +9,9 @@
 // (x pass into LDS, y pass + channel mix into registers).  Tile sums go to the workspace, a second kernel adds them in a fixed
 // order: no floating-point atomics, the same bits on every run and for an item alone or in a batch.
 //
+// drba_ssim2d: the single-channel 2-D ssim of the same file (pytorch_msssim/__init__.py:29-80) on N planes addressed by a row and an
+// item stride (the luma planes of packed 4:2:0 frames): the tile kernel above without the channel axis, one plane per workgroup.
+//
 // drba_frame_error_u8 / _u16 / _f32: sum d^2, sum |d|, max |d| and a count per item, integers for bytes and 16-bit samples and
 // fp64 for floats, through the same two-stage reduction.
 #include "common.hpp"
@@ -197,6 +200,98 @@ __global__ void __launch_bounds__(256) sum_partials_kernel(const double *__restr
   for (int i = threadIdx.x; i < n_parts; i += 256) s += p[i];
   const double tot = block_sum256(s, red);
   if (threadIdx.x == 0) out[blockIdx.x] = tot / count;
+}
+
+// ---- one plane: the 2-D ssim ------------------------------------------------------------------------------------------------
+struct Ssim2dArgs {
+  double g[11];   // the same window as SsimArgs::g
+  double L;       // the value range: the caller's for fp32 samples, 1 for integer ones
+  float maxval;   // what integer samples are divided by
+};
+
+// DT: 0 = fp32, 1 = uint8, 2 = uint16 samples; integer ones as (float)s / (float)maxval, a true fp32 division
+template <int DT>
+__device__ __forceinline__ float load_sample(const void *plane, size_t at, float maxval) {
+  if (DT == 1) return (float)static_cast<const uint8_t *>(plane)[at] / maxval;
+  if (DT == 2) return (float)static_cast<const uint16_t *>(plane)[at] / maxval;
+  return static_cast<const float *>(plane)[at];
+}
+
+// blur_field on one plane: no channel mix
+template <int F>
+__device__ __forceinline__ void blur_plane(const float (*sa)[kHX], const float (*sb)[kHX], double (*tmp)[kTX], const Ssim2dArgs &A,
+                                           double (&out)[2]) {
+  const int tid = threadIdx.x;
+  __syncthreads();  // tmp is free again
+  for (int e = tid; e < kHY * kTX; e += 256) {  // along x
+    const int x = e & (kTX - 1), r = e / kTX;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) s = fma(A.g[k], field<F>(sa[r][x + k], sb[r][x + k]), s);
+    tmp[r][x] = s;
+  }
+  __syncthreads();
+  const int x = tid & (kTX - 1), y0 = tid >> 5;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {  // along y
+    const int y = y0 + 8 * j;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) s = fma(A.g[k], tmp[y + k][x], s);
+    out[j] = s;
+  }
+}
+
+// ssim3d_tile_kernel for single planes: the same 32 x 16 tile, halo, passes and sums, a third of its LDS (two fp32 halo tiles of
+// 26 x 42 and one fp64 row buffer of 26 x 32: 15.4 KB against 46 KB).
+// Occupancy: 8 workgroups (32 waves) per CU, the most the CU's wave slots hold -- the launch bound asks for 8 waves per SIMD, i.e.
+// at most 64 VGPRs, and the kernel needs fewer (ten fp64 results and a window held in SGPRs).  LDS would admit 10 workgroups of
+// 15.4 KB in 160 KB, so the wave slots bind, not LDS.  The kernel alternates LDS-bound passes with barriers between them (ten per
+// tile): with few resident workgroups (the three-channel kernel's 46 KB and 144 VGPRs allow three) a CU idles at every barrier;
+// eight give the scheduler other tiles' passes to run meanwhile.  Measured: 62 VGPRs, no scratch, 41 us per 1080 x 1920 plane
+// against 147 us for the three-channel kernel on the BGR frame (profiles/metrics_yuv.md).
+template <int DT>
+__global__ void __launch_bounds__(256, 8) ssim2d_tile_kernel(const void *__restrict__ p1, const void *__restrict__ p2,
+                                                             double *__restrict__ partial, int H, int W, size_t row_stride,
+                                                             size_t item_stride, int tiles_x, Ssim2dArgs A) {
+  __shared__ float sa[kHY][kHX], sb[kHY][kHX];
+  __shared__ double tmp[kHY][kTX];
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  const size_t base = (size_t)blockIdx.y * item_stride;
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int x0 = tx * kTX - 5, y0 = ty * kTY - 5;
+  for (int e = tid; e < kHY * kHX; e += 256) {  // replicate padding = clamped reads: no read leaves [0, H) x [0, W)
+    const int i = e % kHX, r = e / kHX;
+    const int gx = min(max(x0 + i, 0), W - 1), gy = min(max(y0 + r, 0), H - 1);
+    const size_t at = base + (size_t)gy * row_stride + (size_t)gx;
+    sa[r][i] = load_sample<DT>(p1, at, A.maxval);
+    sb[r][i] = load_sample<DT>(p2, at, A.maxval);
+  }
+  const double C1 = (0.01 * A.L) * (0.01 * A.L), C2 = (0.03 * A.L) * (0.03 * A.L);
+
+  double mu1[2], mu2[2], e11[2], e22[2], e12[2];
+  blur_plane<0>(sa, sb, tmp, A, mu1);  // (its first barrier also publishes sa / sb)
+  blur_plane<1>(sa, sb, tmp, A, mu2);
+  blur_plane<2>(sa, sb, tmp, A, e11);
+  blur_plane<3>(sa, sb, tmp, A, e22);
+  blur_plane<4>(sa, sb, tmp, A, e12);
+
+  const int px = tx * kTX + (tid & (kTX - 1));
+  double part = 0.0;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int py = ty * kTY + (tid >> 5) + 8 * j;
+    if (px < W && py < H) {
+      const double m1 = mu1[j], m2 = mu2[j];
+      const double m1sq = m1 * m1, m2sq = m2 * m2, m12 = m1 * m2;
+      const double s1 = e11[j] - m1sq, s2 = e22[j] - m2sq, s12 = e12[j] - m12;
+      const double v1 = 2.0 * s12 + C2, v2 = (s1 + s2) + C2;
+      part += ((2.0 * m12 + C1) * v1) / (((m1sq + m2sq) + C1) * v2);
+    }
+  }
+  const double tot = block_sum256(part, red);
+  if (tid == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = tot;
 }
 
 // ---- frame differences ---------------------------------------------------------------------------------------------------
@@ -408,6 +503,16 @@ int err_parts(size_t n_per_item, size_t per_thread_bytes_or_elems) {
   return (int)p;
 }
 
+// gaussian(11, 1.5): double exp -> fp32, normalised in fp32 (as scdet.hip), widened
+void gaussian11(double (&out)[11]) {
+  float g[11], sum = 0.f;
+  for (int k = 0; k < 11; ++k) {
+    g[k] = (float)exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
+    sum += g[k];
+  }
+  for (int k = 0; k < 11; ++k) out[k] = (double)(g[k] / sum);
+}
+
 }  // namespace
 
 // ---- entry points -------------------------------------------------------------------------------------------------------------
@@ -430,12 +535,7 @@ extern "C" int drba_ssim3d(const void *img1, const void *img2, double *out, floa
   const int tiles = tiles_x * tiles_y;
 
   SsimArgs A;
-  float g[11], sum = 0.f;
-  for (int k = 0; k < 11; ++k) {  // gaussian(11, 1.5): double exp -> fp32, normalised in fp32 (as scdet.hip)
-    g[k] = (float)exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
-    sum += g[k];
-  }
-  for (int k = 0; k < 11; ++k) A.g[k] = (double)(g[k] / sum);
+  gaussian11(A.g);
   for (int c = 0; c < 3; ++c) {
     for (int s = 0; s < 3; ++s) A.mix[c][s] = 0.0;
     for (int k = 0; k < 11; ++k) {
@@ -459,6 +559,54 @@ extern "C" int drba_ssim3d(const void *img1, const void *img2, double *out, floa
     DRBA_LAUNCH(ssim3d_tile_kernel<true>, dim3(tiles, N), dim3(256), 0, s, img1, img2, partial, range_parts, H, W, tiles_x, A);
   DRBA_CHECK_LAUNCH();
   DRBA_LAUNCH(sum_partials_kernel, dim3(N), dim3(256), 0, s, partial, tiles, 3.0 * (double)H * (double)W, out);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+extern "C" size_t drba_ssim2d_ws_floats(int N, int H, int W) {
+  if (N < 1 || H < 1 || W < 1) return 0;
+  const size_t tiles = (size_t)((W + kTX - 1) / kTX) * (size_t)((H + kTY - 1) / kTY);
+  return (size_t)N * tiles * 2;  // tile sums, doubles
+}
+
+extern "C" int drba_ssim2d(const void *p1, const void *p2, double *out, float *ws, int N, int H, int W, size_t row_stride,
+                           size_t item_stride, int dtype, double maxval, void *stream) {
+  if (!p1 || !p2 || !out || !ws || N < 1 || H < 1 || W < 1) return DRBA_EINVAL;
+  if (dtype < 0 || dtype > 2) return DRBA_EINVAL;
+  if (row_stride < (size_t)W) return DRBA_EINVAL;
+  if (((uintptr_t)ws & 7u) || ((uintptr_t)out & 7u)) return DRBA_EINVAL;
+  Ssim2dArgs A;
+  if (dtype == 0) {
+    if (!(maxval > 0.0) || isinf(maxval)) return DRBA_EINVAL;
+    A.L = maxval;
+    A.maxval = 1.f;
+  } else if (dtype == 1) {
+    if (maxval != 0.0 && maxval != 255.0) return DRBA_EINVAL;
+    A.L = 1.0;
+    A.maxval = 255.f;
+  } else {
+    if ((((uintptr_t)p1 | (uintptr_t)p2) & 1u)) return DRBA_EINVAL;
+    if (!(maxval > 255.0 && maxval <= 65535.0) || maxval != floor(maxval)) return DRBA_EINVAL;
+    A.L = 1.0;
+    A.maxval = (float)maxval;
+  }
+  if (H < 11 || W < 11) return DRBA_EUNSUPPORTED;  // the reference shrinks the window there
+  if (N > 65535) return DRBA_EUNSUPPORTED;
+  const int tiles_x = (W + kTX - 1) / kTX, tiles_y = (H + kTY - 1) / kTY;
+  if ((size_t)tiles_x * tiles_y > 0x7fffffffu) return DRBA_EUNSUPPORTED;
+  const int tiles = tiles_x * tiles_y;
+  gaussian11(A.g);
+
+  double *partial = reinterpret_cast<double *>(ws);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == 0)
+    DRBA_LAUNCH(ssim2d_tile_kernel<0>, dim3(tiles, N), dim3(256), 0, s, p1, p2, partial, H, W, row_stride, item_stride, tiles_x, A);
+  else if (dtype == 1)
+    DRBA_LAUNCH(ssim2d_tile_kernel<1>, dim3(tiles, N), dim3(256), 0, s, p1, p2, partial, H, W, row_stride, item_stride, tiles_x, A);
+  else
+    DRBA_LAUNCH(ssim2d_tile_kernel<2>, dim3(tiles, N), dim3(256), 0, s, p1, p2, partial, H, W, row_stride, item_stride, tiles_x, A);
+  DRBA_CHECK_LAUNCH();
+  DRBA_LAUNCH(sum_partials_kernel, dim3(N), dim3(256), 0, s, partial, tiles, (double)H * (double)W, out);
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }

@@ -1,10 +1,11 @@
 """Picture quality of finished clips, as commands.
 
     python -m drba_amd.evaluate compare A B [--json PATH] [--max-lsb N] [--min-psnr X] [--min-ssim X]
-    python -m drba_amd.evaluate holdout -m rife -i CLIP [-k 3] [-scale 1.0] [-s] [-st 0.3] [--plain] [--weights DIR] [--json PATH]
+    python -m drba_amd.evaluate holdout -m rife -i CLIP [-k 3] [-scale 1.0] [-s] [-st 0.3] [--plain] [--nonlinear] [--deterministic]
+                                        [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--weights DIR] [--json PATH]
 
-`compare` reads two clips frame by frame (the sources infer.py reads: .npz, .npy + .json, a container when OpenCV is
-installed) and prints one JSON line: PSNR, ssim_matlab, the largest difference in LSB and the number of differing bytes, per
+`compare` reads two clips frame by frame (the sources infer.py reads: .npz, .npy + .json, a .y4m stream -- below --, a container
+when OpenCV is installed) and prints one JSON line: PSNR, ssim_matlab, the largest difference in LSB and the number of differing bytes, per
 clip; `--json` adds the per-frame lists.  A gate that is given and violated makes the exit status 1, so "the outputs of two
 builds agree within 1 LSB" is `compare a.npz b.npz --max-lsb 1`.
 
@@ -16,6 +17,22 @@ plain inference_ts on the pair the timestep lies in -- the baseline DRBA's "pres
 16-bit clips (uint16 frames; `maxval` from the .npz entry or the .json sidecar, 65535 when absent) are measured in their own
 steps: the reports carry "depth": 16 and "maxval", the PSNR peak is maxval, `--max-lsb` counts 16-bit steps, and `holdout` emits
 at 16 bits.  Two clips of different depth or maxval are refused.
+
+YUV4MPEG2 clips (a `.y4m` path; `-` is a stream on stdin, for `compare` only: it cannot seek) are measured on the planes as they
+stand in the stream, one frame in memory at a time, nothing converted: `compare a.y4m b.y4m` reports per frame and per clip the
+PSNR of Y, of U and of V, `psnr` -- the squared error pooled over all samples of the three planes, the 4:1:1 weighting 4:2:0 has
+by construction --, the single-channel 2-D SSIM of luma (drba_ssim2d: `ssim_matlab`'s window runs across three colour channels and
+has no meaning on one plane), the largest difference in the clips' own steps and the differing samples; the peak is 255, or 1023
+for C420p10.  `--max-lsb` gates max_lsb, `--min-psnr` the lowest per-frame pooled `psnr`, `--min-ssim` the lowest `ssim_y`; the
+report carries "pixfmt": "yuv420", "depth" (8, or 16 for 10-bit samples, as tools.VideoFI_IO names them), "maxval", "chroma" (the C
+tags of both sides: two 4:2:0 sitings may be compared, the samples are taken as they are) and "color_range".  Refused, both sides
+named: different sizes, depths or XCOLORRANGE (no tag = limited), and a Y4M clip against an array clip.  `compare a.y4m b.y4m
+--max-lsb 0` is the reproducibility gate of `infer.py --deterministic` on Y4M outputs.
+`holdout -i clip.y4m` reads the kept frames through a random-access index of the file (one scan of the FRAME lines), converts
+them on the device (`--yuv-matrix`, `--yuv-range` as in infer.py), emits packed Y, U, V planes at the clip's depth that stay on
+the device, and compares each with the original's planes, uploaded when its turn comes: memory does not grow with the clip.
+Kept frames pass through to_out(to_inp(frame)), which filters their chroma ("Pass-through frames"): their PSNR is
+finite, and the report says so in "kept_passthrough".
 
 Non-finite JSON numbers are written as the strings "inf" / "-inf" / "nan" (float() reads them back).
 """
@@ -33,16 +50,23 @@ from drba_amd import metrics
 # ----------------------------------------------------------------------------------------------------------------- sources
 class ClipSource:
     """The frames of a clip, opened the way tools.VideoFI_IO opens its input: .npz {frames, fps}, .npy (+ .json {"fps"}), anything
-    else through cv2.VideoCapture when OpenCV is installed.  len() is None for a container (known when it has been read)."""
+    else through cv2.VideoCapture when OpenCV is installed.  len() is None for a container (known when it has been read).
+    A .y4m path, or `-` for stdin, is a YUV4MPEG2 clip (_open_y4m): .pixfmt is "yuv420" ("bgr" otherwise) and the frames are
+    y4m.YuvFrames."""
 
     def __init__(self, path):
-        self.path, self._frames, self._cap = path, None, None
-        self.depth, self.maxval = 8, 255
+        self.path, self._frames, self._cap, self._y4m = path, None, None, None
+        self.depth, self.maxval, self.pixfmt = 8, 255, "bgr"
+        if path == "-":  # a YUV4MPEG2 stream on stdin: sequential only
+            self._open_y4m(sys.stdin.buffer, seekable=False)
+            return
         if not os.path.exists(path):
             raise FileNotFoundError(f"can't find the clip {path}")
         ext = os.path.splitext(path)[1].lower()
         maxval = None
-        if ext == ".npz":
+        if ext == ".y4m":
+            self._open_y4m(open(path, "rb"), seekable=True)
+        elif ext == ".npz":
             z = np.load(path)
             self._frames, self.fps = z["frames"], (float(z["fps"]) if "fps" in z.files else 24.0)
             maxval = int(z["maxval"]) if "maxval" in z.files else None
@@ -67,16 +91,44 @@ class ClipSource:
                 raise ValueError(f"{path}: maxval of a 16-bit clip must satisfy 255 < maxval <= 65535, got {maxval}")
             self.depth, self.maxval = 16, (65535 if maxval is None else maxval)
 
+    def _open_y4m(self, f, seekable):
+        """A YUV4MPEG2 clip: frames are y4m.YuvFrames (planar 4:2:0, never converted here).  A seekable file is indexed in one scan of
+        its FRAME lines (y4m.IndexedReader: len() and frame(k)); a pipe is read in order.  Either way one frame is in memory at a
+        time.  depth / maxval as tools.VideoFI_IO names them: 8 / 255, or 16 / 1023 for C420p10."""
+        from drba_amd import y4m
+        self.pixfmt = "yuv420"
+        self._y4m = y4m.IndexedReader(f) if seekable and f.seekable() else y4m.Reader(f)
+        self._indexed = isinstance(self._y4m, y4m.IndexedReader)
+        hdr = self.header = self._y4m.header
+        self.fps = float(hdr.fps)
+        self.size = (hdr.height, hdr.width)
+        self.chroma, self.color_range = hdr.chroma, hdr.color_range
+        if hdr.depth > 8:
+            self.depth, self.maxval = 16, hdr.maxval
+
     def __len__(self):
+        if self._y4m is not None and self._indexed:
+            return len(self._y4m)
         if self._frames is None:
-            raise TypeError("the length of a container is known once it has been read")
+            raise TypeError("the length of a container or of a stream is known once it has been read")
         return len(self._frames)
 
     @property
     def random_access(self):
-        return self._frames is not None
+        return self._frames is not None or (self._y4m is not None and self._indexed)
+
+    def frame(self, k):
+        """frame k of a clip with random access: a contiguous array, or a y4m.YuvFrame read when it is asked for"""
+        if self._y4m is not None and self._indexed:
+            return self._y4m.read_frame(k)
+        if self._frames is None:
+            raise TypeError("this clip has no random access")
+        return np.ascontiguousarray(self._frames[k])
 
     def __iter__(self):
+        if self._y4m is not None:
+            yield from self._y4m
+            return
         if self._frames is not None:
             for k in range(len(self._frames)):
                 yield np.ascontiguousarray(self._frames[k])
@@ -103,7 +155,10 @@ def _jsonable(v):
 def compare(a, b, backend=None):
     """The metrics of clip `b` against clip `a` (two ClipSources, or anything that iterates uint8 [H,W,3] frames).
     ValueError when the frame counts or the frame sizes differ (both values are named).  Two uint16 clips (ClipSource.depth 16)
-    are compared in their own steps, the peak being their maxval; clips of different depth or maxval are refused, both named."""
+    are compared in their own steps, the peak being their maxval; clips of different depth or maxval are refused, both named.
+    Two YUV4MPEG2 clips go to compare_yuv; one against an array clip is refused."""
+    if "yuv420" in (getattr(a, "pixfmt", None), getattr(b, "pixfmt", None)):
+        return compare_yuv(a, b, backend=backend)
     da, db = getattr(a, "depth", None), getattr(b, "depth", None)
     if da is not None and db is not None and (da, getattr(a, "maxval", None)) != (db, getattr(b, "maxval", None)):
         raise ValueError(f"the clips differ in depth: {da}-bit frames with maxval {getattr(a, 'maxval', None)} against {db}-bit "
@@ -134,6 +189,53 @@ def compare(a, b, backend=None):
     return res
 
 
+def _side(clip):
+    """how a refusal names one side: the path and what it holds"""
+    name = getattr(clip, "path", None) or type(clip).__name__
+    if getattr(clip, "pixfmt", None) == "yuv420":
+        h, w = clip.size
+        bits = 10 if clip.depth == 16 else 8
+        return f"{name} (planar 4:2:0, {w}x{h}, {bits}-bit, XCOLORRANGE={clip.color_range or 'none'})"
+    return f"{name} (packed BGR frames)"
+
+
+def compare_yuv(a, b, backend=None):
+    """compare for two YUV4MPEG2 clips (ClipSources of .y4m paths or stdin), plane by plane on the samples as they stand in the
+    streams -- nothing is converted --: metrics.YuvClipMetrics' figures (PSNR of Y, U, V and of the three planes pooled, the 2-D
+    SSIM of luma, the largest difference in the clips' own steps, differing samples) plus "pixfmt", "depth", "maxval", "chroma" (the
+    C tags of the two sides; different 4:2:0 sitings are allowed, the samples are compared as they are) and "color_range".
+    ValueError naming both sides: a Y4M clip against an array clip, different frame sizes, depths or XCOLORRANGE (a stream
+    without the tag is limited range, as infer.py reads it), different lengths."""
+    ya, yb = getattr(a, "pixfmt", None) == "yuv420", getattr(b, "pixfmt", None) == "yuv420"
+    if not (ya and yb):
+        raise ValueError(f"one clip is YUV4MPEG2 and the other is not: {_side(a)} against {_side(b)}; convert one of them first")
+    if tuple(a.size) != tuple(b.size):
+        raise ValueError(f"the clips differ in frame size: {_side(a)} against {_side(b)}")
+    if (a.depth, a.maxval) != (b.depth, b.maxval):
+        raise ValueError(f"the clips differ in depth: {_side(a)} against {_side(b)}; convert one of them first")
+    if (a.color_range or "LIMITED") != (b.color_range or "LIMITED"):
+        raise ValueError(f"the clips differ in sample range: {_side(a)} against {_side(b)}; convert one of them first")
+    if a.random_access and b.random_access and len(a) != len(b):
+        raise ValueError(f"the clips differ in length: {len(a)} frames of {a.path} against {len(b)} of {b.path}")
+    cm = metrics.YuvClipMetrics(backend=backend, maxval=a.maxval)
+    ia, ib = iter(a), iter(b)
+    na = nb = 0
+    while True:
+        fa, fb = next(ia, None), next(ib, None)
+        na, nb = na + (fa is not None), nb + (fb is not None)
+        if fa is None or fb is None:
+            if fa is not None or fb is not None:  # a stream ended early: count the rest of the longer one
+                na += sum(1 for _ in ia)
+                nb += sum(1 for _ in ib)
+                raise ValueError(f"the clips differ in length: {na} frames of {a.path} against {nb} of {b.path}")
+            break
+        cm.add(fa, fb)
+    res = cm.result()
+    res.update({"size": [int(a.size[0]), int(a.size[1])], "pixfmt": "yuv420", "depth": a.depth, "maxval": int(a.maxval),
+                "chroma": [a.chroma, b.chroma], "color_range": a.color_range or b.color_range})
+    return res
+
+
 GATES = (("max_lsb", "max_lsb", lambda v, lim: v <= lim), ("min_psnr", "min_psnr", lambda v, lim: v >= lim),
          ("min_ssim", "min_ssim", lambda v, lim: v >= lim))
 
@@ -161,6 +263,8 @@ def compare_report(res, limits, a_name=None, b_name=None):
     rep.update(summary)
     if "depth" in res:  # 16-bit clips: max_lsb (and its gate) and total_differing are in the clips' own steps and samples
         rep.update({"depth": res["depth"], "maxval": res["maxval"]})
+    if res.get("pixfmt") == "yuv420":  # YUV4MPEG2 clips: the summary above already carries the per-plane figures
+        rep.update({"pixfmt": "yuv420", "chroma": res["chroma"], "color_range": res["color_range"]})
     rep.update({"gates": gates, "ok": ok})
     return rep, ok
 
@@ -185,6 +289,9 @@ class PlainSteps:
         return out, None
 
 
+KEPT_PASSTHROUGH = "to_out(to_inp(frame))"  # what a kept frame of a YUV4MPEG2 hold-out is: converted in and out, chroma filtered
+
+
 def holdout_plan(n_frames, k):
     """-> (m, half): the first m k + 1 frames are used, frames 0, k, .., m k are kept; emission j of the run stands at original
     frame j - half.  ValueError with the reason when k or the clip does not allow the procedure."""
@@ -197,6 +304,11 @@ def holdout_plan(n_frames, k):
     if m < 2:
         raise ValueError(f"a hold-out at -k {k} needs at least {2 * k + 1} frames (three kept ones), the clip has {n_frames}")
     return m, (k - 1) // 2
+
+
+def _frame_at(frames, p):
+    """frame p of an indexable array of frames, or of a ClipSource with random access (a YUV4MPEG2 clip: read now, not kept)"""
+    return frames.frame(p) if hasattr(frames, "frame") else np.ascontiguousarray(frames[p])
 
 
 class _HoldoutIO:
@@ -214,7 +326,7 @@ class _HoldoutIO:
         if self.i > self.m:
             return None
         self.i += 1
-        return np.ascontiguousarray(self.frames[(self.i - 1) * self.k])
+        return _frame_at(self.frames, (self.i - 1) * self.k)
 
     def write_frame(self, x):
         j, p = self.j, self.j - self.half
@@ -222,12 +334,12 @@ class _HoldoutIO:
         if p < 0 or p > self.m * self.k:
             self.skipped.append(j)  # the copies the run emits before the first and after the last frame: no original there
             return
-        (self.kept if p % self.k == 0 else self.held).add(x, np.ascontiguousarray(self.frames[p]))
+        (self.kept if p % self.k == 0 else self.held).add(x, _frame_at(self.frames, p))
         self.pairs.append((j, p))
 
 
 def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.3, plain=False, backend=None, to_inp=None,
-            to_out=None, check_scene=None, maxval=None, linear=True):
+            to_out=None, check_scene=None, maxval=None, linear=True, yuv_matrix="bt709", yuv_range="source"):
     """Keep every k-th frame of `frames` (uint8 [N,H,W,3], indexable), let interpolate_stream fill the gaps at `times = k`
     and compare every emission with the original frame at its position.  -> {"k", "m", "frames_used", "emissions",
     "pairs": [(emission, original)], "kept": ClipMetrics.result() + "positions", "held_out": the same}.
@@ -236,27 +348,49 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
     uint16 frames (samples in [0, maxval], 65535 unless given): the default hooks read and emit 16 bits at that maxval and the
     emissions are compared with the 16-bit originals in their own steps; the result carries "depth": 16 and "maxval".
     linear=False: every DRBA step of the run with the non-linear DistanceRatioMap (infer.py --nonlinear); not together with
-    `plain`, whose steps have no DistanceRatioMap at all.  The result carries "linear"."""
+    `plain`, whose steps have no DistanceRatioMap at all.  The result carries "linear".
+    A YUV4MPEG2 clip (`frames` a ClipSource of a seekable .y4m file): the kept frames are read through its random-access reader and
+    given to the model as y4m.YuvFrames (tools.to_inp converts on the device, `yuv_matrix` / `yuv_range` as in infer.py); every
+    emission leaves as packed Y, U, V planes (ops.to_out_yuv, on the device) and is compared plane by plane
+    (metrics.YuvClipMetrics) with the original's planes, read and uploaded when its turn comes -- nothing is stored, memory does
+    not grow with the clip.  The kept frames pass through to_out(to_inp(frame)): their chroma is interpolated up and averaged
+    down again ("Pass-through frames"), so unlike those of an array clip they do not come back identical and
+    their PSNR is finite; the result says so in "kept_passthrough", beside "pixfmt", "depth" and "maxval"."""
     from drba_amd import infer as drv
     if plain and not linear:
         raise ValueError("--nonlinear and --plain exclude each other: a plain step is inference_ts, it has no DistanceRatioMap to retime")
     m, half = holdout_plan(len(frames), k)
-    deep = getattr(frames, "dtype", None) == np.uint16
+    yuv = getattr(frames, "pixfmt", None) == "yuv420"
+    deep = not yuv and getattr(frames, "dtype", None) == np.uint16
     if maxval is not None and not deep:
         raise ValueError("maxval belongs to uint16 frames")
     mv = (65535 if maxval is None else int(maxval)) if deep else None
     device_out = to_out is None
+    if yuv:
+        if yuv_range not in ("source", "limited", "full"):
+            raise ValueError(f"yuv_range must be source, limited or full, got {yuv_range!r}")
+        full = frames.color_range == "FULL" if yuv_range == "source" else yuv_range == "full"  # (no tag: limited, as infer.py reads it)
+        mv = int(frames.maxval)
     if device_out:
         from drba_amd import ops
-        if deep:
+        if yuv:  # packed planes on the device at the clip's own depth: compared there
+            to_out = lambda x, size: ops.to_out_yuv(x, size, matrix=yuv_matrix, full_range=full, depth=frames.depth,  # noqa: E731
+                                                    maxval=mv if frames.depth == 16 else None)
+        elif deep:
             to_out = lambda x, size: ops.to_out(x, size, depth=16, maxval=mv)  # noqa: E731  (uint16 on the device: compared there)
         else:
             to_out = lambda x, size: ops.to_out(x, size)  # noqa: E731  (uint8 on the device: compared there)
     if to_inp is None and deep:
         from drba_amd.models.utils import tools
         to_inp = lambda fr, size: tools.to_inp(fr, size, maxval=mv)  # noqa: E731
+    if to_inp is None and yuv:
+        from drba_amd.models.utils import tools
+        to_inp = lambda fr, size: tools.to_inp(fr, size, matrix=yuv_matrix, full_range=full)  # noqa: E731
     backend = backend or metrics.default_backend()
-    kept, held = metrics.ClipMetrics(backend=backend, maxval=mv), metrics.ClipMetrics(backend=backend, maxval=mv)
+    if yuv:
+        kept, held = metrics.YuvClipMetrics(backend=backend, maxval=mv), metrics.YuvClipMetrics(backend=backend, maxval=mv)
+    else:
+        kept, held = metrics.ClipMetrics(backend=backend, maxval=mv), metrics.ClipMetrics(backend=backend, maxval=mv)
     io = _HoldoutIO(frames, int(k), m, half, fps, kept, held)
     run = PlainSteps(model) if plain else model
     written = drv.interpolate_stream(run, io, float(fps) * int(k), times=int(k), enable_scdet=enable_scdet,
@@ -269,6 +403,9 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
            "pairs": io.pairs}
     if deep:
         out.update({"depth": 16, "maxval": mv})
+    if yuv:
+        out.update({"pixfmt": "yuv420", "depth": frames.depth, "maxval": mv, "chroma": frames.chroma, "yuv_matrix": yuv_matrix,
+                    "full_range": bool(full), "kept_passthrough": KEPT_PASSTHROUGH})
     for name, cm in (("kept", kept), ("held_out", held)):
         res = cm.result()  # (has waited for every kernel behind the frames)
         res["positions"] = [p for _, p in io.pairs if (p % int(k) == 0) == (name == "kept")]
@@ -284,6 +421,8 @@ def holdout_report(res):
            "plain": res["plain"], "linear": res["linear"]}
     if "depth" in res:
         rep.update({"depth": res["depth"], "maxval": res["maxval"]})
+    if res.get("pixfmt") == "yuv420":
+        rep.update({k: res[k] for k in ("pixfmt", "chroma", "yuv_matrix", "full_range", "kept_passthrough")})
     for name in ("kept", "held_out"):
         r = res[name]
         s = dict(r["summary"])
@@ -313,6 +452,10 @@ def parse_args(argv=None):
     h.add_argument("--plain", action="store_true", help="plain inference_ts in place of every DRBA step (the baseline)")
     h.add_argument("--nonlinear", action="store_true", help="every DRBA step with the non-linear DistanceRatioMap (linear=False); not with --plain")
     h.add_argument("--deterministic", action="store_true", help="bit-reproducible run (infer.py --deterministic): the same clip and command give the same figures")
+    h.add_argument("--yuv-matrix", dest="yuv_matrix", type=str, default="bt709", choices=("bt709", "bt601"),
+                   help="YCbCr matrix of a .y4m clip (default bt709), as in infer.py")
+    h.add_argument("--yuv-range", dest="yuv_range", type=str, default="source", choices=("source", "limited", "full"),
+                   help="sample range of a .y4m clip: the header's XCOLORRANGE (default; limited when it has none) or the one named, as in infer.py")
     h.add_argument("--weights", type=str, default=None, help="weight directory (default: the model's, synthetic if absent)")
     h.add_argument("--json", dest="json_path", type=str, default=None)
     return p.parse_args(argv)
@@ -338,7 +481,8 @@ def main(argv=None, backend=None):
             return 0 if ok else 1
         src = ClipSource(args.input)
         if not src.random_access:
-            raise ValueError("a hold-out needs random access to the clip: use a .npz / .npy source")
+            raise ValueError("a hold-out needs random access to the clip: use a .npz / .npy source"
+                             + (" or a seekable .y4m file" if src.pixfmt == "yuv420" else ""))
         holdout_plan(len(src), args.k)  # refuse before a model is loaded
         if args.plain and args.nonlinear:
             raise ValueError("--nonlinear and --plain exclude each other: a plain step is inference_ts, it has no DistanceRatioMap to retime")
@@ -350,9 +494,12 @@ def main(argv=None, backend=None):
         synthetic = args.weights is None and not (wdir and os.path.isdir(wdir))
         model = drv.load_model(args.model_type, scale=args.scale,
                                weights=tune._synthetic_weights(args.model_type) if synthetic else wdir)
-        res = holdout(model, src._frames, args.k, fps=src.fps, enable_scdet=args.enable_scdet,
-                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend, linear=not args.nonlinear,
-                      **({"maxval": src.maxval} if src.depth == 16 else {}))
+        if src.pixfmt == "yuv420":
+            kw = {"yuv_matrix": args.yuv_matrix, "yuv_range": args.yuv_range}
+        else:
+            kw = {"maxval": src.maxval} if src.depth == 16 else {}
+        res = holdout(model, src if src.pixfmt == "yuv420" else src._frames, args.k, fps=src.fps, enable_scdet=args.enable_scdet,
+                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend, linear=not args.nonlinear, **kw)
         rep = holdout_report(res)
         rep.update({"model": args.model_type, "scale": args.scale, "input": args.input,
                     "weights": "synthetic (drba_amd.utils.synth): the figures say nothing about quality" if synthetic else wdir})

@@ -22,13 +22,20 @@ A back end provides
     collect(slots_list, counts)     -> rows (sum_sq, sum_abs, max_abs, count, ssim) of Python numbers, one per frame;
                                        count = differing bytes (u8) / samples (u16) or non-finite differences (f32); the one
                                        synchronisation
+and, for planar 4:2:0 frames (YUV4MPEG2 clips; YuvClipMetrics, psnr_yuv, ssim_y), beside them and without touching them
+    prepare(x, size)                -> (1-D packed Y, U, V samples, "yuv8" | "yuv16", (1, H, W)); x a y4m.YuvFrame (size from it) or
+                                       a 1-D uint8 / uint16 array or tensor with size = (H, W): what ops.to_out_yuv returns
+    slots_yuv(capacity)             -> result slots: per frame three 4-word error rows (Y, U, V) and one SSIM double
+    measure_yuv(slots, k, a, b, kind, shape, maxval, want_ssim)   enqueue the plane errors (drba_frame_error_u8 / _u16, once per
+                                       plane at its offset inside the packed frame) and the 2-D SSIM of luma (drba_ssim2d)
+    collect_yuv(slots_list, counts) -> rows ((sum_sq, sum_abs, max_abs, differing) of Y, of U, of V, ssim_y); the one synchronisation
 """
 import ctypes as C
 import math
 
 import numpy as np
 
-from drba_amd import _lib
+from drba_amd import _lib, y4m
 
 
 class HipBackend:
@@ -39,8 +46,10 @@ class HipBackend:
         self.ops = ops
         self.device = ops.default_device() if device is None else device
 
-    def prepare(self, x):
+    def prepare(self, x, size=None):
         import torch
+        if size is not None or isinstance(x, y4m.YuvFrame):
+            return self._prepare_yuv(x, size)
         if isinstance(x, np.ndarray):
             x = torch.from_numpy(np.ascontiguousarray(x))
         if not torch.is_tensor(x):
@@ -112,6 +121,68 @@ class HipBackend:
                     e = err[i].view(np.float64)
                     rows.append((float(e[0]), float(e[1]), float(e[2]), int(err[i].view(np.uint64)[3]), float(ssim[i])))
         return rows
+
+    # ---- planar 4:2:0 frames: per-plane errors and the 2-D SSIM of luma (drba_ssim2d) -------------------------------------------
+    def _prepare_yuv(self, x, size):
+        import torch
+        if isinstance(x, y4m.YuvFrame):
+            x, size = torch.from_numpy(x.data if x.data.flags.writeable else x.data.copy()), x.shape[:2]
+        elif isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        if not (torch.is_tensor(x) and x.dim() == 1 and x.dtype in (torch.uint8, torch.uint16)) or size is None:
+            raise TypeError("a planar 4:2:0 frame is a y4m.YuvFrame, or a 1-D uint8 / uint16 array of packed Y, U, V planes with its (H, W)")
+        h, w = int(size[0]), int(size[1])
+        ny, nc = yuv420_samples((h, w))
+        if x.numel() != ny + 2 * nc:
+            raise ValueError(f"a {w}x{h} 4:2:0 frame is {ny + 2 * nc} samples, got {x.numel()}")
+        return x.to(self.device, non_blocking=True).contiguous(), "yuv8" if x.dtype == torch.uint8 else "yuv16", (1, h, w)
+
+    def slots_yuv(self, capacity):
+        import torch
+        # [capacity x 3 planes x 4 error words][capacity SSIM doubles], 8 bytes each: one tensor, one copy back
+        return torch.zeros(int(capacity) * YUV_WORDS, dtype=torch.int64, device=self.device)
+
+    def measure_yuv(self, slots, k, a, b, kind, shape, maxval, want_ssim=True):
+        lib, ops = _lib.load(), self.ops
+        _, h, w = shape
+        cap = slots.numel() // YUV_WORDS
+        if not 0 <= k < cap:
+            raise IndexError(f"slot {k} of {cap}")
+        ny, nc = yuv420_samples((h, w))
+        es = a.element_size()
+        fn = lib.drba_frame_error_u8 if kind == "yuv8" else lib.drba_frame_error_u16
+        ws = ops._workspace(self.device, max(lib.drba_frame_error_ws_floats(1, ny), lib.drba_ssim2d_ws_floats(1, h, w)))
+        for plane, (at, n) in enumerate(((0, ny), (ny, nc), (ny + nc, nc))):  # each plane at its offset inside the packed frame
+            err = C.c_void_p(slots.data_ptr() + 32 * (3 * k + plane))
+            _lib.check(fn(C.c_void_p(a.data_ptr() + at * es), C.c_void_p(b.data_ptr() + at * es), err, ops._p(ws), 1, n, ops._stream()),
+                       "drba_frame_error_" + ("u8" if kind == "yuv8" else "u16"))
+        if want_ssim:
+            out = C.c_void_p(slots.data_ptr() + 8 * (12 * cap + k))
+            _lib.check(lib.drba_ssim2d(ops._p(a), ops._p(b), out, ops._p(ws), 1, h, w, w, ny + 2 * nc, 1 if kind == "yuv8" else 2,
+                                       float(maxval), ops._stream()), "drba_ssim2d")
+
+    def collect_yuv(self, slots_list, counts):
+        import torch
+        if not slots_list:
+            return []
+        caps = [s.numel() // YUV_WORDS for s in slots_list]
+        parts = [torch.cat([s[:12 * n], s[12 * c:12 * c + n]]) for s, c, n in zip(slots_list, caps, counts)]
+        host = (torch.cat(parts) if len(parts) > 1 else parts[0]).cpu().numpy()  # the one synchronisation
+        rows, at = [], 0
+        for n in counts:
+            err, ssim = host[at:at + 12 * n].view(np.uint64).reshape(n, 3, 4), host[at + 12 * n:at + 13 * n].view(np.float64)
+            at += 13 * n
+            rows += [tuple(tuple(int(v) for v in err[i, p]) for p in range(3)) + (float(ssim[i]),) for i in range(n)]
+        return rows
+
+
+YUV_WORDS = 13  # result words of a planar frame: three 4-word error rows (Y, U, V) and one SSIM double
+
+
+def yuv420_samples(size):
+    """(H, W) -> (samples of Y, of U (= of V)) of a packed planar 4:2:0 frame"""
+    (h, w), (hc, wc) = y4m.plane_sizes(*size)
+    return h * w, hc * wc
 
 
 def default_backend():
@@ -244,3 +315,123 @@ class ClipMetrics:
         return summarise([r[0] / e for r, e in zip(rows, self._elems)], [r[4] for r in rows], lsb,
                          [r[3] if k in ("u8", "u16") else 0 for r, k in zip(rows, kinds)], peak,
                          nonfinite=[r[3] if k == "f32" else 0 for r, k in zip(rows, kinds)])
+
+
+# ------------------------------------------------------------------------------------------------- planar 4:2:0 clips
+PLANES = ("y", "u", "v")
+
+
+def _yuv_size(a, b, size):
+    for x in (a, b):
+        if isinstance(x, y4m.YuvFrame):
+            if size is not None and tuple(size) != x.shape[:2]:
+                raise ValueError(f"the frame is {x.shape[:2]}, the size given is {tuple(size)}")
+            size = x.shape[:2]
+    if size is None:
+        raise ValueError("packed Y, U, V planes need their (H, W): pass size=")
+    return int(size[0]), int(size[1])
+
+
+def _yuv_pair(backend, a, b, size):
+    size = _yuv_size(a, b, size)
+    a, ka, sa = backend.prepare(a, size)
+    b, kb, sb = backend.prepare(b, size)
+    if ka != kb or sa != sb:
+        raise ValueError(f"the two frames differ in form: {ka} {sa} against {kb} {sb}")
+    return a, b, ka, sa
+
+
+def _yuv_maxval(kind, maxval):
+    """255 for 8-bit samples; 16-bit ones: `maxval`, 1023 (10 bits, what YUV4MPEG2 carries) unless given"""
+    if kind == "yuv8":
+        if maxval not in (None, 255):
+            raise ValueError(f"8-bit samples have maxval 255, got {maxval!r}")
+        return 255
+    if maxval is not None and (int(maxval) != maxval or not 255 < int(maxval) <= 65535):
+        raise ValueError(f"maxval of 16-bit samples must be an integer with 255 < maxval <= 65535, got {maxval!r}")
+    return 1023 if maxval is None else int(maxval)
+
+
+def summarise_yuv(rows, samples, peak):
+    """-> {"frames", "peak", "per_frame", "summary"} from collect_yuv's rows and the (Y, U (= V)) sample counts per frame: host
+    arithmetic on exact integers.  `psnr` pools the squared error of the three planes over all their samples -- the 4:1:1 weighting
+    4:2:0 has by construction --; the summary follows summarise(), for the pooled figure and with _y / _u / _v for each plane."""
+    n = len(rows)
+    sq = [[r[p][0] for r in rows] for p in range(3)]
+    cnt = [[s[0] for s in samples], [s[1] for s in samples], [s[1] for s in samples]]
+    per = {"psnr_" + name: [psnr_of_mse(sq[p][i] / cnt[p][i], peak) for i in range(n)] for p, name in enumerate(PLANES)}
+    pooled_sq = [sq[0][i] + sq[1][i] + sq[2][i] for i in range(n)]
+    pooled_n = [cnt[0][i] + cnt[1][i] + cnt[2][i] for i in range(n)]
+    per["psnr"] = [psnr_of_mse(pooled_sq[i] / pooled_n[i], peak) for i in range(n)]
+    per["ssim_y"] = [float(r[3]) for r in rows]
+    per["max_lsb"] = [max(r[p][2] for p in range(3)) for r in rows]
+    per["differing"] = [sum(r[p][3] for p in range(3)) for r in rows]
+
+    def mean_finite(ps):
+        finite = [v for v in ps if math.isfinite(v)]
+        return (sum(finite) / len(finite)) if finite else math.inf
+
+    ps, ss = per["psnr"], per["ssim_y"]
+    summary = {"mean_psnr": mean_finite(ps), "psnr_of_mean_mse": psnr_of_mse(sum(pooled_sq) / sum(pooled_n), peak) if n else math.inf}
+    for p, name in enumerate(PLANES):
+        summary["mean_psnr_" + name] = mean_finite(per["psnr_" + name])
+        summary["psnr_of_mean_mse_" + name] = psnr_of_mse(sum(sq[p]) / sum(cnt[p]), peak) if n else math.inf
+    summary.update({"mean_ssim": (sum(ss) / n) if n else math.nan, "min_ssim": min(ss) if n else math.nan,
+                    "max_lsb": max(per["max_lsb"]) if n else 0, "total_differing": int(sum(per["differing"])),
+                    "worst_frame": min(range(n), key=lambda i: (ps[i], ss[i], i)) if n else None})
+    return {"frames": n, "peak": peak, "per_frame": per, "summary": summary}
+
+
+class YuvClipMetrics:
+    """ClipMetrics for planar 4:2:0 frames: add(a, b) takes two y4m.YuvFrames, or 1-D arrays / tensors of packed Y, U, V planes
+    (what ops.to_out_yuv returns: they stay on the device) with size=(H, W) -- one of the two being a YuvFrame gives the size --,
+    enqueues three plane errors and the 2-D SSIM of luma and never waits; result() synchronises once.
+    Per frame: psnr_y / psnr_u / psnr_v, psnr (pooled over the samples of the three planes), ssim_y, max_lsb (the largest
+    difference of the three planes, in the clip's own steps) and differing (samples).  The peak is maxval: 255, or for 16-bit
+    samples `maxval` (1023 unless given)."""
+
+    def __init__(self, backend=None, capacity=256, maxval=None):
+        self.backend = backend or default_backend()
+        self.capacity, self.maxval = int(capacity), maxval
+        self._slots, self._used, self._samples, self._kind = [], [], [], None
+
+    def __len__(self):
+        return sum(self._used)
+
+    def add(self, a, b, size=None):
+        a, b, kind, (_, h, w) = _yuv_pair(self.backend, a, b, size)
+        if self._kind not in (None, kind):
+            raise ValueError(f"a clip has one sample depth: {self._kind} so far, now {kind}")
+        mv = _yuv_maxval(kind, self.maxval)
+        if not self._slots or self._used[-1] == self.capacity:
+            self._slots.append(self.backend.slots_yuv(self.capacity))
+            self._used.append(0)
+        self.backend.measure_yuv(self._slots[-1], self._used[-1], a, b, kind, (1, h, w), mv, True)
+        self._kind = kind
+        self._used[-1] += 1
+        self._samples.append(yuv420_samples((h, w)))
+
+    def result(self):
+        rows = self.backend.collect_yuv(self._slots, list(self._used))
+        return summarise_yuv(rows, self._samples, float(_yuv_maxval(self._kind or "yuv8", self.maxval)))
+
+
+def _one_shot_yuv(a, b, size, want_ssim, backend, maxval):
+    backend = backend or default_backend()
+    a, b, kind, shape = _yuv_pair(backend, a, b, size)
+    mv = _yuv_maxval(kind, maxval)
+    slots = backend.slots_yuv(1)
+    backend.measure_yuv(slots, 0, a, b, kind, shape, mv, want_ssim)
+    return backend.collect_yuv([slots], [1])[0], yuv420_samples(shape[1:]), float(mv)
+
+
+def psnr_yuv(a, b, size=None, backend=None, maxval=None):
+    """{"psnr_y", "psnr_u", "psnr_v", "psnr"} of one pair of planar 4:2:0 frames (peak = maxval; inf for identical planes)"""
+    row, samples, peak = _one_shot_yuv(a, b, size, False, backend, maxval)
+    per = summarise_yuv([row], [samples], peak)["per_frame"]
+    return {k: per[k][0] for k in ("psnr_y", "psnr_u", "psnr_v", "psnr")}
+
+
+def ssim_y(a, b, size=None, backend=None, maxval=None):
+    """The single-channel 2-D ssim (11 x 11 gaussian window, replicate padding) of the luma planes of one pair of 4:2:0 frames"""
+    return _one_shot_yuv(a, b, size, True, backend, maxval)[0][3]

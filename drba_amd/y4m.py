@@ -1,10 +1,11 @@
-"""YUV4MPEG2 (.y4m) streams: header parse and format, a streaming reader and a writer.  Pure Python, no GPU.
+"""YUV4MPEG2 (.y4m) streams: header parse and format, a streaming reader, a random-access reader and a writer.  Pure Python, no GPU.
 
 The format is one text line, `YUV4MPEG2 W.. H.. F.. I.. A.. C.. X..`, then per frame the line `FRAME[ params]` and the three
 planes Y, U, V.  Only progressive planar 4:2:0 at 8 or 10 bits is taken (C420, C420jpeg, C420mpeg2, C420p10): Y is H x W, U and V
 are ceil(H/2) x ceil(W/2), 10-bit samples are little-endian uint16.  A frame travels through the pipeline as a YuvFrame: the packed
 plane bytes as they stand in the stream plus the geometry; the colour conversion happens on the device (ops.to_inp_yuv /
-ops.to_out_yuv), never here.  The reader reads any file object, pipes included, one frame at a time.
+ops.to_out_yuv), never here.  The reader reads any file object, pipes included, one frame at a time; IndexedReader gives len() and
+read_frame(k) on a seekable one.
 """
 import warnings
 from fractions import Fraction
@@ -256,6 +257,52 @@ class Reader:
 
     def __iter__(self):
         return iter(self.read_frame, None)
+
+
+class IndexedReader:
+    """Random access to the frames of a seekable stream: len() and read_frame(k).  One scan at construction reads each `FRAME...\\n`
+    line and seeks over the payload -- a frame header may carry parameters, so the offsets are not assumed uniform -- and keeps one
+    integer per frame; no payload is read before its frame is asked for.  A file object that cannot seek raises Y4MError, and so does
+    a truncated last frame, as in Reader."""
+
+    def __init__(self, fileobj):
+        seekable = getattr(fileobj, "seekable", None)
+        if not (callable(seekable) and seekable() and hasattr(fileobj, "seek") and hasattr(fileobj, "tell")):
+            raise Y4MError("y4m: random access needs a seekable stream (a file, not a pipe)")
+        self.f = fileobj
+        start = fileobj.tell()
+        head = Reader(fileobj)
+        self.header, self.header_bytes = head.header, head.header_bytes
+        end = fileobj.seek(0, 2)
+        size, pos, self._offsets = self.header.frame_bytes, start + head.header_bytes, []
+        while pos < end:
+            fileobj.seek(pos)
+            line = _read_line(fileobj)
+            k = len(self._offsets)
+            if not (line.endswith(b"\n") and (line[:-1] == b"FRAME" or line.startswith(b"FRAME "))):
+                raise Y4MError(f"y4m: frame {k}: expected a FRAME line, got {bytes(line[:24])!r}")
+            pos += len(line)
+            if pos + size > end:
+                raise Y4MError(f"y4m: frame {k} is truncated: {end - pos} of {size} bytes")
+            self._offsets.append(pos)
+            pos += size
+
+    def __len__(self):
+        return len(self._offsets)
+
+    def read_frame(self, k):
+        """-> frame k as a YuvFrame (IndexError outside 0 .. len() - 1)"""
+        if not 0 <= int(k) < len(self._offsets):
+            raise IndexError(f"y4m: frame {k} of {len(self._offsets)}")
+        h = self.header
+        self.f.seek(self._offsets[int(k)])
+        data = _read_exact(self.f, h.frame_bytes)
+        if len(data) != h.frame_bytes:  # (the file shrank after the scan)
+            raise Y4MError(f"y4m: frame {k} is truncated: {len(data)} of {h.frame_bytes} bytes")
+        return YuvFrame(data, h.height, h.width, h.depth)
+
+    def __iter__(self):
+        return (self.read_frame(k) for k in range(len(self._offsets)))
 
 
 class Writer:

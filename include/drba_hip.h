@@ -32,7 +32,9 @@ extern "C" {
 #define DRBA_EUNSUPPORTED (-2) /* shape/config outside what the kernels were built for */
 #define DRBA_ELAUNCH (-3)  /* hipGetLastError() reported a launch failure */
 
-/* ABI version.  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
+/* ABI version.  16: drba_ssim2d / drba_ssim2d_ws_floats (the single-channel 2-D ssim of pytorch_msssim on N planes addressed by a row and
+ * an item stride -- the luma planes of packed 4:2:0 frames --, fp32, uint8 or uint16 samples, fp64 accumulation): additions only,
+ * no earlier entry changes.  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
  * the splat entry points: drba_flow_reverse, drba_drm_rife_linear(_batch), drba_drm_rife_nonlinear(_batch), drba_softsplat and
  * drba_softsplat_index; while it is on, drba_rife_splat_ws_floats reports the larger workspace of the fixed-point accumulator):
  * additions only, nothing changes while the switch is off.  14: planar YCbCr 4:2:0 frames -- drba_to_inp_yuv420_x4 / drba_to_inp16_yuv420_x4 / drba_to_out_yuv420 /
@@ -59,7 +61,7 @@ extern "C" {
  * workspace that must be ZERO on entry (they leave it zero on return: self-cleaning accumulator) instead of clearing it
  * themselves; batched stage entry points added; drba_conv3x3_cfg_family added and configuration ids 19 (LDS-DMA, 32
  * channels) / 20 (K split across waves) behind drba_conv3x3; the allocation exception above.  1: the first release. */
-#define DRBA_ABI_VERSION 15  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
+#define DRBA_ABI_VERSION 16  /* the ONE place the number lives: api_misc.hip returns it, drba_amd/_lib.py parses it */
 int drba_abi_version(void);
 const char *drba_error_string(int code);
 /* ABI 6, debug: with the range check on, every entry point that ran a kernel of family 4 (two fp16 terms per operand:
@@ -313,6 +315,25 @@ int drba_ssim3d_32(const float *x1, const float *x2, float *out, void *stream);
 size_t drba_ssim3d_ws_floats(int N, int H, int W);
 int drba_ssim3d(const void *img1, const void *img2, double *out, float *ws, int N, int H, int W, int dtype, double val_range,
                 void *stream);
+/* ABI 16: drba_ssim2d replaces models/pytorch_msssim/__init__.py:29-80 (ssim) on ONE channel: the mean over all H*W positions of
+ * the 2-D SSIM map of N pairs of single planes, window 11 x 11 (sigma 1.5, built as for drba_ssim3d_32), replicate padding 5 on both
+ * axes, C1 = (0.01 L)^2, C2 = (0.03 L)^2.  There is no channel pass: this is the figure video results quote for luma, where
+ * drba_ssim3d's window runs across three colour channels and has no meaning on a single plane.
+ * Item k of p1 / p2 starts at sample k * item_stride, its row y at y * row_stride further on (strides in SAMPLES, row_stride >= W;
+ * the two operands share them): with item_stride = the size of a packed Y, U, V frame the luma planes of a batch of frames go
+ * through one launch, and a plane inside a wider buffer is read in place.
+ * dtype 0: fp32 samples, L = maxval (the caller's val_range, > 0 and finite; there is no inference from the data).
+ * dtype 1: uint8 samples read as (float)s / 255.f, L = 1; maxval must be 255 (or 0, meaning 255).
+ * dtype 2: uint16 samples (pointers 2-byte aligned) read as (float)s / (float)maxval, L = 1; maxval an integer in (255, 65535]
+ *          (1023: 10-bit data).  Anything else is DRBA_EINVAL.
+ * out: N doubles (8-byte aligned).  ws: drba_ssim2d_ws_floats(N, H, W) floats, 8-byte aligned, any content.
+ * As drba_ssim3d: the five blurred fields are accumulated in fp64, tile sums are added in a fixed order by a second kernel, no
+ * floating-point atomics -- identical planes give exactly 1, the same bits on every run, for an item alone or inside a batch, and
+ * for a plane read through a row stride or from its contiguous copy.  H or W < 11: DRBA_EUNSUPPORTED (the reference shrinks its
+ * window there).  Null pointers, row_stride < W, an odd address at dtype 2 or a maxval outside the above: DRBA_EINVAL. */
+size_t drba_ssim2d_ws_floats(int N, int H, int W);
+int drba_ssim2d(const void *p1, const void *p2, double *out, float *ws, int N, int H, int W, size_t row_stride, size_t item_stride,
+                int dtype, double maxval, void *stream);
 /* Exact differences of N pairs of n_per_item elements, item k at element k * n_per_item of a and b (no alignment is asked of
  * either: the byte kernel reads 16 bytes per load between the unaligned ends).  out, per item, 4 x 8 bytes (8-byte aligned):
  *   _u8 : sum d^2, sum |d|, max |d|, number of d != 0 -- unsigned long long, integer accumulation;
