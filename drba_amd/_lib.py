@@ -92,6 +92,14 @@ SIGNATURES = {
     "drba_to_inp16_yuv420_x4": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _f, _f, _i, _i, _f, _p]),
     "drba_to_out_yuv420": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _p]),
     "drba_to_out16_yuv420": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _f, _p]),
+    "drba_to_inp_pad_x4": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "drba_to_inp16_pad_x4": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p]),
+    "drba_to_out_crop": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "drba_to_out16_crop": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "drba_to_inp_yuv420_pad_x4": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "drba_to_inp16_yuv420_pad_x4": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
+    "drba_to_out_yuv420_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "drba_to_out16_yuv420_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
     "drba_ssim3d_32": (_i, [_p, _p, _p, _p]),
     "drba_ssim3d_ws_floats": (_z, [_i, _i, _i]),
     "drba_ssim3d": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _d, _p]),

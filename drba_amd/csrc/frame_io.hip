@@ -1,5 +1,5 @@
 // The frame source and sink of the pipeline: bilinear resize and the uint8 / uint16 <-> fp32 frame conversions used by
-// to_inp / to_out.  Each conversion is written once, over a sample trait with two instances (bytes, 16-bit samples); the
+// to_inp / to_out, and their copy forms without a resize (fit = pad: replicate padding in, a crop out).  Each conversion is written once, over a sample trait with two instances (bytes, 16-bit samples); the
 // __global__ kernels keep one symbol per depth and form, because the launch trace and the profiles are keyed on them.
 #include "common.hpp"
 
@@ -256,8 +256,124 @@ __device__ __forceinline__ void f32_to_samples_body(const S s, const float *__re
   }
 }
 
+// ---- fit = pad: the frame at the top left of the network tensor, no interpolation (include/drba_hip.h, ABI 16) -------------------
+// Way in, the bottom and right margins repeat the last row and column: out(y, x) = to_unit(in(min(y, Hin - 1), min(x, Win - 1))).
+// Way out, the top-left Hout x Wout window is quantised as it stands; nothing outside it is read.
+//
+// ATen's copy of an axis whose size does not change, fma(1, a, 0 * a): a for finite a, NaN otherwise.  The 16-bit and planar
+// ways out keep it (kCopyTaps) so that a cropped frame is, sample for sample, what the unresized conversion of the same window
+// gives: NaN and +-inf -> 0 at the quantiser.  Only the pixel itself is read.
+__device__ __forceinline__ float aten_copy(float a) { return __fmaf_rn(1.f, a, __fmul_rn(0.f, a)); }
+template <class S>
+__device__ __forceinline__ float crop_value(float a) {
+  if constexpr (S::kCopyTaps)
+    return aten_copy(a);
+  else
+    return a;
+}
+
+// the general form of the way in: one output pixel per lane, any size
+template <class S>
+__device__ __forceinline__ void to_inp_pad_body(const S s, const typename S::sample_t *__restrict__ in, float *__restrict__ out,
+                                                float *__restrict__ out_x4, int Hin, int Win, int Hout, int Wout) {
+  const Tile2D p = tile_pixel(Wout, Hout);
+  if (!p.valid) return;
+  const typename S::sample_t *px = in + ((size_t)min(p.y, Hin - 1) * Win + min(p.x, Win - 1)) * 3;
+  const size_t P = (size_t)Hout * Wout, o = (size_t)p.y * Wout + p.x;
+  float v[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    v[c] = s.to_unit((float)px[c]);
+    out[c * P + o] = v[c];
+  }
+  if (out_x4) *reinterpret_cast<f32x4g *>(out_x4 + 4 * o) = (f32x4g){v[0], v[1], v[2], 0.f};
+}
+// the rows form (an unchanged width that is a multiple of 4: only rows are added): four pixels per lane, as to_inp_rows_body
+template <class S>
+__device__ __forceinline__ void to_inp_pad_rows_body(const S s, const typename S::sample_t *__restrict__ in, float *__restrict__ out,
+                                                     float *__restrict__ out_x4, int Hin, int W, int Hout) {
+  const int W4 = W >> 2;
+  const size_t total = (size_t)W4 * Hout, P = (size_t)Hout * W;
+  for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
+    const int y = (int)(i / W4), x = (int)(i - (size_t)y * W4) * 4;
+    Packed<S> a;
+    S::load12(in + ((size_t)min(y, Hin - 1) * W + x) * 3, a.w);
+    f32x4g o[3];
+#pragma unroll
+    for (int px = 0; px < 4; ++px)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c][px] = s.to_unit(a.sample(px * 3 + c));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4g *>(out + (size_t)c * P + (size_t)y * W + x) = o[c];
+    if (out_x4) {
+#pragma unroll
+      for (int px = 0; px < 4; ++px)
+        *reinterpret_cast<f32x4g *>(out_x4 + ((size_t)y * W + x + px) * 4) = (f32x4g){o[0][px], o[1][px], o[2][px], 0.f};
+    }
+  }
+}
+// the way out: pixel (y, x) of the Hout x Wout window of fp32 [1,3,Hin,Win] -> * scale, quantised
+template <class S>
+__device__ __forceinline__ void to_out_crop_body(const S s, const float *__restrict__ in, typename S::sample_t *__restrict__ out, int Hin,
+                                                 int Win, int Hout, int Wout, int rev) {
+  const Tile2D p = tile_pixel(Wout, Hout);
+  if (!p.valid) return;
+  const size_t P = (size_t)Hin * Win, i = (size_t)p.y * Win + p.x;
+  typename S::sample_t *o = out + ((size_t)p.y * Wout + p.x) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    o[rev ? 2 - c : c] = (typename S::sample_t)s.quantise(__fmul_rn(crop_value<S>(in[c * P + i]), s.scale()));
+}
+template <class S>
+__device__ __forceinline__ void to_out_crop_rows_body(const S s, const float *__restrict__ in, typename S::sample_t *__restrict__ out,
+                                                      int Hin, int W, int Hout, int rev) {
+  const int W4 = W >> 2;
+  const size_t total = (size_t)W4 * Hout, P = (size_t)Hin * W;
+  for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
+    const int y = (int)(i / W4), x = (int)(i - (size_t)y * W4) * 4;
+    uint32_t q[12];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const f32x4g t = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)y * W + x);
+#pragma unroll
+      for (int px = 0; px < 4; ++px) q[px * 3 + (rev ? 2 - c : c)] = s.quantise(__fmul_rn(crop_value<S>(t[px]), s.scale()));
+    }
+    S::store12(out + ((size_t)y * W + x) * 3, q);
+  }
+}
+
 // ---- one kernel symbol per depth and form ---------------------------------------------------------------------------------------
 #define DRBA_FRAME_KERNEL __global__ void __launch_bounds__(256)
+DRBA_FRAME_KERNEL to_inp_pad_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,
+                                    int Hout, int Wout) {
+  to_inp_pad_body(Samples8{}, in, out, out_x4, Hin, Win, Hout, Wout);
+}
+DRBA_FRAME_KERNEL to_inp16_pad_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,
+                                      int Hout, int Wout, float maxval) {
+  to_inp_pad_body(Samples16{maxval}, in, out, out_x4, Hin, Win, Hout, Wout);
+}
+DRBA_FRAME_KERNEL to_inp_pad_rows_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int W,
+                                         int Hout) {
+  to_inp_pad_rows_body(Samples8{}, in, out, out_x4, Hin, W, Hout);
+}
+DRBA_FRAME_KERNEL to_inp16_pad_rows_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin,
+                                           int W, int Hout, float maxval) {
+  to_inp_pad_rows_body(Samples16{maxval}, in, out, out_x4, Hin, W, Hout);
+}
+DRBA_FRAME_KERNEL to_out_crop_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int Win, int Hout, int Wout, int rev) {
+  to_out_crop_body(Samples8{}, in, out, Hin, Win, Hout, Wout, rev);
+}
+DRBA_FRAME_KERNEL to_out16_crop_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int Hin, int Win, int Hout, int Wout, int rev,
+                                       float maxval) {
+  to_out_crop_body(Samples16{maxval}, in, out, Hin, Win, Hout, Wout, rev);
+}
+DRBA_FRAME_KERNEL to_out_crop_rows_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int W, int Hout, int rev) {
+  to_out_crop_rows_body(Samples8{}, in, out, Hin, W, Hout, rev);
+}
+DRBA_FRAME_KERNEL to_out16_crop_rows_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int Hin, int W, int Hout, int rev,
+                                            float maxval) {
+  to_out_crop_rows_body(Samples16{maxval}, in, out, Hin, W, Hout, rev);
+}
 DRBA_FRAME_KERNEL to_inp_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,
                                 int Hout, int Wout, float sy, float sx) {
   to_inp_body(Samples8{}, in, out, out_x4, Hin, Win, Hout, Wout, sy, sx);
@@ -349,6 +465,24 @@ __device__ __forceinline__ void yuv_to_bgr(const YuvIn &k, float y, float u, flo
   const float G = (Y - k.kr * R - k.kb * B) * k.inv_kg;
   bgr[0] = clamp01(B), bgr[1] = clamp01(G), bgr[2] = clamp01(R);
 }
+// yuv_to_bgr with every operation spelled out, for the pad forms (below), which must give the values of their resize siblings at an
+// unchanged size bit for bit.  yuv_to_bgr leaves the contraction to hipcc, and hipcc settles it per body: R and B are
+// fma(coef, C, Y') everywhere, but Y' - Kr R is fma(y_mul, y - y_off, -(Kr R)) -- the product behind Y' taken unrounded -- in the
+// general resize bodies and Y' - (Kr R) on the rounded Y' in the rows bodies (read from the ISA of the 8- and 16-bit kernels of
+// both forms; the two differ by a few ulp in G).  A pad body names the form it stands beside: kFusedLuma = the general one.
+// (Everything else in the planar kernels has one contraction only: the chroma taps are exact, and bgr_to_ycc with the code
+// computation behind it compiles to the same operations in every body.)
+template <bool kFusedLuma>
+__device__ __forceinline__ void yuv_to_bgr_as(const YuvIn &k, float y, float u, float v, float (&bgr)[3]) {
+#pragma clang fp contract(off)  // (the __f*_rn functions are plain operators to hipcc and would be contracted again)
+  const float ys = y - k.y_off, Y = ys * k.y_mul;
+  const float Cb = (u - k.c_off) * k.c_mul, Cr = (v - k.c_off) * k.c_mul;
+  const float R = __builtin_fmaf(k.r_cr, Cr, Y), B = __builtin_fmaf(k.b_cb, Cb, Y);
+  const float krR = k.kr * R, kbB = k.kb * B;
+  const float t = kFusedLuma ? __builtin_fmaf(k.y_mul, ys, -krR) : Y - krR;
+  const float G = (t - kbB) * k.inv_kg;
+  bgr[0] = clamp01(B), bgr[1] = clamp01(G), bgr[2] = clamp01(R);
+}
 // (B, G, R) as the resize left them -> clamped, Y' and the two colour differences
 __device__ __forceinline__ void bgr_to_ycc(const YuvOut &k, float b, float g, float r, float &Y, float &Cb, float &Cr) {
   b = clamp01(b), g = clamp01(g), r = clamp01(r);
@@ -358,8 +492,8 @@ __device__ __forceinline__ void bgr_to_ycc(const YuvOut &k, float b, float g, fl
 }
 
 // the general form of the way in: one output pixel per lane, any size.  Each of the four taps of the resize is a source PIXEL,
-// converted from its luma sample and the 2 x 2 chroma taps of either plane.
-template <class T>
+// converted from its luma sample and the 2 x 2 chroma taps of either plane.  (kSpelled: the pad form, yuv_to_bgr_as.)
+template <class T, bool kSpelled = false>
 __device__ __forceinline__ void yuv_pixel(const YuvIn &k, const T *__restrict__ yp, const T *__restrict__ up, const T *__restrict__ vp,
                                           int ys, int cs, int Hc, int Wc, int sy, int sx, float (&bgr)[3]) {
   const CTap ty = chroma_tap(sy, Hc), tx = chroma_tap(sx, Wc);
@@ -368,7 +502,10 @@ __device__ __forceinline__ void yuv_pixel(const YuvIn &k, const T *__restrict__ 
                   ty.w1 * (tx.w0 * (float)up[r1 + tx.i0] + tx.w1 * (float)up[r1 + tx.i1]);
   const float v = ty.w0 * (tx.w0 * (float)vp[r0 + tx.i0] + tx.w1 * (float)vp[r0 + tx.i1]) +
                   ty.w1 * (tx.w0 * (float)vp[r1 + tx.i0] + tx.w1 * (float)vp[r1 + tx.i1]);
-  yuv_to_bgr(k, (float)yp[(size_t)sy * ys + sx], u, v, bgr);
+  if constexpr (kSpelled)
+    yuv_to_bgr_as<true>(k, (float)yp[(size_t)sy * ys + sx], u, v, bgr);
+  else
+    yuv_to_bgr(k, (float)yp[(size_t)sy * ys + sx], u, v, bgr);
 }
 template <class T>
 __device__ __forceinline__ void to_inp_yuv_body(const YuvIn k, const T *__restrict__ yp, const T *__restrict__ up, const T *__restrict__ vp,
@@ -592,6 +729,165 @@ __device__ __forceinline__ void to_out_yuv_rows_body(const YuvOut k, const float
   }
 }
 
+// ---- fit = pad for planar frames: as the packed forms above -------------------------------------------------------------------------
+// Way in, an output pixel is the source PIXEL at the clamped coordinate (its luma sample and the 2 x 2 chroma taps of that source
+// coordinate), so the margin continues the converted picture and no chroma tap is taken past the frame.
+template <class T>
+__device__ __forceinline__ void to_inp_yuv_pad_body(const YuvIn k, const T *__restrict__ yp, const T *__restrict__ up, const T *__restrict__ vp,
+                                                    int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,
+                                                    int Hout, int Wout) {
+  const Tile2D p = tile_pixel(Wout, Hout);
+  if (!p.valid) return;
+  float v[3];
+  yuv_pixel<T, true>(k, yp, up, vp, ys, cs, (Hin + 1) >> 1, (Win + 1) >> 1, min(p.y, Hin - 1), min(p.x, Win - 1), v);
+  const size_t P = (size_t)Hout * Wout, o = (size_t)p.y * Wout + p.x;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) out[ch * P + o] = v[ch];
+  if (out_x4) *reinterpret_cast<f32x4g *>(out_x4 + 4 * o) = (f32x4g){v[0], v[1], v[2], 0.f};
+}
+// The rows form (an unchanged width that is a multiple of 8): eight pixels of an output row per lane from ONE source row, its
+// 8 luma samples and the two chroma rows of its taps, loaded as in to_inp_yuv_rows_body.
+template <class T>
+__device__ __forceinline__ void to_inp_yuv_pad_rows_body(const YuvIn k, const T *__restrict__ yp, const T *__restrict__ up,
+                                                         const T *__restrict__ vp, int ys, int cs, float *__restrict__ out,
+                                                         float *__restrict__ out_x4, int Hin, int W, int Hout) {
+  const int W8 = W >> 3, Hc = (Hin + 1) >> 1, Wc = W >> 1;
+  const size_t total = (size_t)W8 * Hout, P = (size_t)Hout * W;
+  for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
+    const int y = (int)(i / W8), x = (int)(i - (size_t)y * W8) * 8, xc = x >> 1, sy = min(y, Hin - 1);
+    const CTap ty = chroma_tap(sy, Hc);
+    float ua[6], ub[6], va[6], vb[6], cu[6], cv[6];
+    chroma_raw6(up + (size_t)ty.i0 * cs, Wc, xc, ua), chroma_raw6(vp + (size_t)ty.i0 * cs, Wc, xc, va);
+    chroma_raw6(up + (size_t)ty.i1 * cs, Wc, xc, ub), chroma_raw6(vp + (size_t)ty.i1 * cs, Wc, xc, vb);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) cu[j] = ty.w0 * ua[j] + ty.w1 * ub[j], cv[j] = ty.w0 * va[j] + ty.w1 * vb[j];
+    SampleRow<T, 8> luma;
+    luma.load(yp + (size_t)sy * ys + x);
+    f32x4g o[3][2];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {  // the taps of pixel x + j among the six: to_inp_yuv_rows_body
+      const int c0 = (j + 1) >> 1;
+      const float w0 = (j & 1) ? 0.75f : 0.25f, w1 = (j & 1) ? 0.25f : 0.75f;
+      float px[3];
+      yuv_to_bgr_as<false>(k, luma.sample(j), w0 * cu[c0] + w1 * cu[c0 + 1], w0 * cv[c0] + w1 * cv[c0 + 1], px);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c][j >> 2][j & 3] = px[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      f32x4g *dst = reinterpret_cast<f32x4g *>(out + (size_t)c * P + (size_t)y * W + x);
+      dst[0] = o[c][0], dst[1] = o[c][1];
+    }
+    if (out_x4) {
+      f32x4g *dst = reinterpret_cast<f32x4g *>(out_x4 + ((size_t)y * W + x) * 4);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dst[j] = (f32x4g){o[0][j >> 2][j & 3], o[1][j >> 2][j & 3], o[2][j >> 2][j & 3], 0.f};
+    }
+  }
+}
+
+// Way out: one 2 x 2 luma block of the Hout x Wout window per lane.  A pixel past an odd edge repeats the edge pixel of the WINDOW
+// in the chroma mean, as in to_out_yuv_body: the margin of the network tensor is never read.
+template <class T>
+__device__ __forceinline__ void to_out_yuv_crop_body(const YuvOut k, const float *__restrict__ in, T *__restrict__ yp, T *__restrict__ up,
+                                                     T *__restrict__ vp, int ys, int cs, int Hin, int Win, int Hout, int Wout) {
+  const int Hc = (Hout + 1) >> 1, Wc = (Wout + 1) >> 1;
+  const Tile2D p = tile_pixel(Wc, Hc);
+  if (!p.valid) return;
+  const size_t P = (size_t)Hin * Win;
+  float cb = 0.f, cr = 0.f;
+#pragma unroll
+  for (int dy = 0; dy < 2; ++dy) {
+    const int oy = min(2 * p.y + dy, Hout - 1);
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx) {
+      const int ox = min(2 * p.x + dx, Wout - 1);
+      const float *px = in + (size_t)oy * Win + ox;
+      float Y, Cb, Cr;
+      bgr_to_ycc(k, aten_copy(px[0]), aten_copy(px[P]), aten_copy(px[2 * P]), Y, Cb, Cr);
+      cb += Cb, cr += Cr;
+      if (2 * p.y + dy < Hout && 2 * p.x + dx < Wout) yp[(size_t)oy * ys + ox] = (T)round_sat_u16(k.y_off + k.y_mul * Y, k.maxval);
+    }
+  }
+  const size_t o = (size_t)p.y * cs + p.x;
+  up[o] = (T)round_sat_u16(k.c_off + k.c_mul * (cb * 0.25f), k.maxval);
+  vp[o] = (T)round_sat_u16(k.c_off + k.c_mul * (cr * 0.25f), k.maxval);
+}
+// the rows form: two window rows of four blocks per lane, as to_out_yuv_rows_body
+template <class T>
+__device__ __forceinline__ void to_out_yuv_crop_rows_body(const YuvOut k, const float *__restrict__ in, T *__restrict__ yp,
+                                                          T *__restrict__ up, T *__restrict__ vp, int ys, int cs, int Hin, int W, int Hout) {
+  const int W8 = W >> 3, Hc = (Hout + 1) >> 1;
+  const size_t total = (size_t)W8 * Hc, P = (size_t)Hin * W;
+  for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
+    const int j = (int)(i / W8), x = (int)(i - (size_t)j * W8) * 8;
+    float cb[4] = {0.f, 0.f, 0.f, 0.f}, cr[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int oy = min(2 * j + r, Hout - 1);
+      uint32_t q[8];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        f32x4g ch[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ch[c] = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)oy * W + x + 4 * h);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float Y, Cb, Cr;
+          bgr_to_ycc(k, aten_copy(ch[0][e]), aten_copy(ch[1][e]), aten_copy(ch[2][e]), Y, Cb, Cr);
+          q[4 * h + e] = round_sat_u16(k.y_off + k.y_mul * Y, k.maxval);
+          cb[2 * h + (e >> 1)] += Cb, cr[2 * h + (e >> 1)] += Cr;
+        }
+      }
+      if (2 * j + r < Hout) SampleRow<T, 8>::store(yp + (size_t)oy * ys + x, q);
+    }
+    uint32_t qu[4], qv[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      qu[b] = round_sat_u16(k.c_off + k.c_mul * (cb[b] * 0.25f), k.maxval);
+      qv[b] = round_sat_u16(k.c_off + k.c_mul * (cr[b] * 0.25f), k.maxval);
+    }
+    SampleRow<T, 4>::store(up + (size_t)j * cs + (x >> 1), qu);
+    SampleRow<T, 4>::store(vp + (size_t)j * cs + (x >> 1), qv);
+  }
+}
+
+DRBA_FRAME_KERNEL to_inp_yuv_pad_kernel(YuvIn k, const uint8_t *__restrict__ y, const uint8_t *__restrict__ u, const uint8_t *__restrict__ v,
+                                        int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win, int Hout,
+                                        int Wout) {
+  to_inp_yuv_pad_body(k, y, u, v, ys, cs, out, out_x4, Hin, Win, Hout, Wout);
+}
+DRBA_FRAME_KERNEL to_inp16_yuv_pad_kernel(YuvIn k, const uint16_t *__restrict__ y, const uint16_t *__restrict__ u,
+                                          const uint16_t *__restrict__ v, int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4,
+                                          int Hin, int Win, int Hout, int Wout) {
+  to_inp_yuv_pad_body(k, y, u, v, ys, cs, out, out_x4, Hin, Win, Hout, Wout);
+}
+DRBA_FRAME_KERNEL to_inp_yuv_pad_rows_kernel(YuvIn k, const uint8_t *__restrict__ y, const uint8_t *__restrict__ u,
+                                             const uint8_t *__restrict__ v, int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4,
+                                             int Hin, int W, int Hout) {
+  to_inp_yuv_pad_rows_body(k, y, u, v, ys, cs, out, out_x4, Hin, W, Hout);
+}
+DRBA_FRAME_KERNEL to_inp16_yuv_pad_rows_kernel(YuvIn k, const uint16_t *__restrict__ y, const uint16_t *__restrict__ u,
+                                               const uint16_t *__restrict__ v, int ys, int cs, float *__restrict__ out,
+                                               float *__restrict__ out_x4, int Hin, int W, int Hout) {
+  to_inp_yuv_pad_rows_body(k, y, u, v, ys, cs, out, out_x4, Hin, W, Hout);
+}
+DRBA_FRAME_KERNEL to_out_yuv_crop_kernel(YuvOut k, const float *__restrict__ in, uint8_t *__restrict__ y, uint8_t *__restrict__ u,
+                                         uint8_t *__restrict__ v, int ys, int cs, int Hin, int Win, int Hout, int Wout) {
+  to_out_yuv_crop_body(k, in, y, u, v, ys, cs, Hin, Win, Hout, Wout);
+}
+DRBA_FRAME_KERNEL to_out16_yuv_crop_kernel(YuvOut k, const float *__restrict__ in, uint16_t *__restrict__ y, uint16_t *__restrict__ u,
+                                           uint16_t *__restrict__ v, int ys, int cs, int Hin, int Win, int Hout, int Wout) {
+  to_out_yuv_crop_body(k, in, y, u, v, ys, cs, Hin, Win, Hout, Wout);
+}
+DRBA_FRAME_KERNEL to_out_yuv_crop_rows_kernel(YuvOut k, const float *__restrict__ in, uint8_t *__restrict__ y, uint8_t *__restrict__ u,
+                                              uint8_t *__restrict__ v, int ys, int cs, int Hin, int W, int Hout) {
+  to_out_yuv_crop_rows_body(k, in, y, u, v, ys, cs, Hin, W, Hout);
+}
+DRBA_FRAME_KERNEL to_out16_yuv_crop_rows_kernel(YuvOut k, const float *__restrict__ in, uint16_t *__restrict__ y, uint16_t *__restrict__ u,
+                                                uint16_t *__restrict__ v, int ys, int cs, int Hin, int W, int Hout) {
+  to_out_yuv_crop_rows_body(k, in, y, u, v, ys, cs, Hin, W, Hout);
+}
 DRBA_FRAME_KERNEL to_inp_yuv_kernel(YuvIn k, const uint8_t *__restrict__ y, const uint8_t *__restrict__ u, const uint8_t *__restrict__ v, int ys,
                                     int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win, int Hout, int Wout, float sy,
                                     float sx) {
@@ -665,6 +961,35 @@ int to_out_launch(void (*one)(const float *, T *, int, int, int, int, float, flo
   else
     DRBA_LAUNCH(one, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Win, Hout, Wout, scale_y,
                 scale_x, reverse_channels, maxval...);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+// fit = pad: the network tensor is at least the frame (way in) and the frame at most the network tensor (way out); the rows form
+// under the same rule as above, the width being unchanged where only rows are added or dropped
+template <class T, class... M>
+int to_inp_pad_launch(void (*one)(const T *, float *, float *, int, int, int, int, M...), void (*rows)(const T *, float *, float *, int, int, int, M...),
+                      const T *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, void *stream, M... maxval) {
+  if (!img_hwc || !out || Hin <= 0 || Win <= 0 || Hout < Hin || Wout < Win || ((uintptr_t)out_x4 & 15) != 0) return DRBA_EINVAL;
+  if (rows_form_ok(Win, Wout, 1.f, img_hwc, out))
+    DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4, Hin, Wout,
+                Hout, maxval...);
+  else
+    DRBA_LAUNCH(one, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4, Hin, Win, Hout, Wout, maxval...);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+template <class T, class... M>
+int to_out_crop_launch(void (*one)(const float *, T *, int, int, int, int, int, M...), void (*rows)(const float *, T *, int, int, int, int, M...),
+                       const float *in, T *out_hwc, int Hin, int Win, int Hout, int Wout, int reverse_channels, void *stream, M... maxval) {
+  if (!in || !out_hwc || Hout <= 0 || Wout <= 0 || Hout > Hin || Wout > Win) return DRBA_EINVAL;
+  if (rows_form_ok(Win, Wout, 1.f, out_hwc, in))
+    DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Wout, Hout,
+                reverse_channels, maxval...);
+  else
+    DRBA_LAUNCH(one, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Win, Hout, Wout, reverse_channels,
+                maxval...);
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }
@@ -762,6 +1087,43 @@ int to_out_yuv_launch(void (*one)(YuvOut, const float *, T *, T *, T *, int, int
   return DRBA_OK;
 }
 
+// fit = pad, planar
+template <class T>
+int to_inp_yuv_pad_launch(void (*one)(YuvIn, const T *, const T *, const T *, int, int, float *, float *, int, int, int, int),
+                          void (*rows)(YuvIn, const T *, const T *, const T *, int, int, float *, float *, int, int, int), const T *y,
+                          const T *u, const T *v, int ys, int cs, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, int matrix,
+                          int full_range, float maxval, void *stream) {
+  double kr, kb;
+  if (!yuv_args_ok(y, u, v, ys, cs, out, Hin, Win, Hout, Wout, Hin, Win, maxval) || Hout < Hin || Wout < Win || ((uintptr_t)out_x4 & 15) != 0 ||
+      !yuv_coeffs(matrix, kr, kb))
+    return DRBA_EINVAL;
+  const YuvIn k = yuv_in_consts(kr, kb, full_range, maxval);
+  if (yuv_rows_form_ok(Win, Wout, 1.f, y, u, v, ys, cs, out))
+    DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 3) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, k, y, u, v, ys, cs, out, out_x4, Hin,
+                Wout, Hout);
+  else
+    DRBA_LAUNCH(one, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, k, y, u, v, ys, cs, out, out_x4, Hin, Win, Hout, Wout);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
+template <class T>
+int to_out_yuv_crop_launch(void (*one)(YuvOut, const float *, T *, T *, T *, int, int, int, int, int, int),
+                           void (*rows)(YuvOut, const float *, T *, T *, T *, int, int, int, int, int), const float *in, T *y, T *u, T *v,
+                           int ys, int cs, int Hin, int Win, int Hout, int Wout, int matrix, int full_range, float maxval, void *stream) {
+  double kr, kb;
+  if (!yuv_args_ok(y, u, v, ys, cs, in, Hin, Win, Hout, Wout, Hout, Wout, maxval) || Hout > Hin || Wout > Win || !yuv_coeffs(matrix, kr, kb))
+    return DRBA_EINVAL;
+  const YuvOut k = yuv_out_consts(kr, kb, full_range, maxval);
+  const int Hc = (Hout + 1) / 2, Wc = (Wout + 1) / 2;
+  if (yuv_rows_form_ok(Win, Wout, 1.f, y, u, v, ys, cs, in))
+    DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 3) * Hc)), dim3(kBlock), 0, (hipStream_t)stream, k, in, y, u, v, ys, cs, Hin, Wout, Hout);
+  else
+    DRBA_LAUNCH(one, dim3(tiles_for(Wc, Hc)), dim3(kBlock), 0, (hipStream_t)stream, k, in, y, u, v, ys, cs, Hin, Win, Hout, Wout);
+  DRBA_CHECK_LAUNCH();
+  return DRBA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -844,6 +1206,50 @@ int drba_to_out16_yuv420(const float *in, uint16_t *y, uint16_t *u, uint16_t *v,
                          int Wout, float scale_y, float scale_x, int matrix, int full_range, float maxval, void *stream) {
   return to_out_yuv_launch(to_out16_yuv_kernel, to_out16_yuv_rows_kernel, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout, scale_y,
                            scale_x, matrix, full_range, maxval, stream);
+}
+
+// ---- fit = pad: each entry takes its resize sibling's arguments without the two scale factors -----------------------------------
+int drba_to_inp_pad_x4(const uint8_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, void *stream) {
+  return to_inp_pad_launch(to_inp_pad_kernel, to_inp_pad_rows_kernel, img_hwc, out, out_x4, Hin, Win, Hout, Wout, stream);
+}
+
+int drba_to_inp16_pad_x4(const uint16_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float maxval, void *stream) {
+  if (!maxval_ok(maxval) || ((uintptr_t)img_hwc & 1) != 0) return DRBA_EINVAL;
+  return to_inp_pad_launch(to_inp16_pad_kernel, to_inp16_pad_rows_kernel, img_hwc, out, out_x4, Hin, Win, Hout, Wout, stream, maxval);
+}
+
+int drba_to_out_crop(const float *in, uint8_t *out_hwc, int Hin, int Win, int Hout, int Wout, int reverse_channels, void *stream) {
+  return to_out_crop_launch(to_out_crop_kernel, to_out_crop_rows_kernel, in, out_hwc, Hin, Win, Hout, Wout, reverse_channels, stream);
+}
+
+int drba_to_out16_crop(const float *in, uint16_t *out_hwc, int Hin, int Win, int Hout, int Wout, int reverse_channels, float maxval,
+                       void *stream) {
+  if (!maxval_ok(maxval) || ((uintptr_t)out_hwc & 1) != 0) return DRBA_EINVAL;
+  return to_out_crop_launch(to_out16_crop_kernel, to_out16_crop_rows_kernel, in, out_hwc, Hin, Win, Hout, Wout, reverse_channels, stream, maxval);
+}
+
+int drba_to_inp_yuv420_pad_x4(const uint8_t *y, const uint8_t *u, const uint8_t *v, int y_stride, int c_stride, float *out, float *out_x4,
+                              int Hin, int Win, int Hout, int Wout, int matrix, int full_range, void *stream) {
+  return to_inp_yuv_pad_launch(to_inp_yuv_pad_kernel, to_inp_yuv_pad_rows_kernel, y, u, v, y_stride, c_stride, out, out_x4, Hin, Win, Hout, Wout,
+                               matrix, full_range, 255.f, stream);
+}
+
+int drba_to_inp16_yuv420_pad_x4(const uint16_t *y, const uint16_t *u, const uint16_t *v, int y_stride, int c_stride, float *out, float *out_x4,
+                                int Hin, int Win, int Hout, int Wout, int matrix, int full_range, float maxval, void *stream) {
+  return to_inp_yuv_pad_launch(to_inp16_yuv_pad_kernel, to_inp16_yuv_pad_rows_kernel, y, u, v, y_stride, c_stride, out, out_x4, Hin, Win, Hout,
+                               Wout, matrix, full_range, maxval, stream);
+}
+
+int drba_to_out_yuv420_crop(const float *in, uint8_t *y, uint8_t *u, uint8_t *v, int y_stride, int c_stride, int Hin, int Win, int Hout,
+                            int Wout, int matrix, int full_range, void *stream) {
+  return to_out_yuv_crop_launch(to_out_yuv_crop_kernel, to_out_yuv_crop_rows_kernel, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout,
+                                matrix, full_range, 255.f, stream);
+}
+
+int drba_to_out16_yuv420_crop(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win, int Hout,
+                              int Wout, int matrix, int full_range, float maxval, void *stream) {
+  return to_out_yuv_crop_launch(to_out16_yuv_crop_kernel, to_out16_yuv_crop_rows_kernel, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout,
+                                matrix, full_range, maxval, stream);
 }
 
 }  // extern "C"

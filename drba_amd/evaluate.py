@@ -2,7 +2,8 @@
 
     python -m drba_amd.evaluate compare A B [--json PATH] [--max-lsb N] [--min-psnr X] [--min-ssim X]
     python -m drba_amd.evaluate holdout -m rife -i CLIP [-k 3] [-scale 1.0] [-s] [-st 0.3] [--plain] [--nonlinear] [--deterministic]
-                                        [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--weights DIR] [--json PATH]
+                                        [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--fit resize|pad] [--weights DIR]
+                                        [--json PATH]
 
 `compare` reads two clips frame by frame (the sources infer.py reads: .npz, .npy + .json, a .y4m stream -- below --, a container
 when OpenCV is installed) and prints one JSON line: PSNR, ssim_matlab, the largest difference in LSB and the number of differing bytes, per
@@ -33,6 +34,10 @@ them on the device (`--yuv-matrix`, `--yuv-range` as in infer.py), emits packed 
 the device, and compares each with the original's planes, uploaded when its turn comes: memory does not grow with the clip.
 Kept frames pass through to_out(to_inp(frame)), which filters their chroma ("Pass-through frames"): their PSNR is
 finite, and the report says so in "kept_passthrough".
+
+`holdout --fit pad` pads the kept frames to the network size and crops the emissions (infer.py --fit pad) instead of resizing both
+ways: the scores then carry no resampling loss, a kept frame of an array clip or the luma of an in-gamut Y4M one comes back as it
+went in.  The report names the mode in "fit".
 
 Non-finite JSON numbers are written as the strings "inf" / "-inf" / "nan" (float() reads them back).
 """
@@ -339,7 +344,7 @@ class _HoldoutIO:
 
 
 def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.3, plain=False, backend=None, to_inp=None,
-            to_out=None, check_scene=None, maxval=None, linear=True, yuv_matrix="bt709", yuv_range="source"):
+            to_out=None, check_scene=None, maxval=None, linear=True, yuv_matrix="bt709", yuv_range="source", fit="resize"):
     """Keep every k-th frame of `frames` (uint8 [N,H,W,3], indexable), let interpolate_stream fill the gaps at `times = k`
     and compare every emission with the original frame at its position.  -> {"k", "m", "frames_used", "emissions",
     "pairs": [(emission, original)], "kept": ClipMetrics.result() + "positions", "held_out": the same}.
@@ -355,8 +360,13 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
     (metrics.YuvClipMetrics) with the original's planes, read and uploaded when its turn comes -- nothing is stored, memory does
     not grow with the clip.  The kept frames pass through to_out(to_inp(frame)): their chroma is interpolated up and averaged
     down again ("Pass-through frames"), so unlike those of an array clip they do not come back identical and
-    their PSNR is finite; the result says so in "kept_passthrough", beside "pixfmt", "depth" and "maxval"."""
+    their PSNR is finite; the result says so in "kept_passthrough", beside "pixfmt", "depth" and "maxval".
+    fit="pad": the default hooks pad the frames to the network size and crop the emissions instead of resizing both ways (infer.py
+    --fit pad), so the figures carry no resampling loss; hooks that are given are the caller's.  The result carries "fit"."""
     from drba_amd import infer as drv
+    if fit not in ("resize", "pad"):
+        raise ValueError(f"fit must be resize or pad, got {fit!r}")
+    fit_kw = {} if fit == "resize" else {"fit": fit}
     if plain and not linear:
         raise ValueError("--nonlinear and --plain exclude each other: a plain step is inference_ts, it has no DistanceRatioMap to retime")
     m, half = holdout_plan(len(frames), k)
@@ -375,17 +385,20 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
         from drba_amd import ops
         if yuv:  # packed planes on the device at the clip's own depth: compared there
             to_out = lambda x, size: ops.to_out_yuv(x, size, matrix=yuv_matrix, full_range=full, depth=frames.depth,  # noqa: E731
-                                                    maxval=mv if frames.depth == 16 else None)
+                                                    maxval=mv if frames.depth == 16 else None, **fit_kw)
         elif deep:
-            to_out = lambda x, size: ops.to_out(x, size, depth=16, maxval=mv)  # noqa: E731  (uint16 on the device: compared there)
+            to_out = lambda x, size: ops.to_out(x, size, depth=16, maxval=mv, **fit_kw)  # noqa: E731  (uint16 on the device: compared there)
         else:
-            to_out = lambda x, size: ops.to_out(x, size)  # noqa: E731  (uint8 on the device: compared there)
+            to_out = lambda x, size: ops.to_out(x, size, **fit_kw)  # noqa: E731  (uint8 on the device: compared there)
     if to_inp is None and deep:
         from drba_amd.models.utils import tools
-        to_inp = lambda fr, size: tools.to_inp(fr, size, maxval=mv)  # noqa: E731
+        to_inp = lambda fr, size: tools.to_inp(fr, size, maxval=mv, **fit_kw)  # noqa: E731
     if to_inp is None and yuv:
         from drba_amd.models.utils import tools
-        to_inp = lambda fr, size: tools.to_inp(fr, size, matrix=yuv_matrix, full_range=full)  # noqa: E731
+        to_inp = lambda fr, size: tools.to_inp(fr, size, matrix=yuv_matrix, full_range=full, **fit_kw)  # noqa: E731
+    if to_inp is None and fit_kw:
+        from drba_amd.models.utils import tools
+        to_inp = lambda fr, size: tools.to_inp(fr, size, **fit_kw)  # noqa: E731
     backend = backend or metrics.default_backend()
     if yuv:
         kept, held = metrics.YuvClipMetrics(backend=backend, maxval=mv), metrics.YuvClipMetrics(backend=backend, maxval=mv)
@@ -400,7 +413,7 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
         raise RuntimeError(f"hold-out at k = {k}: the run emitted {written} frames ({len(io.skipped)} without an original), "
                            f"expected {int(k) * (m + 1)} ({2 * half})")
     out = {"k": int(k), "m": m, "frames_used": m * int(k) + 1, "emissions": written, "plain": bool(plain), "linear": bool(linear),
-           "pairs": io.pairs}
+           "fit": fit, "pairs": io.pairs}
     if deep:
         out.update({"depth": 16, "maxval": mv})
     if yuv:
@@ -418,7 +431,7 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
 def holdout_report(res):
     """The JSON object of `holdout` without the per-frame lists."""
     rep = {"command": "holdout", "k": res["k"], "m": res["m"], "frames_used": res["frames_used"], "emissions": res["emissions"],
-           "plain": res["plain"], "linear": res["linear"]}
+           "plain": res["plain"], "linear": res["linear"], "fit": res.get("fit", "resize")}
     if "depth" in res:
         rep.update({"depth": res["depth"], "maxval": res["maxval"]})
     if res.get("pixfmt") == "yuv420":
@@ -456,6 +469,8 @@ def parse_args(argv=None):
                    help="YCbCr matrix of a .y4m clip (default bt709), as in infer.py")
     h.add_argument("--yuv-range", dest="yuv_range", type=str, default="source", choices=("source", "limited", "full"),
                    help="sample range of a .y4m clip: the header's XCOLORRANGE (default; limited when it has none) or the one named, as in infer.py")
+    h.add_argument("--fit", dest="fit", type=str, default="resize", choices=("resize", "pad"),
+                   help="how a frame gets to the network size and back, as in infer.py: resize (default) or pad (no resampling)")
     h.add_argument("--weights", type=str, default=None, help="weight directory (default: the model's, synthetic if absent)")
     h.add_argument("--json", dest="json_path", type=str, default=None)
     return p.parse_args(argv)
@@ -499,7 +514,7 @@ def main(argv=None, backend=None):
         else:
             kw = {"maxval": src.maxval} if src.depth == 16 else {}
         res = holdout(model, src if src.pixfmt == "yuv420" else src._frames, args.k, fps=src.fps, enable_scdet=args.enable_scdet,
-                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend, linear=not args.nonlinear, **kw)
+                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend, linear=not args.nonlinear, fit=args.fit, **kw)
         rep = holdout_report(res)
         rep.update({"model": args.model_type, "scale": args.scale, "input": args.input,
                     "weights": "synthetic (drba_amd.utils.synth): the figures say nothing about quality" if synthetic else wdir})

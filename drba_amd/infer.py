@@ -1,7 +1,7 @@
 """DRBA command line and per-frame driver loop (same CLI as the reference's infer.py).
 
     python infer.py -m rife -i in.npz -o out.npz [-fps 60 | -t 2] [-s] [-st 0.3] [-hw] [-scale 1.0] [--out-depth source|8|16]
-                    [--nonlinear] [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--deterministic]
+                    [--nonlinear] [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--deterministic] [--fit resize|pad]
 
 `--out-depth` is not in the reference: a .npz / .npy clip may hold uint16 frames, and the written frames are 8 or 16 bits deep
 (default: as the source, so an 8-bit clip is handled exactly as before).  `--nonlinear` is not in the reference either: its driver
@@ -16,6 +16,12 @@ A `.y4m` path, or `-` for stdin / stdout, at either end selects the YUV4MPEG2 so
 or 10 bits, converted inside the to_inp / to_out kernels): `ffmpeg -i a.mkv -f yuv4mpegpipe - | python infer.py -m rife -i - -o - -t 2
 | x264 --demuxer y4m -o b.264 -`.  `--yuv-matrix` and `--yuv-range` name the conversion; on a Y4M sink `--out-depth 16` writes
 C420p10.  Nothing is printed to stdout.
+
+`--fit pad` (not in the reference, whose frames are always resized to the network size and back): the frame sits at the top left
+of the network tensor, the bottom and right margins repeat its last row and column and are cropped away on the way out -- no
+resampling in either direction, so a frame the driver only copies (a scene cut, the head and the tail) comes back with the
+source's bytes.  The network sizes are those of `resize`.  Scene detection runs on the padded network input, so its decisions may
+differ from `resize` mode for a pair near the threshold.  The default, `resize`, is unchanged.
 
 The driver logic is host-side Python like the reference; the model calls it makes run on
 the HIP library.  `interpolate_stream` is the loop of reference infer.py:58-174 (drba_amd/driver.py) with the
@@ -59,7 +65,18 @@ def parse_args(argv=None):
     p.add_argument("--deterministic", dest="deterministic", action="store_true", default=False,
                    help="bit-reproducible output: the splats sum in an order fixed by the data and no timing picks a kernel "
                         "configuration (stored winners of `python -m drba_amd.tune` are still used)")
+    p.add_argument("--fit", dest="fit", type=str, default="resize", choices=("resize", "pad"),
+                   help="how a frame gets to the network size and back: resize (default, the reference's behaviour) or pad -- "
+                        "replicate padding at the bottom and right, cropped away on the way out, no resampling")
     return p.parse_args(argv)
+
+
+def fit_of(args):
+    """--fit as the hooks take it.  A namespace built without the flag means resize."""
+    v = getattr(args, "fit", "resize")
+    if v not in ("resize", "pad"):
+        raise ValueError(f"--fit must be resize or pad, got {v!r}")
+    return v
 
 
 def apply_deterministic(args):
@@ -136,22 +153,29 @@ def inference(model, args):
     except ImportError:
         bar, step = None, None
     to_inp = to_out = None
+    # --fit pad: every hook carries the keyword (the plain 8-bit pair too, which otherwise is interpolate_stream's default); a
+    # resize run makes the calls it always made
+    fit_kw = {} if fit_of(args) == "resize" else {"fit": fit_of(args)}
+    if fit_kw:
+        to_inp = lambda fr, size: _tools.to_inp(fr, size, **fit_kw)  # noqa: E731
+        to_out = lambda x, size: _tools.to_out(x, size, **fit_kw)  # noqa: E731
     rgb = bool(getattr(video_io, "wants_rgb", False))
     if rgb:  # encoder pipe / raw sink: BGR -> RGB inside the to_out kernel, not on the host
         video_io.frames_are_rgb = True
-        to_out = lambda x, size: _tools.to_out(x, size, rgb=True)  # noqa: E731
+        to_out = lambda x, size: _tools.to_out(x, size, rgb=True, **fit_kw)  # noqa: E731
     # 16-bit frames at either end: the hooks carry the depth and the clip's maxval, the loop between them never looks at a frame
     if getattr(video_io, "depth", 8) == 16:
-        to_inp = lambda fr, size: _tools.to_inp(fr, size, maxval=video_io.maxval)  # noqa: E731
+        to_inp = lambda fr, size: _tools.to_inp(fr, size, maxval=video_io.maxval, **fit_kw)  # noqa: E731
     if getattr(video_io, "out_depth", 8) == 16:
-        to_out = lambda x, size: _tools.to_out(x, size, rgb=rgb, depth=16, maxval=video_io.out_maxval)  # noqa: E731
+        to_out = lambda x, size: _tools.to_out(x, size, rgb=rgb, depth=16, maxval=video_io.out_maxval, **fit_kw)  # noqa: E731
     # planar 4:2:0 at either end, each on its own: a YuvFrame knows its depth, the planar sink takes the 1-D Y, U, V array
     if getattr(video_io, "pixfmt", "bgr") == "yuv420":
-        to_inp = lambda fr, size: _tools.to_inp(fr, size, matrix=video_io.yuv_matrix, full_range=video_io.yuv_full_range)  # noqa: E731
+        to_inp = lambda fr, size: _tools.to_inp(fr, size, matrix=video_io.yuv_matrix, full_range=video_io.yuv_full_range,  # noqa: E731
+                                                **fit_kw)
     if getattr(video_io, "out_pixfmt", "bgr") == "yuv420":
         mv = video_io.out_maxval if video_io.out_depth == 16 else None
         to_out = lambda x, size: _tools.to_out(x, size, depth=video_io.out_depth, maxval=mv, pixfmt="yuv420",  # noqa: E731
-                                               matrix=video_io.yuv_matrix, full_range=video_io.out_full_range)
+                                               matrix=video_io.yuv_matrix, full_range=video_io.out_full_range, **fit_kw)
     n = interpolate_stream(model, video_io, args.dst_fps, times=args.times, enable_scdet=args.enable_scdet,
                            scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, on_step=step,
                            linear=not getattr(args, "nonlinear", False))
@@ -192,11 +216,17 @@ def inference_sharded(model, args, rank, world, to_inp=None, to_out=None, check_
                          f"{frames.dtype} frames, --out-depth is {getattr(args, 'out_depth', 'source')}; run 16-bit clips on one GPU")
     counts = parallel.emission_counts(len(frames), fps, args.dst_fps, args.times, world)
     sg = parallel.StreamedGather(rank, world, counts, chunk=chunk, device=device, frame_shape=tuple(frames[0].shape))
+    # --fit pad: the default hooks of the shard carry the keyword, as in inference (hooks the caller gives are the caller's)
+    fit_kw = {} if fit_of(args) == "resize" else {"fit": fit_of(args)}
+    if to_inp is None and fit_kw:
+        to_inp = lambda fr, size: _tools.to_inp(fr, size, **fit_kw)  # noqa: E731
     if to_out is None and world > 1 and device is not None and device.type == "cuda":
         # finished frames stay on the device until the gather has moved them (tools.to_out would copy each one to the
         # host only for StreamedGather to copy it back): the uint8 frame is written straight into the send path
         from drba_amd import ops as _ops
-        to_out = lambda x, size: _ops.to_out(x, size)  # noqa: E731
+        to_out = lambda x, size: _ops.to_out(x, size, **fit_kw)  # noqa: E731
+    elif to_out is None and fit_kw:
+        to_out = lambda x, size: _tools.to_out(x, size, **fit_kw)  # noqa: E731
     parallel.interpolate_shard(model, frames, fps, args.dst_fps, rank, world, times=args.times, enable_scdet=args.enable_scdet,
                                scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, check_scene=check_scene,
                                sink=sg.push, linear=not getattr(args, "nonlinear", False))

@@ -29,9 +29,10 @@ def check_cupy_env():
 
 # ----------------------------------------------------------------------------- sizes / conversion
 def get_valid_net_inp_size(img, scale, div=64):
-    """Network input size: each side rounded up so that side*scale is a multiple of `div`
-    (frames are later *resized*, not padded).  Float arithmetic then int(), as in
-    reference tools.py:41-56, so 1080 -> 1088 (div 64), 1152 (div 128); 2160@0.5 -> 2176."""
+    """Network input size: each side rounded up so that side*scale is a multiple of `div`.
+    How a frame gets to that size is to_inp's `fit`: resized to it (the default, as the reference does) or
+    replicate-padded at the bottom and right (fit="pad"); the size is the same either way.  Float arithmetic
+    then int(), as in reference tools.py:41-56, so 1080 -> 1088 (div 64), 1152 (div 128); 2160@0.5 -> 2176."""
     src_h, src_w = int(img.shape[0]), int(img.shape[1])
 
     def round_up(v):
@@ -89,46 +90,58 @@ def resize(tensor, size):
     return _ops.resize_bilinear(tensor, size)
 
 
-def to_inp(npInp, dst_size, device=None, maxval=None, matrix="bt709", full_range=False):
+def _fit_kw(fit):
+    """`fit` as the ops entries take it; the default is left out, so a resize call is the call it always was"""
+    if fit not in _ops.FITS:
+        raise ValueError(f"fit must be one of {_ops.FITS}, got {fit!r}")
+    return {} if fit == "resize" else {"fit": fit}
+
+
+def to_inp(npInp, dst_size, device=None, maxval=None, matrix="bt709", full_range=False, fit="resize"):
     """resize(to_tensor(npInp), dst_size) (tools.py:59-60) as one kernel on the uploaded uint8 frame (the full-size
     fp32 frame of the reference is never materialised); bit-exact with the two-step form.  A uint16 frame goes through the
     16-bit kernel with its `maxval` (65535 unless given).  A planar 4:2:0 frame (y4m.YuvFrame) is uploaded as it stands -- half
     the bytes of a BGR frame -- and converted with `matrix` / `full_range` inside the kernel (ops.to_inp_yuv); the frame knows its
-    own depth."""
+    own depth.  fit="pad" (not in the reference): the frame is replicate-padded to `dst_size` at the bottom and right instead of
+    resized (ops.to_inp)."""
+    fit_kw = _fit_kw(fit)
     device = _ops.default_device() if device is None else device
     if isinstance(npInp, _y4m.YuvFrame):
         if maxval not in (None, npInp.maxval):
             raise ValueError(f"a {npInp.depth}-bit 4:2:0 frame has maxval {npInp.maxval}, got {maxval}")
         planes = torch.from_numpy(npInp.data if npInp.data.flags.writeable else npInp.data.copy()).to(device, non_blocking=True)
         return _ops.to_inp_yuv(planes, npInp.shape[:2], dst_size, matrix=matrix, full_range=full_range,
-                               maxval=None if npInp.depth == 8 else npInp.maxval)
+                               maxval=None if npInp.depth == 8 else npInp.maxval, **fit_kw)
     if torch.is_tensor(npInp):
         u8 = npInp.to(device, non_blocking=True)
     else:
         u8 = torch.from_numpy(np.ascontiguousarray(npInp)).to(device, non_blocking=True)
     if _is_u16(u8):
-        return _ops.to_inp(u8, dst_size, maxval=maxval)
+        return _ops.to_inp(u8, dst_size, maxval=maxval, **fit_kw)
     if maxval is not None:
         raise ValueError("maxval belongs to 16-bit frames (uint16)")
-    return _ops.to_inp(u8, dst_size)
+    return _ops.to_inp(u8, dst_size, **fit_kw)
 
 
-def to_out(tenInp, src_size, rgb=False, depth=8, maxval=None, pixfmt="bgr", matrix="bt709", full_range=False):
+def to_out(tenInp, src_size, rgb=False, depth=8, maxval=None, pixfmt="bgr", matrix="bt709", full_range=False, fit="resize"):
     """to_cv2(resize(tenInp, src_size)) (tools.py:63-64) as one kernel + the D2H copy.  rgb=True returns the frame in RGB
     order (the flip the reference's writer thread does on the host, tools.py:202, done on the device instead).  depth=16
     returns a uint16 frame scaled to `maxval` (65535 unless given), rounded and saturated (ops.to_out).  pixfmt="yuv420" returns
-    the frame as planar 4:2:0 instead, one 1-D array holding Y, U, V (ops.to_out_yuv; at depth 16 scaled to 1023 unless given)."""
+    the frame as planar 4:2:0 instead, one 1-D array holding Y, U, V (ops.to_out_yuv; at depth 16 scaled to 1023 unless given).
+    fit="pad" (not in the reference): the top-left `src_size` window of tenInp is converted as it stands -- the counterpart of
+    to_inp(..., fit="pad") -- instead of the resize."""
     _check_depth(depth, maxval)
+    fit_kw = _fit_kw(fit)
     if pixfmt not in ("bgr", "yuv420"):
         raise ValueError(f"pixfmt must be bgr or yuv420, got {pixfmt!r}")
     if pixfmt == "yuv420":
         if rgb:
             raise ValueError("rgb=True belongs to packed frames (pixfmt='bgr')")
-        frame = _ops.to_out_yuv(tenInp, src_size, matrix=matrix, full_range=full_range, depth=depth, maxval=maxval).cpu().numpy()
+        frame = _ops.to_out_yuv(tenInp, src_size, matrix=matrix, full_range=full_range, depth=depth, maxval=maxval, **fit_kw).cpu().numpy()
     elif depth == 16:
-        frame = _ops.to_out(tenInp, src_size, rgb=rgb, depth=16, maxval=maxval).cpu().numpy()
+        frame = _ops.to_out(tenInp, src_size, rgb=rgb, depth=16, maxval=maxval, **fit_kw).cpu().numpy()
     else:
-        frame = _ops.to_out(tenInp, src_size, rgb=rgb).cpu().numpy()
+        frame = _ops.to_out(tenInp, src_size, rgb=rgb, **fit_kw).cpu().numpy()
     # the copy has waited for every kernel behind this frame: had one of the two-term fp16 kernels overflowed on the way, its
     # status byte is set by now -- raise here rather than hand the frame to the writer (ops.check_overflow: a host memory read)
     _ops.check_overflow(tenInp.device)

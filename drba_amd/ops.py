@@ -582,9 +582,25 @@ def f32nchw_to_u16hwc(x, maxval=None):
     return _f32nchw_to_hwc(x, torch.uint16, maxval)
 
 
-def to_inp(img_u8, dst_size, maxval=None):
+FITS = ("resize", "pad")
+
+
+def _fit(fit, way, frame, net):
+    """`fit` of the four frame conversions -> whether it is "pad".  "resize" (the default, the reference's behaviour): the frame is
+    resampled to the network size and back.  "pad": the frame sits at the top left of the network tensor, the bottom and right
+    margins repeat its last row and column on the way in and are cropped away on the way out -- no interpolation in either
+    direction, so the network tensor must be at least the frame."""
+    if fit not in FITS:
+        raise ValueError(f"fit must be one of {FITS}, got {fit!r}")
+    if fit == "pad" and (net[0] < frame[0] or net[1] < frame[1]):
+        raise ValueError(f"fit='pad' on the way {way}: the network tensor {tuple(net)} is smaller than the frame {tuple(frame)}")
+    return fit == "pad"
+
+
+def to_inp(img_u8, dst_size, maxval=None, fit="resize"):
     """tools.to_inp on a device-resident frame: uint8 [H,W,3] -> fp32 [1,3,*dst_size] in [0,1], one kernel.  A uint16 [H,W,3]
-    frame takes the 16-bit kernel: its samples are divided by `maxval` (65535 unless given; 255 < maxval <= 65535)."""
+    frame takes the 16-bit kernel: its samples are divided by `maxval` (65535 unless given; 255 < maxval <= 65535).
+    fit="pad": replicate padding to `dst_size` instead of the resize (_fit)."""
     if not (_is_frame(img_u8, torch.uint8) or _is_frame(img_u8, torch.uint16)):
         raise _lib.DrbaHipError("expected a CUDA uint8 or uint16 [H,W,3] tensor")
     size, tag, mv = _sample_kind(img_u8.dtype, maxval)
@@ -594,21 +610,25 @@ def to_inp(img_u8, dst_size, maxval=None):
     out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=img.device)
     # ... and the same frame pixel-major, [H,W,4]: what the gathers read their image taps from (IMG_X4), written in the same pass
     x4 = torch.empty((ho, wo, 4), dtype=torch.float32, device=img.device) if IMG_X4 else None
-    sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))  # ATen: static_cast<float>(in) / out
-    entry = f"drba_to_inp{tag}_x4"
-    _lib.check(_timed("to_inp" + tag, (h, w, ho, wo), 3.0 * size * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
-                      lambda: getattr(_lib.load(), entry)(_p(img), _p(out), _p(x4), h, w, ho, wo, sy, sx, *mv, _stream())), entry)
+    pad = _fit(fit, "in", (h, w), (ho, wo))
+    # ATen: static_cast<float>(in) / out
+    scales = () if pad else (float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo)))
+    entry = f"drba_to_inp{tag}_pad_x4" if pad else f"drba_to_inp{tag}_x4"
+    _lib.check(_timed("to_inp" + tag + ("_pad" if pad else ""), (h, w, ho, wo),
+                      3.0 * size * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
+                      lambda: getattr(_lib.load(), entry)(_p(img), _p(out), _p(x4), h, w, ho, wo, *scales, *mv, _stream())), entry)
     if x4 is not None:
         _set_copy(out, "_drba_x4", x4)
     return out
 
 
-def to_out(x, src_size, rgb=False, depth=8, maxval=None):
+def to_out(x, src_size, rgb=False, depth=8, maxval=None, fit="resize"):
     """tools.to_out without the D2H copy: fp32 [1,3,h,w] -> uint8 [*src_size,3] on the device, one kernel
     (resize + *255. truncation; rgb=True also flips BGR -> RGB for the encoder pipe).
     depth=16: a torch.uint16 [*src_size,3] frame instead -- resize, * maxval (65535 unless given), rounded to nearest even and
     saturated to [0, maxval], NaN -> 0: the 8-bit path keeps the reference's truncation because its bytes must equal the
-    reference's, a 16-bit frame has no reference to equal."""
+    reference's, a 16-bit frame has no reference to equal.
+    fit="pad": the top-left `src_size` window of x is quantised as it stands instead of the resize (_fit)."""
     if depth not in (8, 16):
         raise ValueError(f"depth must be 8 or 16, got {depth!r}")
     if depth == 8 and maxval is not None:
@@ -617,13 +637,14 @@ def to_out(x, src_size, rgb=False, depth=8, maxval=None):
     assert x.shape[0] == 1 and x.shape[1] == 3
     h, w = x.shape[2:]
     ho, wo = int(src_size[0]), int(src_size[1])
-    sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))
+    pad = _fit(fit, "out", (ho, wo), (h, w))
+    scales = () if pad else (float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo)))
     dtype = torch.uint16 if depth == 16 else torch.uint8
     size, tag, mv = _sample_kind(dtype, maxval)
     out = torch.empty((ho, wo, 3), dtype=dtype, device=x.device)
-    entry = "drba_to_out" + tag
-    _lib.check(_timed("to_out" + tag, (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 3.0 * size * ho * wo, "byte",
-                      lambda: getattr(_lib.load(), entry)(_p(x), _p(out), h, w, ho, wo, sy, sx, 1 if rgb else 0, *mv, _stream())), entry)
+    entry = "drba_to_out" + tag + ("_crop" if pad else "")
+    _lib.check(_timed("to_out" + tag + ("_crop" if pad else ""), (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 3.0 * size * ho * wo, "byte",
+                      lambda: getattr(_lib.load(), entry)(_p(x), _p(out), h, w, ho, wo, *scales, 1 if rgb else 0, *mv, _stream())), entry)
     return out
 
 
@@ -651,11 +672,13 @@ def yuv420_layout(size):
     return h * w, hc * wc, hc, wc
 
 
-def to_inp_yuv(planes, size, dst_size, matrix="bt709", full_range=False, maxval=None):
+def to_inp_yuv(planes, size, dst_size, matrix="bt709", full_range=False, maxval=None, fit="resize"):
     """to_inp for a planar YCbCr 4:2:0 frame on the device: `planes` is one contiguous 1-D tensor holding Y [H,W], then U, then V
     [ceil(H/2),ceil(W/2)] of a frame of `size` = (H, W) -- uint8 samples, or uint16 ones in [0, maxval] (1023 unless given) --
     -> fp32 [1,3,*dst_size] in [0,1], BGR channel order, one kernel: chroma interpolation, colour conversion and the resize
-    (include/drba_hip.h, ABI 14).  The [H,W,4] copy is written in the same pass, as in to_inp."""
+    (include/drba_hip.h, ABI 14).  The [H,W,4] copy is written in the same pass, as in to_inp.
+    fit="pad": the converted frame is replicate-padded to `dst_size` instead of resized (_fit); a margin pixel is the converted
+    pixel of the clamped source coordinate."""
     if not (torch.is_tensor(planes) and planes.is_cuda and planes.dim() == 1 and planes.dtype in (torch.uint8, torch.uint16)):
         raise _lib.DrbaHipError("expected a CUDA uint8 or uint16 1-D tensor of packed Y, U, V planes")
     mid, dtype, tag, mv = _yuv_args(matrix, 8 if planes.dtype == torch.uint8 else 16, maxval)
@@ -667,37 +690,42 @@ def to_inp_yuv(planes, size, dst_size, matrix="bt709", full_range=False, maxval=
     ho, wo = int(dst_size[0]), int(dst_size[1])
     out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=planes.device)
     x4 = torch.empty((ho, wo, 4), dtype=torch.float32, device=planes.device) if IMG_X4 else None
-    sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))
+    pad = _fit(fit, "in", (h, w), (ho, wo))
+    scales = () if pad else (float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo)))
     es = planes.element_size()
     base = planes.data_ptr()
     y, u, v = C.c_void_p(base), C.c_void_p(base + ny * es), C.c_void_p(base + (ny + nc) * es)
-    entry = f"drba_to_inp{tag}_yuv420_x4"
-    _lib.check(_timed("to_inp_yuv" + tag, (h, w, ho, wo), 1.5 * es * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
-                      lambda: getattr(_lib.load(), entry)(y, u, v, w, wc, _p(out), _p(x4), h, w, ho, wo, sy, sx, mid, 1 if full_range else 0,
+    entry = f"drba_to_inp{tag}_yuv420_pad_x4" if pad else f"drba_to_inp{tag}_yuv420_x4"
+    _lib.check(_timed("to_inp_yuv" + tag + ("_pad" if pad else ""), (h, w, ho, wo),
+                      1.5 * es * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
+                      lambda: getattr(_lib.load(), entry)(y, u, v, w, wc, _p(out), _p(x4), h, w, ho, wo, *scales, mid, 1 if full_range else 0,
                                                           *mv, _stream())), entry)
     if x4 is not None:
         _set_copy(out, "_drba_x4", x4)
     return out
 
 
-def to_out_yuv(x, src_size, matrix="bt709", full_range=False, depth=8, maxval=None):
+def to_out_yuv(x, src_size, matrix="bt709", full_range=False, depth=8, maxval=None, fit="resize"):
     """to_out to a planar YCbCr 4:2:0 frame on the device: fp32 [1,3,h,w] (BGR) -> ONE contiguous 1-D tensor holding Y [*src_size],
     then U, then V [ceil(H/2),ceil(W/2)], uint8 (depth 8) or uint16 scaled to `maxval` (depth 16; 1023 unless given): resize, clamp,
-    colour conversion, 2 x 2 chroma mean, round to nearest even, in one kernel.  One D2H copy and one write per frame."""
+    colour conversion, 2 x 2 chroma mean, round to nearest even, in one kernel.  One D2H copy and one write per frame.
+    fit="pad": the top-left `src_size` window of x is converted as it stands instead of the resize (_fit); the chroma mean never
+    reads the margin."""
     mid, dtype, tag, mv = _yuv_args(matrix, depth, maxval)
     x = _f32(x)
     assert x.shape[0] == 1 and x.shape[1] == 3
     h, w = x.shape[2:]
     ho, wo = int(src_size[0]), int(src_size[1])
     ny, nc, _, wc = yuv420_layout((ho, wo))
-    sy, sx = float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo))
+    pad = _fit(fit, "out", (ho, wo), (h, w))
+    scales = () if pad else (float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo)))
     out = torch.empty(ny + 2 * nc, dtype=dtype, device=x.device)
     es = out.element_size()
     base = out.data_ptr()
     y, u, v = C.c_void_p(base), C.c_void_p(base + ny * es), C.c_void_p(base + (ny + nc) * es)
-    entry = f"drba_to_out{tag}_yuv420"
-    _lib.check(_timed("to_out_yuv" + tag, (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 1.5 * es * ho * wo, "byte",
-                      lambda: getattr(_lib.load(), entry)(_p(x), y, u, v, wo, wc, h, w, ho, wo, sy, sx, mid, 1 if full_range else 0, *mv,
+    entry = f"drba_to_out{tag}_yuv420" + ("_crop" if pad else "")
+    _lib.check(_timed("to_out_yuv" + tag + ("_crop" if pad else ""), (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 1.5 * es * ho * wo, "byte",
+                      lambda: getattr(_lib.load(), entry)(_p(x), y, u, v, wo, wc, h, w, ho, wo, *scales, mid, 1 if full_range else 0, *mv,
                                                           _stream())), entry)
     return out
 

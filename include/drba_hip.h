@@ -34,7 +34,9 @@ extern "C" {
 
 /* ABI version.  16: drba_ssim2d / drba_ssim2d_ws_floats (the single-channel 2-D ssim of pytorch_msssim on N planes addressed by a row and
  * an item stride -- the luma planes of packed 4:2:0 frames --, fp32, uint8 or uint16 samples, fp64 accumulation): additions only,
- * no earlier entry changes.  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
+ * no earlier entry changes; and, added under the same number, the fit = pad frame conversions -- drba_to_inp_pad_x4 / drba_to_inp16_pad_x4 /
+ * drba_to_out_crop / drba_to_out16_crop / drba_to_inp_yuv420_pad_x4 / drba_to_inp16_yuv420_pad_x4 / drba_to_out_yuv420_crop /
+ * drba_to_out16_yuv420_crop (replicate padding on the way in, a crop on the way out, no interpolation): additions only.  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
  * the splat entry points: drba_flow_reverse, drba_drm_rife_linear(_batch), drba_drm_rife_nonlinear(_batch), drba_softsplat and
  * drba_softsplat_index; while it is on, drba_rife_splat_ws_floats reports the larger workspace of the fixed-point accumulator):
  * additions only, nothing changes while the switch is off.  14: planar YCbCr 4:2:0 frames -- drba_to_inp_yuv420_x4 / drba_to_inp16_yuv420_x4 / drba_to_out_yuv420 /
@@ -294,6 +296,32 @@ int drba_to_out_yuv420(const float *in, uint8_t *y, uint8_t *u, uint8_t *v, int 
                        int Wout, float scale_y, float scale_x, int matrix, int full_range, void *stream);
 int drba_to_out16_yuv420(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win,
                          int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range, float maxval, void *stream);
+/* ABI 16, fit = pad: the eight conversions above without a resize.  Each entry takes its sibling's arguments minus the two scale
+ * factors and has the same general and rows forms under the same rule (the width unchanged and a
+ * multiple of 4, or of 8 for planar frames, the pointers aligned as there).
+ * Way in (Hout >= Hin and Wout >= Win, otherwise DRBA_EINVAL): the frame sits at the top left of the network tensor and the bottom
+ * and right margins repeat its last row and column, out(y, x) = to_unit(in(min(y, Hin - 1), min(x, Win - 1))); a planar frame gives
+ * the converted PIXEL of the clamped source coordinate (its luma sample, the 2 x 2 chroma taps of that coordinate).  The values
+ * inside the frame are those of the resize entries called with Hout = Hin, Wout = Win, bit for bit.
+ * Way out (Hout <= Hin and Wout <= Win, otherwise DRBA_EINVAL): the top-left Hout x Wout window of fp32 [1,3,Hin,Win] goes through
+ * each depth's quantiser as it stands -- bytes: trunc(x * 255); 16-bit and planar: the copy of an unresized axis (a non-finite
+ * value becomes NaN, then 0), round to nearest even, saturate; planar chroma is the 2 x 2 mean over the WINDOW, a pixel past an odd
+ * edge repeating the window's edge pixel.  Only the pixel itself is read: nothing outside the window, no neighbour. */
+int drba_to_inp_pad_x4(const uint8_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, void *stream);
+int drba_to_inp16_pad_x4(const uint16_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float maxval,
+                         void *stream);
+int drba_to_out_crop(const float *in, uint8_t *out_hwc, int Hin, int Win, int Hout, int Wout, int reverse_channels, void *stream);
+int drba_to_out16_crop(const float *in, uint16_t *out_hwc, int Hin, int Win, int Hout, int Wout, int reverse_channels, float maxval,
+                       void *stream);
+int drba_to_inp_yuv420_pad_x4(const uint8_t *y, const uint8_t *u, const uint8_t *v, int y_stride, int c_stride, float *out,
+                              float *out_x4, int Hin, int Win, int Hout, int Wout, int matrix, int full_range, void *stream);
+int drba_to_inp16_yuv420_pad_x4(const uint16_t *y, const uint16_t *u, const uint16_t *v, int y_stride, int c_stride, float *out,
+                                float *out_x4, int Hin, int Win, int Hout, int Wout, int matrix, int full_range, float maxval,
+                                void *stream);
+int drba_to_out_yuv420_crop(const float *in, uint8_t *y, uint8_t *u, uint8_t *v, int y_stride, int c_stride, int Hin, int Win,
+                            int Hout, int Wout, int matrix, int full_range, void *stream);
+int drba_to_out16_yuv420_crop(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win,
+                              int Hout, int Wout, int matrix, int full_range, float maxval, void *stream);
 
 /* ---- scene-cut metric: tools.py:27-30 + pytorch_msssim/__init__.py:83-136 (ssim_matlab)
  * x1, x2: [1,3,32,32] thumbnails (already resized); out: 1 float on device. */
