@@ -101,6 +101,8 @@ SIGNATURES = {
     "drba_to_out_yuv420_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "drba_to_out16_yuv420_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
     "drba_ssim3d_32": (_i, [_p, _p, _p, _p]),
+    "drba_dup_stats_ws_floats": (_z, [_i, _i, _i]),
+    "drba_dup_stats_f32": (_i, [_p, _p, _i, _i, _i, _f, _p, _p, _p]),
     "drba_ssim3d_ws_floats": (_z, [_i, _i, _i]),
     "drba_ssim3d": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _d, _p]),
     "drba_ssim2d_ws_floats": (_z, [_i, _i, _i]),

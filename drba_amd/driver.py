@@ -34,8 +34,72 @@ class SceneCuts:
         return self.known[k]
 
 
+class KeptFrames:
+    """--dedup's filter over the frame source: next() hands out the network inputs of the frames that are kept, in order, None past
+    the end.  Every raw frame of get(k) is converted once with to_inp and tested against the previous SOURCE frame, kept or not
+    (drba_amd.dedup: mpdecimate's rule on ops.dup_stats), so the decisions do not depend on one another and are asked for `ahead`
+    frames before they are needed: by the time one is read (after its own event) the host is not in lock step with the device.
+    A dropped frame is never seen by the driver -- no prefetch_frame, no prefetch_pair, no scene test.  Frame 0 is kept; after
+    settings.max_run drops in a row the next frame is kept untested; if fewer than two frames would be kept the last one is too.
+    kept[u] is the source index of the u-th kept frame, total the number of source frames once the source has ended; on_kept(k)
+    fires as frame k is kept.  check_dup(a, b) -> bool, called in place, replaces the device test (frames on the host).
+    stream() -> the HIP stream to_inp and the tests run on for a frame on the device (the model's intake stream) or None: every
+    frame is made there and handed to the stream current at next() (drba_amd.handoff)."""
+
+    def __init__(self, get, to_inp, settings, check_dup=None, stream=None, on_kept=None, ahead=4):
+        self.get, self.to_inp, self.set, self.check_dup, self.on_kept = get, to_inp, settings, check_dup, on_kept
+        self.stream_of, self.stream, self.ahead = stream, None, max(int(ahead), 1)
+        self.kept, self.total = [], None
+        self._q, self._read, self._prev, self._run = [], 0, None, 0  # _q: [k, network input, pending test, event, the frame before]
+
+    def _fill(self):
+        while len(self._q) <= self.ahead and self.total is None:
+            raw = self.get(self._read)
+            if raw is None:
+                self.total = self._read
+                break
+            if self._read == 0 and self.stream_of is not None:
+                self.stream = self.stream_of()
+            with contextlib.nullcontext() if self.stream is None else torch.cuda.stream(self.stream):
+                x = self.to_inp(raw)
+                test = None
+                if self._prev is not None and self.check_dup is None:
+                    from drba_amd import ops
+                    test = ops.dup_stats_async(self._prev, x, self.set.lo)
+                ev = handoff.event_on(self.stream) if self.stream is not None and x.is_cuda else None
+            self._q.append([self._read, x, test, ev, self._prev])
+            self._read, self._prev = self._read + 1, x
+
+    def _repeats(self, x, test, prev):
+        if self.check_dup is not None:
+            return bool(self.check_dup(prev, x))
+        from drba_amd import dedup, ops
+        host, ev = test
+        ev.synchronize()
+        return dedup.is_dup(*ops.dup_stats_decode(host), hi=self.set.hi, frac=self.set.frac)
+
+    def next(self):
+        while True:
+            self._fill()
+            if not self._q:
+                return None
+            k, x, test, ev, prev = self._q.pop(0)
+            self._fill()  # (is frame k the last of the source?)
+            last = self.total is not None and not self._q
+            if k > 0 and self._run < self.set.max_run and not (last and len(self.kept) < 2) and self._repeats(x, test, prev):
+                self._run += 1
+                continue
+            self._run = 0
+            self.kept.append(k)
+            if self.on_kept is not None:
+                self.on_kept(k)
+            if ev is not None:
+                handoff.hand_to(torch.cuda.current_stream(x.device), x, ev)
+            return x
+
+
 def run(model, get, pair, first, to_inp, emit, cuts, ts_of, state=(False, None), head=True, tail=True, on_step=None,
-        announce_ungrouped=False, linear=True):
+        announce_ungrouped=False, linear=True, even_of=None):
     """Drive the model from loop iteration `first` until the frame source ends.
 
     get(k): raw source frame k, or None past the end (not asked again after that).  pair: [I0, I1], the network inputs of
@@ -45,6 +109,8 @@ def run(model, get, pair, first, to_inp, emit, cuts, ts_of, state=(False, None),
     ts_of(idx) -> tools.calc_t of iteration idx.  state: (cut_left, reuse) entering iteration `first` when there is no head
     (the head is a cold start and tests the first pair itself).  on_step(idx) fires after the head (idx = first), after
     every iteration and after the tail.  announce_ungrouped: name the following iterations to a GROUP = 1 model too.
+    even_of(idx) -> bool (--dedup; None: every iteration): are the two intervals of iteration idx equal?  An iteration over unequal
+    ones is two pairwise steps, `reuse` is dropped as beside a cut, and no group or look-ahead is announced across it.
     linear: the `linear` of every inference_ts_drba call -- True, the reference driver's (infer.py:143); False runs the clip
     through the non-linear DistanceRatioMap (get_drm_t), which the reference's model entry point defaults to but its driver never
     asks for.
@@ -139,14 +205,19 @@ def run(model, get, pair, first, to_inp, emit, cuts, ts_of, state=(False, None),
             reuse = None
             out = model.inference_ts(I0, I1, ts[ts <= 1])
             out.extend([I1 for _ in ts[ts > 1] - 1])
-        elif can_look and ahead:
+        elif even_of is not None and not even_of(idx):
+            # unequal intervals: the DistanceRatioMap compares distances over two equal ones -- the two pairs on their own, as beside a cut
+            reuse = None
+            out = model.inference_ts(I0, I1, ts[ts <= 1])
+            out.extend(model.inference_ts(I1, I2, ts[ts > 1] - 1))
+        elif can_look and ahead and (even_of is None or even_of(idx + 1)):
             look = (ahead[0], ts_of(idx + 1))
             if prefetch is not None and (group > 1 or announce_ungrouped):
                 # the following iterations, as far as they are DRBA steps too (no cut up to the last frame named): the model may
                 # take them in one stacked pass with this one and stage the group after them
                 entries, prev = [], I2
                 for j, x in enumerate(ahead):
-                    if cuts.cut(idx + 2 + j, prev, x):
+                    if cuts.cut(idx + 2 + j, prev, x) or (even_of is not None and not even_of(idx + 1 + j)):
                         break
                     entries += [x, ts_of(idx + 1 + j)]
                     prev = x

@@ -3,7 +3,9 @@
     python -m drba_amd.evaluate compare A B [--json PATH] [--max-lsb N] [--min-psnr X] [--min-ssim X]
     python -m drba_amd.evaluate holdout -m rife -i CLIP [-k 3] [-scale 1.0] [-s] [-st 0.3] [--plain] [--nonlinear] [--deterministic]
                                         [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--fit resize|pad] [--weights DIR]
-                                        [--json PATH]
+                                        [--dedup [--dedup-hi X] [--dedup-lo X] [--dedup-frac X] [--dedup-max N]] [--json PATH]
+    python -m drba_amd.evaluate dups CLIP [-m rife] [-scale 1.0] [--fit resize|pad] [--dedup-hi X] [--dedup-lo X] [--dedup-frac X]
+                                          [--dedup-max N] [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--json PATH]
 
 `compare` reads two clips frame by frame (the sources infer.py reads: .npz, .npy + .json, a .y4m stream -- below --, a container
 when OpenCV is installed) and prints one JSON line: PSNR, ssim_matlab, the largest difference in LSB and the number of differing bytes, per
@@ -38,6 +40,11 @@ finite, and the report says so in "kept_passthrough".
 `holdout --fit pad` pads the kept frames to the network size and crops the emissions (infer.py --fit pad) instead of resizing both
 ways: the scores then carry no resampling loss, a kept frame of an array clip or the luma of an in-gamut Y4M one comes back as it
 went in.  The report names the mode in "fit".
+
+`dups` is how the thresholds of `infer.py --dedup` are picked for a noisy encode: for every source pair of a clip (.npz, .npy, .y4m) it
+prints the duplicate statistic of the two network inputs -- `max_block`, `n_above / n_blocks` (drba_amd.ops.dup_stats; the frames are
+converted as infer.py converts them for the model named by -m / -scale / --fit) -- and the decision, then the runs of repeats and how many
+frames the filter keeps, and one JSON line with the kept indices.  `holdout --dedup` runs the hold-out with the filter on.
 
 Non-finite JSON numbers are written as the strings "inf" / "-inf" / "nan" (float() reads them back).
 """
@@ -344,7 +351,8 @@ class _HoldoutIO:
 
 
 def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.3, plain=False, backend=None, to_inp=None,
-            to_out=None, check_scene=None, maxval=None, linear=True, yuv_matrix="bt709", yuv_range="source", fit="resize"):
+            to_out=None, check_scene=None, maxval=None, linear=True, yuv_matrix="bt709", yuv_range="source", fit="resize", dedup=None,
+            check_dup=None):
     """Keep every k-th frame of `frames` (uint8 [N,H,W,3], indexable), let interpolate_stream fill the gaps at `times = k`
     and compare every emission with the original frame at its position.  -> {"k", "m", "frames_used", "emissions",
     "pairs": [(emission, original)], "kept": ClipMetrics.result() + "positions", "held_out": the same}.
@@ -362,7 +370,9 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
     down again ("Pass-through frames"), so unlike those of an array clip they do not come back identical and
     their PSNR is finite; the result says so in "kept_passthrough", beside "pixfmt", "depth" and "maxval".
     fit="pad": the default hooks pad the frames to the network size and crop the emissions instead of resizing both ways (infer.py
-    --fit pad), so the figures carry no resampling loss; hooks that are given are the caller's.  The result carries "fit"."""
+    --fit pad), so the figures carry no resampling loss; hooks that are given are the caller's.  The result carries "fit".
+    dedup / check_dup: interpolate_stream's (infer.py --dedup) -- repeats among the KEPT frames are dropped and the steps retimed; the
+    emissions and what they are compared with stay the same.  The result carries "dedup_kept", the kept indices among the kept frames."""
     from drba_amd import infer as drv
     if fit not in ("resize", "pad"):
         raise ValueError(f"fit must be resize or pad, got {fit!r}")
@@ -406,14 +416,17 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
         kept, held = metrics.ClipMetrics(backend=backend, maxval=mv), metrics.ClipMetrics(backend=backend, maxval=mv)
     io = _HoldoutIO(frames, int(k), m, half, fps, kept, held)
     run = PlainSteps(model) if plain else model
+    dedup_kept = []
     written = drv.interpolate_stream(run, io, float(fps) * int(k), times=int(k), enable_scdet=enable_scdet,
                                      scdet_threshold=scdet_threshold, to_inp=to_inp, to_out=to_out, check_scene=check_scene,
-                                     linear=bool(linear))
+                                     linear=bool(linear), dedup=dedup, check_dup=check_dup, on_kept=dedup_kept.append)
     if written != int(k) * (m + 1) or len(io.skipped) != 2 * half:
         raise RuntimeError(f"hold-out at k = {k}: the run emitted {written} frames ({len(io.skipped)} without an original), "
                            f"expected {int(k) * (m + 1)} ({2 * half})")
     out = {"k": int(k), "m": m, "frames_used": m * int(k) + 1, "emissions": written, "plain": bool(plain), "linear": bool(linear),
            "fit": fit, "pairs": io.pairs}
+    if dedup:
+        out["dedup_kept"] = dedup_kept
     if deep:
         out.update({"depth": 16, "maxval": mv})
     if yuv:
@@ -434,6 +447,8 @@ def holdout_report(res):
            "plain": res["plain"], "linear": res["linear"], "fit": res.get("fit", "resize")}
     if "depth" in res:
         rep.update({"depth": res["depth"], "maxval": res["maxval"]})
+    if "dedup_kept" in res:
+        rep["dedup_kept"] = res["dedup_kept"]
     if res.get("pixfmt") == "yuv420":
         rep.update({k: res[k] for k in ("pixfmt", "chroma", "yuv_matrix", "full_range", "kept_passthrough")})
     for name in ("kept", "held_out"):
@@ -444,7 +459,74 @@ def holdout_report(res):
     return rep
 
 
+# ----------------------------------------------------------------------------------------------------------------- repeats
+PAD_SIZE = {"rife": 64, "gmfss": 64, "gmfss_union": 128}  # the models' pad_size: the network size follows from it without loading one
+
+
+def dups(src, settings=None, model_type="rife", scale=1.0, fit="resize", yuv_matrix="bt709", yuv_range="source", stats=None, to_inp=None,
+         out=None):
+    """The duplicate statistic of every source pair of a ClipSource, on the network inputs infer.py would make for the model, and what
+    the --dedup filter does with them.  Prints one line per pair and the runs of repeats to `out` (None: nothing); -> {"pairs":
+    [{"pair", "max_block", "n_above", "n_blocks", "dup"}], "runs": [[first repeated frame, length]], "kept": [...], "frames"}.
+    stats(a, b, lo) -> (max_block, n_above, n_blocks) and to_inp(frame, size): the device's unless given."""
+    from drba_amd import dedup as _dedup
+    from drba_amd.models.utils import tools
+    s = settings or _dedup.Settings()
+    if model_type not in PAD_SIZE:
+        raise ValueError(f"model_type must be one of {sorted(PAD_SIZE)}, got {model_type!r}")
+    if stats is None:
+        from drba_amd import ops
+        stats = ops.dup_stats
+    if to_inp is None:
+        kw = {} if fit == "resize" else {"fit": fit}
+        if src.pixfmt == "yuv420":
+            full = src.color_range == "FULL" if yuv_range == "source" else yuv_range == "full"
+            kw.update(matrix=yuv_matrix, full_range=full)
+        elif src.depth == 16:
+            kw["maxval"] = src.maxval
+        to_inp = lambda fr, size: tools.to_inp(fr, size, **kw)  # noqa: E731
+    pairs, prev, size = [], None, None
+    for k, fr in enumerate(src):
+        if size is None:
+            size = tools.get_valid_net_inp_size(fr, scale, div=PAD_SIZE[model_type])["dst_size"]
+        x = to_inp(fr, size)
+        if prev is not None:
+            mx, na, nb = stats(prev, x, s.lo)
+            d = bool(_dedup.is_dup(mx, na, nb, hi=s.hi, frac=s.frac))
+            pairs.append({"pair": [k - 1, k], "max_block": mx, "n_above": na, "n_blocks": nb, "dup": d})
+            if out is not None:
+                print(f"{k - 1:6d} -> {k:<6d} max_block {mx:.5f} ({mx * 255:6.2f}/255)  n_above {na} / {nb} ({na / nb:.3f})  "
+                      f"{'repeat' if d else 'new'}", file=out)
+        prev = x
+    n = len(pairs) + 1 if prev is not None else 0
+    kept = _dedup.kept_indices([p["dup"] for p in pairs], s.max_run) if n else []
+    runs, k = [], 1
+    while k < n:
+        if pairs[k - 1]["dup"]:
+            j = k
+            while j < n and pairs[j - 1]["dup"]:
+                j += 1
+            runs.append([k, j - k])
+            k = j
+        else:
+            k += 1
+    if out is not None:
+        for first, length in runs:
+            print(f"frames {first} .. {first + length - 1}: {length} repeat{'s' if length > 1 else ''} of frame {first - 1}"
+                  + (f" (at most {s.max_run} in a row are dropped)" if length > s.max_run else ""), file=out)
+        print(f"{len(kept)} of {n} frames kept (hi {s.hi:.5f}, lo {s.lo:.5f}, frac {s.frac}, max {s.max_run})", file=out)
+    return {"pairs": pairs, "runs": runs, "kept": kept, "frames": n}
+
+
 # ----------------------------------------------------------------------------------------------------------------- command line
+def _dedup_flags(p):
+    from drba_amd import dedup as _dedup
+    p.add_argument("--dedup-hi", dest="dedup_hi", type=float, default=_dedup.HI, help="as in infer.py (default 12/255)")
+    p.add_argument("--dedup-lo", dest="dedup_lo", type=float, default=_dedup.LO, help="as in infer.py (default 5/255)")
+    p.add_argument("--dedup-frac", dest="dedup_frac", type=float, default=_dedup.FRAC, help="as in infer.py (default 0.33)")
+    p.add_argument("--dedup-max", dest="dedup_max", type=int, default=_dedup.MAX_RUN, help="as in infer.py (default 3)")
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="python -m drba_amd.evaluate", description="PSNR / SSIM of finished clips")
     sub = p.add_subparsers(dest="command", required=True)
@@ -472,7 +554,18 @@ def parse_args(argv=None):
     h.add_argument("--fit", dest="fit", type=str, default="resize", choices=("resize", "pad"),
                    help="how a frame gets to the network size and back, as in infer.py: resize (default) or pad (no resampling)")
     h.add_argument("--weights", type=str, default=None, help="weight directory (default: the model's, synthetic if absent)")
+    h.add_argument("--dedup", action="store_true", help="drop repeated frames among the kept ones and retime the steps (infer.py --dedup)")
+    _dedup_flags(h)
     h.add_argument("--json", dest="json_path", type=str, default=None)
+    d = sub.add_parser("dups", help="the duplicate statistic of every source pair of a clip and what --dedup does with it")
+    d.add_argument("clip")
+    d.add_argument("-m", "--model_type", dest="model_type", type=str, default="rife", help="the model whose network size the frames are brought to")
+    d.add_argument("-scale", "--scale", dest="scale", type=float, default=1.0)
+    d.add_argument("--fit", dest="fit", type=str, default="resize", choices=("resize", "pad"))
+    d.add_argument("--yuv-matrix", dest="yuv_matrix", type=str, default="bt709", choices=("bt709", "bt601"))
+    d.add_argument("--yuv-range", dest="yuv_range", type=str, default="source", choices=("source", "limited", "full"))
+    _dedup_flags(d)
+    d.add_argument("--json", dest="json_path", type=str, default=None)
     return p.parse_args(argv)
 
 
@@ -494,6 +587,14 @@ def main(argv=None, backend=None):
             print(json.dumps(_jsonable(rep)))
             _write_json(args.json_path, rep, {"per_frame": res["per_frame"]})
             return 0 if ok else 1
+        if args.command == "dups":
+            from drba_amd import dedup as _dedup
+            res = dups(ClipSource(args.clip), _dedup.Settings(args.dedup_hi, args.dedup_lo, args.dedup_frac, args.dedup_max), args.model_type,
+                       args.scale, args.fit, args.yuv_matrix, args.yuv_range, out=sys.stdout)
+            rep = {"command": "dups", "input": args.clip, "frames": res["frames"], "kept": res["kept"], "runs": res["runs"]}
+            print(json.dumps(_jsonable(rep)))
+            _write_json(args.json_path, rep, {"pairs": res["pairs"]})
+            return 0
         src = ClipSource(args.input)
         if not src.random_access:
             raise ValueError("a hold-out needs random access to the clip: use a .npz / .npy source"
@@ -514,7 +615,8 @@ def main(argv=None, backend=None):
         else:
             kw = {"maxval": src.maxval} if src.depth == 16 else {}
         res = holdout(model, src if src.pixfmt == "yuv420" else src._frames, args.k, fps=src.fps, enable_scdet=args.enable_scdet,
-                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend, linear=not args.nonlinear, fit=args.fit, **kw)
+                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend, linear=not args.nonlinear, fit=args.fit,
+                      dedup=drv.dedup_of(args), **kw)
         rep = holdout_report(res)
         rep.update({"model": args.model_type, "scale": args.scale, "input": args.input,
                     "weights": "synthetic (drba_amd.utils.synth): the figures say nothing about quality" if synthetic else wdir})

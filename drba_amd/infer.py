@@ -2,6 +2,7 @@
 
     python infer.py -m rife -i in.npz -o out.npz [-fps 60 | -t 2] [-s] [-st 0.3] [-hw] [-scale 1.0] [--out-depth source|8|16]
                     [--nonlinear] [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--deterministic] [--fit resize|pad]
+                    [--dedup [--dedup-hi 0.047] [--dedup-lo 0.0196] [--dedup-frac 0.33] [--dedup-max 3]]
 
 `--out-depth` is not in the reference: a .npz / .npy clip may hold uint16 frames, and the written frames are 8 or 16 bits deep
 (default: as the source, so an 8-bit clip is handled exactly as before).  `--nonlinear` is not in the reference either: its driver
@@ -23,6 +24,12 @@ resampling in either direction, so a frame the driver only copies (a scene cut, 
 source's bytes.  The network sizes are those of `resize`.  Scene detection runs on the padded network input, so its decisions may
 differ from `resize` mode for a pair near the threshold.  The default, `resize`, is unchanged.
 
+`--dedup` (not in the reference, whose README leaves repeated frames to a separate tool): a source frame that repeats its predecessor
+(ffmpeg mpdecimate's rule, tested on the device: drba_amd.ops.dup_stats) is dropped before the model sees it, at most `--dedup-max` in a
+row, and the steps are retimed across the gaps (drba_amd/dedup.py): the clip written has the same frames at the same instants, but the
+motion of a drawing held for two frames is spread over both instead of being packed into the interval where it changes.  With every
+source and sink; `python -m drba_amd.evaluate dups clip` prints the figures the thresholds are chosen from.
+
 The driver logic is host-side Python like the reference; the model calls it makes run on
 the HIP library.  `interpolate_stream` is the loop of reference infer.py:58-174 (drba_amd/driver.py) with the
 module globals turned into arguments, so tests can drive it with any model object.
@@ -31,6 +38,7 @@ import argparse
 import os
 import time
 
+from drba_amd import dedup as _dedup
 from drba_amd import driver
 from drba_amd.models.utils import tools as _tools
 
@@ -68,7 +76,27 @@ def parse_args(argv=None):
     p.add_argument("--fit", dest="fit", type=str, default="resize", choices=("resize", "pad"),
                    help="how a frame gets to the network size and back: resize (default, the reference's behaviour) or pad -- "
                         "replicate padding at the bottom and right, cropped away on the way out, no resampling")
+    p.add_argument("--dedup", dest="dedup", action="store_true", default=False,
+                   help="drop repeated source frames (drawings on twos, threes, fours) and interpolate across the gaps: the same "
+                        "frames at the same instants are written (ffmpeg mpdecimate's rule; not in the frame-sharded run)")
+    p.add_argument("--dedup-hi", dest="dedup_hi", type=float, default=_dedup.HI,
+                   help="a frame is no repeat if one 8x8 block differs from the previous source frame by more than this on average, "
+                        "on the [0, 1] scale (default 12/255)")
+    p.add_argument("--dedup-lo", dest="dedup_lo", type=float, default=_dedup.LO,
+                   help="... or if more than --dedup-frac of the blocks differ by more than this (default 5/255)")
+    p.add_argument("--dedup-frac", dest="dedup_frac", type=float, default=_dedup.FRAC, help="see --dedup-lo (default 0.33)")
+    p.add_argument("--dedup-max", dest="dedup_max", type=int, default=_dedup.MAX_RUN,
+                   help="at most this many frames in a row are dropped; the next one is kept whatever the test says (default 3)")
     return p.parse_args(argv)
+
+
+def dedup_of(args):
+    """--dedup and its settings as interpolate_stream takes them: None (off) or a drba_amd.dedup.Settings.  A namespace built without
+    the flags means off / the defaults."""
+    if not getattr(args, "dedup", False):
+        return None
+    return _dedup.Settings(getattr(args, "dedup_hi", _dedup.HI), getattr(args, "dedup_lo", _dedup.LO),
+                           getattr(args, "dedup_frac", _dedup.FRAC), getattr(args, "dedup_max", _dedup.MAX_RUN))
 
 
 def fit_of(args):
@@ -112,9 +140,13 @@ def load_model(model_type, scale=1.0, device=None, weights=None):
 
 
 def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, scdet_threshold=0.3,
-                       to_inp=None, to_out=None, check_scene=None, on_step=None, linear=True):
+                       to_inp=None, to_out=None, check_scene=None, on_step=None, linear=True, dedup=None, check_dup=None, on_kept=None):
     """Run the whole clip: drba_amd.driver.run from a cold start, head and tail included.  Returns the number of frames written.
-    linear=False: every DRBA step with the non-linear DistanceRatioMap (--nonlinear)."""
+    linear=False: every DRBA step with the non-linear DistanceRatioMap (--nonlinear).
+    dedup (--dedup; None: off, True: the defaults, a drba_amd.dedup.Settings or a dict of its fields): repeated source frames are
+    dropped before the model sees them and the steps are retimed across the gaps -- the same number of frames at the same instants is
+    written (drba_amd.dedup).  check_dup(a, b) -> bool replaces the device test; on_kept(k) fires for every kept source index k, in
+    order; on_step then fires once per source frame the finished steps have passed (a progress bar counts source frames)."""
     to_inp = to_inp or _tools.to_inp
     to_out = to_out or _tools.to_out
     src_fps = video_io.src_fps
@@ -129,12 +161,50 @@ def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, s
             video_io.write_frame(to_out(x, src_size))
             written += 1
 
+    mapper = _tools.TMapper(src_fps, dst_fps, times)
+    cuts = driver.SceneCuts(enable_scdet, scdet_threshold, check_scene)
+    settings = _dedup.settings_of(dedup)
+    if settings is not None:
+        size = {}
+
+        def convert(raw):
+            if not size:
+                size.update(_tools.get_valid_net_inp_size(raw, model.scale, div=model.pad_size))
+            return to_inp(raw, size["dst_size"])
+
+        def intake():  # the stream driver.run takes its frames in on, when the model offers one (decided once the first frame is here)
+            if not (getattr(model, "supports_lookahead", False) and getattr(model, "prefetch_frame", None) is not None):
+                return None
+            offer = getattr(model, "intake_stream", None)
+            import torch
+            if offer is None or not torch.cuda.is_available():
+                return None
+            dev = getattr(model, "device", None)
+            return offer(torch.device("cuda", torch.cuda.current_device()) if dev is None else dev)
+
+        kept = driver.KeptFrames(lambda k: video_io.read_frame(), convert, settings, check_dup=check_dup, stream=intake, on_kept=on_kept)
+        pair = [kept.next(), kept.next()]
+        src_size = size["src_size"]
+        sched = _dedup.Retimed(lambda idx: _tools.calc_t(idx, times, mapper), kept.kept, lambda: kept.total)
+        passed = -1
+
+        def step(idx):  # step s of the driver (head 0, iteration u: u + 1, the tail last) has passed source frame k_s, the tail all
+            nonlocal passed
+            upto = kept.kept[idx] if idx < len(kept.kept) - 1 or kept.total is None else kept.total - 1
+            if on_step is not None:
+                for j in range(passed + 1, upto + 1):
+                    on_step(j)
+            passed = max(passed, upto)
+
+        driver.run(model, lambda k: kept.next(), pair, 0, to_inp=lambda x: x, emit=emit, cuts=cuts, ts_of=sched.ts_of, on_step=step,
+                   linear=linear, even_of=sched.even_of)
+        return written
+
     i0, i1 = video_io.read_frame(), video_io.read_frame()
     size = _tools.get_valid_net_inp_size(i0, model.scale, div=model.pad_size)
     src_size, dst_size = size["src_size"], size["dst_size"]
-    mapper = _tools.TMapper(src_fps, dst_fps, times)
     driver.run(model, lambda k: video_io.read_frame(), [to_inp(i0, dst_size), to_inp(i1, dst_size)], 0,
-               to_inp=lambda raw: to_inp(raw, dst_size), emit=emit, cuts=driver.SceneCuts(enable_scdet, scdet_threshold, check_scene),
+               to_inp=lambda raw: to_inp(raw, dst_size), emit=emit, cuts=cuts,
                ts_of=lambda idx: _tools.calc_t(idx, times, mapper), on_step=on_step, linear=linear)
     return written
 
@@ -178,7 +248,7 @@ def inference(model, args):
                                                matrix=video_io.yuv_matrix, full_range=video_io.out_full_range, **fit_kw)
     n = interpolate_stream(model, video_io, args.dst_fps, times=args.times, enable_scdet=args.enable_scdet,
                            scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, on_step=step,
-                           linear=not getattr(args, "nonlinear", False))
+                           linear=not getattr(args, "nonlinear", False), dedup=dedup_of(args))
     while not video_io.finish_writing():
         time.sleep(0.01)
     video_io.close()
@@ -196,6 +266,10 @@ def inference_sharded(model, args, rank, world, to_inp=None, to_out=None, check_
     import numpy as np
 
     from drba_amd import parallel
+    # every rank sees the same flag: all of them refuse here, before the clip is opened, the gather exists or any collective runs
+    if dedup_of(args) is not None:
+        raise ValueError("the frame-sharded run does not take --dedup (which frames are kept decides every rank's share of the clip "
+                         "and its schedule): run --dedup on one GPU")
     apply_deterministic(args)
     ext = os.path.splitext(args.input)[1].lower()
     if ext == ".npz":

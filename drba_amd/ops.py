@@ -757,6 +757,43 @@ def ssim_thumb32_async(x1, x2):
     return host, ev
 
 
+def _dup_stats_enqueue(x1, x2, lo):
+    """drba_dup_stats_f32 on the current stream -> the device tensor [3] (int32 words: max_block's float bits, n_above, n_blocks)."""
+    a, b = _f32(x1, "x1"), _f32(x2, "x2")
+    if a.dim() != 4 or a.shape[0] != 1 or a.shape != b.shape:
+        raise ValueError(f"dup_stats takes two [1, c, h, w] tensors of one shape, got {tuple(x1.shape)} and {tuple(x2.shape)}")
+    c, h, w = (int(v) for v in a.shape[1:])
+    lib = _lib.load()
+    out = torch.empty(3, dtype=torch.int32, device=a.device)
+    ws = torch.empty(max(int(lib.drba_dup_stats_ws_floats(c, h, w)), 1), dtype=torch.float32, device=a.device)
+    first = _trace_pos()
+    _lib.check(lib.drba_dup_stats_f32(_p(a), _p(b), c, h, w, float(lo), _p(out), _p(ws), _stream()), "drba_dup_stats_f32")
+    _tag(first, [(8.0 * c * h * w, "byte", f"dup_stats {(c, h, w)}"), None])  # the streaming pass, then the fold of its partials
+    return out
+
+
+def dup_stats_decode(host):
+    """The three words drba_dup_stats_f32 wrote, on the host -> (max_block, n_above, n_blocks) as Python numbers."""
+    return float(host[:1].view(torch.float32).item()), int(host[1].item()), int(host[2].item())
+
+
+def dup_stats(x1, x2, lo):
+    """The duplicate-frame statistic of two network inputs [1, c, h, w] (include/drba_hip.h: drba_dup_stats_f32): the largest mean of
+    |x1 - x2| over an 8 x 8 block, the number of blocks whose mean is > lo, the number of blocks.  One D2H read."""
+    return dup_stats_decode(_dup_stats_enqueue(x1, x2, lo).cpu())
+
+
+def dup_stats_async(x1, x2, lo):
+    """The same without waiting for it: -> (pinned host tensor [3] int32, event), as ssim_thumb32_async.  The words are read
+    (dup_stats_decode) after event.synchronize() -- that test's own event: the caller's stream is never drained."""
+    out = _dup_stats_enqueue(x1, x2, lo)
+    host = torch.empty(3, dtype=torch.int32, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(out.device))
+    return host, ev
+
+
 # ----------------------------------------------------------------------------- convolutions
 # Kernel-configuration choice.  The library's cost model gives a default; with AUTOTUNE on (default) the
 # first call for a new layer shape times every configuration built for that stride once on the device

@@ -36,7 +36,9 @@ extern "C" {
  * an item stride -- the luma planes of packed 4:2:0 frames --, fp32, uint8 or uint16 samples, fp64 accumulation): additions only,
  * no earlier entry changes; and, added under the same number, the fit = pad frame conversions -- drba_to_inp_pad_x4 / drba_to_inp16_pad_x4 /
  * drba_to_out_crop / drba_to_out16_crop / drba_to_inp_yuv420_pad_x4 / drba_to_inp16_yuv420_pad_x4 / drba_to_out_yuv420_crop /
- * drba_to_out16_yuv420_crop (replicate padding on the way in, a crop on the way out, no interpolation): additions only.  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
+ * drba_to_out16_yuv420_crop (replicate padding on the way in, a crop on the way out, no interpolation): additions only; and, under the
+ * same number again, drba_dup_stats_f32 / drba_dup_stats_ws_floats (the duplicate-frame statistic of --dedup): additions only (a library
+ * without them does not load: drba_amd/_lib.py resolves every entry).  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
  * the splat entry points: drba_flow_reverse, drba_drm_rife_linear(_batch), drba_drm_rife_nonlinear(_batch), drba_softsplat and
  * drba_softsplat_index; while it is on, drba_rife_splat_ws_floats reports the larger workspace of the fixed-point accumulator):
  * additions only, nothing changes while the switch is off.  14: planar YCbCr 4:2:0 frames -- drba_to_inp_yuv420_x4 / drba_to_inp16_yuv420_x4 / drba_to_out_yuv420 /
@@ -380,6 +382,17 @@ int drba_frame_error_f32(const float *a, const float *b, double *out, float *ws,
 size_t drba_frame_error_u16_ws_floats(int N, size_t n_per_item);
 int drba_frame_error_u16(const uint16_t *a, const uint16_t *b, unsigned long long *out, float *ws, int N, size_t n_per_item,
                          void *stream);
+/* The duplicate-frame statistic (--dedup; ffmpeg mpdecimate's block test on the [0, 1] scale): a, b fp32 [1,c,h,w].  Over 8 x 8 pixel
+ * blocks aligned at the origin -- right and bottom edge blocks are partial and divided by their own pixel count -- the mean of
+ * |a - b| over the block's pixels and all c channels.  out, 3 x 4 bytes (4-byte aligned):
+ *   float max_block: the largest block mean;  int32 n_above: the number of blocks whose mean is > lo;  int32 n_blocks.
+ * Every block sum is taken in an order fixed by the data layout, and the frame-level results are a maximum and an integer count
+ * folded from per-workgroup partials (no atomics): two calls on the same inputs return the same bytes, in every mode.  16-byte loads
+ * where a and b are 16-byte aligned and the row start allows, scalar loads elsewhere: the same sums either way.
+ * ws: drba_dup_stats_ws_floats(c, h, w) floats, 4-byte aligned, any content.  Null pointers, c, h or w < 1: DRBA_EINVAL; 2^31 blocks
+ * and more: DRBA_EUNSUPPORTED (the query returns 0 for both). */
+size_t drba_dup_stats_ws_floats(int c, int h, int w);
+int drba_dup_stats_f32(const float *a, const float *b, int c, int h, int w, float lo, void *out, float *ws, void *stream);
 
 /* ---- convolutions (models/rife_426_heavy/IFNet_HDv3.py:11-16, :28-47, :50-59, :65-82) ------
  * fp32 implicit GEMM on v_mfma_f32_16x16x4_f32.  Weights must be pre-packed by the matching
