@@ -1,6 +1,7 @@
 """Per-operator fp64 parity checks of the GMFlow / GMFSS glue kernels (gmflow.hip, gmfss_glue.hip, the small kernels of
-splat_warp.hip and the layout kernels of ifnet_glue.hip and frame_io.hip), shared by tests/test_gpu_op_parity.py,
-tests/test_op_checks_cpu.py and the diagnostic report (python -m tests.gpu_report).
+splat_warp.hip and the layout kernels of ifnet_glue.hip and frame_io.hip), of the generic forward splat (splat_warp.hip:
+drba_softsplat, _index, _again, _gather_quad) and of resize_bilinear_scale and flow_distance, shared by
+tests/test_gpu_op_parity.py, tests/test_op_checks_cpu.py and the diagnostic report (python -m tests.gpu_report).
 
 Every check takes the device the inputs go to and the `ops` namespace under test (default: drba_amd.ops; the CPU test hands
 in a torch stand-in, with and without a planted defect) and returns rows (name, err, tol, extra) with the pass rule of every
@@ -19,6 +20,11 @@ Two places where ATen's CPU result is not the specification are written out inst
   * a zeros-padding bilinear sample at a non-finite coordinate is 0 (every tap is outside the image; ATen's CPU kernel forms
     0 * NaN there, its CUDA kernel -- what the reference model runs on -- skips the taps);
   * InstanceNorm of a one-element plane is 0 (variance 0; F.instance_norm refuses the shape).
+The splat's reference takes its targets as the specification does, as the fp32 sum x + flow, and evaluates everything after
+that in fp64 (softsplat_ref): with fp64 targets a source next to an integer lands on other pixels than the specified ones, and
+the fp32 oracle's "error" against such a reference (1e-4 at 37 x 83, above 1 for avg at 1024 x 1280) would set a tolerance
+that detects nothing.  A finite target beyond the int32 range contributes nothing (softsplat_ref), and flow_distance is +inf
+where the fp32 squares overflow (flow_distance_ref).
 Inputs regenerate from seeds (cases.rnd, synth._smooth_field)."""
 import torch
 import torch.nn.functional as F
@@ -594,10 +600,369 @@ def check_metric_input(dev, ops=None):
     return rows
 
 
+# ----------------------------------------------------------------------------------------- softsplat
+# The generic forward splat (drba_softsplat, _index, _again, _gather_quad: count, three-kernel scan, fill, optional segment sort,
+# two gathers) against softsplat.py:248-367 / softsplat_torch.py:19-179 as oracle/ops.py restates them.
+SPLAT_MODES = ("sum", "avg", "linear", "soft")
+SPLAT_MAP = (37, 83)      # partial 32 x 8 tiles on both axes
+SPLAT_BIG = (1024, 1280)  # 1 313 025 keys: scan_sums goes round more than once, the count / fill grid-stride loops 2.5 times
+SPLAT_CHANNELS = (1, 2, 3, 15, 16, 17, 20, 32, 36, 64)  # both sides of the 16-channel chunk, quad (C >= 16, C % 4 == 0) and planar tails
+SCAN_CASES = ((1, 63, 63), (2, 63, 63), (1, 63, 64), (3, 63, 64), (3,) + SPLAT_MAP)  # (N, H, W) of the scan-geometry rows
+_SPLAT_REFS = {}  # row name -> (fp64 reference, fp32 oracle, the inputs they were computed from): once per process, never written to
+
+
+def splat_keys(n, h, w):
+    """entries of the key grid the sources are sorted on: footprints start anywhere in (-1 .. W-1) x (-1 .. H-1) of every image"""
+    return n * (h + 1) * (w + 1)
+
+
+def _grid32(h, w):
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    return torch.stack([xs, ys])
+
+
+def splat_segment_sizes(flow):
+    """how many sources share each footprint origin (floor of the fp32 target) that has any: the segment lengths of the index"""
+    n, _, h, w = flow.shape
+    t = (_grid32(h, w) + flow).floor()
+    ok = torch.isfinite(t).all(1) & (t[:, 0] >= -1) & (t[:, 0] <= w - 1) & (t[:, 1] >= -1) & (t[:, 1] <= h - 1)
+    key = (torch.arange(n).view(n, 1, 1) * (h + 1) + t[:, 1] + 1) * (w + 1) + t[:, 0] + 1
+    return torch.bincount(key[ok].long())
+
+
+def softsplat_ref(x, flow, metric, mode, dtype=torch.float64):
+    """oracle.ops.softsplat in `dtype` on the targets the specification defines: X = x + flow is an fp32 sum (its first rounding,
+    and what decides which four pixels a source lands on); weights, products, sums and the normalisation are then evaluated in
+    `dtype`.  For float64 the flow handed to the dtype-generic oracle is X - x, exact in fp64, so that x + flow gives X back.
+    Written out, because the oracle's int cast is not the specification there: a finite target beyond the int32 range has no
+    corner inside the image (the reference's (int) saturates), so its source is skipped like one with a non-finite target."""
+    _, _, h, w = flow.shape
+    g = _grid32(h, w)
+    t = g + flow
+    far = t.abs() > 2.0 ** 30
+    if dtype == torch.float32:
+        f = torch.where(far, torch.full_like(flow, float("inf")), flow)
+    else:
+        t = torch.where(far, torch.full_like(t, float("inf")), t)
+        f = t.to(dtype) - g.to(dtype)
+        fin = torch.isfinite(t)
+        assert torch.equal((g.to(dtype) + f)[fin], t.to(dtype)[fin])
+    return oops.softsplat(x.to(dtype), f, None if metric is None else metric.to(dtype), mode)
+
+
+def splat_refs(name, x, flow, metric, mode):
+    """(fp64 reference, fp32 oracle) of a row, computed at its first use; a later use of the name must bring the same inputs"""
+    ins = (x, flow, metric)
+    if name not in _SPLAT_REFS:
+        _SPLAT_REFS[name] = (softsplat_ref(x, flow, metric, mode), softsplat_ref(x, flow, metric, mode, torch.float32),
+                             tuple(None if t is None else t.clone() for t in ins))
+    for was, now in zip(_SPLAT_REFS[name][2], ins):
+        assert (was is None and now is None) or (was is not None and now is not None and _mismatches(now, was) == 0), name
+    return _SPLAT_REFS[name][:2]
+
+
+def _splat_row(rows, ops, dev, name, x, flow, metric, mode, extra="", run=None):
+    """one value row of ops.softsplat(x, flow, metric, mode), or of run(x, flow, metric) on the device tensors"""
+    ref64, ref32 = splat_refs(f"{mode} {name}", x, flow, metric, mode)
+    xd, fd, md = x.to(dev), flow.to(dev), None if metric is None else metric.to(dev)
+    got = ops.softsplat(xd, fd, md, mode) if run is None else run(xd, fd, md)
+    rows.append(value_row("softsplat", f"{mode} {name}", got, ref64, ref32, extra))
+
+
+def splat_inputs(n, c, h, w, seed, mode="sum", sigma=2.0, positive=False):
+    """x, flow, metric of a well-conditioned row: same-sign metrics where the metric is the weight itself (linear)"""
+    x = torch.rand(n, c, h, w, generator=torch.Generator().manual_seed(seed)) + 0.5 if positive else cases.rnd((n, c, h, w), seed, 1.0)
+    flow = cases.rnd((n, 2, h, w), seed + 1, sigma)
+    metric = None
+    if mode.startswith("linear"):
+        metric = cases.rnd((n, 1, h, w), seed + 2, 1.0).abs() + 0.1
+    elif mode.startswith("soft"):
+        metric = cases.rnd((n, 1, h, w), seed + 2, 1.0)
+    return x, flow, metric
+
+
+def _f32_next(v, towards):
+    return float(torch.nextafter(torch.tensor(float(v)), torch.tensor(float(towards))))
+
+
+def border_flow(h, w, seed, alone=False):
+    """[1, 2, h, w]: sigma = 2 noise, and sources whose targets are constructed (and asserted, as the fp32 sums they are):
+    column 0 walks X over an integer, -1, its two fp32 neighbours, (-1, 0), W-1, (W-1, W), W, its lower neighbour, below -1 and
+    above W (x = 0: the sum is the flow itself); row 0 does the same for Y; a 4 x 4 block takes every combination of
+    {-1, -0.5, last, last + 0.5} on the two axes (the four corners of the image among them); source (0, 0) lands on the upper
+    neighbours of (-1, -1); a few targets sit exactly on interior integers.
+    alone=True: every other source leaves the image and the walks take every second row / column, so that a constructed source is
+    the only one on its pixels -- under avg-zeroeps such a pixel is the source's value whatever the weight (2^-24 next to -1), and
+    0 if the footprint is lost."""
+    f = torch.full((1, 2, h, w), 1e4) if alone else cases.rnd((1, 2, h, w), seed, 2.0)
+    step = 2 if alone else 1
+
+    def walk(size):
+        return [5.0, -1.0, _f32_next(-1, 0), _f32_next(-1, -2), -0.5, size - 1.0, size - 0.5, float(size), _f32_next(size, 0), -1.5, -40.0,
+                size + 0.5, size + 40.0]
+
+    want = {(0, 0): (_f32_next(-1, 0), _f32_next(-1, 0))}  # (y, x) of the source -> its target (X, Y)
+    for k, t in enumerate(walk(w)):
+        want[(step * k + 2, 0)] = (t, step * k + 2 + 0.25)
+    for k, t in enumerate(walk(h)):
+        want[(0, step * k + 2)] = (step * k + 2 + 0.25, t)
+    for i, cx in enumerate((-1.0, -0.5, w - 1.0, w - 0.5)):
+        for j, cy in enumerate((-1.0, -0.5, h - 1.0, h - 0.5)):
+            want[(20 + j, 20 + i)] = (cx, cy)
+    want[(30, 30)], want[(30, 31)], want[(31, 30)] = (12.0, 7.0), (0.0, 0.0), (w - 1.0, h - 1.0)
+    for (y, x), (tx, ty) in want.items():
+        f[0, 0, y, x], f[0, 1, y, x] = tx - x, ty - y
+    t = _grid32(h, w) + f[0]
+    for (y, x), (tx, ty) in want.items():
+        assert float(t[0, y, x]) == float(torch.tensor(tx)) and float(t[1, y, x]) == float(torch.tensor(ty)), (y, x, tx, ty)
+    return f
+
+
+def nonfinite_flow(h, w, seed):
+    """sigma = 2 noise with +-inf, NaN and +-1e30 in either component (and in both): none of these sources contributes"""
+    f = cases.rnd((1, 2, h, w), seed, 2.0)
+    inf, nan = float("inf"), float("nan")
+    for k, (u, v) in enumerate(((inf, 0.3), (0.3, -inf), (nan, 0.3), (0.3, nan), (1e30, 0.3), (0.3, -1e30), (-1e30, 1e30), (inf, nan), (-inf, inf))):
+        f[0, 0, 3 + 2 * k, 4 + 5 * k], f[0, 1, 3 + 2 * k, 4 + 5 * k] = u, v
+    return f
+
+
+def small_normaliser_inputs(seed):
+    """Positive inputs, a flow that leaves the first columns uncovered (holes: normaliser exactly 0), and soft metrics around -12
+    in the left half (normaliser ~ 6e-6: addeps' 1e-7 is 1.6 % of it, clipeps' bound below it) and around -20 in the right half
+    (normaliser ~ 2e-9: clipeps divides by 1e-7 instead).  Same-sign weights: every quotient is well conditioned."""
+    h, w = SPLAT_MAP
+    x, flow, _ = splat_inputs(1, 3, h, w, seed, sigma=1.0, positive=True)
+    flow[:, 0] += 6.3
+    metric = cases.rnd((1, 1, h, w), seed + 2, 0.3) - 12.0
+    metric[..., w // 2:] -= 8.0
+    return x, flow, metric
+
+
+ONTO = (41.25, 17.5)  # dyadic: the four weights are 0.375, 0.125, 0.375, 0.125, exact in fp32
+
+
+def onto_flow(h, w):
+    """every source of an h x w map onto ONTO: one segment of h * w records"""
+    g = _grid32(h, w)
+    return torch.stack([ONTO[0] - g[0], ONTO[1] - g[1]])[None].contiguous()
+
+
+def onto_inputs(c, h, w, seed):
+    """Positive inputs in [0.5, 1.5) on the 2^-6 grid.  With ONTO's weights every product is a multiple of 2^-9 below 0.6, and a
+    sum of h * w = 3071 of them stays below 2^11: at most 20 bits, so every fp32 partial sum is exact in any order, and so is
+    the normaliser.  What is left of the fp32 floor is avg's one division (and its 1e-7), so the rule's first term governs:
+    2e-5 * |ref|max ~ 2e-5 * 3071 * 0.375 = 0.023 for sum, below the 0.0625 = 0.5 * 0.125 that one lost or doubled record is
+    worth at the least."""
+    return 0.5 + torch.floor(torch.rand(1, c, h, w, generator=torch.Generator().manual_seed(seed)) * 64.0) / 64.0
+
+
+def zoom_flow(h, w):
+    """zoom-out by 5 about the centre, fractional targets: 25 sources start their footprint at every pixel they reach"""
+    g = _grid32(h, w)
+    return torch.stack([-0.8 * (g[0] - w / 2 + 0.3), -0.8 * (g[1] - h / 2 + 0.2)])[None].contiguous()
+
+
+REUSE_ROW = "soft softsplat_many reuse_index=True C=17 N=2 %dx%d" % SPLAT_MAP
+
+
+def many_inputs():
+    """inputs of C = 3, 64 and 17 (the largest is not the first) for one soft index at N = 2"""
+    h, w = SPLAT_MAP
+    xs = [splat_inputs(2, c, h, w, 2220 + k, positive=True)[0] for k, c in enumerate((3, 64, 17))]
+    _, flow, metric = splat_inputs(2, 1, h, w, 2230, "soft")
+    return xs, flow, metric
+
+
+def _variants_differ(rows_tol, x, flow, metric, main, sub):
+    """the fp64 references of the three eps variants on this input: the one under test is at least 100 tolerances from the others"""
+    mine = softsplat_ref(x, flow, metric, f"{main}-{sub}")
+    for other in ("addeps", "zeroeps", "clipeps"):
+        if other != sub:
+            d = (softsplat_ref(x, flow, metric, f"{main}-{other}") - mine).abs()
+            assert float(d[torch.isfinite(d)].max()) > 100.0 * rows_tol, (main, sub, other)
+
+
+def check_softsplat(dev, ops=None):
+    """Borders, non-finite values, degenerate and partial-tile shapes, N > 1, the channel tails of both gathers, the three
+    normalisers where they differ, many-to-one segments and every calling path, at 37 x 83 and below."""
+    ops = ops or default_ops()
+    rows = []
+    h, w = SPLAT_MAP
+    # ---- borders: constructed targets, every mode that has a normaliser of its own
+    bf = border_flow(h, w, 2000)
+    for k, mode in enumerate(("sum", "avg", "soft")):
+        x, _, metric = splat_inputs(1, 3, h, w, 2010 + 3 * k, mode)
+        _splat_row(rows, ops, dev, f"borders C=3 {h}x{w}", x, bf, metric, mode)
+    alone = border_flow(h, w, 2000, alone=True)
+    for mode in ("sum", "avg-zeroeps"):
+        _splat_row(rows, ops, dev, f"borders, every other source outside, C=3 {h}x{w}", torch.rand(1, 3, h, w, generator=torch.Generator().manual_seed(2005)) + 0.5,
+                   alone, None, mode)
+    nf = nonfinite_flow(h, w, 2020)
+    for k, mode in enumerate(("sum", "avg")):
+        x, _, metric = splat_inputs(1, 3, h, w, 2030 + 3 * k, mode)
+        _splat_row(rows, ops, dev, f"flow +-inf NaN +-1e30 C=3 {h}x{w}", x, nf, metric, mode)
+    inf, nan = float("inf"), float("nan")
+    for k, mode in enumerate(("avg", "linear", "soft")):
+        x, flow, metric = splat_inputs(1, 3, h, w, 2040 + 3 * k, mode)
+        x[0, 1, 12, 12], x[0, 0, 15, 15], x[0, 2, 18, 40] = nan, inf, -inf
+        if metric is not None:
+            metric[0, 0, 5, 5], metric[0, 0, 9, 9], metric[0, 0, 25, 60] = nan, inf, (-inf if mode == "soft" else 0.0)
+        _splat_row(rows, ops, dev, f"NaN and inf in input and metric C=3 {h}x{w}", x, flow, metric, mode)
+    # ---- shapes: one pixel, one row, one column; N = 3 of partial tiles
+    one = torch.tensor([[0.0, 0.0], [-0.5, -0.25], [0.5, 0.5]]).view(3, 2, 1, 1)
+    for mode in ("sum", "avg"):
+        _splat_row(rows, ops, dev, "N=3 C=2 1x1", cases.rnd((3, 2, 1, 1), 2050, 1.0), one, None, mode)
+    x, flow, metric = splat_inputs(1, 3, 1, w, 2053, "soft")
+    flow[:, 1] *= 0.3
+    _splat_row(rows, ops, dev, f"C=3 1x{w}", x, flow, metric, "soft")
+    x, flow, metric = splat_inputs(2, 3, h, 1, 2056, "linear")
+    flow[:, 0] *= 0.3
+    _splat_row(rows, ops, dev, f"N=2 C=3 {h}x1", x, flow, metric, "linear")
+    for k, mode in enumerate(SPLAT_MODES):
+        x, flow, metric = splat_inputs(3, 5, h, w, 2060 + 3 * k, mode)
+        _splat_row(rows, ops, dev, f"N=3 C=5 {h}x{w}", x, flow, metric, mode)
+    # ---- channels: every count with two of the four modes, every mode with five counts, N = 2; the quad tails under linear and
+    # soft (C = 20) and sum and avg (C = 36), the planar tail (C = 17) under avg and linear, and under sum by a row of its own
+    for k, c in enumerate(SPLAT_CHANNELS):
+        for mode in (SPLAT_MODES[k % 4], SPLAT_MODES[(k + 1) % 4]) + (("sum",) if c == 17 else ()):
+            x, flow, metric = splat_inputs(2, c, h, w, 2100 + 3 * k, mode)
+            _splat_row(rows, ops, dev, f"N=2 C={c} {h}x{w}", x, flow, metric, mode)
+    # ---- normalisers: inputs on which the three eps variants give three answers
+    x, flow, metric = small_normaliser_inputs(2200)
+    holes = int((softsplat_ref(torch.ones(1, 1, h, w), flow, None, "sum") == 0).sum())
+    assert holes > 0
+    for sub in ("zeroeps", "clipeps", "addeps"):
+        _splat_row(rows, ops, dev, f"normaliser 6e-6 | 2e-9, {holes} holes", x, flow, metric, f"soft-{sub}")
+        _variants_differ(rows[-1][2], x, flow, metric, "soft", sub)
+    neg = -3e-6 * (1.0 + 0.3 * torch.rand(1, 1, h, w, generator=torch.Generator().manual_seed(2203)))
+    for sub in ("clipeps", "zeroeps"):  # (addeps on this input divides by ~0 where the normaliser is near -1e-7: no row)
+        _splat_row(rows, ops, dev, f"all-negative metric ~-3e-6, {holes} holes", x, flow, neg, f"linear-{sub}")
+        _variants_differ(rows[-1][2], x, flow, neg, "linear", sub)
+    for sub in ("addeps", "zeroeps", "clipeps"):
+        _splat_row(rows, ops, dev, f"C=3 {h}x{w}, {holes} holes", x, flow, None, f"avg-{sub}")
+    # ---- many sources on one pixel
+    ci = cases.ops_inputs()
+    _splat_row(rows, ops, dev, "zoom-out x0.25 C=16 48x80", ci["x16"], ci["flow_converge"], ci["metric"], "soft")
+    _splat_row(rows, ops, dev, "zoom-out x0.25 C=3 48x80", ci["x3"], ci["flow_converge"], None, "sum")
+    x, _, metric = splat_inputs(1, 3, h, w, 2213, "linear")
+    _splat_row(rows, ops, dev, f"zoom-out x0.2 C=3 {h}x{w}", x, zoom_flow(h, w), metric, "linear", "segments of 25 records")
+    x, onto = onto_inputs(2, h, w, 2210), onto_flow(h, w)
+    for mode in ("sum", "avg"):
+        _splat_row(rows, ops, dev, f"every source onto {ONTO} C=2 {h}x{w}", x, onto, None, mode, f"one segment of {h * w} records")
+    # ---- calling paths
+    xs, flow, metric = many_inputs()
+    fd, md = flow.to(dev), metric.to(dev)
+    outs = ops.softsplat_many([x.to(dev) for x in xs], fd, md, "soft")
+    for x, got in zip(xs, outs):
+        name = f"soft softsplat_many [3, 64, 17] C={x.shape[1]} N=2 {h}x{w}"
+        rows.append(value_row("softsplat", name, got, *splat_refs(name, x, flow, metric, "soft")))
+    # (fd, md: the tensors the index was built from.  The values do not tell a reused index from a rebuilt one; that only the
+    # gather is launched is asserted from the kernel trace, test_gpu_op_parity.py::test_softsplat_reuse_index_launches_one_gather)
+    got = ops.softsplat_many([xs[2].to(dev)], fd, md, "soft", reuse_index=True)[0]
+    rows.append(value_row("softsplat", REUSE_ROW, got, *splat_refs(REUSE_ROW, xs[2], flow, metric, "soft")))
+    x, flow, metric = splat_inputs(2, 20, h, w, 2240, "linear")
+    _splat_row(rows, ops, dev, f"keep_quad=True N=2 C=20 {h}x{w}", x, flow, metric, "linear", run=lambda a, f, m: ops.softsplat(a, f, m, "linear", keep_quad=True))
+    x, flow, _ = splat_inputs(1, 3, h, w, 2250)
+    buf = torch.full((1, 6, h, w), -7.25).to(dev)
+
+    def into_slice(a, f, m):
+        ops.softsplat(a, f, m, "avg", out=buf[:, 2:5])
+        return buf[:, 2:5]  # (what the buffer holds, not what the call returned)
+
+    _splat_row(rows, ops, dev, f"out= channels 2-4 of [1, 6, {h}, {w}]", x, flow, None, "avg", run=into_slice)
+    rows.append(exact_row("softsplat", "out= channels 2-4: the rest of the buffer", buf[:, (0, 1, 5)], torch.full((1, 3, h, w), -7.25)))
+    return rows
+
+
+def check_softsplat_scan(dev, ops=None):
+    """Scan geometry: one full block, two blocks, a ragged second block, image boundaries inside a scan block."""
+    ops = ops or default_ops()
+    rows = []
+    for k, (n, h, w) in enumerate(SCAN_CASES):
+        keys = splat_keys(n, h, w)
+        for mode in (SPLAT_MODES[k % 4], SPLAT_MODES[(k + 1) % 4]):
+            x, flow, metric = splat_inputs(n, 3, h, w, 2300 + 3 * k, mode)
+            _splat_row(rows, ops, dev, f"N={n} C=3 {h}x{w}", x, flow, metric, mode, f"keys={keys}")
+    return rows
+
+
+def check_softsplat_big(dev, ops=None):
+    """One map past every single-round bound of the index: 1 313 025 keys, sigma = 6 flow."""
+    ops = ops or default_ops()
+    rows = []
+    h, w = SPLAT_BIG
+    for k, (c, mode) in enumerate(((3, "avg"), (2, "soft"))):
+        x, flow, metric = splat_inputs(1, c, h, w, 2400 + 3 * k, mode, sigma=6.0)
+        _splat_row(rows, ops, dev, f"C={c} {h}x{w}", x, flow, metric, mode, f"keys={splat_keys(1, h, w)}")
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- resize_bilinear_scale
+RESIZE_SCALE_CASES = ((2, 3, 37, 53, 0.5), (1, 2, 45, 83, 0.25), (1, 3, 13, 45, 2.0), (2, 2, 4, 5, 0.25), (1, 3) + BIG_MAP + (0.5,))
+
+
+def resize_scale_ref(x, factor):
+    """F.interpolate(x, scale_factor=factor, mode="bilinear", align_corners=False) written out (GMFSS.py's _half, IFNet's
+    stage inputs): out size floor(in * factor); the source coordinate of output i is max((i + 0.5) / factor - 0.5, 0) -- the
+    multiplier is 1 / factor as given, not the ratio of the sizes --, taps i0 = min(floor(s), in - 1) and min(i0 + 1, in - 1)."""
+    def axis(n_in):
+        n_out = int(n_in * factor)
+        s = ((torch.arange(n_out, dtype=x.dtype) + 0.5) * (1.0 / factor) - 0.5).clamp(min=0.0)
+        i0 = s.floor().clamp(max=n_in - 1)
+        return i0.long(), (i0 + 1).clamp(max=n_in - 1).long(), s - i0
+
+    y0, y1, ly = axis(x.shape[2])
+    x0, x1, lx = axis(x.shape[3])
+    ly = ly.view(-1, 1)
+    top = x[:, :, y0][:, :, :, x0] * (1 - lx) + x[:, :, y0][:, :, :, x1] * lx
+    bot = x[:, :, y1][:, :, :, x0] * (1 - lx) + x[:, :, y1][:, :, :, x1] * lx
+    return top * (1 - ly) + bot * ly
+
+
+def check_resize_scale(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    for i, (n, c, h, w, s) in enumerate(RESIZE_SCALE_CASES):
+        x = cases.rnd((n, c, h, w), 2500 + i, 2.0)
+        ho, wo = int(h * s), int(w * s)
+        got = ops.resize_bilinear_scale(x.to(dev), (ho, wo), 1.0 / s)
+        rows.append(value_row("resize_bilinear_scale", f"[{n}x{c}] {h}x{w} x{s:g} -> {ho}x{wo}", got, resize_scale_ref(x.double(), s),
+                              F.interpolate(x, scale_factor=s, mode="bilinear", align_corners=False)))
+    return rows
+
+
+# ----------------------------------------------------------------------------------------- flow_distance
+def flow_distance_ref(flow):
+    """tools.py:77-80: sqrt(u^2 + v^2), computed by the reference in fp32 -- so where the fp32 squares (or their sum) overflow
+    the specified answer is +inf, whatever the exact magnitude; everywhere else the exact value in fp64."""
+    u, v = flow[:, 0:1], flow[:, 1:2]
+    d = torch.sqrt(u.double() ** 2 + v.double() ** 2)
+    over = torch.isinf(u.float() ** 2 + v.float() ** 2)
+    return torch.where(over, torch.full_like(d, float("inf")), d)
+
+
+def check_flow_distance(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    for i, shape in enumerate(((2, 2, 13, 45), (1, 2) + BIG_MAP)):
+        f = cases.rnd(shape, 2600 + i, 5.0)
+        rows.append(value_row("flow_distance", f"{list(shape)}", ops.flow_distance(f.to(dev)), flow_distance_ref(f), oops.distance(f)))
+    inf, nan = float("inf"), float("nan")
+    u = torch.tensor([0.0, -0.0, 1e-40, 3.0, nan, 1.0, inf, -inf, inf, 2e19, -1.5e19, 1e30, 1e-20, -0.0])
+    v = torch.tensor([-0.0, 0.0, 0.0, -4.0, 1.0, nan, 1.0, 2.0, nan, 0.0, 1.5e19, -1e30, 1e-20, 5.0])
+    f = torch.stack([u, v]).view(1, 2, 1, -1)
+    rows.append(value_row("flow_distance", "+-0, denormal, NaN, +-inf, squares that overflow fp32", ops.flow_distance(f.to(dev)), flow_distance_ref(f),
+                          oops.distance(f)))
+    return rows
+
+
+SPLAT_CHECKS = (check_softsplat, check_softsplat_scan, check_softsplat_big)  # the generic splat's families, for tests that take them together
 CHECKS = (  # (section title, check): one operator family each
     ("op softmax_rows_", check_softmax_rows), ("op instance_norm", check_instance_norm), ("op conv_direct", check_conv_direct),
     ("op local_corr_flow", check_local_corr_flow), ("op local_attn_flow", check_local_attn_flow),
     ("op convex_upsample", check_convex_upsample), ("op flow_warp", check_flow_warp), ("op backwarp", check_backwarp),
     ("op resize_bilinear_ac", check_resize_bilinear_ac), ("op layernorm", check_layernorm), ("op gelu", check_gelu), ("op bmm", check_bmm),
     ("op pointwise", check_pointwise), ("op layouts", check_layouts), ("op hole tests", check_hole_tests), ("op drm", check_drm),
-    ("op metric_input", check_metric_input))
+    ("op metric_input", check_metric_input), ("op softsplat", check_softsplat), ("op softsplat scan geometry", check_softsplat_scan),
+    ("op softsplat big map", check_softsplat_big), ("op resize_bilinear_scale", check_resize_scale), ("op flow_distance", check_flow_distance))

@@ -222,7 +222,28 @@ def test_operator_cases_hold_their_bars_in_the_mode(hip_backend):
     from tests import op_checks
     with mode():
         for _title, check in op_checks.CHECKS:
-            _assert_rows(check(hip_backend.dev))
+            if check not in op_checks.SPLAT_CHECKS:  # (the next test runs those)
+                _assert_rows(check(hip_backend.dev))
+
+
+def test_softsplat_rows_hold_their_bars_in_the_mode(hip_backend):
+    """The generic splat's fp64 rows with the mode on, against their own bars: splat_sort_segments then orders every segment of
+    the global records before the gathers.  The many-to-one, N = 3 and big-map rows are there, and between them they take
+    sort_segment through both of its branches -- computed from the flows: the N = 3 maps hold shared segments of a few records
+    and the zoom-out by 4 segments of exactly 16, the last length of the insertion branch; the zoom-out by 5 holds segments of
+    25 and the one-target map is one segment of 3071 records (heap)."""
+    from tests import cases, op_checks
+    h, w = op_checks.SPLAT_MAP
+    small = op_checks.splat_segment_sizes(op_checks.splat_inputs(3, 5, h, w, 2060)[1])
+    assert 2 <= int(small.max()) <= 16, int(small.max())
+    assert int(op_checks.splat_segment_sizes(op_checks.onto_flow(h, w)).max()) == h * w
+    assert int(op_checks.splat_segment_sizes(cases.ops_inputs()["flow_converge"]).max()) == 16
+    assert 16 < int(op_checks.splat_segment_sizes(op_checks.zoom_flow(h, w)).max()) <= 36
+    with mode():
+        rows = [r for check in op_checks.SPLAT_CHECKS for r in check(hip_backend.dev)]
+    for must in ("every source onto", "zoom-out", "N=3 C=5", "N=3 C=3", "1024x1280"):
+        assert sum(must in r[0] for r in rows) >= 2, must
+    _assert_rows(rows)
 
 
 def test_glue_splat_rows_hold_their_bars_in_the_mode(hip_backend):

@@ -1,6 +1,7 @@
-"""GPU (-m gpu): every pointwise / gather / reduction kernel of the GMFlow and GMFSS glue on its own against a float64
-reference (tests/op_checks.py), at the sizes where kernels go wrong: image borders, partial tiles and blocks, every dispatch
-branch, batch > 1, grid-stride loops that go round twice.  One operator family per test, so that a failure names it.
+"""GPU (-m gpu): every pointwise / gather / reduction kernel of the GMFlow and GMFSS glue, the generic forward splat
+(count, scan, fill, gathers), resize_bilinear_scale and flow_distance on their own against a float64 reference
+(tests/op_checks.py), at the sizes where kernels go wrong: image borders, partial tiles and blocks, every dispatch branch,
+batch > 1, grid-stride loops and scan rounds that go round twice.  One operator family per test, so that a failure names it.
 
 Value rows: tol = max(2e-5 max(1, |ref|max), 3 x the fp32 oracle's own error on that input); decisions and data movement:
 bit-exact.  tests/test_op_checks_cpu.py shows on the CPU that these rows fail for a wrong operator."""
@@ -89,6 +90,121 @@ def test_metric_input(hip_backend):
     _assert_rows(op_checks.check_metric_input(hip_backend.dev))
 
 
+SCAN_PER_BLOCK = 4096         # kScanPerBlock, drba_amd/csrc/splat_warp.hip:668 (keys per scan_block workgroup), restated
+SCAN_SUMS_ROUND = 256         # block sums scan_sums takes per round of its carry loop, splat_warp.hip:734 (b0 += 256)
+GRID_STRIDE = 2048 * 256      # kMaxBlocks x kBlock, drba_amd/csrc/common.hpp:92-96 (grid_for): pixels one round of a grid-stride loop covers
+
+
+def _scan_blocks(n, h, w):
+    return -(-op_checks.splat_keys(n, h, w) // SCAN_PER_BLOCK)
+
+
+def test_softsplat(hip_backend):
+    _assert_rows(op_checks.check_softsplat(hip_backend.dev))
+
+
+def test_softsplat_scan_geometry(hip_backend):
+    """One full scan block, two, a ragged second one, image boundaries inside a block -- asserted from the restated constant, so
+    that a change of kScanPerBlock fails here instead of silently un-covering the multi-block scan."""
+    assert [op_checks.splat_keys(*c) for c in op_checks.SCAN_CASES[:3]] == [SCAN_PER_BLOCK, 2 * SCAN_PER_BLOCK, SCAN_PER_BLOCK + 64]
+    assert [_scan_blocks(*c) for c in op_checks.SCAN_CASES] == [1, 2, 2, 4, 3]
+    for n, h, w in op_checks.SCAN_CASES[3:]:  # N = 3: no image starts on a block boundary, and some block holds keys of two images
+        starts = [k * (h + 1) * (w + 1) for k in (1, 2)]
+        assert all(s % SCAN_PER_BLOCK for s in starts) and starts[0] // SCAN_PER_BLOCK < _scan_blocks(n, h, w) - 1
+    rows = op_checks.check_softsplat_scan(hip_backend.dev)
+    assert all(f"keys={op_checks.splat_keys(*c)}" in " ".join(r[3] for r in rows) for c in op_checks.SCAN_CASES)
+    _assert_rows(rows)
+
+
+def test_softsplat_big_map(hip_backend):
+    """scan_sums goes round its carry loop more than once (nb > 256, dozens of blocks in the second round) and the grid-stride
+    loops of splat_sort_count / splat_sort_fill more than twice: code that no smaller map of the suite runs."""
+    h, w = op_checks.SPLAT_BIG
+    nb = _scan_blocks(1, h, w)
+    assert nb > SCAN_SUMS_ROUND + 32 and op_checks.splat_keys(1, h, w) > 1_200_000  # splat_warp.hip:668, 734
+    assert h * w > 2 * GRID_STRIDE                                                 # common.hpp:92-96
+    _assert_rows(op_checks.check_softsplat_big(hip_backend.dev))
+
+
+def test_resize_bilinear_scale(hip_backend):
+    _assert_rows(op_checks.check_resize_scale(hip_backend.dev))
+
+
+def test_flow_distance(hip_backend):
+    _assert_rows(op_checks.check_flow_distance(hip_backend.dev))
+
+
+WS_GUARD = 4096
+WS_SHAPES = ((1, 1, 1), (1, 2, 2), (1, 1, 2), (1, 2, 4),  # (N, H, W): L = N (H + 1) (W + 1) = 4, 9, 6, 15 -- every residue mod 4, one block
+             (1, 63, 64), (1, 90, 90), (2, 78, 80), (1, 128, 130))  # 4160 (2 blocks), 8281 (3), 12798 (4), 16899 (5): residues 0, 1, 2, 3
+
+
+def test_softsplat_workspace_guard(hip_backend):
+    """drba_softsplat on a workspace of exactly drba_softsplat_ws_floats(N, C, H, W) floats followed by 4096 sentinel floats (one
+    allocation: nothing is written outside allocated memory whatever the layout does): the sentinels are untouched and the
+    output holds its fp64 row, for every residue of the key count mod 4 (the alignment padding of start / bsum / rec in
+    splat_ws), 1 to 5 scan blocks, a quad-gather and a planar-gather channel count each."""
+    import ctypes as C
+    from drba_amd import _lib, ops
+    lib, dev = _lib.load(), hip_backend.dev
+    keys = [op_checks.splat_keys(*s) for s in WS_SHAPES]
+    assert {k % 4 for k in keys} == {0, 1, 2, 3} and {-(-k // SCAN_PER_BLOCK) for k in keys} == {1, 2, 3, 4, 5}
+    assert {k % 4 for k in keys[:4]} == {0, 1, 2, 3} == {k % 4 for k in keys[4:]}
+    rows = []
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    for i, (n, h, w) in enumerate(WS_SHAPES):
+        for c in (16, 3):
+            mode = op_checks.SPLAT_MODES[(i + c) % 4]
+            x, flow, metric = op_checks.splat_inputs(n, c, h, w, 2700 + 3 * i, mode, sigma=1.5)
+            size = lib.drba_softsplat_ws_floats(n, c, h, w)
+            ws = torch.full((size + WS_GUARD,), 1.2345e-3, device=dev)
+            out = torch.full((n, c, h, w), float("nan"), device=dev)
+            xd, fd, md = x.to(dev), flow.to(dev), None if metric is None else metric.to(dev)
+            rc = lib.drba_softsplat(ptr(xd), ptr(fd), C.c_void_p(0) if md is None else ptr(md), ptr(out), ptr(ws), n, c, h, w, ops._MODES[mode], 0,
+                                    ops._stream())
+            assert rc == 0, (rc, n, c, h, w)
+            name = f"{mode} ws guard N={n} C={c} {h}x{w}"
+            rows.append(op_checks.value_row("softsplat", name, out, *op_checks.splat_refs(name, x, flow, metric, mode),
+                                            f"keys={keys[i]} ws={size} floats"))
+            rows.append(op_checks.exact_row("softsplat", f"{name}: the {WS_GUARD} floats behind the workspace", ws[size:],
+                                            torch.full((WS_GUARD,), 1.2345e-3)))
+    _assert_rows(rows)
+
+
+def test_softsplat_reuse_index_launches_one_gather(hip_backend):
+    """check_softsplat's reuse_index=True row again, with the kernel trace on: the values are the same whether the index was
+    reused or quietly rebuilt, the launches are not.  A reused index is one gather launch and nothing of count / scan / fill;
+    after an in-place update of the flow the same call has to rebuild (ops.softsplat_many drops its token), and the trace shows
+    that too -- so the first assertion is not one that any call would pass."""
+    from drba_amd import ops
+    dev = hip_backend.dev
+    xs, flow, metric = op_checks.many_inputs()
+    fd, md, x17 = flow.to(dev), metric.to(dev), xs[2].to(dev)
+
+    def traced():
+        torch.cuda.synchronize()
+        ops.trace_begin()
+        try:
+            got = ops.softsplat_many([x17], fd, md, "soft", reuse_index=True)[0]
+            torch.cuda.synchronize()
+        finally:
+            recs = ops.trace_end()
+        return got, [r["name"] for r in recs]
+
+    ops.softsplat_many([x.to(dev) for x in xs], fd, md, "soft")
+    got, names = traced()
+    print(f"  reuse_index=True launches: {names}")
+    assert len(names) == 1 and "splat_sorted_gather" in names[0], names
+    rows = [op_checks.value_row("softsplat", op_checks.REUSE_ROW, got, *op_checks.splat_refs(op_checks.REUSE_ROW, xs[2], flow, metric, "soft"))]
+    fd.add_(0.0)  # same values, a new version: the index on record is no longer vouched for
+    got, names = traced()
+    print(f"  reuse_index=True after an in-place update of the flow: {names}")
+    assert any("splat_sort_count" in n for n in names) and any("splat_sort_fill" in n for n in names), names
+    rows.append(op_checks.value_row("softsplat", op_checks.REUSE_ROW + ", flow updated in place: rebuilt", got,
+                                    *op_checks.splat_refs(op_checks.REUSE_ROW, xs[2], flow, metric, "soft")))
+    _assert_rows(rows)
+
+
 def test_documented_refusals(hip_backend):
     """Shapes a launcher documents as refused raise DrbaHipError; nothing is launched for them."""
     from drba_amd import _lib, ops
@@ -106,4 +222,6 @@ def test_documented_refusals(hip_backend):
             ops.metric_input(z(1, 3, h, w), z(1, 3, h, w), z(1, 2, h, w), z(1, 2, h, w))
     with pytest.raises(_lib.DrbaHipError):
         ops.softmax_rows_(z(2, 3, 5), 0.0)  # scale must be positive
+    with pytest.raises(_lib.DrbaHipError):  # a channel slice of N = 2 is not contiguous: the gathers store through a raw pointer
+        ops.softsplat(z(2, 3, 8, 8), z(2, 2, 8, 8), None, "avg", out=z(2, 6, 8, 8)[:, 1:4])
     torch.cuda.synchronize()

@@ -1,8 +1,9 @@
 """CPU (-m "not gpu"): the per-operator checks of tests/op_checks.py CAN fail, and their references are right.
 
 The "implementation under test" here is a torch-fp32 stand-in for drba_amd.ops, written tap by tap the way the kernels are
-(explicit window loops, explicit bilinear gathers, explicit index arithmetic) -- not with the unfold / grid_sample /
-F.interpolate forms the fp64 references use -- so that two independent statements of every formula meet:
+(explicit window loops, explicit bilinear gathers, explicit index arithmetic; the forward splat as a key per source, the
+sources ordered by key and the outputs summing their four segments) -- not with the unfold / grid_sample / F.interpolate /
+corner-by-corner scatter forms the fp64 references use -- so that two independent statements of every formula meet:
   1. every fp64 reference agrees with the fp32 oracle / torch form of the same formula within fp32 roundoff (the measured
      floor of each row is bounded by a figure derived from the number format and the operation's conditioning);
   2. the stand-in passes every row;
@@ -200,6 +201,79 @@ def _metric_input(img0, img1, f01, f10, defect=False):
     return torch.cat([img0, img1, -m0, -m1, f01[:, 0:1] / hx, f01[:, 1:2] / hy, f10[:, 0:1] / hx, f10[:, 1:2] / hy, occ(df), occ(db)], 1)
 
 
+def _softsplat(x, flow, metric, mode, out=None, keep_quad=False, defect=None):
+    """The generic splat in the kernels' form: one key per source (the pixel its 2 x 2 footprint starts at, on the
+    (H + 1) x (W + 1) grid of every image), the sources ordered by key, and every output summing the records of the four keys
+    that cover it, footprint row by footprint row, right key before left -- weight = m * (wx * wy), value * weight, the
+    normaliser the sum of the weights.  (The oracle scatters corner by corner in source order, value * m first.)"""
+    main, _, sub = mode.partition("-")
+    n, c, h, w = x.shape
+    if defect == "base_of_image0":  # image n reads the records of image 0
+        flow = flow[0:1].expand(n, 2, h, w)
+        metric = None if metric is None else metric[0:1].expand(n, 1, h, w)
+    if defect == "tail_repeats" and c == 17:
+        x = torch.cat([x[:, :16], x[:, 15:16]], 1)
+    xs, ys = _grid(n, h, w)
+    X, Y = xs + flow[:, 0], ys + flow[:, 1]
+    fx, fy = X.floor(), Y.floor()
+    first = 0.0 if defect == "no_minus1" else -1.0
+    ok = torch.isfinite(X) & torch.isfinite(Y) & (fx >= first) & (fx <= w - 1) & (fy >= first) & (fy <= h - 1)
+    img = torch.arange(n).view(n, 1, 1).expand(n, h, w)[ok]
+    src = torch.arange(h * w).view(1, h, w).expand(n, h, w)[ok]
+    m = torch.ones(n, h, w) if main in ("sum", "avg") else (metric[:, 0] if main == "linear" else metric[:, 0].exp())
+    X, Y, fx, fy, m = X[ok], Y[ok], fx[ok], fy[ok], m[ok]
+    key = img * ((h + 1) * (w + 1)) + (fy.long() + 1) * (w + 1) + (fx.long() + 1)
+    order = torch.sort(key, stable=True).indices
+    if defect == "lost_keys":
+        order = order[key[order] < (1 << 20)]
+    img, src, X, Y, fx, fy, m = (t[order] for t in (img, src, X, Y, fx, fy, m))
+    vals = x.permute(0, 2, 3, 1).reshape(n * h * w, c)[img * (h * w) + src]
+    acc, nrm = torch.zeros(n * h * w, c), torch.zeros(n * h * w)
+    for dy in (0, 1):
+        for dx in (1, 0):
+            wgt = m * ((X - fx if dx else (fx + 1) - X) * (Y - fy if dy else (fy + 1) - Y))
+            px, py = fx.long() + dx, fy.long() + dy
+            inb = (px >= 0) & (px < w) & (py >= 0) & (py < h)
+            lin = (img * (h * w) + py * w + px)[inb]
+            nrm.index_add_(0, lin, wgt[inb])
+            acc.index_add_(0, lin, vals[inb] * wgt[inb].unsqueeze(1))
+    if main != "sum":
+        if sub in ("", "addeps") or defect == "zeroeps_as_addeps":
+            nrm = nrm + 0.0000001
+        elif sub == "zeroeps":
+            nrm = torch.where(nrm == 0, torch.ones_like(nrm), nrm)
+        else:
+            nrm = nrm.clamp(min=0.0000001)
+        acc = acc / nrm.unsqueeze(1)
+    res = acc.view(n, h, w, c).permute(0, 3, 1, 2).contiguous()
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
+def _softsplat_many(inputs, flow, metric, mode, outs=None, reuse_index=False, keep_quad=False):
+    return [_softsplat(x, flow, metric, mode, None if outs is None else outs[k]) for k, x in enumerate(inputs)]
+
+
+def _resize_bilinear_scale(x, size, src_scale, defect=False):
+    (hi, wi), (ho, wo) = x.shape[2:], size
+
+    def axis(n_in, n_out):
+        mul = n_in / n_out if defect else src_scale
+        s = (mul * (torch.arange(n_out, dtype=torch.float32) + 0.5) - 0.5).clamp(min=0)
+        i0 = s.floor().clamp(max=n_in - 1)
+        return i0.long(), (i0 + 1).clamp(max=n_in - 1).long(), s - i0
+
+    y0, y1, ly = axis(hi, ho)
+    x0, x1, lx = axis(wi, wo)
+    out = torch.empty(x.shape[0], x.shape[1], ho, wo)
+    for oy in range(ho):  # row by row: four taps, horizontal lerp first
+        a, b, cc, d = x[:, :, y0[oy]][..., x0], x[:, :, y0[oy]][..., x1], x[:, :, y1[oy]][..., x0], x[:, :, y1[oy]][..., x1]
+        out[:, :, oy] = (1 - ly[oy]) * ((1 - lx) * a + lx * b) + ly[oy] * ((1 - lx) * cc + lx * d)
+    return out
+
+
 def _to_inp(img_u8, dst_size):
     out = F.interpolate(img_u8.permute(2, 0, 1)[None].float() / 255.0, size=tuple(dst_size), mode="bilinear", align_corners=False)
     x4 = torch.zeros(dst_size[0], dst_size[1], 4)
@@ -212,7 +286,8 @@ STANDIN = dict(
     softmax_rows_=_softmax_rows_, instance_norm=_instance_norm, conv_direct=_conv_direct, local_corr_flow=_local_corr_flow,
     local_attn_flow=_local_attn_flow, convex_upsample=_convex_upsample, flow_warp=_flow_warp, backwarp=_backwarp,
     resize_bilinear_ac=_resize_bilinear_ac, layernorm=_layernorm, timestep_fix=_timestep_fix, drm_ratio=_drm_ratio,
-    metric_input=_metric_input, to_inp=_to_inp,
+    metric_input=_metric_input, to_inp=_to_inp, softsplat=_softsplat, softsplat_many=_softsplat_many,
+    resize_bilinear_scale=_resize_bilinear_scale, flow_distance=lambda f: (f[:, 0:1] * f[:, 0:1] + f[:, 1:2] * f[:, 1:2]).sqrt(),
     gelu=lambda x: 0.5 * x * (1 + torch.erf(x * 0.7071067811865476)),
     bmm=lambda a, b, trans_b: torch.einsum("bmk,bnk->bmn", a, b) if trans_b else torch.einsum("bmk,bkn->bmn", a, b),
     add_act=lambda a, b, relu=False: (a + b).clamp(min=0) if relu else a + b,
@@ -313,6 +388,8 @@ def test_standin_passes_every_check(clean):
     assert not bad, "\n".join(f"{r[0]}: err={r[1]:.3e} tol={r[2]:.1e} {r[3]}" for r in bad)
     ops_seen = set().union(*(used for _, used in clean.values()))
     assert ops_seen == set(STANDIN), sorted(set(STANDIN) ^ ops_seen)  # every operator of the issue is exercised by some check
+    # SPLAT_CHECKS (what the deterministic-mode tests split CHECKS by) is exactly the families that call the generic splat
+    assert set(op_checks.SPLAT_CHECKS) == {check for title, check in op_checks.CHECKS if {"softsplat", "softsplat_many"} & clean[title][1]}
 
 
 def test_metric_input_masks_are_mostly_stable_and_two_sided(clean):
@@ -323,8 +400,11 @@ def test_metric_input_masks_are_mostly_stable_and_two_sided(clean):
 
 
 # ----------------------------------------------------------------------------------------- 3. planted defects
-def _with(fn):
-    return lambda *a, **k: fn(*a, defect=True, **k)
+def _with(fn, defect=True):
+    """fn with its planted defect: the only one it has, or the named one of several"""
+    variant = lambda *a, **k: fn(*a, defect=defect, **k)  # noqa: E731
+    variant.defect = defect
+    return variant
 
 
 DEFECTS = (  # (operator of the stand-in, its defective variant, the operator family that must fail, a row that must fail)
@@ -343,10 +423,19 @@ DEFECTS = (  # (operator of the stand-in, its defective variant, the operator fa
     ("flow_warp", lambda x, f: _backwarp(x, f, "border"), "flow_warp", "amp30"),
     ("local_corr_flow", lambda a, b, r: _local_corr_flow(F.pad(a, (r, r, r, r)), F.pad(b, (r, r, r, r)), r)[:, :, r:-r, r:-r].contiguous(),
      "local_corr_flow", "13x45"),
+    # the generic splat: the carry of scan_sums' second round, the key column / row of footprints that start at -1, the tail
+    # of the 16-channel chunk, the per-image offset of the segment table, the eps variants; the resize's multiplier
+    ("softsplat", _with(_softsplat, "lost_keys"), "softsplat", "1024x1280"),
+    ("softsplat", _with(_softsplat, "no_minus1"), "softsplat", "borders"),
+    ("softsplat", _with(_softsplat, "tail_repeats"), "softsplat", "N=2 C=17"),
+    ("softsplat", _with(_softsplat, "base_of_image0"), "softsplat", "N=3 C=5"),
+    ("softsplat", _with(_softsplat, "zeroeps_as_addeps"), "softsplat", "soft-zeroeps normaliser"),
+    ("resize_bilinear_scale", _with(_resize_bilinear_scale), "resize_bilinear_scale", "37x53"),
 )
+DEFECT_IDS = [d[0] + (" " + d[1].defect if isinstance(getattr(d[1], "defect", None), str) else "") for d in DEFECTS]
 
 
-@pytest.mark.parametrize("name,variant,family,must_fail", DEFECTS, ids=[d[0] for d in DEFECTS])
+@pytest.mark.parametrize("name,variant,family,must_fail", DEFECTS, ids=DEFECT_IDS)
 def test_planted_defect_fails_its_row_and_only_its_operator(clean, name, variant, family, must_fail):
     touched = [(title, check) for title, check in op_checks.CHECKS if name in clean[title][1]]
     assert touched  # (a check that never calls the operator cannot change: its rows are the clean ones, which pass)
