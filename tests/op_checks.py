@@ -1,6 +1,8 @@
 """Per-operator fp64 parity checks of the GMFlow / GMFSS glue kernels (gmflow.hip, gmfss_glue.hip, the small kernels of
 splat_warp.hip and the layout kernels of ifnet_glue.hip and frame_io.hip), of the generic forward splat (splat_warp.hip:
-drba_softsplat, _index, _again, _gather_quad) and of resize_bilinear_scale and flow_distance, shared by
+drba_softsplat, _index, _again, _gather_quad), of resize_bilinear_scale and flow_distance, and of the IFNet stage glue
+(ifnet_glue.hip, flow_terms.hpp, stage_conv.hip, stage_conv16.hip: stage-input gathers, the gathers fused with conv0[0], the
+flow update, the final warp + blend -- in the forms the pipeline runs them), shared by
 tests/test_gpu_op_parity.py, tests/test_op_checks_cpu.py and the diagnostic report (python -m tests.gpu_report).
 
 Every check takes the device the inputs go to and the `ops` namespace under test (default: drba_amd.ops; the CPU test hands
@@ -16,10 +18,14 @@ where `floor` is the max error of the fp32 oracle / fp32 torch evaluation of the
 fp64 reference: measured per row, printed in the row, never calibrated against the code under test.  Decisions (masks, hole
 tests, the DRM retiming walk) and pure data movement are compared bit for bit: err = number of differing elements, tol = 0.
 
-Two places where ATen's CPU result is not the specification are written out instead of taken from ATen:
+Three places where ATen's CPU result is not the specification are written out instead of taken from ATen:
   * a zeros-padding bilinear sample at a non-finite coordinate is 0 (every tap is outside the image; ATen's CPU kernel forms
     0 * NaN there, its CUDA kernel -- what the reference model runs on -- skips the taps);
-  * InstanceNorm of a one-element plane is 0 (variance 0; F.instance_norm refuses the shape).
+  * InstanceNorm of a one-element plane is 0 (variance 0; F.instance_norm refuses the shape);
+  * a bilinear resize by 1 (the scale-1 stage's interpolate(x, scale_factor=1)) is the identity, also at a non-finite pixel
+    (_down; ATen's weight-0 tap makes a NaN of it, at the pixel on the CPU and at its neighbour on the GPU).
+A stage input is reported as one row per channel group (frames, features, timestep, mask / feat, flow: magnitudes 1, 4, 1, 3
+and up to thousands), each with its own |ref|max and floor, so that the flow channels do not set what the frames are allowed.
 The splat's reference takes its targets as the specification does, as the fp32 sum x + flow, and evaluates everything after
 that in fp64 (softsplat_ref): with fp64 targets a source next to an integer lands on other pixels than the specified ones, and
 the fp32 oracle's "error" against such a reference (1e-4 at 37 x 83, above 1 for avg at 1024 x 1280) would set a tolerance
@@ -957,6 +963,382 @@ def check_flow_distance(dev, ops=None):
     return rows
 
 
+# ----------------------------------------------------------------------------------------- IFNet stage glue
+# ifnet_glue.hip, flow_terms.hpp, stage_conv.hip, stage_conv16.hip in the forms the pipeline runs: frames read from their
+# [H, W, 4] copies (ops.rgbx), pair-only features, the running flow as terms (one-row term maps among them), the fused
+# first convolution at scale 1 and 2, the final blend at the frame's own resolution with four terms.  References from
+# IFNet_HDv3.py:85-95 (IFBlock.forward) and :146-167 (the stage loop and the final blend).
+STAGE_GROUPS = (("frames", 0, 6), ("features", 6, 38), ("timestep", 38, 39), ("mask/feat", 39, 48), ("flow", 48, 52))
+T_SCALAR = 0.37
+
+
+def up(t, s):
+    return F.interpolate(t, scale_factor=float(s), mode="bilinear", align_corners=False)
+
+
+def _down(x, s):
+    """F.interpolate(x, scale_factor=1 / s) (IFNet_HDv3.py:85,87).  At s = 1 it is the identity, and written as one: ATen forms
+    t0 + 0 * (t1 - t0) there, NaN at a non-finite pixel (its CUDA kernel: 1 * t0 + 0 * t1, NaN at the neighbour instead), which is
+    not the specification of a resize by 1."""
+    return x if s == 1 else F.interpolate(x, scale_factor=1.0 / s, mode="bilinear", align_corners=False)
+
+
+def running_flow(terms, tmp_prev, sp):
+    """IFNet_HDv3.py:146-160: sum of up(t_i[:, :4], s_i) * s_i over the earlier head outputs (oldest first, possibly none) and the
+    newest one, tmp_prev at scale sp."""
+    fl = None
+    for t, s in list(terms) + [(tmp_prev, sp)]:
+        d = up(t[:, :4], s) * s
+        fl = d if fl is None else fl + d
+    return fl
+
+
+def update_ref(tmp, flow_in, s):
+    """IFNet_HDv3.py:92-95,160 -> (flow_in + up(tmp[:, :4]) * s, mask, feat)"""
+    u = up(tmp, s)
+    fd = u[:, :4] * s
+    return (fd if flow_in is None else flow_in + fd), u[:, 4:5], u[:, 5:13]
+
+
+def stage_input_ref(img0, img1, f0, f1, timestep, flow, tmp_prev, sp, s):
+    """IFNet_HDv3.py:85-95,151-156: the IFBlock's input at 1 / s.  flow None: the first stage's 39 channels."""
+    tmap = timestep if torch.is_tensor(timestep) else torch.full_like(img0[:, :1], float(timestep))
+    if flow is None:
+        return _down(torch.cat((img0, img1, f0, f1, tmap), 1), s)
+    u = up(tmp_prev, sp)
+    warp = lambda x, f: backwarp_ref(x, f, "border")  # noqa: E731
+    x = torch.cat((warp(img0, flow[:, :2]), warp(img1, flow[:, 2:4]), warp(f0, flow[:, :2]), warp(f1, flow[:, 2:4]), tmap, u[:, 4:5], u[:, 5:13]), 1)
+    return torch.cat((_down(x, s), _down(flow, s) * (1.0 / s)), 1)
+
+
+def blend_ref(img0, img1, flow, mask_logit):
+    """IFNet_HDv3.py:163-167"""
+    m = torch.sigmoid(mask_logit)
+    return backwarp_ref(img0, flow[:, :2], "border") * m + backwarp_ref(img1, flow[:, 2:4], "border") * (1 - m)
+
+
+def stage_conv_ref(img0, img1, f0, f1, timestep, flow, tmp_prev, sp, s, w, b):
+    """conv0[0] of the IFBlock (IFNet_HDv3.py:8-14,68) on its stage input"""
+    return F.leaky_relu(F.conv2d(stage_input_ref(img0, img1, f0, f1, timestep, flow, tmp_prev, sp, s), w, b, stride=2, padding=1), 0.2)
+
+
+def _fold_input_ref(img0, img1, f0, f1, timestep, prior, tmp_prev, sp, s):
+    return stage_input_ref(img0, img1, f0, f1, timestep, update_ref(tmp_prev, prior, sp)[0], tmp_prev, sp, s)
+
+
+def _lazy_input_ref(img0, img1, f0, f1, timestep, terms, tmp_prev, sp, s):
+    return stage_input_ref(img0, img1, f0, f1, timestep, running_flow(terms, tmp_prev, sp), tmp_prev, sp, s)
+
+
+def _cast(a, dt):
+    if torch.is_tensor(a):
+        return a.to(dt)
+    if isinstance(a, (list, tuple)):
+        return type(a)(_cast(b, dt) for b in a)
+    return a
+
+
+_GLUE_REFS = {}  # key -> (fp64 reference, fp32 form): computed once per process, never written to
+
+
+def refs(fn, *args, key=None):
+    """(fn in float64, fn in float32) on the same arguments: the reference and the floor of a row.  key: the name the pair is
+    kept under (the inputs regenerate from seeds, so a key names one set of arguments)."""
+    if key is None:
+        return fn(*_cast(args, torch.float64)), fn(*_cast(args, torch.float32))
+    if key not in _GLUE_REFS:
+        _GLUE_REFS[key] = refs(fn, *args)
+    return _GLUE_REFS[key]
+
+
+def glue_frames(n, h, w, seed):
+    """img0, img1 [n, 3, h, w] in [0, 1], f0, f1 [n, 16, h, w] of amplitude 4, a timestep map [n, 1, h, w]: smooth fields, so that
+    the fp32 floor of a warped row (the coordinate's round trip through [-1, 1], a few ulps of W - 1, times the largest
+    neighbour difference) stays below the rule's first term"""
+    sm = lambda c, k: _smooth(n * c, h, w, seed + k).view(n, c, h, w)  # noqa: E731
+    return sm(3, 0), sm(3, 1), (sm(16, 2) - 0.5) * 8.0, (sm(16, 3) - 0.5) * 8.0, sm(1, 4)
+
+
+def glue_heads(n, h, w, scales, seed, rough=None):
+    """{s: head output [n, 13, h / s, w / s]}: flow channels of amplitude 2 / s (the update up(t[:, :4]) * s is a few pixels per
+    stage); rough=s: that term's update has sigma 4 w, so that most samples clamp at the border"""
+    out = {}
+    for s in scales:
+        assert h % s == 0 and w % s == 0, (h, w, s)  # (the reference model cannot form other sizes)
+        t = cases.rnd((n, 13, h // s, w // s), seed + s, 1.0)
+        t[:, :4] *= 2.0 / s * (2.0 * w if s == rough else 1.0)
+        out[s] = t
+    return out
+
+
+def flows4(h, w, seed):
+    """name -> [1, 4, h, w] of warp_flows: channels 0-1 warp img0, 2-3 img1"""
+    return {k: v.reshape(1, 4, h, w) for k, v in warp_flows(2, h, w, seed).items()}
+
+
+def glue_item(dev, ops, fr, k, x4=False, pair=False, tscalar=None):
+    """(img0, img1, timestep, f0, f1) of item k on the device, as tensors of its own: the layout copies live on the tensor object"""
+    img0, img1, f0, f1, tm = (t[k:k + 1].clone().to(dev) for t in fr)
+    if x4:
+        ops.rgbx(img0), ops.rgbx(img1)
+    if pair:
+        f0, f1 = ops.pair_interleaved(f0), ops.pair_interleaved(f1)
+    return (img0, img1, tm if tscalar is None else tscalar, f0, f1)
+
+
+def stage_rows(op, name, got, ref64, ref32):
+    """one row per channel group of a stage input, each with its own |ref|max and floor"""
+    if got.dim() != 4 or got.shape[1] != ref64.shape[1]:
+        return [Row(op, name, float("inf"), 0.0, f"shape {tuple(got.shape)} for {tuple(ref64.shape)}")]
+    return [value_row(op, f"{name} {g}", got[:, a:b], ref64[:, a:b], ref32[:, a:b]) for g, a, b in STAGE_GROUPS if b <= ref64.shape[1]]
+
+
+def _scalar_t(r):
+    """the references of the same row with the scalar timestep: a constant map stays the constant under the downsample"""
+    out = []
+    for t in r:
+        t = t.clone()
+        t[:, 38] = T_SCALAR
+        out.append(t)
+    return out
+
+
+FIRST_CASES = (((64, 128), (16, 4, 1)), ((72, 136), (4, 2, 1)), ((70, 90), (1,)))
+
+
+def check_stage_input_first(dev, ops=None):
+    """The first stage (no flow, 39 channels): ifblock_input_pixel / ifblock_input_kernel<false, ...>, planar and pair-only features."""
+    ops = ops or default_ops()
+    rows = []
+    for i, ((h, w), scales) in enumerate(FIRST_CASES):
+        fr = glue_frames(1, h, w, 3000 + 10 * i)
+        for s in scales:
+            r = refs(stage_input_ref, *fr, None, None, 1.0, s, key=f"first {h}x{w} s={s}")
+            for tscalar in (None, T_SCALAR):
+                rr = r if tscalar is None else _scalar_t(r)
+                for pair in (False, True):
+                    it = glue_item(dev, ops, fr, 0, pair=pair, tscalar=tscalar)
+                    got = ops.ifblock_input(it[0], it[1], it[3], it[4], it[2], None, None, 1.0, s)
+                    name = f"first {h}x{w} s={s} t={'map' if tscalar is None else 'scalar'} features={'pair-only' if pair else 'planar'}"
+                    rows += stage_rows("ifblock_input", name, got, *rr)
+    h, w, s = 72, 136, 2
+    fr = glue_frames(3, h, w, 3050)
+    items = [glue_item(dev, ops, fr, k, pair=True) for k in range(3)]
+    out = torch.full((3, 39, h // s, w // s), float("nan")).to(dev)
+    ops.stage_inputs(items, None, None, 1.0, s, out, lds=False)
+    rows += stage_rows("stage_inputs", f"first B=3 {h}x{w} s={s} lds=False features=pair-only", out, *refs(stage_input_ref, *fr, None, None, 1.0, s, key="first B=3"))
+    return rows
+
+
+def _stage_inputs_out(ops, dev, items, flows, tp, sp, s, fold=False, terms=None):
+    """ops.stage_inputs into a NaN-filled [B, 52, h / s, w / s] -> (out, the folded flows or None)"""
+    h, w = items[0][0].shape[2:]
+    out = torch.full((len(items), 52, h // s, w // s), float("nan")).to(dev)
+    fo = ops.stage_inputs(items, flows, tp, float(sp), float(s), out, fold=fold, terms=terms)
+    return out, fo
+
+
+def check_stage_input_warped(dev, ops=None):
+    """Warped stage inputs with the flow finished (FMODE 0), folded (1) and as terms (2); planar and [H, W, 4] frames."""
+    ops = ops or default_ops()
+    rows = []
+    D = lambda t: t.to(dev)  # noqa: E731
+    # ---- finished flow: whole tiles (vector stores) at 64 x 128, ragged tiles (scalar stores) at 72 x 136
+    for i, ((h, w), scales) in enumerate((((64, 128), (8, 2, 1)), ((72, 136), (4, 2, 1)))):
+        fr = glue_frames(1, h, w, 3100 + 10 * i)
+        heads = glue_heads(1, h, w, [2 * s for s in scales], 3120 + 100 * i)
+        for s in scales:
+            sp, tp = 2 * s, heads[2 * s]
+            for fname, flow in flows4(h, w, 3140 + 10 * i).items():
+                tag = f"{h}x{w} s={s} {fname}"
+                r = refs(stage_input_ref, *fr, flow, tp, float(sp), s, key="warped " + tag)
+                it = glue_item(dev, ops, fr, 0)
+                got = ops.ifblock_input(it[0], it[1], it[3], it[4], it[2], D(flow), D(tp), float(sp), float(s))
+                rows += stage_rows("ifblock_input", f"warped {tag} t=map", got, *r)
+                got = ops.ifblock_input_lds(it[0], it[1], it[3], it[4], T_SCALAR, D(flow), D(tp), float(sp), float(s))
+                rows += stage_rows("ifblock_input_lds", f"{tag} t=scalar", got, *_scalar_t(r))
+                if s <= 2:
+                    got, _ = _stage_inputs_out(ops, dev, [glue_item(dev, ops, fr, 0, x4=True)], [D(flow)], D(tp), sp, s)
+                    rows += stage_rows("stage_inputs", f"{tag} x4 t=map", got, *r)
+    # ---- the previous stage's update folded in, with a prior flow (planar frames) and with none (x4 frames, the batched entry)
+    for i, (h, w, s) in enumerate(((64, 128, 2), (64, 128, 1), (70, 90, 1), (72, 136, 2))):
+        fr = glue_frames(1, h, w, 3200 + 10 * i)
+        sp, tp = 2 * s, glue_heads(1, h, w, [2 * s], 3220 + 100 * i)[2 * s]
+        prior = flows4(h, w, 3240 + 10 * i)["smooth"] * 0.5
+        tag = f"fold {h}x{w} s={s}"
+        it = glue_item(dev, ops, fr, 0)
+        got, fo = ops.ifblock_input_lds(it[0], it[1], it[3], it[4], it[2], D(prior), D(tp), float(sp), float(s), fold=True)
+        rows.append(value_row("ifblock_input_lds", f"{tag} prior flow: flow_out", fo, *refs(lambda t, f: update_ref(t, f, sp)[0], tp, prior, key=tag + " flow")))
+        rows += stage_rows("ifblock_input_lds", f"{tag} prior flow", got, *refs(_fold_input_ref, *fr, prior, tp, float(sp), s, key=tag))
+        got, fo = _stage_inputs_out(ops, dev, [glue_item(dev, ops, fr, 0, x4=True)], [None], D(tp), sp, s, fold=True)
+        rows.append(value_row("stage_inputs", f"{tag} no prior flow x4: flow_out", fo[0], *refs(lambda t: update_ref(t, None, sp)[0], tp, key=tag + " flow, no prior")))
+        rows += stage_rows("stage_inputs", f"{tag} no prior flow x4", got, *refs(_fold_input_ref, *fr, None, tp, float(sp), s, key=tag + ", no prior"))
+
+    # ---- the flow as terms
+    def lazy(n, h, w, s, tscales, seed, x4s, rough=None):
+        fr = glue_frames(n, h, w, seed)
+        sp = 2 * s
+        heads = glue_heads(n, h, w, list(tscales) + [sp], seed + 20, rough)
+        terms = [(heads[t], float(t)) for t in tscales]
+        r = refs(_lazy_input_ref, *fr, terms, heads[sp], float(sp), s, key=f"lazy input {seed}")
+        for x4 in x4s:
+            items = [glue_item(dev, ops, fr, k, x4=x4) for k in range(n)]
+            got, _ = _stage_inputs_out(ops, dev, items, None, D(heads[sp]), sp, s, terms=[(D(t), ts) for t, ts in terms])
+            name = f"lazy {'B=%d ' % n if n > 1 else ''}{h}x{w} s={s} terms={tuple(tscales)}{' rough' if rough else ''} {'x4' if x4 else 'planar'}"
+            rows.extend(stage_rows("stage_inputs", name, got, *r))
+
+    lazy(1, 64, 128, 8, (), 3300, (False,))
+    lazy(1, 64, 128, 4, (16,), 3310, (False,))
+    lazy(1, 64, 128, 2, (16, 8), 3320, (False, True))
+    lazy(1, 64, 128, 1, (16, 8, 4), 3330, (False, True))
+    lazy(1, 16, 48, 1, (16, 8, 4), 3340, (True,))       # the oldest term map is 1 x 3
+    lazy(3, 96, 160, 2, (16, 8), 3350, (True,))          # 12 tiles x 3 items
+    lazy(1, 72, 136, 2, (8,), 3380, (True,))             # ragged tiles: four sample points per output, the scalar stores
+    lazy(1, 64, 128, 1, (16, 8, 4), 3360, (True,), rough=16)
+    lazy(1, 64, 128, 4, (16,), 3370, (False,), rough=16)
+    return rows
+
+
+def check_stage_conv_fused(dev, ops=None):
+    """The stage input fused with conv0[0] (stage_conv.hip, stage_conv16.hip) against torch in fp64 end to end."""
+    ops = ops or default_ops()
+    rows = []
+    D = lambda t: t.to(dev)  # noqa: E731
+    was = getattr(ops, "STAGE_CONV_TWO_TERM", None)
+
+    def conv_of(cout, seed):
+        wt, bs = cases.rnd((cout, 52, 3, 3), seed, 1.0 / (52 * 9) ** 0.5), cases.rnd((cout,), seed + 1, 0.1)
+        return wt, bs, ops.Conv3x3(wt, bs, 2, True, None, device=dev)
+
+    def run(name, conv, items, h, w, s, sp, tp, ref, flows=None, fold=False, terms=None, flow_ref=None):
+        assert ops.stage_conv0_ok(conv, h, w, float(s), float(sp), items=items), f"stage_conv0_ok refuses {name}"
+        y, fo = ops.stage_conv0(items, flows, D(tp), float(sp), conv, fold=fold, terms=terms, scale=s)
+        rows.append(value_row("stage_conv0", name, y, *ref))
+        if fold:
+            rows.append(value_row("stage_conv0", f"{name}: flow_out", fo[0], *flow_ref))
+
+    try:
+        for two in (True, False):
+            ops.STAGE_CONV_TWO_TERM = two
+            form = "two-term" if two else "fp32"
+            for i, (h, w) in enumerate(((64, 128), (70, 90), (38, 66))):
+                fr = glue_frames(1, h, w, 3400 + 10 * i)
+                tscales = (16, 8, 4) if (h, w) == (64, 128) else ()  # (70 and 38 are multiples of 2 only: no earlier stage can exist)
+                heads = glue_heads(1, h, w, tscales + (2,), 3420 + 100 * i)
+                tp = heads[2]
+                wt, bs, conv = conv_of(16, 3440 + 10 * i)
+                flow = flows4(h, w, 3460 + 10 * i)["smooth"]
+                for x4 in (True, False):
+                    tag = f"{form} s=1 {h}x{w} {'x4' if x4 else 'planar'}"
+                    item = lambda: [glue_item(dev, ops, fr, 0, x4=x4)]  # noqa: E731
+                    run(f"{tag} finished flow", conv, item(), h, w, 1, 2, tp, refs(stage_conv_ref, *fr, flow, tp, 2.0, 1, wt, bs, key=f"conv {h}x{w} finished"),
+                        flows=[D(flow)])
+                    prior = flow * 0.5 if x4 else None
+                    fref = refs(lambda t, f: update_ref(t, f, 2)[0], tp, prior, key=f"conv {h}x{w} fold flow {x4}")
+                    run(f"{tag} fold, {'a' if x4 else 'no'} prior flow", conv, item(), h, w, 1, 2, tp,
+                        refs(lambda *a: stage_conv_ref(*a[:5], update_ref(a[6], a[5], 2)[0], *a[6:]), *fr, prior, tp, 2.0, 1, wt, bs, key=f"conv {h}x{w} fold {x4}"),
+                        flows=[None if prior is None else D(prior)], fold=True, flow_ref=fref)
+                    terms = [(heads[t], float(t)) for t in tscales]
+                    run(f"{tag} terms={tscales}", conv, item(), h, w, 1, 2, tp,
+                        refs(lambda *a: stage_conv_ref(*a[:5], running_flow(a[5], a[6], 2.0), *a[6:]), *fr, terms, tp, 2.0, 1, wt, bs, key=f"conv {h}x{w} terms"),
+                        terms=[(D(t), ts) for t, ts in terms])
+        ops.STAGE_CONV_TWO_TERM = True  # scale 2: the two-term kernel only, lazy flow, x4 frames
+        for i, (n, h, w, tscales) in enumerate(((1, 64, 128, (16, 8)), (1, 72, 104, (8,)), (3, 96, 160, (16, 8)))):
+            fr = glue_frames(n, h, w, 3500 + 10 * i)
+            heads = glue_heads(n, h, w, tscales + (4,), 3520 + 100 * i)
+            terms = [(heads[t], float(t)) for t in tscales]
+            for cout in (16, 32):
+                wt, bs, conv = conv_of(cout, 3540 + 10 * i + cout)
+                items = [glue_item(dev, ops, fr, k, x4=True) for k in range(n)]
+                run(f"two-term s=2 cout={cout} {'B=%d ' % n if n > 1 else ''}{h}x{w} terms={tscales} x4", conv, items, h, w, 2, 4, heads[4],
+                    refs(lambda *a: stage_conv_ref(*a[:5], running_flow(a[5], a[6], 4.0), *a[6:]), *fr, terms, heads[4], 4.0, 2, wt, bs,
+                         key=f"conv s=2 {h}x{w} {cout}"),
+                    terms=[(D(t), ts) for t, ts in terms])
+    finally:
+        ops.STAGE_CONV_TWO_TERM = was
+    return rows
+
+
+def check_flow_update(dev, ops=None):
+    ops = ops or default_ops()
+    rows = []
+    D = lambda t: t.to(dev)  # noqa: E731
+    for i, (h, w, s) in enumerate(((64, 128, 16), (64, 128, 2), (64, 128, 1), (70, 90, 2))):
+        tmp = glue_heads(1, h, w, [s], 3600 + 100 * i)[s]
+        flow = flows4(h, w, 3620 + 10 * i)["amp30"]
+        tag = f"{h}x{w} s={s}"
+        gf, gm, gfe = ops.ifblock_update(D(tmp), D(flow), h, w, float(s), want_mask_feat=True)
+        r64, r32 = refs(update_ref, tmp, flow, s, key="update " + tag)
+        rows.append(value_row("ifblock_update", f"{tag} flow", gf, r64[0], r32[0]))
+        rows.append(value_row("ifblock_update", f"{tag} mask", gm, r64[1], r32[1]))
+        rows.append(value_row("ifblock_update", f"{tag} feat", gfe, r64[2], r32[2]))
+        rows.append(value_row("ifblock_update", f"{tag} no prior flow, no mask / feat", ops.ifblock_update(D(tmp), None, h, w, float(s)),
+                              *refs(lambda t: update_ref(t, None, s)[0], tmp, key="update, no prior " + tag)))
+    h, w, s = 64, 128, 2
+    tmp = glue_heads(3, h, w, [s], 3700)[s]
+    f1 = flows4(h, w, 3710)["smooth"]
+    got = ops.flow_updates(D(tmp), [None, D(f1), None], h, w, float(s))
+    for k, f in enumerate((None, f1, None)):
+        rows.append(value_row("flow_updates", f"B=3 {h}x{w} s={s} item {k} ({'a' if f is not None else 'no'} prior flow)", got[k],
+                              *refs(lambda t, p: update_ref(t, p, s)[0], tmp[k:k + 1], f, key=f"updates {k}")))
+    return rows
+
+
+def _blend_fold_ref(img0, img1, prior, tmp, s):
+    fl, mask, _ = update_ref(tmp, prior, s)
+    return blend_ref(img0, img1, fl, mask)
+
+
+def _blend_lazy_ref(img0, img1, terms, tmp, s):
+    return blend_ref(img0, img1, running_flow(terms, tmp, s), up(tmp, s)[:, 4:5])
+
+
+def check_warp_blend(dev, ops=None):
+    """The final warp + blend: flow finished, folded, and as terms -- at the frame's own resolution (S1) and staged."""
+    ops = ops or default_ops()
+    rows = []
+    D = lambda t: t.to(dev)  # noqa: E731
+    for i, (h, w, s) in enumerate(((37, 83, 1), (64, 128, 1), (64, 128, 2), (38, 66, 2))):
+        fr = glue_frames(1, h, w, 3800 + 10 * i)
+        tmp = glue_heads(1, h, w, [s], 3820 + 100 * i)[s]
+        img0, img1 = D(fr[0]), D(fr[1])
+        for fname, flow in flows4(h, w, 3840 + 10 * i).items():
+            tag = f"{h}x{w} head s={s} {fname}"
+            rows.append(value_row("warp_blend", tag, ops.warp_blend(img0, img1, D(flow), D(tmp), float(s)),
+                                  *refs(lambda a, b, f, t: blend_ref(a, b, f, up(t, s)[:, 4:5]), fr[0], fr[1], flow, tmp, key="blend " + tag)))
+            rows.append(value_row("warp_blend_fold", tag + " as prior flow", ops.warp_blend_fold(img0, img1, D(flow), D(tmp), float(s)),
+                                  *refs(_blend_fold_ref, fr[0], fr[1], flow, tmp, s, key="blend fold " + tag)))
+        rows.append(value_row("warp_blend_fold", f"{h}x{w} head s={s} no prior flow", ops.warp_blend_fold(img0, img1, None, D(tmp), float(s)),
+                              *refs(_blend_fold_ref, fr[0], fr[1], None, tmp, s, key=f"blend fold {h}x{w} {s}, no prior")))
+        if (h, w) == (64, 128):  # mask logits x 30: the sigmoid saturates both ways
+            sat = tmp.clone()
+            sat[:, 4] *= 30.0
+            flow = flows4(h, w, 3840 + 10 * i)["smooth"]
+            rows.append(value_row("warp_blend", f"{h}x{w} head s={s} smooth, saturating mask", ops.warp_blend(img0, img1, D(flow), D(sat), float(s)),
+                                  *refs(lambda a, b, f, t: blend_ref(a, b, f, up(t, s)[:, 4:5]), fr[0], fr[1], flow, sat, key=f"blend saturating {s}")))
+
+    def lazy(n, h, w, last, tscales, seed, x4s, rough=None):
+        fr = glue_frames(n, h, w, seed)
+        heads = glue_heads(n, h, w, list(tscales) + [last], seed + 20, rough)
+        terms = [(heads[t], float(t)) for t in tscales]
+        r = refs(_blend_lazy_ref, fr[0], fr[1], terms, heads[last], last, key=f"lazy blend {seed}")
+        for x4 in x4s:
+            items = [glue_item(dev, ops, fr, k, x4=x4)[:2] for k in range(n)]
+            got = torch.cat(list(ops.warp_blend_lazy(items, [(D(t), ts) for t, ts in terms], D(heads[last]), float(last))))
+            name = f"{'S1' if last == 1 else 'staged'} {'B=%d ' % n if n > 1 else ''}{h}x{w} last={last} terms={tuple(tscales)}{' rough' if rough else ''} " \
+                   f"{'x4' if x4 else 'planar'}"
+            rows.append(value_row("warp_blend_lazy", name, got, *r))
+
+    lazy(1, 48, 80, 1, (16, 8, 4, 2), 3900, (False, True))   # 2.5 x 6 tiles
+    lazy(1, 16, 48, 1, (16, 8, 4, 2), 3910, (False, True))   # the oldest term map is 1 x 3
+    lazy(1, 38, 66, 1, (2,), 3920, (False, True))            # the term footprint under a 32 x 8 tile is the 18 x 6 capacity
+    lazy(3, 48, 80, 1, (16, 8, 4, 2), 3930, (True,))
+    lazy(1, 48, 80, 1, (16, 8, 4, 2), 3940, (True,), rough=16)
+    lazy(1, 64, 128, 2, (32, 16, 8, 4), 3950, (False, True))  # the 4K half-scale configuration
+    lazy(1, 48, 80, 2, (16, 8, 4), 3960, (False, True))
+    return rows
+
+
 SPLAT_CHECKS = (check_softsplat, check_softsplat_scan, check_softsplat_big)  # the generic splat's families, for tests that take them together
 CHECKS = (  # (section title, check): one operator family each
     ("op softmax_rows_", check_softmax_rows), ("op instance_norm", check_instance_norm), ("op conv_direct", check_conv_direct),
@@ -965,4 +1347,7 @@ CHECKS = (  # (section title, check): one operator family each
     ("op resize_bilinear_ac", check_resize_bilinear_ac), ("op layernorm", check_layernorm), ("op gelu", check_gelu), ("op bmm", check_bmm),
     ("op pointwise", check_pointwise), ("op layouts", check_layouts), ("op hole tests", check_hole_tests), ("op drm", check_drm),
     ("op metric_input", check_metric_input), ("op softsplat", check_softsplat), ("op softsplat scan geometry", check_softsplat_scan),
-    ("op softsplat big map", check_softsplat_big), ("op resize_bilinear_scale", check_resize_scale), ("op flow_distance", check_flow_distance))
+    ("op softsplat big map", check_softsplat_big), ("op resize_bilinear_scale", check_resize_scale), ("op flow_distance", check_flow_distance),
+    ("op stage input, first stage", check_stage_input_first), ("op stage input, warped", check_stage_input_warped),
+    ("op stage input + conv0[0] fused", check_stage_conv_fused), ("op flow update", check_flow_update), ("op warp + blend", check_warp_blend))
+GLUE_CHECKS = (check_stage_input_first, check_stage_input_warped, check_stage_conv_fused, check_flow_update, check_warp_blend)

@@ -1,7 +1,9 @@
 """GPU (-m gpu): every pointwise / gather / reduction kernel of the GMFlow and GMFSS glue, the generic forward splat
-(count, scan, fill, gathers), resize_bilinear_scale and flow_distance on their own against a float64 reference
-(tests/op_checks.py), at the sizes where kernels go wrong: image borders, partial tiles and blocks, every dispatch branch,
-batch > 1, grid-stride loops and scan rounds that go round twice.  One operator family per test, so that a failure names it.
+(count, scan, fill, gathers), resize_bilinear_scale, flow_distance and the IFNet stage glue (stage-input gathers, the gathers
+fused with conv0[0], flow update, final warp + blend: [H,W,4] frames, pair-only features, the flow as terms, the blend at the
+frame's own resolution) on their own against a float64 reference (tests/op_checks.py), at the sizes where kernels go wrong:
+image borders, partial tiles and blocks, every dispatch branch, batch > 1, grid-stride loops and scan rounds that go round
+twice.  One operator family per test, so that a failure names it.
 
 Value rows: tol = max(2e-5 max(1, |ref|max), 3 x the fp32 oracle's own error on that input); decisions and data movement:
 bit-exact.  tests/test_op_checks_cpu.py shows on the CPU that these rows fail for a wrong operator."""
@@ -134,6 +136,116 @@ def test_flow_distance(hip_backend):
     _assert_rows(op_checks.check_flow_distance(hip_backend.dev))
 
 
+# ----------------------------------------------------------------------------------------- the IFNet stage glue
+def test_stage_input_first(hip_backend):
+    _assert_rows(op_checks.check_stage_input_first(hip_backend.dev))
+
+
+def test_stage_input_warped(hip_backend):
+    _assert_rows(op_checks.check_stage_input_warped(hip_backend.dev))
+
+
+def test_stage_conv_fused(hip_backend):
+    _assert_rows(op_checks.check_stage_conv_fused(hip_backend.dev))
+
+
+def test_flow_update(hip_backend):
+    _assert_rows(op_checks.check_flow_update(hip_backend.dev))
+
+
+def test_warp_blend(hip_backend):
+    _assert_rows(op_checks.check_warp_blend(hip_backend.dev))
+
+
+def _traced(fn):
+    """fn() -> (its result, the kernel names launched inside it)"""
+    from drba_amd import ops
+    torch.cuda.synchronize()
+    ops.trace_begin()
+    try:
+        got = fn()
+        torch.cuda.synchronize()
+    finally:
+        recs = ops.trace_end()
+    return got, [r["name"] for r in recs]
+
+
+B_ = {True: "true", False: "false"}
+GLUE_FORMS = (  # regular expressions over the kernel names, template arguments as tests/golden/ops_launches.json shows them
+    [rf"ifblock_input_lds<{B_[sg]}, ?{fm}, ?{B_[vs]}>" for sg in (True, False) for fm in (0, 1, 2) for vs in (True, False)]
+    + [rf"ifblock_input_pixel<{B_[hf]}, ?true>" for hf in (True, False)]
+    + [rf"ifblock_input_kernel<{B_[hf]}, ?false, ?1>" for hf in (True, False)]
+    + [r"warp_blend_fold_kernel<true, ?true>", r"warp_blend_fold_kernel<true>|warp_blend_fold_kernel<true, ?false>",
+       r"warp_blend_fold_kernel<false>|warp_blend_fold_kernel<false, ?false>", r"warp_blend_kernel", r"ifblock_update_kernel",
+       r"stage_conv16<", r"stage_conv16_s2<.*Geo<\d+, ?1>", r"stage_conv16_s2<.*Geo<\d+, ?2>"]
+    + [rf"stage_conv0<{fm}," for fm in (0, 1, 2)])
+
+
+def test_glue_rows_run_the_branches_they_name(hip_backend):
+    """The five glue checks again under the kernel trace: every form of the stage-input gathers (one sample point or four, flow
+    finished / folded / as terms, vector or scalar stores), the first stage's two kernels with and without a flow, the three
+    blends, both fused convolutions at scale 1 and the scale-2 one with one and two n-tiles were launched at least once -- a
+    later change of a tile size or a dispatch rule that un-covers a form fails here instead of passing quietly."""
+    import re
+    _, names = _traced(lambda: [check(hip_backend.dev) for check in op_checks.GLUE_CHECKS])
+    seen = sorted(set(names))
+    print("  launched:\n    " + "\n    ".join(seen))
+    missing = [f for f in GLUE_FORMS if not any(re.search(f, n) for n in seen)]
+    assert not missing, f"never launched: {missing}\nlaunched: {seen}"
+
+
+def test_layout_copies_are_what_is_read(hip_backend):
+    """Which layout a gather reads is a run-time pointer, invisible in the trace.  The copy ops.rgbx / ops.pair_interleaved
+    returns is scaled by 2 in place (the frame's own version does not move, so the copy stays current): where the copy is read,
+    the frame (feature) channels double exactly and nothing else moves; at scale 4 stage_inputs hands no copies over and the
+    result is the same bit for bit."""
+    from drba_amd import ops
+    dev = hip_backend.dev
+    h, w = 64, 128
+    fr = op_checks.glue_frames(1, h, w, 4000)
+    heads = op_checks.glue_heads(1, h, w, (16, 8, 4, 2, 1), 4010)
+    D = lambda t: t.to(dev)  # noqa: E731
+    flow = D(op_checks.flows4(h, w, 4020)["smooth"])
+    wt, bs = op_checks.cases.rnd((16, 52, 3, 3), 4030, 1.0 / (52 * 9) ** 0.5), op_checks.cases.rnd((16,), 4031, 0.1)
+    conv = ops.Conv3x3(wt, bs, 2, True, None, device=dev)
+
+    def stage(it, s):
+        return op_checks._stage_inputs_out(ops, dev, [it], [flow], D(heads[2 * s]), 2 * s, s)[0]
+
+    def blend(it, last, tscales):
+        return ops.warp_blend_lazy([it[:2]], [(D(heads[t]), float(t)) for t in tscales], D(heads[last]), float(last))[0]
+
+    runs = {"ifblock_input_lds s=1": lambda it: stage(it, 1), "ifblock_input_lds s=2": lambda it: stage(it, 2),
+            "ifblock_input_lds s=4": lambda it: stage(it, 4), "stage_conv0 s=1": lambda it: ops.stage_conv0([it], [flow], D(heads[2]), 2.0, conv)[0],
+            "warp_blend_lazy S1": lambda it: blend(it, 1, (8, 4, 2)), "warp_blend_lazy staged": lambda it: blend(it, 2, (16, 8, 4))}
+    for name, run in runs.items():
+        it = op_checks.glue_item(dev, ops, fr, 0, x4=True)
+        before = run(it).clone()
+        for img in it[:2]:
+            v = img._version
+            ops.rgbx(img).mul_(2.0)
+            assert img._version == v and ops._x4_of(img) is not None
+        after = run(it)
+        torch.cuda.synchronize()
+        assert float(before.abs().max()) > 0 and torch.isfinite(before).all()
+        if name.endswith("s=4"):
+            assert torch.equal(after, before), f"{name}: the [H,W,4] copies are read"
+        elif name.startswith("stage_conv0"):
+            assert not torch.equal(after, before), f"{name}: the [H,W,4] copies are not read"
+        elif name.startswith("warp_blend"):
+            assert torch.equal(after, 2.0 * before), f"{name}: the [H,W,4] copies are not what is read"
+        else:
+            assert torch.equal(after[:, :6], 2.0 * before[:, :6]) and torch.equal(after[:, 6:], before[:, 6:]), f"{name}: the [H,W,4] copies are not what is read"
+    for s in (4, 1):  # the first stage: ifblock_input_kernel / ifblock_input_pixel <false, ...> on pair-only features
+        it = op_checks.glue_item(dev, ops, fr, 0, pair=True)
+        assert ops.is_pair(it[3]) and ops.is_pair(it[4])
+        before = ops.ifblock_input(it[0], it[1], it[3], it[4], it[2], None, None, 1.0, float(s)).clone()
+        it[3].mul_(2.0), it[4].mul_(2.0)
+        after = ops.ifblock_input(it[0], it[1], it[3], it[4], it[2], None, None, 1.0, float(s))
+        assert torch.equal(after[:, 6:38], 2.0 * before[:, 6:38]) and torch.equal(after[:, :6], before[:, :6]) and torch.equal(after[:, 38:], before[:, 38:])
+    torch.cuda.synchronize()
+
+
 WS_GUARD = 4096
 WS_SHAPES = ((1, 1, 1), (1, 2, 2), (1, 1, 2), (1, 2, 4),  # (N, H, W): L = N (H + 1) (W + 1) = 4, 9, 6, 15 -- every residue mod 4, one block
              (1, 63, 64), (1, 90, 90), (2, 78, 80), (1, 128, 130))  # 4160 (2 blocks), 8281 (3), 12798 (4), 16899 (5): residues 0, 1, 2, 3
@@ -224,4 +336,24 @@ def test_documented_refusals(hip_backend):
         ops.softmax_rows_(z(2, 3, 5), 0.0)  # scale must be positive
     with pytest.raises(_lib.DrbaHipError):  # a channel slice of N = 2 is not contiguous: the gathers store through a raw pointer
         ops.softsplat(z(2, 3, 8, 8), z(2, 2, 8, 8), None, "avg", out=z(2, 6, 8, 8)[:, 1:4])
+    # the IFNet stage glue: the pyramid rules that bound the staged footprints
+    h, w = 32, 64
+    img, f, t = z(1, 3, h, w), z(1, 16, h, w), z(1, 1, h, w)
+    item = [(img, img, t, f, f)]
+    ops.pair_interleaved(f)  # (the layout copy the warped entry points make of planar features on first use: not the refused launch)
+    head =lambda s, n=1: z(n, 13, h // s, w // s)  # noqa: E731
+
+    def refused(call):
+        def go():
+            with pytest.raises(_lib.DrbaHipError):
+                call()
+        _, names = _traced(go)
+        assert names == [], names
+
+    refused(lambda: ops.stage_inputs(item, None, head(4), 4.0, 2.0, z(1, 52, h // 2, w // 2), terms=[(head(4), 4.0)]))  # a term below 2 x prev_scale
+    refused(lambda: ops.ifblock_input_lds(img, img, f, f, t, None, head(8), 8.0, 4.0, fold=True))                       # a fold at scale 4
+    refused(lambda: ops.ifblock_input_lds(img, img, f, f, t, z(1, 4, h, w), head(4), 4.0, 1.0))                         # prev_scale != 2 x scale
+    refused(lambda: ops.warp_blend_lazy([(img, img)], [(head(2), 2.0)], head(2), 2.0))                                  # a term at the last head's scale
+    refused(lambda: ops.warp_blend_lazy([(img, img)], [(head(s), float(s)) for s in (32, 16, 8, 4, 2)], head(1), 1.0))  # > MAX_FLOW_TERMS terms
+    assert _lib.MAX_FLOW_TERMS == 4
     torch.cuda.synchronize()

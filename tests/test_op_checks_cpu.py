@@ -2,7 +2,8 @@
 
 The "implementation under test" here is a torch-fp32 stand-in for drba_amd.ops, written tap by tap the way the kernels are
 (explicit window loops, explicit bilinear gathers, explicit index arithmetic; the forward splat as a key per source, the
-sources ordered by key and the outputs summing their four segments) -- not with the unfold / grid_sample / F.interpolate /
+sources ordered by key and the outputs summing their four segments; the IFNet stage glue with a source index and weight per
+axis, 2 x 2 gathers at clamped coordinates and the running flow summed term by term) -- not with the unfold / grid_sample / F.interpolate /
 corner-by-corner scatter forms the fp64 references use -- so that two independent statements of every formula meet:
   1. every fp64 reference agrees with the fp32 oracle / torch form of the same formula within fp32 roundoff (the measured
      floor of each row is bounded by a figure derived from the number format and the operation's conditioning);
@@ -98,9 +99,10 @@ def _convex_upsample(mask, flow, factor, defect=False):
     return up.permute(0, 3, 1, 4, 2).reshape(1, 2, k * h, k * w)  # [c, y, ii, x, jj]
 
 
-def _bilinear(x, sx, sy, padding):
+def _bilinear(x, sx, sy, padding, edge=False):
     """x [N, C, H, W] sampled at pixel coordinates sx, sy [N, H, W]: four bounds-checked taps (zeros) or clamped coordinates
-    (border); a non-finite coordinate has no tap inside the image."""
+    (border); a non-finite coordinate has no tap inside the image.  edge (planted): a sample in the last column takes its left
+    tap from the column before it, as a pair load based at W - 2 invites."""
     n, c, h, w = x.shape
     if padding == "border":
         sx, sy = sx.clamp(0, w - 1), sy.clamp(0, h - 1)
@@ -112,6 +114,8 @@ def _bilinear(x, sx, sy, padding):
     flat = x.reshape(n, c, h * w)
     for dx, dy, wgt in ((0, 0, (1 - wx1) * (1 - wy1)), (1, 0, wx1 * (1 - wy1)), (0, 1, (1 - wx1) * wy1), (1, 1, wx1 * wy1)):
         xi, yi = x0 + dx, y0 + dy
+        if edge and dx == 0:
+            xi = torch.where(x0 >= w - 1, x0 - 1, xi)
         ok = fin & (xi >= 0) & (xi < w) & (yi >= 0) & (yi < h)
         idx = (yi.clamp(0, h - 1) * w + xi.clamp(0, w - 1)).long().view(n, 1, h * w).expand(n, c, h * w)
         out += flat.gather(2, idx).view(n, c, h, w) * (wgt * ok).unsqueeze(1)
@@ -282,6 +286,171 @@ def _to_inp(img_u8, dst_size):
     return out
 
 
+# ---- the IFNet stage glue, tap by tap: lerp_src per axis, 2 x 2 gathers at clamped coordinates, the running flow term by term
+def _axis(n_in, n_out, mul, ac=False):
+    """source index pair and the weight of the second tap of every output index along one axis (align_corners=False; ac: planted)"""
+    i = torch.arange(n_out, dtype=torch.float32)
+    s = i * ((n_in - 1) / max(n_out - 1, 1)) if ac else (mul * (i + 0.5) - 0.5).clamp(min=0)
+    i0 = s.floor().clamp(max=n_in - 1)
+    return i0.long(), (i0 + 1).clamp(max=n_in - 1).long(), s - i0
+
+
+def _lerp_resize(x, size, mul, ac=False, tile_clamp=False):
+    if mul == 1.0 and tuple(size) == tuple(x.shape[2:]) and not ac:
+        return x  # weights (1, 0): the zero-weight taps are skipped
+    y0, y1, ly = _axis(x.shape[2], size[0], mul, ac)
+    x0, x1, lx = _axis(x.shape[3], size[1], mul, ac)
+    if tile_clamp:  # planted: the footprint under a 32-pixel tile staged 17 columns wide instead of 18
+        x1 = torch.minimum(x1, x0[(torch.arange(size[1]) // 32) * 32] + 16)
+    ly = ly.view(-1, 1)
+    r0, r1 = x[:, :, y0], x[:, :, y1]
+    top = (1 - lx) * r0[..., x0] + lx * r0[..., x1]
+    bot = (1 - lx) * r1[..., x0] + lx * r1[..., x1]
+    return (1 - ly) * top + ly * bot
+
+
+def _up(t, s, **kw):
+    return _lerp_resize(t, (int(t.shape[2] * s), int(t.shape[3] * s)), 1.0 / s, **kw)
+
+
+def _dn(x, s):
+    return _lerp_resize(x, (int(x.shape[2] * (1.0 / s)), int(x.shape[3] * (1.0 / s))), float(s))
+
+
+def _warp(x, flow, edge=False):
+    n, _, h, w = x.shape
+    gx = torch.linspace(-1.0, 1.0, w).view(1, 1, w) + flow[:, 0] / ((w - 1.0) / 2.0)
+    gy = torch.linspace(-1.0, 1.0, h).view(1, h, 1) + flow[:, 1] / ((h - 1.0) / 2.0)
+    return _bilinear(x, (gx + 1) * ((w - 1.0) / 2.0), (gy + 1) * ((h - 1.0) / 2.0), "border", edge)
+
+
+def _rgbx(img):
+    c = getattr(img, "_drba_x4", None)
+    if c is None or c[1] != img._version:
+        img._drba_x4 = (torch.stack([img[0, 0], img[0, 1], img[0, 2], torch.zeros_like(img[0, 0])], -1), img._version)
+    return img._drba_x4[0]
+
+
+def _frame(img, x4):
+    """the frame as the gather reads it: from its [H, W, 4] copy where it carries a current one and the entry point takes it"""
+    c = getattr(img, "_drba_x4", None)
+    if x4 and c is not None and c[1] == img._version:
+        return c[0][..., :3].permute(2, 0, 1)[None]
+    return img
+
+
+def _planar(f, as_planar=False):
+    """features [1, 16, H, W] of either layout (as_planar, planted: the pair-only tensor [8, H, W, 2] read as planes)"""
+    if not (f.dim() == 4 and f.shape[0] == 8 and f.shape[3] == 2):
+        return f
+    c2, h, w, _ = f.shape
+    return f.reshape(1, 2 * c2, h, w) if as_planar else f.permute(0, 3, 1, 2).reshape(1, 2 * c2, h, w)
+
+
+def _flow_update(tmp, flow_in, s):
+    fd = _up(tmp[:, :4], s) * s
+    return fd if flow_in is None else flow_in + fd
+
+
+def _terms_flow(terms, tmp, s_last, defect=None):
+    """the running flow: oldest term first, every product and sum in fp32, the newest head output last"""
+    seq = list(terms) + [(tmp, s_last)]
+    fl = None
+    for k, (t, s) in enumerate(seq):
+        last = k == len(seq) - 1
+        d = _up(t[:, :4], s, tile_clamp=defect == "tile_clamp" and not last)
+        if defect == "neighbour" and last:  # the pixel to the right
+            d = d[..., torch.arange(1, d.shape[3] + 1).clamp(max=d.shape[3] - 1)]
+        d = d * (s_last if defect == "oldest_scale" and k == 0 and not last else s)
+        fl = d if fl is None else fl + d
+    return fl
+
+
+def _stage_core(img0, img1, f0, f1, timestep, flow, tmp_prev, sp, s, x4, defect=None):
+    i0, i1 = _frame(img0, x4), _frame(img1, x4)
+    f0, f1 = _planar(f0, defect == "pair_as_planar"), _planar(f1, defect == "pair_as_planar")
+    tm = timestep if torch.is_tensor(timestep) else torch.full_like(i0[:, :1], float(timestep))
+    if flow is None:
+        return _dn(torch.cat((i0, i1, f0, f1, tm), 1), s)
+    edge = defect == "edge_tap"
+    x = torch.cat((_warp(i0, flow[:, :2], edge), _warp(i1, flow[:, 2:4], edge), _warp(f0, flow[:, :2], edge), _warp(f1, flow[:, 2:4], edge), tm,
+                   _up(tmp_prev[:, 4:13], sp)), 1)
+    fl = _dn(flow, s)
+    return torch.cat((_dn(x, s), fl if defect == "flow_unscaled" else fl / s), 1)
+
+
+def _ifblock_input(img0, img1, f0, f1, timestep, flow, tmp_prev, prev_scale, scale, out=None, defect=None):
+    return _stage_core(img0, img1, f0, f1, timestep, flow, tmp_prev, prev_scale, scale, False, defect)
+
+
+def _ifblock_input_lds(img0, img1, f0, f1, timestep, flow, tmp_prev, prev_scale, scale, out=None, fold=False, defect=None):
+    if fold:
+        flow = _flow_update(tmp_prev, flow, prev_scale)
+    r = _stage_core(img0, img1, f0, f1, timestep, flow, tmp_prev, prev_scale, scale, False, defect)
+    return (r, flow) if fold else r
+
+
+def _stage_inputs(items, flows, tmp_prev, prev_scale, scale, out, fold=False, lds=True, terms=None, defect=None):
+    folded = []
+    for k, it in enumerate(items):
+        tp = None if tmp_prev is None else tmp_prev[k:k + 1]
+        if terms is not None:
+            fl = _terms_flow([(t[k:k + 1], s) for t, s in terms], tp, prev_scale, defect)
+        else:
+            fl = None if flows is None else flows[k]
+            if fold:
+                fl = _flow_update(tp, fl, prev_scale)
+                folded.append(fl)
+        out[k:k + 1] = _stage_core(it[0], it[1], it[3], it[4], it[2], fl, tp, prev_scale, scale, lds and scale <= 2, defect)
+    return folded if fold else None
+
+
+class _Conv3x3:
+    def __init__(self, w, b, stride, act, beta, device=None):
+        assert stride == 2 and act and beta is None
+        self.w, self.b, self.cout = w, b, w.shape[0]
+
+
+def _stage_conv0_ok(conv, H, W, scale, prev_scale, items=None):
+    if scale == 2:
+        return prev_scale == 4 and conv.cout in (16, 32) and items is not None and all(_frame(it[0], True) is not it[0] for it in items)
+    return scale == 1 and prev_scale == 2 and conv.cout == 16
+
+
+def _stage_conv0(items, flows, tmp_prev, prev_scale, conv, fold=False, terms=None, scale=1, out=None):
+    h, w = items[0][0].shape[2:]
+    xin = torch.empty(len(items), 52, h // scale, w // scale)
+    fo = _stage_inputs(items, flows, tmp_prev, prev_scale, scale, xin, fold=fold, terms=terms)
+    return F.leaky_relu(F.conv2d(xin, conv.w, conv.b, stride=2, padding=1), 0.2), fo
+
+
+def _ifblock_update(tmp, flow_in, H, W, scale, want_mask_feat=False):
+    flow = _flow_update(tmp, flow_in, scale)
+    return (flow, _up(tmp[:, 4:5], scale), _up(tmp[:, 5:13], scale)) if want_mask_feat else flow
+
+
+def _flow_updates(tmp, flows, H, W, scale, whole=False, defect=False):
+    return [_flow_update(tmp[k:k + 1], flows[0 if defect else k], scale) for k in range(tmp.shape[0])]
+
+
+def _blend(i0, i1, flow, logit):
+    m = 1.0 / (1.0 + torch.exp(-logit))
+    return _warp(i0, flow[:, :2]) * m + _warp(i1, flow[:, 2:4]) * (1.0 - m)
+
+
+def _warp_blend(img0, img1, flow, tmp_last, scale, defect=False):
+    return _blend(img0, img1, flow, _up(tmp_last[:, 4:5], scale, ac=defect))
+
+
+def _warp_blend_fold(img0, img1, flow_prev, tmp_last, scale):
+    return _blend(img0, img1, _flow_update(tmp_last, flow_prev, scale), _up(tmp_last[:, 4:5], scale))
+
+
+def _warp_blend_lazy(items, terms, tmp_last, scale, defect=None):
+    return [_blend(_frame(it[0], True), _frame(it[1], True), _terms_flow([(t[k:k + 1], s) for t, s in terms], tmp_last[k:k + 1], scale, defect),
+                   _up(tmp_last[k:k + 1, 4:5], scale)) for k, it in enumerate(items)]
+
+
 STANDIN = dict(
     softmax_rows_=_softmax_rows_, instance_norm=_instance_norm, conv_direct=_conv_direct, local_corr_flow=_local_corr_flow,
     local_attn_flow=_local_attn_flow, convex_upsample=_convex_upsample, flow_warp=_flow_warp, backwarp=_backwarp,
@@ -299,7 +468,9 @@ STANDIN = dict(
     .permute(0, 1, 4, 2, 5, 3).reshape(x.shape[0], x.shape[1] // 4, 2 * x.shape[2], 2 * x.shape[3]),
     pair_interleaved=lambda f: torch.stack([f[0, 0::2], f[0, 1::2]], -1),
     quad_interleaved=lambda x: torch.stack([x[:, i::4].flatten(2) for i in range(4)], -1),
-    rgbx=lambda img: torch.stack([img[0, 0], img[0, 1], img[0, 2], torch.zeros_like(img[0, 0])], -1),
+    rgbx=_rgbx, ifblock_input=_ifblock_input, ifblock_input_lds=_ifblock_input_lds, stage_inputs=_stage_inputs, Conv3x3=_Conv3x3,
+    stage_conv0_ok=_stage_conv0_ok, stage_conv0=_stage_conv0, ifblock_update=_ifblock_update, flow_updates=_flow_updates,
+    warp_blend=_warp_blend, warp_blend_fold=_warp_blend_fold, warp_blend_lazy=_warp_blend_lazy,
     fill_holes=lambda aligned, cover, value: torch.where(cover < 0.999, value, aligned),
     drm_retime=lambda d, t, precision=1e-3: odrm.drm_to_t(d, t, precision),
 )
@@ -431,6 +602,17 @@ DEFECTS = (  # (operator of the stand-in, its defective variant, the operator fa
     ("softsplat", _with(_softsplat, "base_of_image0"), "softsplat", "N=3 C=5"),
     ("softsplat", _with(_softsplat, "zeroeps_as_addeps"), "softsplat", "soft-zeroeps normaliser"),
     ("resize_bilinear_scale", _with(_resize_bilinear_scale), "resize_bilinear_scale", "37x53"),
+    # the IFNet stage glue: the oldest term times the newest scale; term taps clamped at a tile-local footprint one column short;
+    # the left tap of a sample in the last column; flow / scale forgotten; the mask upsampled with align_corners=True; the S1 blend
+    # reading the last head's flow at the right-hand neighbour; item 0's prior flow for every item; pair-only features read as planes
+    ("stage_inputs", _with(_stage_inputs, "oldest_scale"), "stage_inputs", "lazy 64x128 s=1 terms=(16, 8, 4) planar"),
+    ("warp_blend_lazy", _with(_warp_blend_lazy, "tile_clamp"), "warp_blend_lazy", "38x66 last=1 terms=(2,)"),
+    ("ifblock_input_lds", _with(_ifblock_input_lds, "edge_tap"), "ifblock_input_lds", "integer"),
+    ("ifblock_input", _with(_ifblock_input, "flow_unscaled"), "ifblock_input", "s=8 smooth t=map flow"),
+    ("warp_blend", _with(_warp_blend), "warp_blend", "head s=2"),
+    ("warp_blend_lazy", _with(_warp_blend_lazy, "neighbour"), "warp_blend_lazy", "S1 48x80"),
+    ("flow_updates", _with(_flow_updates), "flow_updates", "item 1"),
+    ("ifblock_input", _with(_ifblock_input, "pair_as_planar"), "ifblock_input", "features=pair-only features"),
 )
 DEFECT_IDS = [d[0] + (" " + d[1].defect if isinstance(getattr(d[1], "defect", None), str) else "") for d in DEFECTS]
 
