@@ -56,6 +56,7 @@ import sys
 
 import numpy as np
 
+from drba_amd import frames as _frames
 from drba_amd import metrics
 
 
@@ -78,16 +79,9 @@ class ClipSource:
         maxval = None
         if ext == ".y4m":
             self._open_y4m(open(path, "rb"), seekable=True)
-        elif ext == ".npz":
-            z = np.load(path)
-            self._frames, self.fps = z["frames"], (float(z["fps"]) if "fps" in z.files else 24.0)
-            maxval = int(z["maxval"]) if "maxval" in z.files else None
-        elif ext == ".npy":
-            self._frames = np.load(path, mmap_mode="r")
-            side = os.path.splitext(path)[0] + ".json"
-            meta = json.load(open(side)) if os.path.exists(side) else {}
-            self.fps = float(meta["fps"]) if "fps" in meta else 24.0
-            maxval = int(meta["maxval"]) if "maxval" in meta else None
+        elif ext in (".npz", ".npy"):
+            self._frames, fps, maxval = _frames.open_array_clip(path)
+            self.fps = 24.0 if fps is None else fps
         else:
             try:
                 import cv2  # noqa: WPS433 (optional dependency)
@@ -353,7 +347,7 @@ class _HoldoutIO:
 def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.3, plain=False, backend=None, to_inp=None,
             to_out=None, check_scene=None, maxval=None, linear=True, yuv_matrix="bt709", yuv_range="source", fit="resize", dedup=None,
             check_dup=None):
-    """Keep every k-th frame of `frames` (uint8 [N,H,W,3], indexable), let interpolate_stream fill the gaps at `times = k`
+    """Keep every k-th frame of `frames` (uint8 [N,H,W,3], indexable, or a ClipSource with random access), let interpolate_stream fill the gaps at `times = k`
     and compare every emission with the original frame at its position.  -> {"k", "m", "frames_used", "emissions",
     "pairs": [(emission, original)], "kept": ClipMetrics.result() + "positions", "held_out": the same}.
     to_inp / to_out / check_scene / backend: the hooks of interpolate_stream and of drba_amd.metrics (defaults: the device
@@ -376,39 +370,18 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
     from drba_amd import infer as drv
     if fit not in ("resize", "pad"):
         raise ValueError(f"fit must be resize or pad, got {fit!r}")
-    fit_kw = {} if fit == "resize" else {"fit": fit}
     if plain and not linear:
         raise ValueError("--nonlinear and --plain exclude each other: a plain step is inference_ts, it has no DistanceRatioMap to retime")
     m, half = holdout_plan(len(frames), k)
-    yuv = getattr(frames, "pixfmt", None) == "yuv420"
-    deep = not yuv and getattr(frames, "dtype", None) == np.uint16
-    if maxval is not None and not deep:
-        raise ValueError("maxval belongs to uint16 frames")
-    mv = (65535 if maxval is None else int(maxval)) if deep else None
+    fmt = _frames.source_format(frames, maxval, yuv_matrix, yuv_range)  # (refuses a maxval given for frames that are not uint16)
+    yuv = fmt.pixfmt == "yuv420"
+    deep = not yuv and fmt.depth == 16
+    mv = fmt.maxval if yuv or deep else None
     device_out = to_out is None
-    if yuv:
-        if yuv_range not in ("source", "limited", "full"):
-            raise ValueError(f"yuv_range must be source, limited or full, got {yuv_range!r}")
-        full = frames.color_range == "FULL" if yuv_range == "source" else yuv_range == "full"  # (no tag: limited, as infer.py reads it)
-        mv = int(frames.maxval)
-    if device_out:
-        from drba_amd import ops
-        if yuv:  # packed planes on the device at the clip's own depth: compared there
-            to_out = lambda x, size: ops.to_out_yuv(x, size, matrix=yuv_matrix, full_range=full, depth=frames.depth,  # noqa: E731
-                                                    maxval=mv if frames.depth == 16 else None, **fit_kw)
-        elif deep:
-            to_out = lambda x, size: ops.to_out(x, size, depth=16, maxval=mv, **fit_kw)  # noqa: E731  (uint16 on the device: compared there)
-        else:
-            to_out = lambda x, size: ops.to_out(x, size, **fit_kw)  # noqa: E731  (uint8 on the device: compared there)
-    if to_inp is None and deep:
-        from drba_amd.models.utils import tools
-        to_inp = lambda fr, size: tools.to_inp(fr, size, maxval=mv, **fit_kw)  # noqa: E731
-    if to_inp is None and yuv:
-        from drba_amd.models.utils import tools
-        to_inp = lambda fr, size: tools.to_inp(fr, size, matrix=yuv_matrix, full_range=full, **fit_kw)  # noqa: E731
-    if to_inp is None and fit_kw:
-        from drba_amd.models.utils import tools
-        to_inp = lambda fr, size: tools.to_inp(fr, size, **fit_kw)  # noqa: E731
+    # the emissions are what the clip's frames are -- uint8, uint16 or packed planes at the clip's own depth -- and by default stay on
+    # the device, where they are compared
+    inp, out = _frames.hooks(fmt, fmt, fit, on_device=True)
+    to_inp, to_out = to_inp or inp, to_out or out
     backend = backend or metrics.default_backend()
     if yuv:
         kept, held = metrics.YuvClipMetrics(backend=backend, maxval=mv), metrics.YuvClipMetrics(backend=backend, maxval=mv)
@@ -431,12 +404,13 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
         out.update({"depth": 16, "maxval": mv})
     if yuv:
         out.update({"pixfmt": "yuv420", "depth": frames.depth, "maxval": mv, "chroma": frames.chroma, "yuv_matrix": yuv_matrix,
-                    "full_range": bool(full), "kept_passthrough": KEPT_PASSTHROUGH})
+                    "full_range": fmt.full_range, "kept_passthrough": KEPT_PASSTHROUGH})
     for name, cm in (("kept", kept), ("held_out", held)):
         res = cm.result()  # (has waited for every kernel behind the frames)
         res["positions"] = [p for _, p in io.pairs if (p % int(k) == 0) == (name == "kept")]
         out[name] = res
     if device_out:
+        from drba_amd import ops
         ops.check_overflow()  # what tools.to_out asks per frame: an overflow of the two-term fp16 kernels raises
     return out
 
@@ -478,13 +452,8 @@ def dups(src, settings=None, model_type="rife", scale=1.0, fit="resize", yuv_mat
         from drba_amd import ops
         stats = ops.dup_stats
     if to_inp is None:
-        kw = {} if fit == "resize" else {"fit": fit}
-        if src.pixfmt == "yuv420":
-            full = src.color_range == "FULL" if yuv_range == "source" else yuv_range == "full"
-            kw.update(matrix=yuv_matrix, full_range=full)
-        elif src.depth == 16:
-            kw["maxval"] = src.maxval
-        to_inp = lambda fr, size: tools.to_inp(fr, size, **kw)  # noqa: E731
+        fmt = _frames.source_format(src, yuv_matrix=yuv_matrix, yuv_range=yuv_range)
+        to_inp, _ = _frames.hooks(fmt, fmt, fit)
     pairs, prev, size = [], None, None
     for k, fr in enumerate(src):
         if size is None:
@@ -610,13 +579,10 @@ def main(argv=None, backend=None):
         synthetic = args.weights is None and not (wdir and os.path.isdir(wdir))
         model = drv.load_model(args.model_type, scale=args.scale,
                                weights=tune._synthetic_weights(args.model_type) if synthetic else wdir)
-        if src.pixfmt == "yuv420":
-            kw = {"yuv_matrix": args.yuv_matrix, "yuv_range": args.yuv_range}
-        else:
-            kw = {"maxval": src.maxval} if src.depth == 16 else {}
-        res = holdout(model, src if src.pixfmt == "yuv420" else src._frames, args.k, fps=src.fps, enable_scdet=args.enable_scdet,
-                      scdet_threshold=args.scdet_threshold, plain=args.plain, backend=backend, linear=not args.nonlinear, fit=args.fit,
-                      dedup=drv.dedup_of(args), **kw)
+        # (the clip itself says what its frames are -- depth, maxval, 4:2:0 --: frames.source_format, which holdout asks)
+        res = holdout(model, src, args.k, fps=src.fps, enable_scdet=args.enable_scdet, scdet_threshold=args.scdet_threshold,
+                      plain=args.plain, backend=backend, linear=not args.nonlinear, fit=args.fit, dedup=drv.dedup_of(args),
+                      yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range)
         rep = holdout_report(res)
         rep.update({"model": args.model_type, "scale": args.scale, "input": args.input,
                     "weights": "synthetic (drba_amd.utils.synth): the figures say nothing about quality" if synthetic else wdir})

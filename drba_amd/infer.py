@@ -40,6 +40,7 @@ import time
 
 from drba_amd import dedup as _dedup
 from drba_amd import driver
+from drba_amd import frames as _frames
 from drba_amd.models.utils import tools as _tools
 
 
@@ -222,30 +223,11 @@ def inference(model, args):
         step = lambda _i: bar.update(1)  # noqa: E731
     except ImportError:
         bar, step = None, None
-    to_inp = to_out = None
-    # --fit pad: every hook carries the keyword (the plain 8-bit pair too, which otherwise is interpolate_stream's default); a
-    # resize run makes the calls it always made
-    fit_kw = {} if fit_of(args) == "resize" else {"fit": fit_of(args)}
-    if fit_kw:
-        to_inp = lambda fr, size: _tools.to_inp(fr, size, **fit_kw)  # noqa: E731
-        to_out = lambda x, size: _tools.to_out(x, size, **fit_kw)  # noqa: E731
-    rgb = bool(getattr(video_io, "wants_rgb", False))
-    if rgb:  # encoder pipe / raw sink: BGR -> RGB inside the to_out kernel, not on the host
+    if video_io.sink_format.rgb:  # encoder pipe / raw sink: BGR -> RGB inside the to_out kernel, not on the host
         video_io.frames_are_rgb = True
-        to_out = lambda x, size: _tools.to_out(x, size, rgb=True, **fit_kw)  # noqa: E731
-    # 16-bit frames at either end: the hooks carry the depth and the clip's maxval, the loop between them never looks at a frame
-    if getattr(video_io, "depth", 8) == 16:
-        to_inp = lambda fr, size: _tools.to_inp(fr, size, maxval=video_io.maxval, **fit_kw)  # noqa: E731
-    if getattr(video_io, "out_depth", 8) == 16:
-        to_out = lambda x, size: _tools.to_out(x, size, rgb=rgb, depth=16, maxval=video_io.out_maxval, **fit_kw)  # noqa: E731
-    # planar 4:2:0 at either end, each on its own: a YuvFrame knows its depth, the planar sink takes the 1-D Y, U, V array
-    if getattr(video_io, "pixfmt", "bgr") == "yuv420":
-        to_inp = lambda fr, size: _tools.to_inp(fr, size, matrix=video_io.yuv_matrix, full_range=video_io.yuv_full_range,  # noqa: E731
-                                                **fit_kw)
-    if getattr(video_io, "out_pixfmt", "bgr") == "yuv420":
-        mv = video_io.out_maxval if video_io.out_depth == 16 else None
-        to_out = lambda x, size: _tools.to_out(x, size, depth=video_io.out_depth, maxval=mv, pixfmt="yuv420",  # noqa: E731
-                                               matrix=video_io.yuv_matrix, full_range=video_io.out_full_range, **fit_kw)
+    # the hooks carry what the two ends' frames are (depth and maxval, planar 4:2:0, RGB order) and --fit: the loop between them
+    # never looks at a frame, and a plain 8-bit resize run makes the calls it always made
+    to_inp, to_out = _frames.hooks(video_io.src_format, video_io.sink_format, fit_of(args))
     n = interpolate_stream(model, video_io, args.dst_fps, times=args.times, enable_scdet=args.enable_scdet,
                            scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, on_step=step,
                            linear=not getattr(args, "nonlinear", False), dedup=dedup_of(args))
@@ -271,36 +253,22 @@ def inference_sharded(model, args, rank, world, to_inp=None, to_out=None, check_
         raise ValueError("the frame-sharded run does not take --dedup (which frames are kept decides every rank's share of the clip "
                          "and its schedule): run --dedup on one GPU")
     apply_deterministic(args)
-    ext = os.path.splitext(args.input)[1].lower()
-    if ext == ".npz":
-        z = np.load(args.input)
-        frames, fps = z["frames"], (float(z["fps"]) if "fps" in z.files else 24.0)
-    elif ext == ".npy":
-        frames = np.load(args.input, mmap_mode="r")
-        side = os.path.splitext(args.input)[0] + ".json"
-        fps = 24.0
-        if os.path.exists(side):
-            import json
-            fps = float(json.load(open(side))["fps"])
-    else:
+    if os.path.splitext(args.input)[1].lower() not in (".npz", ".npy"):
         raise RuntimeError("the frame-sharded run needs random access to the clip: use a .npz / .npy source")
+    frames, fps, _ = _frames.open_array_clip(args.input)
+    fps = 24.0 if fps is None else fps
     # every rank sees the same clip and the same flag: all of them refuse here, before the gather exists and before any collective
     if frames.dtype == np.uint16 or out_depth_of(args) == 16:
         raise ValueError(f"the frame-sharded run carries 8-bit frames only (the gather to the writer moves uint8): {args.input} holds "
                          f"{frames.dtype} frames, --out-depth is {getattr(args, 'out_depth', 'source')}; run 16-bit clips on one GPU")
     counts = parallel.emission_counts(len(frames), fps, args.dst_fps, args.times, world)
     sg = parallel.StreamedGather(rank, world, counts, chunk=chunk, device=device, frame_shape=tuple(frames[0].shape))
-    # --fit pad: the default hooks of the shard carry the keyword, as in inference (hooks the caller gives are the caller's)
-    fit_kw = {} if fit_of(args) == "resize" else {"fit": fit_of(args)}
-    if to_inp is None and fit_kw:
-        to_inp = lambda fr, size: _tools.to_inp(fr, size, **fit_kw)  # noqa: E731
-    if to_out is None and world > 1 and device is not None and device.type == "cuda":
-        # finished frames stay on the device until the gather has moved them (tools.to_out would copy each one to the
-        # host only for StreamedGather to copy it back): the uint8 frame is written straight into the send path
-        from drba_amd import ops as _ops
-        to_out = lambda x, size: _ops.to_out(x, size, **fit_kw)  # noqa: E731
-    elif to_out is None and fit_kw:
-        to_out = lambda x, size: _tools.to_out(x, size, **fit_kw)  # noqa: E731
+    # the default hooks of the shard: 8-bit BGR frames and --fit, as in inference (hooks the caller gives are the caller's).  On the
+    # GPUs finished frames stay on the device until the gather has moved them (tools.to_out would copy each one to the host only
+    # for StreamedGather to copy it back): the uint8 frame is written straight into the send path
+    bgr8 = _frames.FrameFormat()
+    inp, out = _frames.hooks(bgr8, bgr8, fit_of(args), on_device=world > 1 and device is not None and device.type == "cuda")
+    to_inp, to_out = to_inp or inp, to_out or out
     parallel.interpolate_shard(model, frames, fps, args.dst_fps, rank, world, times=args.times, enable_scdet=args.enable_scdet,
                                scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, check_scene=check_scene,
                                sink=sg.push, linear=not getattr(args, "nonlinear", False))

@@ -5,7 +5,6 @@ Python like the reference.  Anything that touches pixels on the hot path (resize
 distance, scene check) dispatches to the HIP library through drba_amd.ops; there is no
 CPU fallback in this module.
 """
-import json
 import math
 import weakref
 import os
@@ -17,6 +16,7 @@ from queue import Queue
 import numpy as np
 import torch
 
+from drba_amd import frames as _frames
 from drba_amd import ops as _ops
 from drba_amd import y4m as _y4m
 
@@ -266,6 +266,9 @@ class VideoFI_IO:
     hooks perform: .yuv_full_range for the way in (the header's XCOLORRANGE; without one, what `yuv_range` says, limited by
     default), .out_full_range for the way out (`yuv_range`, or the way in's when it is `source`).  The sink's header carries the
     source's C tag, A, I and X tags through and the exact frame rate (y4m.output_fps).
+
+    .src_format / .sink_format say all of the above about the two ends as one drba_amd.frames.FrameFormat each: what the frame hooks
+    are built from (frames.hooks).
     """
 
     def __init__(self, input_path, output_path, dst_fps=60, times=-1, hwaccel=False, src_fps=None, out_depth=None,
@@ -277,10 +280,8 @@ class VideoFI_IO:
         self.pixfmt = "bgr"
         if yuv_matrix not in _ops.YUV_MATRICES:
             raise ValueError(f"yuv_matrix must be one of {sorted(_ops.YUV_MATRICES)}, got {yuv_matrix!r}")
-        if yuv_range not in ("source", "limited", "full"):
-            raise ValueError(f"yuv_range must be source, limited or full, got {yuv_range!r}")
         self.yuv_matrix = yuv_matrix
-        self.yuv_full_range = yuv_range == "full"
+        self.yuv_full_range = _frames.full_range(yuv_range, None, tag_wins=True)  # (refuses an unknown yuv_range)
         src_ratio = None
         ext = os.path.splitext(input_path)[1].lower()
         if input_path == "-" or ext == ".y4m":
@@ -289,24 +290,13 @@ class VideoFI_IO:
             self.pixfmt = "yuv420"
             if hdr.depth > 8:
                 self.depth, self.maxval = 16, hdr.maxval
-            if hdr.color_range is not None:
-                self.yuv_full_range = hdr.color_range == "FULL"
+            self.yuv_full_range = _frames.full_range(yuv_range, hdr.color_range, tag_wins=True)
             src_ratio = (hdr.fps_num, hdr.fps_den)
             self.src_fps = float(src_fps if src_fps is not None else hdr.fps)
             self.total_frames_count = float(self._y4m_in.frame_count_estimate())
             self.height, self.width = hdr.height, hdr.width
         elif ext in (".npz", ".npy"):
-            if ext == ".npz":
-                z = np.load(input_path)
-                self._frames = z["frames"]
-                fps = float(z["fps"]) if "fps" in z.files else None
-                maxval = int(z["maxval"]) if "maxval" in z.files else None
-            else:
-                self._frames = np.load(input_path, mmap_mode="r")
-                side = os.path.splitext(input_path)[0] + ".json"
-                meta = json.load(open(side)) if os.path.exists(side) else {}
-                fps = float(meta["fps"]) if "fps" in meta else None
-                maxval = int(meta["maxval"]) if "maxval" in meta else None
+            self._frames, fps, maxval = _frames.open_array_clip(input_path)
             if self._frames.dtype == np.uint16:
                 self.depth, self.maxval = 16, _ops._maxval(maxval)
             self.src_fps = float(src_fps if src_fps is not None else (fps if fps is not None else 24.0))
@@ -353,6 +343,10 @@ class VideoFI_IO:
         # are already RGB (to_out(..., rgb=True) flips on the device) by setting frames_are_rgb
         self.wants_rgb = self._sink_frames is None and self._y4m_out is None
         self.frames_are_rgb = False
+        # the two ends as the frame hooks are built from them (drba_amd.frames.hooks)
+        self.src_format = _frames.FrameFormat(self.pixfmt, self.depth, self.maxval, yuv_matrix, self.yuv_full_range)
+        self.sink_format = _frames.FrameFormat(self.out_pixfmt, self.out_depth, self.out_maxval, yuv_matrix, self.out_full_range,
+                                               rgb=self.wants_rgb)
         self._sink_error = None
         self.read_buffer = Queue(maxsize=100)
         # the Y4M sink writes each frame as it arrives and may be a pipe into an encoder that is slower than this pipeline: its

@@ -499,8 +499,7 @@ def resize_bilinear(x, size):
     n, c, h, w = x.shape
     ho, wo = int(size[0]), int(size[1])
     out = torch.empty((n, c, ho, wo), dtype=torch.float32, device=x.device)
-    sy = float(np.float32(h) / np.float32(ho))  # ATen: static_cast<float>(in) / out
-    sx = float(np.float32(w) / np.float32(wo))
+    sy, sx = _scales(False, (h, w), (ho, wo))
     nbytes = 4.0 * n * c * (min(h * w, 4 * ho * wo) + ho * wo)
     _lib.check(_timed("resize_bilinear", (n * c, h, w, ho, wo), nbytes, "byte", lambda: _lib.load().drba_resize_bilinear(
         _p(x), _p(out), n * c, h, w, ho, wo, sy, sx, _stream())), "drba_resize_bilinear")
@@ -597,6 +596,28 @@ def _fit(fit, way, frame, net):
     return fit == "pad"
 
 
+def _scales(pad, src, dst):
+    """the two coordinate multipliers of a resizing entry, ATen's static_cast<float>(in) / out; the pad / crop entries take none"""
+    return () if pad else tuple(float(np.float32(s) / np.float32(d)) for s, d in zip(src, dst))
+
+
+def _x4_like(out):
+    """the [H,W,4] copy of the network input `out` that its kernel writes in the same pass: what the gathers read image taps from"""
+    return torch.empty((out.shape[2], out.shape[3], 4), dtype=torch.float32, device=out.device) if IMG_X4 else None
+
+
+def _with_x4(out, x4):
+    if x4 is not None:
+        _set_copy(out, "_drba_x4", x4)
+    return out
+
+
+def _plane_ptrs(planes, ny, nc):
+    """the Y, U, V pointers of a packed planar tensor: `ny` samples of Y, then `nc` of U, then `nc` of V"""
+    base, es = planes.data_ptr(), planes.element_size()
+    return C.c_void_p(base), C.c_void_p(base + ny * es), C.c_void_p(base + (ny + nc) * es)
+
+
 def to_inp(img_u8, dst_size, maxval=None, fit="resize"):
     """tools.to_inp on a device-resident frame: uint8 [H,W,3] -> fp32 [1,3,*dst_size] in [0,1], one kernel.  A uint16 [H,W,3]
     frame takes the 16-bit kernel: its samples are divided by `maxval` (65535 unless given; 255 < maxval <= 65535).
@@ -608,18 +629,14 @@ def to_inp(img_u8, dst_size, maxval=None, fit="resize"):
     h, w = img.shape[:2]
     ho, wo = int(dst_size[0]), int(dst_size[1])
     out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=img.device)
-    # ... and the same frame pixel-major, [H,W,4]: what the gathers read their image taps from (IMG_X4), written in the same pass
-    x4 = torch.empty((ho, wo, 4), dtype=torch.float32, device=img.device) if IMG_X4 else None
+    x4 = _x4_like(out)
     pad = _fit(fit, "in", (h, w), (ho, wo))
-    # ATen: static_cast<float>(in) / out
-    scales = () if pad else (float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo)))
+    scales = _scales(pad, (h, w), (ho, wo))
     entry = f"drba_to_inp{tag}_pad_x4" if pad else f"drba_to_inp{tag}_x4"
     _lib.check(_timed("to_inp" + tag + ("_pad" if pad else ""), (h, w, ho, wo),
                       3.0 * size * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
                       lambda: getattr(_lib.load(), entry)(_p(img), _p(out), _p(x4), h, w, ho, wo, *scales, *mv, _stream())), entry)
-    if x4 is not None:
-        _set_copy(out, "_drba_x4", x4)
-    return out
+    return _with_x4(out, x4)
 
 
 def to_out(x, src_size, rgb=False, depth=8, maxval=None, fit="resize"):
@@ -638,7 +655,7 @@ def to_out(x, src_size, rgb=False, depth=8, maxval=None, fit="resize"):
     h, w = x.shape[2:]
     ho, wo = int(src_size[0]), int(src_size[1])
     pad = _fit(fit, "out", (ho, wo), (h, w))
-    scales = () if pad else (float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo)))
+    scales = _scales(pad, (h, w), (ho, wo))
     dtype = torch.uint16 if depth == 16 else torch.uint8
     size, tag, mv = _sample_kind(dtype, maxval)
     out = torch.empty((ho, wo, 3), dtype=dtype, device=x.device)
@@ -689,20 +706,16 @@ def to_inp_yuv(planes, size, dst_size, matrix="bt709", full_range=False, maxval=
         raise _lib.DrbaHipError(f"a {w}x{h} 4:2:0 frame is {ny + 2 * nc} samples, got {planes.numel()}")
     ho, wo = int(dst_size[0]), int(dst_size[1])
     out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=planes.device)
-    x4 = torch.empty((ho, wo, 4), dtype=torch.float32, device=planes.device) if IMG_X4 else None
+    x4 = _x4_like(out)
     pad = _fit(fit, "in", (h, w), (ho, wo))
-    scales = () if pad else (float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo)))
-    es = planes.element_size()
-    base = planes.data_ptr()
-    y, u, v = C.c_void_p(base), C.c_void_p(base + ny * es), C.c_void_p(base + (ny + nc) * es)
+    scales = _scales(pad, (h, w), (ho, wo))
+    es, (y, u, v) = planes.element_size(), _plane_ptrs(planes, ny, nc)
     entry = f"drba_to_inp{tag}_yuv420_pad_x4" if pad else f"drba_to_inp{tag}_yuv420_x4"
     _lib.check(_timed("to_inp_yuv" + tag + ("_pad" if pad else ""), (h, w, ho, wo),
                       1.5 * es * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
                       lambda: getattr(_lib.load(), entry)(y, u, v, w, wc, _p(out), _p(x4), h, w, ho, wo, *scales, mid, 1 if full_range else 0,
                                                           *mv, _stream())), entry)
-    if x4 is not None:
-        _set_copy(out, "_drba_x4", x4)
-    return out
+    return _with_x4(out, x4)
 
 
 def to_out_yuv(x, src_size, matrix="bt709", full_range=False, depth=8, maxval=None, fit="resize"):
@@ -718,11 +731,9 @@ def to_out_yuv(x, src_size, matrix="bt709", full_range=False, depth=8, maxval=No
     ho, wo = int(src_size[0]), int(src_size[1])
     ny, nc, _, wc = yuv420_layout((ho, wo))
     pad = _fit(fit, "out", (ho, wo), (h, w))
-    scales = () if pad else (float(np.float32(h) / np.float32(ho)), float(np.float32(w) / np.float32(wo)))
+    scales = _scales(pad, (h, w), (ho, wo))
     out = torch.empty(ny + 2 * nc, dtype=dtype, device=x.device)
-    es = out.element_size()
-    base = out.data_ptr()
-    y, u, v = C.c_void_p(base), C.c_void_p(base + ny * es), C.c_void_p(base + (ny + nc) * es)
+    es, (y, u, v) = out.element_size(), _plane_ptrs(out, ny, nc)
     entry = f"drba_to_out{tag}_yuv420" + ("_crop" if pad else "")
     _lib.check(_timed("to_out_yuv" + tag + ("_crop" if pad else ""), (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 1.5 * es * ho * wo, "byte",
                       lambda: getattr(_lib.load(), entry)(_p(x), y, u, v, wo, wc, h, w, ho, wo, *scales, mid, 1 if full_range else 0, *mv,
