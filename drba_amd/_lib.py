@@ -100,6 +100,14 @@ SIGNATURES = {
     "drba_to_inp16_yuv420_pad_x4": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "drba_to_out_yuv420_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "drba_to_out16_yuv420_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
+    "drba_to_inp_yuv_x4": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _f, _f, _i, _i, _i, _p]),
+    "drba_to_inp16_yuv_x4": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _f, _f, _i, _i, _i, _f, _p]),
+    "drba_to_out_yuv": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _p]),
+    "drba_to_out16_yuv": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _f, _p]),
+    "drba_to_inp_yuv_pad_x4": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "drba_to_inp16_yuv_pad_x4": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
+    "drba_to_out_yuv_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "drba_to_out16_yuv_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
     "drba_ssim3d_32": (_i, [_p, _p, _p, _p]),
     "drba_dup_stats_ws_floats": (_z, [_i, _i, _i]),
     "drba_dup_stats_f32": (_i, [_p, _p, _i, _i, _i, _f, _p, _p, _p]),

@@ -852,6 +852,251 @@ __device__ __forceinline__ void to_out_yuv_crop_rows_body(const YuvOut k, const 
   }
 }
 
+// ---- planar 4:2:2 and 4:4:4 (include/drba_hip.h: the drba_to_*_yuv* entries that take a layout) ------------------------------------
+// Chroma at full vertical resolution: U and V are [H][ceil(W / SX)] with SX = 2 (4:2:2) or 1 (4:4:4).  A chroma row belongs to the
+// luma row of the same index, so no vertical tap is taken; horizontally 4:2:2 keeps the centre-sited pair of chroma_tap and 4:4:4 reads
+// the sample itself.  The way out means over the SX pixels of a pair.  All eight bodies spell their arithmetic out (contraction off,
+// explicit fma): a pad / crop body and its resize sibling run the same operations on a pixel, so the two agree bit for bit at an
+// unchanged size by construction, not by what hipcc settles per body (yuv_to_bgr_as).  The 4:2:0 bodies above are not touched.
+__device__ __forceinline__ void bgr_to_ycc_as(const YuvOut &k, float b, float g, float r, float &Y, float &Cb, float &Cr) {
+#pragma clang fp contract(off)
+  b = clamp01(b), g = clamp01(g), r = clamp01(r);
+  Y = __builtin_fmaf(k.kb, b, __builtin_fmaf(k.kg, g, k.kr * r));
+  Cb = (b - Y) * k.cb_mul;
+  Cr = (r - Y) * k.cr_mul;
+}
+__device__ __forceinline__ uint32_t yuv_code(float off, float mul, float v, float maxval) {
+#pragma clang fp contract(off)
+  return round_sat_u16(__builtin_fmaf(mul, v, off), maxval);
+}
+// the mean of the SX colour differences of a chroma sample (sum of SX terms, in pixel order)
+template <int SX>
+__device__ __forceinline__ float chroma_mean(float sum) {
+  return SX == 2 ? sum * 0.5f : sum;
+}
+
+// one source pixel (sy, sx) of a 4:2:2 / 4:4:4 frame -> (B, G, R)
+template <class T, int SX>
+__device__ __forceinline__ void yuvl_pixel(const YuvIn &k, const T *__restrict__ yp, const T *__restrict__ up, const T *__restrict__ vp,
+                                           int ys, int cs, int Wc, int sy, int sx, float (&bgr)[3]) {
+  const size_t r = (size_t)sy * cs;
+  float u, v;
+  if constexpr (SX == 2) {
+    const CTap tx = chroma_tap(sx, Wc);
+    u = tx.w0 * (float)up[r + tx.i0] + tx.w1 * (float)up[r + tx.i1];  // exact: quarters of samples of at most 16 bits
+    v = tx.w0 * (float)vp[r + tx.i0] + tx.w1 * (float)vp[r + tx.i1];
+  } else {
+    u = (float)up[r + sx], v = (float)vp[r + sx];
+  }
+  yuv_to_bgr_as<false>(k, (float)yp[(size_t)sy * ys + sx], u, v, bgr);
+}
+// eight consecutive pixels x .. x + 7 of source row sy with aligned loads: 8 luma samples, and per chroma plane the 4 samples under
+// them plus their two neighbours (4:2:2: chroma_raw6 without the vertical taps) or the 8 samples themselves (4:4:4)
+template <class T, int SX>
+__device__ __forceinline__ void yuvl_row8(const YuvIn &k, const T *__restrict__ yp, const T *__restrict__ up, const T *__restrict__ vp,
+                                          int ys, int cs, int Wc, int sy, int x, float (&px)[8][3]) {
+  SampleRow<T, 8> luma;
+  luma.load(yp + (size_t)sy * ys + x);
+  const T *urow = up + (size_t)sy * cs, *vrow = vp + (size_t)sy * cs;
+  if constexpr (SX == 2) {
+    float cu[6], cv[6];
+    chroma_raw6(urow, Wc, x >> 1, cu), chroma_raw6(vrow, Wc, x >> 1, cv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {  // the taps of pixel x + j among the six: to_inp_yuv_rows_body
+      const int c0 = (j + 1) >> 1;
+      const float w0 = (j & 1) ? 0.75f : 0.25f, w1 = (j & 1) ? 0.25f : 0.75f;
+      yuv_to_bgr_as<false>(k, luma.sample(j), w0 * cu[c0] + w1 * cu[c0 + 1], w0 * cv[c0] + w1 * cv[c0 + 1], px[j]);
+    }
+  } else {
+    SampleRow<T, 8> u, v;
+    u.load(urow + x), v.load(vrow + x);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) yuv_to_bgr_as<false>(k, luma.sample(j), u.sample(j), v.sample(j), px[j]);
+  }
+}
+// 8 pixels of an output row -> the three planes (two 16-byte stores each) and the pixel-major copy
+__device__ __forceinline__ void store_row8(const f32x4g (&o)[3][2], float *__restrict__ out, float *__restrict__ out_x4, size_t P, size_t at) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    f32x4g *dst = reinterpret_cast<f32x4g *>(out + (size_t)c * P + at);
+    dst[0] = o[c][0], dst[1] = o[c][1];
+  }
+  if (out_x4) {
+    f32x4g *dst = reinterpret_cast<f32x4g *>(out_x4 + at * 4);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dst[j] = (f32x4g){o[0][j >> 2][j & 3], o[1][j >> 2][j & 3], o[2][j >> 2][j & 3], 0.f};
+  }
+}
+
+// way in, general form: to_inp_yuv_body with yuvl_pixel
+template <class T, int SX>
+__device__ __forceinline__ void to_inp_yuvl_body(const YuvIn k, const T *__restrict__ yp, const T *__restrict__ up, const T *__restrict__ vp,
+                                                 int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,
+                                                 int Hout, int Wout, float sy, float sx) {
+  const Tile2D p = tile_pixel(Wout, Hout);
+  if (!p.valid) return;
+  const Lerp ly = lerp_src_aten(p.y, sy, Hin), lx = lerp_src_aten(p.x, sx, Win);
+  const int Wc = (Win + SX - 1) / SX;
+  float a[3], b[3], c[3], d[3];
+  yuvl_pixel<T, SX>(k, yp, up, vp, ys, cs, Wc, ly.i0, lx.i0, a);
+  yuvl_pixel<T, SX>(k, yp, up, vp, ys, cs, Wc, ly.i0, lx.i1, b);
+  yuvl_pixel<T, SX>(k, yp, up, vp, ys, cs, Wc, ly.i1, lx.i0, c);
+  yuvl_pixel<T, SX>(k, yp, up, vp, ys, cs, Wc, ly.i1, lx.i1, d);
+  const size_t P = (size_t)Hout * Wout, o = (size_t)p.y * Wout + p.x;
+  float v[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    v[ch] = lerp2_aten(ly, lx, a[ch], b[ch], c[ch], d[ch]);
+    out[ch * P + o] = v[ch];
+  }
+  if (out_x4) *reinterpret_cast<f32x4g *>(out_x4 + 4 * o) = (f32x4g){v[0], v[1], v[2], 0.f};
+}
+// way in, rows form: eight pixels of an output row per lane from its two source rows, ONE chroma row per luma row
+template <class T, int SX>
+__device__ __forceinline__ void to_inp_yuvl_rows_body(const YuvIn k, const T *__restrict__ yp, const T *__restrict__ up,
+                                                      const T *__restrict__ vp, int ys, int cs, float *__restrict__ out,
+                                                      float *__restrict__ out_x4, int Hin, int W, int Hout, float sy) {
+  const int W8 = W >> 3, Wc = W / SX;
+  const size_t total = (size_t)W8 * Hout, P = (size_t)Hout * W;
+  for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
+    const int y = (int)(i / W8), x = (int)(i - (size_t)y * W8) * 8;
+    const Lerp ly = lerp_src_aten(y, sy, Hin);
+    float p0[8][3], p1[8][3];
+    yuvl_row8<T, SX>(k, yp, up, vp, ys, cs, Wc, ly.i0, x, p0);
+    yuvl_row8<T, SX>(k, yp, up, vp, ys, cs, Wc, ly.i1, x, p1);
+    f32x4g o[3][2];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c][j >> 2][j & 3] = __fmaf_rn(ly.w0, p0[j][c], __fmul_rn(ly.w1, p1[j][c]));
+    store_row8(o, out, out_x4, P, (size_t)y * W + x);
+  }
+}
+// fit = pad, way in: the converted pixel of the clamped source coordinate
+template <class T, int SX>
+__device__ __forceinline__ void to_inp_yuvl_pad_body(const YuvIn k, const T *__restrict__ yp, const T *__restrict__ up,
+                                                     const T *__restrict__ vp, int ys, int cs, float *__restrict__ out,
+                                                     float *__restrict__ out_x4, int Hin, int Win, int Hout, int Wout) {
+  const Tile2D p = tile_pixel(Wout, Hout);
+  if (!p.valid) return;
+  float v[3];
+  yuvl_pixel<T, SX>(k, yp, up, vp, ys, cs, (Win + SX - 1) / SX, min(p.y, Hin - 1), min(p.x, Win - 1), v);
+  const size_t P = (size_t)Hout * Wout, o = (size_t)p.y * Wout + p.x;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) out[ch * P + o] = v[ch];
+  if (out_x4) *reinterpret_cast<f32x4g *>(out_x4 + 4 * o) = (f32x4g){v[0], v[1], v[2], 0.f};
+}
+template <class T, int SX>
+__device__ __forceinline__ void to_inp_yuvl_pad_rows_body(const YuvIn k, const T *__restrict__ yp, const T *__restrict__ up,
+                                                          const T *__restrict__ vp, int ys, int cs, float *__restrict__ out,
+                                                          float *__restrict__ out_x4, int Hin, int W, int Hout) {
+  const int W8 = W >> 3, Wc = W / SX;
+  const size_t total = (size_t)W8 * Hout, P = (size_t)Hout * W;
+  for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
+    const int y = (int)(i / W8), x = (int)(i - (size_t)y * W8) * 8;
+    float px[8][3];
+    yuvl_row8<T, SX>(k, yp, up, vp, ys, cs, Wc, min(y, Hin - 1), x, px);
+    f32x4g o[3][2];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c][j >> 2][j & 3] = px[j][c];
+    store_row8(o, out, out_x4, P, (size_t)y * W + x);
+  }
+}
+
+// way out, general form: the SX pixels of one chroma sample per lane (a horizontal pair, or the pixel itself), so the mean stays in
+// the lane; a pixel past an odd last column repeats it in the mean and is not stored.  kCrop: the window as it stands (fit = pad).
+template <class T, int SX, bool kCrop>
+__device__ __forceinline__ void to_out_yuvl_body(const YuvOut k, const float *__restrict__ in, T *__restrict__ yp, T *__restrict__ up,
+                                                 T *__restrict__ vp, int ys, int cs, int Hin, int Win, int Hout, int Wout, float sy,
+                                                 float sx) {
+#pragma clang fp contract(off)
+  const int Wc = (Wout + SX - 1) / SX;
+  const Tile2D p = tile_pixel(Wc, Hout);
+  if (!p.valid) return;
+  const size_t P = (size_t)Hin * Win;
+  Lerp ly;
+  if constexpr (!kCrop) ly = lerp_out<Samples16>(p.y, sy, Hin, Hout);
+  float cb = 0.f, cr = 0.f;
+#pragma unroll
+  for (int dx = 0; dx < SX; ++dx) {
+    const int ox = min(SX * p.x + dx, Wout - 1);
+    float ch[3];
+    if constexpr (kCrop) {
+      const float *px = in + (size_t)p.y * Win + ox;
+      ch[0] = aten_copy(px[0]), ch[1] = aten_copy(px[P]), ch[2] = aten_copy(px[2 * P]);
+    } else {
+      const Lerp lx = lerp_out<Samples16>(ox, sx, Win, Wout);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float *r0 = in + c * P + (size_t)ly.i0 * Win, *r1 = in + c * P + (size_t)ly.i1 * Win;
+        ch[c] = lerp2_aten(ly, lx, r0[lx.i0], r0[lx.i1], r1[lx.i0], r1[lx.i1]);
+      }
+    }
+    float Y, Cb, Cr;
+    bgr_to_ycc_as(k, ch[0], ch[1], ch[2], Y, Cb, Cr);
+    cb = __fadd_rn(cb, Cb), cr = __fadd_rn(cr, Cr);
+    if (SX * p.x + dx < Wout) yp[(size_t)p.y * ys + ox] = (T)yuv_code(k.y_off, k.y_mul, Y, k.maxval);
+  }
+  const size_t o = (size_t)p.y * cs + p.x;
+  up[o] = (T)yuv_code(k.c_off, k.c_mul, chroma_mean<SX>(cb), k.maxval);
+  vp[o] = (T)yuv_code(k.c_off, k.c_mul, chroma_mean<SX>(cr), k.maxval);
+}
+// way out, rows form: eight pixels of ONE output row per lane, 16-byte loads of the fp32 planes, one store of 8 luma samples and one
+// of 4 (4:2:2) or 8 (4:4:4) samples per chroma plane
+template <class T, int SX, bool kCrop>
+__device__ __forceinline__ void to_out_yuvl_rows_body(const YuvOut k, const float *__restrict__ in, T *__restrict__ yp, T *__restrict__ up,
+                                                      T *__restrict__ vp, int ys, int cs, int Hin, int W, int Hout, float sy) {
+#pragma clang fp contract(off)
+  constexpr int NC = 8 / SX;
+  const int W8 = W >> 3;
+  const size_t total = (size_t)W8 * Hout, P = (size_t)Hin * W;
+  for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
+    const int oy = (int)(i / W8), x = (int)(i - (size_t)oy * W8) * 8;
+    Lerp ly;
+    if constexpr (kCrop)
+      ly.i0 = ly.i1 = oy, ly.w0 = 1.f, ly.w1 = 0.f;
+    else
+      ly = lerp_out<Samples16>(oy, sy, Hin, Hout);
+    float cb[8], cr[8];
+    uint32_t q[8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      f32x4g ch[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const f32x4g t = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)ly.i0 * W + x + 4 * h);
+        if constexpr (kCrop) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) ch[c][e] = aten_copy(t[e]);
+        } else {
+          const f32x4g u = *reinterpret_cast<const f32x4g *>(in + (size_t)c * P + (size_t)ly.i1 * W + x + 4 * h);
+#pragma unroll
+          for (int e = 0; e < 4; ++e)  // the horizontal pass is ATen's copy, then the vertical lerp: to_out_yuv_rows_body
+            ch[c][e] = __fmaf_rn(ly.w0, aten_copy(t[e]), __fmul_rn(ly.w1, aten_copy(u[e])));
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float Y;
+        bgr_to_ycc_as(k, ch[0][e], ch[1][e], ch[2][e], Y, cb[4 * h + e], cr[4 * h + e]);
+        q[4 * h + e] = yuv_code(k.y_off, k.y_mul, Y, k.maxval);
+      }
+    }
+    SampleRow<T, 8>::store(yp + (size_t)oy * ys + x, q);
+    uint32_t qu[NC], qv[NC];
+#pragma unroll
+    for (int b = 0; b < NC; ++b) {
+      const float sb = SX == 2 ? __fadd_rn(cb[2 * b], cb[2 * b + 1]) : cb[b], sr = SX == 2 ? __fadd_rn(cr[2 * b], cr[2 * b + 1]) : cr[b];
+      qu[b] = yuv_code(k.c_off, k.c_mul, chroma_mean<SX>(sb), k.maxval);
+      qv[b] = yuv_code(k.c_off, k.c_mul, chroma_mean<SX>(sr), k.maxval);
+    }
+    SampleRow<T, NC>::store(up + (size_t)oy * cs + x / SX, qu);
+    SampleRow<T, NC>::store(vp + (size_t)oy * cs + x / SX, qv);
+  }
+}
+
 DRBA_FRAME_KERNEL to_inp_yuv_pad_kernel(YuvIn k, const uint8_t *__restrict__ y, const uint8_t *__restrict__ u, const uint8_t *__restrict__ v,
                                         int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win, int Hout,
                                         int Wout) {
@@ -923,6 +1168,51 @@ DRBA_FRAME_KERNEL to_out16_yuv_rows_kernel(YuvOut k, const float *__restrict__ i
                                            uint16_t *__restrict__ v, int ys, int cs, int Hin, int W, int Hout, float sy) {
   to_out_yuv_rows_body(k, in, y, u, v, ys, cs, Hin, W, Hout, sy);
 }
+// 4:2:2 and 4:4:4: the eight kernels of a (depth, layout) pair; D is empty or 16, L the layout's name, SX its horizontal factor
+#define DRBA_YUVL_KERNELS(D, T, L, SX)                                                                                                    \
+  DRBA_FRAME_KERNEL to_inp##D##_yuv##L##_kernel(YuvIn k, const T *__restrict__ y, const T *__restrict__ u, const T *__restrict__ v,      \
+                                                int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,  \
+                                                int Hout, int Wout, float sy, float sx) {                                               \
+    to_inp_yuvl_body<T, SX>(k, y, u, v, ys, cs, out, out_x4, Hin, Win, Hout, Wout, sy, sx);                                               \
+  }                                                                                                                                       \
+  DRBA_FRAME_KERNEL to_inp##D##_yuv##L##_rows_kernel(YuvIn k, const T *__restrict__ y, const T *__restrict__ u, const T *__restrict__ v, \
+                                                     int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin,      \
+                                                     int W, int Hout, float sy) {                                                       \
+    to_inp_yuvl_rows_body<T, SX>(k, y, u, v, ys, cs, out, out_x4, Hin, W, Hout, sy);                                                      \
+  }                                                                                                                                       \
+  DRBA_FRAME_KERNEL to_inp##D##_yuv##L##_pad_kernel(YuvIn k, const T *__restrict__ y, const T *__restrict__ u, const T *__restrict__ v,  \
+                                                    int ys, int cs, float *__restrict__ out, float *__restrict__ out_x4, int Hin,       \
+                                                    int Win, int Hout, int Wout) {                                                      \
+    to_inp_yuvl_pad_body<T, SX>(k, y, u, v, ys, cs, out, out_x4, Hin, Win, Hout, Wout);                                                   \
+  }                                                                                                                                       \
+  DRBA_FRAME_KERNEL to_inp##D##_yuv##L##_pad_rows_kernel(YuvIn k, const T *__restrict__ y, const T *__restrict__ u,                      \
+                                                         const T *__restrict__ v, int ys, int cs, float *__restrict__ out,              \
+                                                         float *__restrict__ out_x4, int Hin, int W, int Hout) {                        \
+    to_inp_yuvl_pad_rows_body<T, SX>(k, y, u, v, ys, cs, out, out_x4, Hin, W, Hout);                                                      \
+  }                                                                                                                                       \
+  DRBA_FRAME_KERNEL to_out##D##_yuv##L##_kernel(YuvOut k, const float *__restrict__ in, T *__restrict__ y, T *__restrict__ u,            \
+                                                T *__restrict__ v, int ys, int cs, int Hin, int Win, int Hout, int Wout, float sy,      \
+                                                float sx) {                                                                             \
+    to_out_yuvl_body<T, SX, false>(k, in, y, u, v, ys, cs, Hin, Win, Hout, Wout, sy, sx);                                                 \
+  }                                                                                                                                       \
+  DRBA_FRAME_KERNEL to_out##D##_yuv##L##_rows_kernel(YuvOut k, const float *__restrict__ in, T *__restrict__ y, T *__restrict__ u,       \
+                                                     T *__restrict__ v, int ys, int cs, int Hin, int W, int Hout, float sy) {           \
+    to_out_yuvl_rows_body<T, SX, false>(k, in, y, u, v, ys, cs, Hin, W, Hout, sy);                                                        \
+  }                                                                                                                                       \
+  DRBA_FRAME_KERNEL to_out##D##_yuv##L##_crop_kernel(YuvOut k, const float *__restrict__ in, T *__restrict__ y, T *__restrict__ u,       \
+                                                     T *__restrict__ v, int ys, int cs, int Hin, int Win, int Hout, int Wout) {         \
+    to_out_yuvl_body<T, SX, true>(k, in, y, u, v, ys, cs, Hin, Win, Hout, Wout, 1.f, 1.f);                                                \
+  }                                                                                                                                       \
+  DRBA_FRAME_KERNEL to_out##D##_yuv##L##_crop_rows_kernel(YuvOut k, const float *__restrict__ in, T *__restrict__ y,                     \
+                                                          T *__restrict__ u, T *__restrict__ v, int ys, int cs, int Hin, int W,         \
+                                                          int Hout) {                                                                   \
+    to_out_yuvl_rows_body<T, SX, true>(k, in, y, u, v, ys, cs, Hin, W, Hout, 1.f);                                                        \
+  }
+DRBA_YUVL_KERNELS(, uint8_t, 422, 2)
+DRBA_YUVL_KERNELS(16, uint16_t, 422, 2)
+DRBA_YUVL_KERNELS(, uint8_t, 444, 1)
+DRBA_YUVL_KERNELS(16, uint16_t, 444, 1)
+#undef DRBA_YUVL_KERNELS
 #undef DRBA_FRAME_KERNEL
 
 // ---- launch helpers: one per operation; M... is empty for bytes and (float maxval) for 16-bit samples ---------------------------
@@ -1034,18 +1324,21 @@ YuvOut yuv_out_consts(double kr, double kb, int full_range, double m) {
   c.maxval = (float)m;
   return c;
 }
-// The rows form: an unchanged width that is a multiple of 8, luma rows aligned to 8 samples and chroma rows to 4 (pointers and
-// strides), 16-byte aligned fp32 rows.
+// The rows form: an unchanged width that is a multiple of 8, luma rows aligned to 8 samples and chroma rows to the 8 / subx samples
+// under them -- 4 for 4:2:0 and 4:2:2, 8 for 4:4:4 -- (pointers and strides), 16-byte aligned fp32 rows.
 template <class T>
-bool yuv_rows_form_ok(int Win, int Wout, float scale_x, const T *y, const T *u, const T *v, int ys, int cs, const float *planes) {
-  return Win == Wout && scale_x == 1.f && (Wout & 7) == 0 && (ys & 7) == 0 && (cs & 3) == 0 &&
-         (((uintptr_t)y & (8 * sizeof(T) - 1)) | (((uintptr_t)u | (uintptr_t)v) & (4 * sizeof(T) - 1)) | ((uintptr_t)planes & 15)) == 0;
+bool yuv_rows_form_ok(int Win, int Wout, float scale_x, const T *y, const T *u, const T *v, int ys, int cs, const float *planes,
+                      int subx = 2) {
+  const int nc = 8 / subx;
+  return Win == Wout && scale_x == 1.f && (Wout & 7) == 0 && (ys & 7) == 0 && (cs & (nc - 1)) == 0 &&
+         (((uintptr_t)y & (8 * sizeof(T) - 1)) | (((uintptr_t)u | (uintptr_t)v) & (nc * sizeof(T) - 1)) | ((uintptr_t)planes & 15)) == 0;
 }
 template <class T>
 bool yuv_args_ok(const T *y, const T *u, const T *v, int ys, int cs, const float *planes, int Hin, int Win, int Hout, int Wout, int H, int W,
-                 float maxval) {
-  // (H, W): the size of the planar frame, which the strides must hold; every plane aligned to its sample
-  return y && u && v && planes && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && ys >= W && cs >= (W + 1) / 2 && H > 0 &&
+                 float maxval, int subx = 2) {
+  // (H, W): the size of the planar frame, which the strides must hold (a chroma row is ceil(W / subx) samples); every plane aligned
+  // to its sample
+  return y && u && v && planes && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && ys >= W && cs >= (W + subx - 1) / subx && H > 0 &&
          (((uintptr_t)y | (uintptr_t)u | (uintptr_t)v) & (sizeof(T) - 1)) == 0 && (sizeof(T) == 1 || maxval_ok(maxval));
 }
 
@@ -1053,12 +1346,13 @@ template <class T>
 int to_inp_yuv_launch(void (*one)(YuvIn, const T *, const T *, const T *, int, int, float *, float *, int, int, int, int, float, float),
                       void (*rows)(YuvIn, const T *, const T *, const T *, int, int, float *, float *, int, int, int, float), const T *y,
                       const T *u, const T *v, int ys, int cs, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y,
-                      float scale_x, int matrix, int full_range, float maxval, void *stream) {
+                      float scale_x, int matrix, int full_range, float maxval, void *stream, int subx = 2) {
   double kr, kb;
-  if (!yuv_args_ok(y, u, v, ys, cs, out, Hin, Win, Hout, Wout, Hin, Win, maxval) || ((uintptr_t)out_x4 & 15) != 0 || !yuv_coeffs(matrix, kr, kb))
+  if (!yuv_args_ok(y, u, v, ys, cs, out, Hin, Win, Hout, Wout, Hin, Win, maxval, subx) || ((uintptr_t)out_x4 & 15) != 0 ||
+      !yuv_coeffs(matrix, kr, kb))
     return DRBA_EINVAL;
   const YuvIn k = yuv_in_consts(kr, kb, full_range, maxval);
-  if (yuv_rows_form_ok(Win, Wout, scale_x, y, u, v, ys, cs, out))
+  if (yuv_rows_form_ok(Win, Wout, scale_x, y, u, v, ys, cs, out, subx))
     DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 3) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, k, y, u, v, ys, cs, out, out_x4, Hin,
                 Wout, Hout, scale_y);
   else
@@ -1072,12 +1366,12 @@ template <class T>
 int to_out_yuv_launch(void (*one)(YuvOut, const float *, T *, T *, T *, int, int, int, int, int, int, float, float),
                       void (*rows)(YuvOut, const float *, T *, T *, T *, int, int, int, int, int, float), const float *in, T *y, T *u, T *v,
                       int ys, int cs, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range,
-                      float maxval, void *stream) {
+                      float maxval, void *stream, int subx = 2, int suby = 2) {
   double kr, kb;
-  if (!yuv_args_ok(y, u, v, ys, cs, in, Hin, Win, Hout, Wout, Hout, Wout, maxval) || !yuv_coeffs(matrix, kr, kb)) return DRBA_EINVAL;
+  if (!yuv_args_ok(y, u, v, ys, cs, in, Hin, Win, Hout, Wout, Hout, Wout, maxval, subx) || !yuv_coeffs(matrix, kr, kb)) return DRBA_EINVAL;
   const YuvOut k = yuv_out_consts(kr, kb, full_range, maxval);
-  const int Hc = (Hout + 1) / 2, Wc = (Wout + 1) / 2;
-  if (yuv_rows_form_ok(Win, Wout, scale_x, y, u, v, ys, cs, in))
+  const int Hc = (Hout + suby - 1) / suby, Wc = (Wout + subx - 1) / subx;  // a lane takes the pixels of one chroma sample (general form)
+  if (yuv_rows_form_ok(Win, Wout, scale_x, y, u, v, ys, cs, in, subx))
     DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 3) * Hc)), dim3(kBlock), 0, (hipStream_t)stream, k, in, y, u, v, ys, cs, Hin, Wout, Hout,
                 scale_y);
   else
@@ -1092,13 +1386,13 @@ template <class T>
 int to_inp_yuv_pad_launch(void (*one)(YuvIn, const T *, const T *, const T *, int, int, float *, float *, int, int, int, int),
                           void (*rows)(YuvIn, const T *, const T *, const T *, int, int, float *, float *, int, int, int), const T *y,
                           const T *u, const T *v, int ys, int cs, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, int matrix,
-                          int full_range, float maxval, void *stream) {
+                          int full_range, float maxval, void *stream, int subx = 2) {
   double kr, kb;
-  if (!yuv_args_ok(y, u, v, ys, cs, out, Hin, Win, Hout, Wout, Hin, Win, maxval) || Hout < Hin || Wout < Win || ((uintptr_t)out_x4 & 15) != 0 ||
-      !yuv_coeffs(matrix, kr, kb))
+  if (!yuv_args_ok(y, u, v, ys, cs, out, Hin, Win, Hout, Wout, Hin, Win, maxval, subx) || Hout < Hin || Wout < Win ||
+      ((uintptr_t)out_x4 & 15) != 0 || !yuv_coeffs(matrix, kr, kb))
     return DRBA_EINVAL;
   const YuvIn k = yuv_in_consts(kr, kb, full_range, maxval);
-  if (yuv_rows_form_ok(Win, Wout, 1.f, y, u, v, ys, cs, out))
+  if (yuv_rows_form_ok(Win, Wout, 1.f, y, u, v, ys, cs, out, subx))
     DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 3) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, k, y, u, v, ys, cs, out, out_x4, Hin,
                 Wout, Hout);
   else
@@ -1110,13 +1404,15 @@ int to_inp_yuv_pad_launch(void (*one)(YuvIn, const T *, const T *, const T *, in
 template <class T>
 int to_out_yuv_crop_launch(void (*one)(YuvOut, const float *, T *, T *, T *, int, int, int, int, int, int),
                            void (*rows)(YuvOut, const float *, T *, T *, T *, int, int, int, int, int), const float *in, T *y, T *u, T *v,
-                           int ys, int cs, int Hin, int Win, int Hout, int Wout, int matrix, int full_range, float maxval, void *stream) {
+                           int ys, int cs, int Hin, int Win, int Hout, int Wout, int matrix, int full_range, float maxval, void *stream,
+                           int subx = 2, int suby = 2) {
   double kr, kb;
-  if (!yuv_args_ok(y, u, v, ys, cs, in, Hin, Win, Hout, Wout, Hout, Wout, maxval) || Hout > Hin || Wout > Win || !yuv_coeffs(matrix, kr, kb))
+  if (!yuv_args_ok(y, u, v, ys, cs, in, Hin, Win, Hout, Wout, Hout, Wout, maxval, subx) || Hout > Hin || Wout > Win ||
+      !yuv_coeffs(matrix, kr, kb))
     return DRBA_EINVAL;
   const YuvOut k = yuv_out_consts(kr, kb, full_range, maxval);
-  const int Hc = (Hout + 1) / 2, Wc = (Wout + 1) / 2;
-  if (yuv_rows_form_ok(Win, Wout, 1.f, y, u, v, ys, cs, in))
+  const int Hc = (Hout + suby - 1) / suby, Wc = (Wout + subx - 1) / subx;
+  if (yuv_rows_form_ok(Win, Wout, 1.f, y, u, v, ys, cs, in, subx))
     DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 3) * Hc)), dim3(kBlock), 0, (hipStream_t)stream, k, in, y, u, v, ys, cs, Hin, Wout, Hout);
   else
     DRBA_LAUNCH(one, dim3(tiles_for(Wc, Hc)), dim3(kBlock), 0, (hipStream_t)stream, k, in, y, u, v, ys, cs, Hin, Win, Hout, Wout);
@@ -1250,6 +1546,96 @@ int drba_to_out16_yuv420_crop(const float *in, uint16_t *y, uint16_t *u, uint16_
                               int Wout, int matrix, int full_range, float maxval, void *stream) {
   return to_out_yuv_crop_launch(to_out16_yuv_crop_kernel, to_out16_yuv_crop_rows_kernel, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout,
                                 matrix, full_range, maxval, stream);
+}
+
+// ---- planar frames by layout: 420 (the entries above), 422, 444; anything else is DRBA_EINVAL ---------------------------------------
+#define DRBA_BY_LAYOUT(launch, D, one, rows, ...)                                                                  \
+  switch (layout) {                                                                                               \
+    case 420: return launch(one(D, 420), rows(D, 420), __VA_ARGS__, 2, 2);                                         \
+    case 422: return launch(one(D, 422), rows(D, 422), __VA_ARGS__, 2, 1);                                         \
+    case 444: return launch(one(D, 444), rows(D, 444), __VA_ARGS__, 1, 1);                                         \
+    default: return DRBA_EINVAL;                                                                                  \
+  }
+#define DRBA_BY_LAYOUT_IN(launch, D, one, rows, ...)                                                               \
+  switch (layout) {                                                                                               \
+    case 420: return launch(one(D, 420), rows(D, 420), __VA_ARGS__, 2);                                            \
+    case 422: return launch(one(D, 422), rows(D, 422), __VA_ARGS__, 2);                                            \
+    case 444: return launch(one(D, 444), rows(D, 444), __VA_ARGS__, 1);                                            \
+    default: return DRBA_EINVAL;                                                                                  \
+  }
+// (the 4:2:0 kernels keep their names without the layout)
+#define to_inp_yuv420_kernel to_inp_yuv_kernel
+#define to_inp16_yuv420_kernel to_inp16_yuv_kernel
+#define to_inp_yuv420_rows_kernel to_inp_yuv_rows_kernel
+#define to_inp16_yuv420_rows_kernel to_inp16_yuv_rows_kernel
+#define to_inp_yuv420_pad_kernel to_inp_yuv_pad_kernel
+#define to_inp16_yuv420_pad_kernel to_inp16_yuv_pad_kernel
+#define to_inp_yuv420_pad_rows_kernel to_inp_yuv_pad_rows_kernel
+#define to_inp16_yuv420_pad_rows_kernel to_inp16_yuv_pad_rows_kernel
+#define to_out_yuv420_kernel to_out_yuv_kernel
+#define to_out16_yuv420_kernel to_out16_yuv_kernel
+#define to_out_yuv420_rows_kernel to_out_yuv_rows_kernel
+#define to_out16_yuv420_rows_kernel to_out16_yuv_rows_kernel
+#define to_out_yuv420_crop_kernel to_out_yuv_crop_kernel
+#define to_out16_yuv420_crop_kernel to_out16_yuv_crop_kernel
+#define to_out_yuv420_crop_rows_kernel to_out_yuv_crop_rows_kernel
+#define to_out16_yuv420_crop_rows_kernel to_out16_yuv_crop_rows_kernel
+#define K_INP(D, L) to_inp##D##_yuv##L##_kernel
+#define K_INP_ROWS(D, L) to_inp##D##_yuv##L##_rows_kernel
+#define K_INP_PAD(D, L) to_inp##D##_yuv##L##_pad_kernel
+#define K_INP_PAD_ROWS(D, L) to_inp##D##_yuv##L##_pad_rows_kernel
+#define K_OUT(D, L) to_out##D##_yuv##L##_kernel
+#define K_OUT_ROWS(D, L) to_out##D##_yuv##L##_rows_kernel
+#define K_OUT_CROP(D, L) to_out##D##_yuv##L##_crop_kernel
+#define K_OUT_CROP_ROWS(D, L) to_out##D##_yuv##L##_crop_rows_kernel
+
+int drba_to_inp_yuv_x4(const uint8_t *y, const uint8_t *u, const uint8_t *v, int y_stride, int c_stride, float *out, float *out_x4, int Hin,
+                       int Win, int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range, int layout, void *stream) {
+  DRBA_BY_LAYOUT_IN(to_inp_yuv_launch, , K_INP, K_INP_ROWS, y, u, v, y_stride, c_stride, out, out_x4, Hin, Win, Hout, Wout, scale_y, scale_x,
+                    matrix, full_range, 255.f, stream)
+}
+
+int drba_to_inp16_yuv_x4(const uint16_t *y, const uint16_t *u, const uint16_t *v, int y_stride, int c_stride, float *out, float *out_x4,
+                         int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range, int layout,
+                         float maxval, void *stream) {
+  DRBA_BY_LAYOUT_IN(to_inp_yuv_launch, 16, K_INP, K_INP_ROWS, y, u, v, y_stride, c_stride, out, out_x4, Hin, Win, Hout, Wout, scale_y,
+                    scale_x, matrix, full_range, maxval, stream)
+}
+
+int drba_to_out_yuv(const float *in, uint8_t *y, uint8_t *u, uint8_t *v, int y_stride, int c_stride, int Hin, int Win, int Hout, int Wout,
+                    float scale_y, float scale_x, int matrix, int full_range, int layout, void *stream) {
+  DRBA_BY_LAYOUT(to_out_yuv_launch, , K_OUT, K_OUT_ROWS, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout, scale_y, scale_x, matrix,
+                 full_range, 255.f, stream)
+}
+
+int drba_to_out16_yuv(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win, int Hout,
+                      int Wout, float scale_y, float scale_x, int matrix, int full_range, int layout, float maxval, void *stream) {
+  DRBA_BY_LAYOUT(to_out_yuv_launch, 16, K_OUT, K_OUT_ROWS, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout, scale_y, scale_x, matrix,
+                 full_range, maxval, stream)
+}
+
+int drba_to_inp_yuv_pad_x4(const uint8_t *y, const uint8_t *u, const uint8_t *v, int y_stride, int c_stride, float *out, float *out_x4,
+                           int Hin, int Win, int Hout, int Wout, int matrix, int full_range, int layout, void *stream) {
+  DRBA_BY_LAYOUT_IN(to_inp_yuv_pad_launch, , K_INP_PAD, K_INP_PAD_ROWS, y, u, v, y_stride, c_stride, out, out_x4, Hin, Win, Hout, Wout,
+                    matrix, full_range, 255.f, stream)
+}
+
+int drba_to_inp16_yuv_pad_x4(const uint16_t *y, const uint16_t *u, const uint16_t *v, int y_stride, int c_stride, float *out, float *out_x4,
+                             int Hin, int Win, int Hout, int Wout, int matrix, int full_range, int layout, float maxval, void *stream) {
+  DRBA_BY_LAYOUT_IN(to_inp_yuv_pad_launch, 16, K_INP_PAD, K_INP_PAD_ROWS, y, u, v, y_stride, c_stride, out, out_x4, Hin, Win, Hout, Wout,
+                    matrix, full_range, maxval, stream)
+}
+
+int drba_to_out_yuv_crop(const float *in, uint8_t *y, uint8_t *u, uint8_t *v, int y_stride, int c_stride, int Hin, int Win, int Hout,
+                         int Wout, int matrix, int full_range, int layout, void *stream) {
+  DRBA_BY_LAYOUT(to_out_yuv_crop_launch, , K_OUT_CROP, K_OUT_CROP_ROWS, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout, matrix,
+                 full_range, 255.f, stream)
+}
+
+int drba_to_out16_yuv_crop(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win, int Hout,
+                           int Wout, int matrix, int full_range, int layout, float maxval, void *stream) {
+  DRBA_BY_LAYOUT(to_out_yuv_crop_launch, 16, K_OUT_CROP, K_OUT_CROP_ROWS, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout, matrix,
+                 full_range, maxval, stream)
 }
 
 }  // extern "C"

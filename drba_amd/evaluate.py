@@ -31,6 +31,8 @@ report carries "pixfmt": "yuv420", "depth" (8, or 16 for 10-bit samples, as tool
 tags of both sides: two 4:2:0 sitings may be compared, the samples are taken as they are) and "color_range".  Refused, both sides
 named: different sizes, depths or XCOLORRANGE (no tag = limited), and a Y4M clip against an array clip.  `compare a.y4m b.y4m
 --max-lsb 0` is the reproducibility gate of `infer.py --deterministic` on Y4M outputs.
+A clip may be planar 4:2:2 or 4:4:4 (C422, C422p10, C444, C444p10): the per-plane figures use that layout's plane sizes, the report's
+"pixfmt" names it ("yuv422", "yuv444"), and two clips of different layouts are refused, both C tags named.
 `holdout -i clip.y4m` reads the kept frames through a random-access index of the file (one scan of the FRAME lines), converts
 them on the device (`--yuv-matrix`, `--yuv-range` as in infer.py), emits packed Y, U, V planes at the clip's depth that stay on
 the device, and compares each with the original's planes, uploaded when its turn comes: memory does not grow with the clip.
@@ -102,10 +104,10 @@ class ClipSource:
         its FRAME lines (y4m.IndexedReader: len() and frame(k)); a pipe is read in order.  Either way one frame is in memory at a
         time.  depth / maxval as tools.VideoFI_IO names them: 8 / 255, or 16 / 1023 for C420p10."""
         from drba_amd import y4m
-        self.pixfmt = "yuv420"
-        self._y4m = y4m.IndexedReader(f) if seekable and f.seekable() else y4m.Reader(f)
+        self._y4m = y4m.IndexedReader(f, accept=y4m.ACCEPT_ALL) if seekable and f.seekable() else y4m.Reader(f, accept=y4m.ACCEPT_ALL)
         self._indexed = isinstance(self._y4m, y4m.IndexedReader)
         hdr = self.header = self._y4m.header
+        self.layout, self.pixfmt = hdr.layout, "yuv" + hdr.layout  # "yuv420" | "yuv422" | "yuv444"
         self.fps = float(hdr.fps)
         self.size = (hdr.height, hdr.width)
         self.chroma, self.color_range = hdr.chroma, hdr.color_range
@@ -163,7 +165,7 @@ def compare(a, b, backend=None):
     ValueError when the frame counts or the frame sizes differ (both values are named).  Two uint16 clips (ClipSource.depth 16)
     are compared in their own steps, the peak being their maxval; clips of different depth or maxval are refused, both named.
     Two YUV4MPEG2 clips go to compare_yuv; one against an array clip is refused."""
-    if "yuv420" in (getattr(a, "pixfmt", None), getattr(b, "pixfmt", None)):
+    if any(getattr(c, "pixfmt", None) in _frames.YUV_PIXFMTS for c in (a, b)):
         return compare_yuv(a, b, backend=backend)
     da, db = getattr(a, "depth", None), getattr(b, "depth", None)
     if da is not None and db is not None and (da, getattr(a, "maxval", None)) != (db, getattr(b, "maxval", None)):
@@ -198,10 +200,12 @@ def compare(a, b, backend=None):
 def _side(clip):
     """how a refusal names one side: the path and what it holds"""
     name = getattr(clip, "path", None) or type(clip).__name__
-    if getattr(clip, "pixfmt", None) == "yuv420":
+    if getattr(clip, "pixfmt", None) in _frames.YUV_PIXFMTS:
         h, w = clip.size
         bits = 10 if clip.depth == 16 else 8
-        return f"{name} (planar 4:2:0, {w}x{h}, {bits}-bit, XCOLORRANGE={clip.color_range or 'none'})"
+        lay = _frames.YUV_PIXFMTS[clip.pixfmt]
+        tag = "" if lay == "420" else f" C{clip.chroma},"  # (what a 4:2:0 refusal says is what it always said)
+        return f"{name} (planar 4:{lay[1]}:{lay[2]},{tag} {w}x{h}, {bits}-bit, XCOLORRANGE={clip.color_range or 'none'})"
     return f"{name} (packed BGR frames)"
 
 
@@ -212,9 +216,12 @@ def compare_yuv(a, b, backend=None):
     C tags of the two sides; different 4:2:0 sitings are allowed, the samples are compared as they are) and "color_range".
     ValueError naming both sides: a Y4M clip against an array clip, different frame sizes, depths or XCOLORRANGE (a stream
     without the tag is limited range, as infer.py reads it), different lengths."""
-    ya, yb = getattr(a, "pixfmt", None) == "yuv420", getattr(b, "pixfmt", None) == "yuv420"
+    ya, yb = getattr(a, "pixfmt", None) in _frames.YUV_PIXFMTS, getattr(b, "pixfmt", None) in _frames.YUV_PIXFMTS
     if not (ya and yb):
         raise ValueError(f"one clip is YUV4MPEG2 and the other is not: {_side(a)} against {_side(b)}; convert one of them first")
+    if a.pixfmt != b.pixfmt:
+        raise ValueError(f"the clips differ in chroma layout: C{a.chroma or '420jpeg'} against C{b.chroma or '420jpeg'} "
+                         f"({_side(a)} against {_side(b)}); convert one of them first")
     if tuple(a.size) != tuple(b.size):
         raise ValueError(f"the clips differ in frame size: {_side(a)} against {_side(b)}")
     if (a.depth, a.maxval) != (b.depth, b.maxval):
@@ -237,7 +244,7 @@ def compare_yuv(a, b, backend=None):
             break
         cm.add(fa, fb)
     res = cm.result()
-    res.update({"size": [int(a.size[0]), int(a.size[1])], "pixfmt": "yuv420", "depth": a.depth, "maxval": int(a.maxval),
+    res.update({"size": [int(a.size[0]), int(a.size[1])], "pixfmt": a.pixfmt, "depth": a.depth, "maxval": int(a.maxval),
                 "chroma": [a.chroma, b.chroma], "color_range": a.color_range or b.color_range})
     return res
 
@@ -269,8 +276,8 @@ def compare_report(res, limits, a_name=None, b_name=None):
     rep.update(summary)
     if "depth" in res:  # 16-bit clips: max_lsb (and its gate) and total_differing are in the clips' own steps and samples
         rep.update({"depth": res["depth"], "maxval": res["maxval"]})
-    if res.get("pixfmt") == "yuv420":  # YUV4MPEG2 clips: the summary above already carries the per-plane figures
-        rep.update({"pixfmt": "yuv420", "chroma": res["chroma"], "color_range": res["color_range"]})
+    if res.get("pixfmt") in _frames.YUV_PIXFMTS:  # YUV4MPEG2 clips: the summary above already carries the per-plane figures
+        rep.update({"pixfmt": res["pixfmt"], "chroma": res["chroma"], "color_range": res["color_range"]})
     rep.update({"gates": gates, "ok": ok})
     return rep, ok
 
@@ -374,7 +381,7 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
         raise ValueError("--nonlinear and --plain exclude each other: a plain step is inference_ts, it has no DistanceRatioMap to retime")
     m, half = holdout_plan(len(frames), k)
     fmt = _frames.source_format(frames, maxval, yuv_matrix, yuv_range)  # (refuses a maxval given for frames that are not uint16)
-    yuv = fmt.pixfmt == "yuv420"
+    yuv = fmt.pixfmt in _frames.YUV_PIXFMTS
     deep = not yuv and fmt.depth == 16
     mv = fmt.maxval if yuv or deep else None
     device_out = to_out is None
@@ -403,7 +410,7 @@ def holdout(model, frames, k=3, fps=24.0, enable_scdet=False, scdet_threshold=0.
     if deep:
         out.update({"depth": 16, "maxval": mv})
     if yuv:
-        out.update({"pixfmt": "yuv420", "depth": frames.depth, "maxval": mv, "chroma": frames.chroma, "yuv_matrix": yuv_matrix,
+        out.update({"pixfmt": fmt.pixfmt, "depth": frames.depth, "maxval": mv, "chroma": frames.chroma, "yuv_matrix": yuv_matrix,
                     "full_range": fmt.full_range, "kept_passthrough": KEPT_PASSTHROUGH})
     for name, cm in (("kept", kept), ("held_out", held)):
         res = cm.result()  # (has waited for every kernel behind the frames)
@@ -423,7 +430,7 @@ def holdout_report(res):
         rep.update({"depth": res["depth"], "maxval": res["maxval"]})
     if "dedup_kept" in res:
         rep["dedup_kept"] = res["dedup_kept"]
-    if res.get("pixfmt") == "yuv420":
+    if res.get("pixfmt") in _frames.YUV_PIXFMTS:
         rep.update({k: res[k] for k in ("pixfmt", "chroma", "yuv_matrix", "full_range", "kept_passthrough")})
     for name in ("kept", "held_out"):
         r = res[name]
@@ -567,7 +574,7 @@ def main(argv=None, backend=None):
         src = ClipSource(args.input)
         if not src.random_access:
             raise ValueError("a hold-out needs random access to the clip: use a .npz / .npy source"
-                             + (" or a seekable .y4m file" if src.pixfmt == "yuv420" else ""))
+                             + (" or a seekable .y4m file" if src.pixfmt in _frames.YUV_PIXFMTS else ""))
         holdout_plan(len(src), args.k)  # refuse before a model is loaded
         if args.plain and args.nonlinear:
             raise ValueError("--nonlinear and --plain exclude each other: a plain step is inference_ts, it has no DistanceRatioMap to retime")

@@ -7,8 +7,10 @@ a line in `inp_keywords` / `out_keywords`, and whoever fills the field in (tools
 
 The rule of the keyword sets: A DEFAULT IS LEFT OUT.  A plain 8-bit BGR resize run calls tools.to_inp(frame, size) and
 tools.to_out(x, size) with no keyword at all, as the reference does, and every keyword appears only for the frames that need it
-(two exceptions are kept as they always were: a 16-bit BGR sink names `rgb` even when it is False, and a 4:2:0 sink names all five
-of its keywords).  Stand-ins with closed signatures rely on it.
+(two exceptions are kept as they always were: a 16-bit BGR sink names `rgb` even when it is False, and a planar sink names all five
+of its keywords).  Stand-ins with closed signatures rely on it.  The chroma layout follows the rule: a 4:2:0 end says nothing about
+it, a 4:2:2 or 4:4:4 sink says `pixfmt="yuv422"` / `"yuv444"` to tools.to_out and `layout="422"` / `"444"` to ops.to_out_yuv; a source
+frame (y4m.YuvFrame) carries its own layout.
 
 Nothing here touches the GPU, and nothing that does is imported when the module is loaded.
 """
@@ -21,15 +23,18 @@ import numpy as np
 
 @dataclass(frozen=True)
 class FrameFormat:
-    """One end of a run.  depth 8 | 16 is the sample type (uint8 | uint16; a 10-bit 4:2:0 clip is depth 16 with maxval 1023),
-    maxval the largest sample (255 at depth 8); matrix / full_range name the YCbCr conversion of a 4:2:0 end; rgb (a sink only): the
-    sink takes RGB order, not BGR."""
-    pixfmt: str = "bgr"  # "bgr" | "yuv420"
+    """One end of a run.  depth 8 | 16 is the sample type (uint8 | uint16; a 10-bit planar clip is depth 16 with maxval 1023),
+    maxval the largest sample (255 at depth 8); matrix / full_range name the YCbCr conversion of a planar end, whose chroma layout
+    the pixfmt names; rgb (a sink only): the sink takes RGB order, not BGR."""
+    pixfmt: str = "bgr"  # "bgr" | "yuv420" | "yuv422" | "yuv444"
     depth: int = 8
     maxval: int = 255
     matrix: str = "bt709"
     full_range: bool = False
     rgb: bool = False
+
+
+YUV_PIXFMTS = {"yuv420": "420", "yuv422": "422", "yuv444": "444"}  # a planar pixfmt -> its chroma layout (y4m.LAYOUTS)
 
 
 def open_array_clip(path):
@@ -60,10 +65,10 @@ def full_range(yuv_range, tag, tag_wins):
 def source_format(clip, maxval=None, yuv_matrix="bt709", yuv_range="source"):
     """The format of what evaluate reads: an evaluate.ClipSource (array clip or YUV4MPEG2), or a bare [N,H,W,3] array, whose
     `maxval` (65535 unless given) belongs to uint16 frames only."""
-    if getattr(clip, "pixfmt", None) == "yuv420":
+    if getattr(clip, "pixfmt", None) in YUV_PIXFMTS:
         if maxval is not None:
             raise ValueError("maxval belongs to uint16 frames")
-        return FrameFormat("yuv420", clip.depth, int(clip.maxval), yuv_matrix, full_range(yuv_range, clip.color_range, tag_wins=False))
+        return FrameFormat(clip.pixfmt, clip.depth, int(clip.maxval), yuv_matrix, full_range(yuv_range, clip.color_range, tag_wins=False))
     if getattr(clip, "depth", 16 if getattr(clip, "dtype", None) == np.uint16 else 8) != 16:
         if maxval is not None:
             raise ValueError("maxval belongs to uint16 frames")
@@ -78,8 +83,8 @@ def _fit_keywords(fit):
 
 
 def inp_keywords(fmt, fit):
-    """What tools.to_inp is told about a source frame.  A 4:2:0 frame (y4m.YuvFrame) carries its own depth and maxval."""
-    if fmt.pixfmt == "yuv420":
+    """What tools.to_inp is told about a source frame.  A planar frame (y4m.YuvFrame) carries its own depth, maxval and layout."""
+    if fmt.pixfmt in YUV_PIXFMTS:
         return {"matrix": fmt.matrix, "full_range": fmt.full_range, **_fit_keywords(fit)}
     if fmt.depth == 16:
         return {"maxval": fmt.maxval, **_fit_keywords(fit)}
@@ -87,12 +92,14 @@ def inp_keywords(fmt, fit):
 
 
 def out_keywords(fmt, fit, on_device=False):
-    """What tools.to_out is told about the sink's frames; on_device: what ops.to_out -- ops.to_out_yuv for a 4:2:0 sink -- is told
-    (the frame stays on the device: no `rgb`, and the entry says the pixel format)."""
+    """What tools.to_out is told about the sink's frames; on_device: what ops.to_out -- ops.to_out_yuv for a planar sink -- is told
+    (the frame stays on the device: no `rgb`, and the entry says the pixel format; a layout other than 4:2:0 is named)."""
     mv = fmt.maxval if fmt.depth == 16 else None
-    if fmt.pixfmt == "yuv420":
+    if fmt.pixfmt in YUV_PIXFMTS:
         kw = {"matrix": fmt.matrix, "full_range": fmt.full_range, "depth": fmt.depth, "maxval": mv}
-        return {**kw, **({} if on_device else {"pixfmt": "yuv420"}), **_fit_keywords(fit)}
+        layout = YUV_PIXFMTS[fmt.pixfmt]
+        said = ({} if layout == "420" else {"layout": layout}) if on_device else {"pixfmt": fmt.pixfmt}
+        return {**kw, **said, **_fit_keywords(fit)}
     if fmt.depth == 16:
         return {**({} if on_device else {"rgb": fmt.rgb}), "depth": 16, "maxval": mv, **_fit_keywords(fit)}
     return {**({"rgb": True} if fmt.rgb and not on_device else {}), **_fit_keywords(fit)}
@@ -111,7 +118,7 @@ def hooks(src_format, sink_format, fit, on_device=False):
     where, entry = tools, "to_out"
     if on_device:
         from drba_amd import ops as where
-        entry = "to_out_yuv" if sink_format.pixfmt == "yuv420" else "to_out"
+        entry = "to_out_yuv" if sink_format.pixfmt in YUV_PIXFMTS else "to_out"
 
     def to_out(x, size):
         return getattr(where, entry)(x, size, **kout)

@@ -2,7 +2,7 @@
 
     python infer.py -m rife -i in.npz -o out.npz [-fps 60 | -t 2] [-s] [-st 0.3] [-hw] [-scale 1.0] [--out-depth source|8|16]
                     [--nonlinear] [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--deterministic] [--fit resize|pad]
-                    [--dedup [--dedup-hi 0.047] [--dedup-lo 0.0196] [--dedup-frac 0.33] [--dedup-max 3]]
+                    [--dedup [--dedup-hi 0.047] [--dedup-lo 0.0196] [--dedup-frac 0.33] [--dedup-max 3]] [--out-chroma source|420|422|444]
 
 `--out-depth` is not in the reference: a .npz / .npy clip may hold uint16 frames, and the written frames are 8 or 16 bits deep
 (default: as the source, so an 8-bit clip is handled exactly as before).  `--nonlinear` is not in the reference either: its driver
@@ -16,7 +16,11 @@ run is reproducible too, but not promised to equal the sequential one.
 A `.y4m` path, or `-` for stdin / stdout, at either end selects the YUV4MPEG2 source or sink (drba_amd/y4m.py; planar 4:2:0 at 8
 or 10 bits, converted inside the to_inp / to_out kernels): `ffmpeg -i a.mkv -f yuv4mpegpipe - | python infer.py -m rife -i - -o - -t 2
 | x264 --demuxer y4m -o b.264 -`.  `--yuv-matrix` and `--yuv-range` name the conversion; on a Y4M sink `--out-depth 16` writes
-C420p10.  Nothing is printed to stdout.
+C420p10.  Nothing is printed to stdout.  A Y4M source may also be planar 4:2:2 or 4:4:4 (C422, C422p10, C444, C444p10), and
+`--out-chroma` names the Y4M sink's layout: `source` (default) writes the source's when it is a Y4M stream and 4:2:0 otherwise, so a
+4:2:0 clip and every run without a Y4M sink are what they were; `--out-chroma 444` keeps the full-resolution colour of the generated
+frames (`-f yuv4mpegpipe -pix_fmt yuv444p10le` in, `--out-chroma 444 --out-depth 16` out).  With any other sink a value but `source`
+is refused before the model is built.
 
 `--fit pad` (not in the reference, whose frames are always resized to the network size and back): the frame sits at the top left
 of the network tensor, the bottom and right margins repeat its last row and column and are cropped away on the way out -- no
@@ -77,6 +81,9 @@ def parse_args(argv=None):
     p.add_argument("--fit", dest="fit", type=str, default="resize", choices=("resize", "pad"),
                    help="how a frame gets to the network size and back: resize (default, the reference's behaviour) or pad -- "
                         "replicate padding at the bottom and right, cropped away on the way out, no resampling")
+    p.add_argument("--out-chroma", dest="out_chroma", type=str, default="source", choices=("source", "420", "422", "444"),
+                   help="chroma layout of a .y4m sink: the source's when it is a Y4M stream, else 4:2:0 (default), or 4:2:0 / 4:2:2 / "
+                        "4:4:4 (C444p10 with --out-depth 16); refused with any other sink")
     p.add_argument("--dedup", dest="dedup", action="store_true", default=False,
                    help="drop repeated source frames (drawings on twos, threes, fours) and interpolate across the gaps: the same "
                         "frames at the same instants are written (ffmpeg mpdecimate's rule; not in the frame-sharded run)")
@@ -113,6 +120,14 @@ def apply_deterministic(args):
     if getattr(args, "deterministic", False):
         from drba_amd import ops
         ops.set_deterministic(True)
+
+
+def out_chroma_of(args):
+    """--out-chroma as VideoFI_IO takes it, checked against the sink (tools.out_layout: ValueError for a sink that is not Y4M and a
+    value other than source).  A namespace built without the flag means source."""
+    v = getattr(args, "out_chroma", "source")
+    _tools.out_layout(v, args.output, None)
+    return v
 
 
 def out_depth_of(args):
@@ -216,6 +231,8 @@ def inference(model, args):
     for flag, dflt in (("yuv_matrix", "bt709"), ("yuv_range", "source")):  # a namespace built without the flags means the defaults
         if getattr(args, flag, dflt) != dflt:
             depth_kw[flag] = getattr(args, flag)
+    if out_chroma_of(args) != "source":
+        depth_kw["out_chroma"] = out_chroma_of(args)
     video_io = _tools.VideoFI_IO(args.input, args.output, dst_fps=args.dst_fps, times=args.times, hwaccel=args.hwaccel, **depth_kw)
     try:
         from tqdm import tqdm
@@ -294,6 +311,7 @@ def main(argv=None):
     # alone leaves the store off); nothing is written before the first winner is stored
     from drba_amd import tunecache
     tunecache.default_on()
+    out_chroma_of(args)  # refuses --out-chroma with a sink that is not Y4M before the model is built
     apply_deterministic(args)  # before the model is built: nothing it does at load is timed in this mode
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1:

@@ -46,10 +46,10 @@ class HipBackend:
         self.ops = ops
         self.device = ops.default_device() if device is None else device
 
-    def prepare(self, x, size=None):
+    def prepare(self, x, size=None, layout="420"):
         import torch
         if size is not None or isinstance(x, y4m.YuvFrame):
-            return self._prepare_yuv(x, size)
+            return self._prepare_yuv(x, size, layout)
         if isinstance(x, np.ndarray):
             x = torch.from_numpy(np.ascontiguousarray(x))
         if not torch.is_tensor(x):
@@ -123,18 +123,20 @@ class HipBackend:
         return rows
 
     # ---- planar 4:2:0 frames: per-plane errors and the 2-D SSIM of luma (drba_ssim2d) -------------------------------------------
-    def _prepare_yuv(self, x, size):
+    def _prepare_yuv(self, x, size, layout="420"):
         import torch
         if isinstance(x, y4m.YuvFrame):
+            if x.layout != layout:
+                raise ValueError(f"the frame is 4:{x.layout[1]}:{x.layout[2]}, the layout given is {layout!r}")
             x, size = torch.from_numpy(x.data if x.data.flags.writeable else x.data.copy()), x.shape[:2]
         elif isinstance(x, np.ndarray):
             x = torch.from_numpy(np.ascontiguousarray(x))
         if not (torch.is_tensor(x) and x.dim() == 1 and x.dtype in (torch.uint8, torch.uint16)) or size is None:
             raise TypeError("a planar 4:2:0 frame is a y4m.YuvFrame, or a 1-D uint8 / uint16 array of packed Y, U, V planes with its (H, W)")
         h, w = int(size[0]), int(size[1])
-        ny, nc = yuv420_samples((h, w))
+        ny, nc = yuv_samples((h, w), layout)
         if x.numel() != ny + 2 * nc:
-            raise ValueError(f"a {w}x{h} 4:2:0 frame is {ny + 2 * nc} samples, got {x.numel()}")
+            raise ValueError(f"a {w}x{h} 4:{layout[1]}:{layout[2]} frame is {ny + 2 * nc} samples, got {x.numel()}")
         return x.to(self.device, non_blocking=True).contiguous(), "yuv8" if x.dtype == torch.uint8 else "yuv16", (1, h, w)
 
     def slots_yuv(self, capacity):
@@ -142,13 +144,13 @@ class HipBackend:
         # [capacity x 3 planes x 4 error words][capacity SSIM doubles], 8 bytes each: one tensor, one copy back
         return torch.zeros(int(capacity) * YUV_WORDS, dtype=torch.int64, device=self.device)
 
-    def measure_yuv(self, slots, k, a, b, kind, shape, maxval, want_ssim=True):
+    def measure_yuv(self, slots, k, a, b, kind, shape, maxval, want_ssim=True, layout="420"):
         lib, ops = _lib.load(), self.ops
         _, h, w = shape
         cap = slots.numel() // YUV_WORDS
         if not 0 <= k < cap:
             raise IndexError(f"slot {k} of {cap}")
-        ny, nc = yuv420_samples((h, w))
+        ny, nc = yuv_samples((h, w), layout)
         es = a.element_size()
         fn = lib.drba_frame_error_u8 if kind == "yuv8" else lib.drba_frame_error_u16
         ws = ops._workspace(self.device, max(lib.drba_frame_error_ws_floats(1, ny), lib.drba_ssim2d_ws_floats(1, h, w)))
@@ -183,6 +185,17 @@ def yuv420_samples(size):
     """(H, W) -> (samples of Y, of U (= of V)) of a packed planar 4:2:0 frame"""
     (h, w), (hc, wc) = y4m.plane_sizes(*size)
     return h * w, hc * wc
+
+
+def yuv_samples(size, layout="420"):
+    """yuv420_samples for a chroma layout: "420" | "422" | "444" (y4m.plane_sizes)"""
+    (h, w), (hc, wc) = y4m.plane_sizes(*size, layout)
+    return h * w, hc * wc
+
+
+def _layout_kw(layout):
+    """what a back end is told about the layout: nothing for 4:2:0 (a default is left out: back ends written for 4:2:0 keep working)"""
+    return {} if layout == "420" else {"layout": layout}
 
 
 def default_backend():
@@ -321,6 +334,16 @@ class ClipMetrics:
 PLANES = ("y", "u", "v")
 
 
+def _yuv_layout(a, b, layout):
+    """the one layout of a pair: a YuvFrame's own, or the one given for packed planes (4:2:0 unless said)"""
+    for x in (a, b):
+        if isinstance(x, y4m.YuvFrame):
+            if layout is not None and layout != x.layout:
+                raise ValueError(f"the two frames differ in chroma layout: C{x.layout} against C{layout}")
+            layout = x.layout
+    return "420" if layout is None else layout
+
+
 def _yuv_size(a, b, size):
     for x in (a, b):
         if isinstance(x, y4m.YuvFrame):
@@ -332,10 +355,10 @@ def _yuv_size(a, b, size):
     return int(size[0]), int(size[1])
 
 
-def _yuv_pair(backend, a, b, size):
+def _yuv_pair(backend, a, b, size, layout="420"):
     size = _yuv_size(a, b, size)
-    a, ka, sa = backend.prepare(a, size)
-    b, kb, sb = backend.prepare(b, size)
+    a, ka, sa = backend.prepare(a, size, **_layout_kw(layout))
+    b, kb, sb = backend.prepare(b, size, **_layout_kw(layout))
     if ka != kb or sa != sb:
         raise ValueError(f"the two frames differ in form: {ka} {sa} against {kb} {sb}")
     return a, b, ka, sa
@@ -355,7 +378,7 @@ def _yuv_maxval(kind, maxval):
 def summarise_yuv(rows, samples, peak):
     """-> {"frames", "peak", "per_frame", "summary"} from collect_yuv's rows and the (Y, U (= V)) sample counts per frame: host
     arithmetic on exact integers.  `psnr` pools the squared error of the three planes over all their samples -- the 4:1:1 weighting
-    4:2:0 has by construction --; the summary follows summarise(), for the pooled figure and with _y / _u / _v for each plane."""
+    4:2:0 has by construction, 2:1:1 for 4:2:2 and 1:1:1 for 4:4:4 --; the summary follows summarise(), for the pooled figure and with _y / _u / _v for each plane."""
     n = len(rows)
     sq = [[r[p][0] for r in rows] for p in range(3)]
     cnt = [[s[0] for s in samples], [s[1] for s in samples], [s[1] for s in samples]]
@@ -393,41 +416,48 @@ class YuvClipMetrics:
     def __init__(self, backend=None, capacity=256, maxval=None):
         self.backend = backend or default_backend()
         self.capacity, self.maxval = int(capacity), maxval
-        self._slots, self._used, self._samples, self._kind = [], [], [], None
+        self._slots, self._used, self._samples, self._kind, self._layout = [], [], [], None, None
 
     def __len__(self):
         return sum(self._used)
 
-    def add(self, a, b, size=None):
-        a, b, kind, (_, h, w) = _yuv_pair(self.backend, a, b, size)
+    def add(self, a, b, size=None, layout=None):
+        """layout: the chroma layout of packed planes ("420" unless given); a YuvFrame carries its own"""
+        layout = _yuv_layout(a, b, layout)
+        a, b, kind, (_, h, w) = _yuv_pair(self.backend, a, b, size, layout)
         if self._kind not in (None, kind):
             raise ValueError(f"a clip has one sample depth: {self._kind} so far, now {kind}")
+        if self._layout not in (None, layout):
+            raise ValueError(f"a clip has one chroma layout: {self._layout} so far, now {layout}")
+        self._layout = layout
         mv = _yuv_maxval(kind, self.maxval)
         if not self._slots or self._used[-1] == self.capacity:
             self._slots.append(self.backend.slots_yuv(self.capacity))
             self._used.append(0)
-        self.backend.measure_yuv(self._slots[-1], self._used[-1], a, b, kind, (1, h, w), mv, True)
+        self.backend.measure_yuv(self._slots[-1], self._used[-1], a, b, kind, (1, h, w), mv, True, **_layout_kw(layout))
         self._kind = kind
         self._used[-1] += 1
-        self._samples.append(yuv420_samples((h, w)))
+        self._samples.append(yuv_samples((h, w), layout))
 
     def result(self):
         rows = self.backend.collect_yuv(self._slots, list(self._used))
         return summarise_yuv(rows, self._samples, float(_yuv_maxval(self._kind or "yuv8", self.maxval)))
 
 
-def _one_shot_yuv(a, b, size, want_ssim, backend, maxval):
+def _one_shot_yuv(a, b, size, want_ssim, backend, maxval, layout=None):
     backend = backend or default_backend()
-    a, b, kind, shape = _yuv_pair(backend, a, b, size)
+    layout = _yuv_layout(a, b, layout)
+    a, b, kind, shape = _yuv_pair(backend, a, b, size, layout)
     mv = _yuv_maxval(kind, maxval)
     slots = backend.slots_yuv(1)
-    backend.measure_yuv(slots, 0, a, b, kind, shape, mv, want_ssim)
-    return backend.collect_yuv([slots], [1])[0], yuv420_samples(shape[1:]), float(mv)
+    backend.measure_yuv(slots, 0, a, b, kind, shape, mv, want_ssim, **_layout_kw(layout))
+    return backend.collect_yuv([slots], [1])[0], yuv_samples(shape[1:], layout), float(mv)
 
 
-def psnr_yuv(a, b, size=None, backend=None, maxval=None):
-    """{"psnr_y", "psnr_u", "psnr_v", "psnr"} of one pair of planar 4:2:0 frames (peak = maxval; inf for identical planes)"""
-    row, samples, peak = _one_shot_yuv(a, b, size, False, backend, maxval)
+def psnr_yuv(a, b, size=None, backend=None, maxval=None, layout=None):
+    """{"psnr_y", "psnr_u", "psnr_v", "psnr"} of one pair of planar frames (peak = maxval; inf for identical planes); layout: of packed
+    planes, 4:2:0 unless given"""
+    row, samples, peak = _one_shot_yuv(a, b, size, False, backend, maxval, layout)
     per = summarise_yuv([row], [samples], peak)["per_frame"]
     return {k: per[k][0] for k in ("psnr_y", "psnr_u", "psnr_v", "psnr")}
 

@@ -100,18 +100,19 @@ def _fit_kw(fit):
 def to_inp(npInp, dst_size, device=None, maxval=None, matrix="bt709", full_range=False, fit="resize"):
     """resize(to_tensor(npInp), dst_size) (tools.py:59-60) as one kernel on the uploaded uint8 frame (the full-size
     fp32 frame of the reference is never materialised); bit-exact with the two-step form.  A uint16 frame goes through the
-    16-bit kernel with its `maxval` (65535 unless given).  A planar 4:2:0 frame (y4m.YuvFrame) is uploaded as it stands -- half
-    the bytes of a BGR frame -- and converted with `matrix` / `full_range` inside the kernel (ops.to_inp_yuv); the frame knows its
-    own depth.  fit="pad" (not in the reference): the frame is replicate-padded to `dst_size` at the bottom and right instead of
+    16-bit kernel with its `maxval` (65535 unless given).  A planar frame (y4m.YuvFrame: 4:2:0, 4:2:2 or 4:4:4) is uploaded as it
+    stands -- half the bytes of a BGR frame at 4:2:0 -- and converted with `matrix` / `full_range` inside the kernel
+    (ops.to_inp_yuv); the frame knows its own depth and layout.  fit="pad" (not in the reference): the frame is replicate-padded to `dst_size` at the bottom and right instead of
     resized (ops.to_inp)."""
     fit_kw = _fit_kw(fit)
     device = _ops.default_device() if device is None else device
     if isinstance(npInp, _y4m.YuvFrame):
         if maxval not in (None, npInp.maxval):
-            raise ValueError(f"a {npInp.depth}-bit 4:2:0 frame has maxval {npInp.maxval}, got {maxval}")
+            raise ValueError(f"a {npInp.depth}-bit planar frame has maxval {npInp.maxval}, got {maxval}")
         planes = torch.from_numpy(npInp.data if npInp.data.flags.writeable else npInp.data.copy()).to(device, non_blocking=True)
         return _ops.to_inp_yuv(planes, npInp.shape[:2], dst_size, matrix=matrix, full_range=full_range,
-                               maxval=None if npInp.depth == 8 else npInp.maxval, **fit_kw)
+                               maxval=None if npInp.depth == 8 else npInp.maxval, **fit_kw,
+                               **({} if npInp.layout == "420" else {"layout": npInp.layout}))
     if torch.is_tensor(npInp):
         u8 = npInp.to(device, non_blocking=True)
     else:
@@ -127,17 +128,20 @@ def to_out(tenInp, src_size, rgb=False, depth=8, maxval=None, pixfmt="bgr", matr
     """to_cv2(resize(tenInp, src_size)) (tools.py:63-64) as one kernel + the D2H copy.  rgb=True returns the frame in RGB
     order (the flip the reference's writer thread does on the host, tools.py:202, done on the device instead).  depth=16
     returns a uint16 frame scaled to `maxval` (65535 unless given), rounded and saturated (ops.to_out).  pixfmt="yuv420" returns
-    the frame as planar 4:2:0 instead, one 1-D array holding Y, U, V (ops.to_out_yuv; at depth 16 scaled to 1023 unless given).
+    the frame as planar 4:2:0 instead, one 1-D array holding Y, U, V (ops.to_out_yuv; at depth 16 scaled to 1023 unless given);
+    "yuv422" and "yuv444" the same with those chroma layouts.
     fit="pad" (not in the reference): the top-left `src_size` window of tenInp is converted as it stands -- the counterpart of
     to_inp(..., fit="pad") -- instead of the resize."""
     _check_depth(depth, maxval)
     fit_kw = _fit_kw(fit)
-    if pixfmt not in ("bgr", "yuv420"):
-        raise ValueError(f"pixfmt must be bgr or yuv420, got {pixfmt!r}")
-    if pixfmt == "yuv420":
+    if pixfmt != "bgr" and pixfmt not in _frames.YUV_PIXFMTS:
+        raise ValueError(f"pixfmt must be bgr, yuv420, yuv422 or yuv444, got {pixfmt!r}")
+    if pixfmt in _frames.YUV_PIXFMTS:
         if rgb:
             raise ValueError("rgb=True belongs to packed frames (pixfmt='bgr')")
-        frame = _ops.to_out_yuv(tenInp, src_size, matrix=matrix, full_range=full_range, depth=depth, maxval=maxval, **fit_kw).cpu().numpy()
+        layout_kw = {} if pixfmt == "yuv420" else {"layout": _frames.YUV_PIXFMTS[pixfmt]}
+        frame = _ops.to_out_yuv(tenInp, src_size, matrix=matrix, full_range=full_range, depth=depth, maxval=maxval, **fit_kw,
+                                **layout_kw).cpu().numpy()
     elif depth == 16:
         frame = _ops.to_out(tenInp, src_size, rgb=rgb, depth=16, maxval=maxval, **fit_kw).cpu().numpy()
     else:
@@ -238,6 +242,20 @@ def calc_t(idx, times, t_mapper):
 
 
 # ----------------------------------------------------------------------------- frame source / sink
+def out_layout(out_chroma, output_path, src_layout):
+    """--out-chroma (source | 420 | 422 | 444) -> the chroma layout of a Y4M sink ("420" | "422" | "444"), None for any other sink,
+    which refuses a value other than `source` (ValueError).  `source`: src_layout when the source is a Y4M stream (None otherwise:
+    4:2:0, as before the flag existed)."""
+    if out_chroma not in ("source",) + tuple(_y4m.LAYOUTS):
+        raise ValueError(f"out_chroma must be source, 420, 422 or 444, got {out_chroma!r}")
+    if not (output_path == "-" or os.path.splitext(output_path)[1].lower() == ".y4m"):
+        if out_chroma != "source":
+            raise ValueError(f"--out-chroma {out_chroma} needs a YUV4MPEG2 sink (a .y4m path or -), not {output_path}: the other sinks "
+                             "take packed frames, and the encoder pipe stays yuv420p")
+        return None
+    return (src_layout or "420") if out_chroma == "source" else out_chroma
+
+
 class VideoFI_IO:
     """Frame source/sink with the reference's interface (tools.py:156-213): read_frame(),
     write_frame(), finish_writing(), .src_fps, .total_frames_count, .width, .height.
@@ -267,13 +285,19 @@ class VideoFI_IO:
     default), .out_full_range for the way out (`yuv_range`, or the way in's when it is `source`).  The sink's header carries the
     source's C tag, A, I and X tags through and the exact frame rate (y4m.output_fps).
 
+    Chroma layouts: a Y4M source may be 4:2:0, 4:2:2 or 4:4:4 (C422, C422p10, C444, C444p10: .pixfmt "yuv422" / "yuv444", frames
+    carry their layout).  `out_chroma` (source | 420 | 422 | 444) names the Y4M sink's layout: `source` is the source's when it is a
+    Y4M stream and 4:2:0 otherwise; .out_pixfmt and the sink header's C tag follow it (C444p10 at out_depth 16).  Any other sink
+    refuses a value other than `source`: the encoder pipe stays yuv420p.
+
     .src_format / .sink_format say all of the above about the two ends as one drba_amd.frames.FrameFormat each: what the frame hooks
     are built from (frames.hooks).
     """
 
     def __init__(self, input_path, output_path, dst_fps=60, times=-1, hwaccel=False, src_fps=None, out_depth=None,
-                 yuv_matrix="bt709", yuv_range="source"):
+                 yuv_matrix="bt709", yuv_range="source", out_chroma="source"):
         self.input_path, self.output_path = input_path, output_path
+        self.out_layout = out_layout(out_chroma, output_path, None)  # (refuses before anything is opened)
         self._cv2 = None
         self._y4m_in = self._y4m_out = None
         self.depth, self.maxval = 8, 255
@@ -285,9 +309,9 @@ class VideoFI_IO:
         src_ratio = None
         ext = os.path.splitext(input_path)[1].lower()
         if input_path == "-" or ext == ".y4m":
-            self._y4m_in = _y4m.Reader(sys.stdin.buffer if input_path == "-" else open(input_path, "rb"))
+            self._y4m_in = _y4m.Reader(sys.stdin.buffer if input_path == "-" else open(input_path, "rb"), accept=_y4m.ACCEPT_ALL)
             hdr = self._y4m_in.header
-            self.pixfmt = "yuv420"
+            self.pixfmt = "yuv" + hdr.layout
             if hdr.depth > 8:
                 self.depth, self.maxval = 16, hdr.maxval
             self.yuv_full_range = _frames.full_range(yuv_range, hdr.color_range, tag_wins=True)
@@ -329,7 +353,8 @@ class VideoFI_IO:
         self.out_pixfmt = "bgr"
         self.out_full_range = self.yuv_full_range if yuv_range == "source" else yuv_range == "full"
         if output_path == "-" or oext == ".y4m":
-            self.out_pixfmt = "yuv420"
+            self.out_layout = out_layout(out_chroma, output_path, self._y4m_in.header.layout if self._y4m_in is not None else None)
+            self.out_pixfmt = "yuv" + self.out_layout
             if self.out_depth == 16:
                 self.out_maxval = 1023  # 10 bits is what the format and the encoders carry
             self._y4m_out = _y4m.Writer(sys.stdout.buffer if output_path == "-" else open(output_path, "wb"),
@@ -365,10 +390,8 @@ class VideoFI_IO:
         if src_fps is not None or src_ratio is None:
             src_ratio = self.src_fps
         num, den = _y4m.output_fps(src_ratio, dst_fps, times)
-        if self.out_depth == 16:
-            chroma = "420p10"
-        else:
-            chroma = src.chroma if src is not None and src.depth == 8 and src.chroma is not None else "420jpeg"
+        chroma = _y4m.chroma_tag(self.out_layout, 10 if self.out_depth == 16 else 8,
+                                 like=src.chroma if src is not None and src.depth == 8 else None)
         color_range = None
         if yuv_range != "source" or (src is not None and src.color_range is not None):
             color_range = "FULL" if self.out_full_range else "LIMITED"

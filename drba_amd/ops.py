@@ -689,39 +689,64 @@ def yuv420_layout(size):
     return h * w, hc * wc, hc, wc
 
 
-def to_inp_yuv(planes, size, dst_size, matrix="bt709", full_range=False, maxval=None, fit="resize"):
-    """to_inp for a planar YCbCr 4:2:0 frame on the device: `planes` is one contiguous 1-D tensor holding Y [H,W], then U, then V
-    [ceil(H/2),ceil(W/2)] of a frame of `size` = (H, W) -- uint8 samples, or uint16 ones in [0, maxval] (1023 unless given) --
-    -> fp32 [1,3,*dst_size] in [0,1], BGR channel order, one kernel: chroma interpolation, colour conversion and the resize
-    (include/drba_hip.h, ABI 14).  The [H,W,4] copy is written in the same pass, as in to_inp.
+YUV_LAYOUTS = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}  # name -> (horizontal, vertical) subsampling factor of U and V
+
+
+YUV_SAMPLES_PER_PIXEL = {"420": 1.5, "422": 2.0, "444": 3.0}  # the byte model of the conversions (_timed)
+
+
+def yuv_layout(size, layout="420"):
+    """yuv420_layout for any of YUV_LAYOUTS: U and V are [ceil(H / sy)][ceil(W / sx)]"""
+    if layout not in YUV_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(YUV_LAYOUTS)}, got {layout!r}")
+    sx, sy = YUV_LAYOUTS[layout]
+    h, w = int(size[0]), int(size[1])
+    hc, wc = (h + sy - 1) // sy, (w + sx - 1) // sx
+    return h * w, hc * wc, hc, wc
+
+
+def _yuv_name(layout):
+    return "4:" + ":".join(layout[1:])
+
+
+def to_inp_yuv(planes, size, dst_size, matrix="bt709", full_range=False, maxval=None, fit="resize", layout="420"):
+    """to_inp for a planar YCbCr frame on the device: `planes` is one contiguous 1-D tensor holding Y [H,W], then U, then V
+    ([ceil(H/2),ceil(W/2)] for layout "420", [H,ceil(W/2)] for "422", [H,W] for "444") of a frame of `size` = (H, W) -- uint8
+    samples, or uint16 ones in [0, maxval] (1023 unless given) -- -> fp32 [1,3,*dst_size] in [0,1], BGR channel order, one kernel:
+    chroma interpolation (along the subsampled axes only), colour conversion and the resize (include/drba_hip.h, ABI 14 and 16).
+    The [H,W,4] copy is written in the same pass, as in to_inp.
     fit="pad": the converted frame is replicate-padded to `dst_size` instead of resized (_fit); a margin pixel is the converted
     pixel of the clamped source coordinate."""
     if not (torch.is_tensor(planes) and planes.is_cuda and planes.dim() == 1 and planes.dtype in (torch.uint8, torch.uint16)):
         raise _lib.DrbaHipError("expected a CUDA uint8 or uint16 1-D tensor of packed Y, U, V planes")
     mid, dtype, tag, mv = _yuv_args(matrix, 8 if planes.dtype == torch.uint8 else 16, maxval)
     h, w = int(size[0]), int(size[1])
-    ny, nc, _, wc = yuv420_layout((h, w))
+    ny, nc, _, wc = yuv_layout((h, w), layout)
     planes = planes.contiguous()
     if planes.numel() != ny + 2 * nc:
-        raise _lib.DrbaHipError(f"a {w}x{h} 4:2:0 frame is {ny + 2 * nc} samples, got {planes.numel()}")
+        raise _lib.DrbaHipError(f"a {w}x{h} {_yuv_name(layout)} frame is {ny + 2 * nc} samples, got {planes.numel()}")
     ho, wo = int(dst_size[0]), int(dst_size[1])
     out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=planes.device)
     x4 = _x4_like(out)
     pad = _fit(fit, "in", (h, w), (ho, wo))
     scales = _scales(pad, (h, w), (ho, wo))
     es, (y, u, v) = planes.element_size(), _plane_ptrs(planes, ny, nc)
-    entry = f"drba_to_inp{tag}_yuv420_pad_x4" if pad else f"drba_to_inp{tag}_yuv420_x4"
-    _lib.check(_timed("to_inp_yuv" + tag + ("_pad" if pad else ""), (h, w, ho, wo),
-                      1.5 * es * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
+    # 4:2:0 keeps its own entries (and names in the trace and the profiles); the other layouts say which they are
+    fmt, lay = ("yuv420", ()) if layout == "420" else ("yuv", (int(layout),))
+    entry = f"drba_to_inp{tag}_{fmt}_pad_x4" if pad else f"drba_to_inp{tag}_{fmt}_x4"
+    name = "to_inp_yuv" + ("" if layout == "420" else layout) + tag + ("_pad" if pad else "")
+    _lib.check(_timed(name, (h, w, ho, wo),
+                      YUV_SAMPLES_PER_PIXEL[layout] * es * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
                       lambda: getattr(_lib.load(), entry)(y, u, v, w, wc, _p(out), _p(x4), h, w, ho, wo, *scales, mid, 1 if full_range else 0,
-                                                          *mv, _stream())), entry)
+                                                          *lay, *mv, _stream())), entry)
     return _with_x4(out, x4)
 
 
-def to_out_yuv(x, src_size, matrix="bt709", full_range=False, depth=8, maxval=None, fit="resize"):
-    """to_out to a planar YCbCr 4:2:0 frame on the device: fp32 [1,3,h,w] (BGR) -> ONE contiguous 1-D tensor holding Y [*src_size],
-    then U, then V [ceil(H/2),ceil(W/2)], uint8 (depth 8) or uint16 scaled to `maxval` (depth 16; 1023 unless given): resize, clamp,
-    colour conversion, 2 x 2 chroma mean, round to nearest even, in one kernel.  One D2H copy and one write per frame.
+def to_out_yuv(x, src_size, matrix="bt709", full_range=False, depth=8, maxval=None, fit="resize", layout="420"):
+    """to_out to a planar YCbCr frame on the device: fp32 [1,3,h,w] (BGR) -> ONE contiguous 1-D tensor holding Y [*src_size],
+    then U, then V (their sizes by `layout`, as in to_inp_yuv), uint8 (depth 8) or uint16 scaled to `maxval` (depth 16; 1023 unless
+    given): resize, clamp, colour conversion, the chroma mean (2 x 2 for "420", the horizontal pair for "422", none for "444"),
+    round to nearest even, in one kernel.  One D2H copy and one write per frame.
     fit="pad": the top-left `src_size` window of x is converted as it stands instead of the resize (_fit); the chroma mean never
     reads the margin."""
     mid, dtype, tag, mv = _yuv_args(matrix, depth, maxval)
@@ -729,15 +754,17 @@ def to_out_yuv(x, src_size, matrix="bt709", full_range=False, depth=8, maxval=No
     assert x.shape[0] == 1 and x.shape[1] == 3
     h, w = x.shape[2:]
     ho, wo = int(src_size[0]), int(src_size[1])
-    ny, nc, _, wc = yuv420_layout((ho, wo))
+    ny, nc, _, wc = yuv_layout((ho, wo), layout)
     pad = _fit(fit, "out", (ho, wo), (h, w))
     scales = _scales(pad, (h, w), (ho, wo))
     out = torch.empty(ny + 2 * nc, dtype=dtype, device=x.device)
     es, (y, u, v) = out.element_size(), _plane_ptrs(out, ny, nc)
-    entry = f"drba_to_out{tag}_yuv420" + ("_crop" if pad else "")
-    _lib.check(_timed("to_out_yuv" + tag + ("_crop" if pad else ""), (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 1.5 * es * ho * wo, "byte",
-                      lambda: getattr(_lib.load(), entry)(_p(x), y, u, v, wo, wc, h, w, ho, wo, *scales, mid, 1 if full_range else 0, *mv,
-                                                          _stream())), entry)
+    fmt, lay = ("yuv420", ()) if layout == "420" else ("yuv", (int(layout),))
+    entry = f"drba_to_out{tag}_{fmt}" + ("_crop" if pad else "")
+    name = "to_out_yuv" + ("" if layout == "420" else layout) + tag + ("_crop" if pad else "")
+    _lib.check(_timed(name, (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + YUV_SAMPLES_PER_PIXEL[layout] * es * ho * wo, "byte",
+                      lambda: getattr(_lib.load(), entry)(_p(x), y, u, v, wo, wc, h, w, ho, wo, *scales, mid, 1 if full_range else 0, *lay,
+                                                          *mv, _stream())), entry)
     return out
 
 

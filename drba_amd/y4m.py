@@ -1,8 +1,9 @@
 """YUV4MPEG2 (.y4m) streams: header parse and format, a streaming reader, a random-access reader and a writer.  Pure Python, no GPU.
 
 The format is one text line, `YUV4MPEG2 W.. H.. F.. I.. A.. C.. X..`, then per frame the line `FRAME[ params]` and the three
-planes Y, U, V.  Only progressive planar 4:2:0 at 8 or 10 bits is taken (C420, C420jpeg, C420mpeg2, C420p10): Y is H x W, U and V
-are ceil(H/2) x ceil(W/2), 10-bit samples are little-endian uint16.  A frame travels through the pipeline as a YuvFrame: the packed
+planes Y, U, V.  Progressive planar 4:2:0 at 8 or 10 bits is taken (C420, C420jpeg, C420mpeg2, C420p10): Y is H x W, U and V
+are ceil(H/2) x ceil(W/2), 10-bit samples are little-endian uint16 -- and, by a caller that says it can convert them (`accept=`:
+the parser is strict by default), planar 4:2:2 (C422, C422p10: U and V are H x ceil(W/2)) and 4:4:4 (C444, C444p10: H x W).  A frame travels through the pipeline as a YuvFrame: the packed
 plane bytes as they stand in the stream plus the geometry; the colour conversion happens on the device (ops.to_inp_yuv /
 ops.to_out_yuv), never here.  The reader reads any file object, pipes included, one frame at a time; IndexedReader gives len() and
 read_frame(k) on a seekable one.
@@ -15,6 +16,10 @@ import numpy as np
 MAGIC = b"YUV4MPEG2"
 CHROMA_8 = ("420", "420jpeg", "420mpeg2")  # all read with the one centre-sited filter pair; the tag is carried through
 CHROMA_10 = ("420p10",)
+ACCEPT_420 = CHROMA_8 + CHROMA_10  # what parse_header, Reader and IndexedReader take unless told otherwise
+CHROMA_WIDE = {"422": ("422", 8), "422p10": ("422", 10), "444": ("444", 8), "444p10": ("444", 10)}  # tag -> (layout, bits)
+ACCEPT_ALL = ACCEPT_420 + tuple(CHROMA_WIDE)  # ... and what a caller that converts every layout passes as `accept`
+LAYOUTS = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}  # layout -> (horizontal, vertical) subsampling factor of U and V
 MAX_LINE = 4096
 
 
@@ -22,9 +27,29 @@ class Y4MError(ValueError):
     pass
 
 
-def plane_sizes(height, width):
-    """-> ((H, W), (Hc, Wc)): odd sizes are legal, chroma rounds up"""
-    return (int(height), int(width)), ((int(height) + 1) // 2, (int(width) + 1) // 2)
+def plane_sizes(height, width, layout="420"):
+    """-> ((H, W), (Hc, Wc)): odd sizes are legal, chroma rounds up along the axes the layout subsamples"""
+    if layout not in LAYOUTS:
+        raise Y4MError(f"unknown chroma layout {layout!r}: one of {sorted(LAYOUTS)}")
+    sx, sy = LAYOUTS[layout]
+    return (int(height), int(width)), ((int(height) + sy - 1) // sy, (int(width) + sx - 1) // sx)
+
+
+def layout_of(tag):
+    """the chroma layout of a C tag (without the C; None: no tag, 4:2:0) -> "420" | "422" | "444" (a key of LAYOUTS)"""
+    return CHROMA_WIDE[tag][0] if tag in CHROMA_WIDE else "420"
+
+
+def chroma_tag(layout, depth, like=None):
+    """the C tag a sink of `layout` writes at 8 bits or at 10 (depth > 8); `like`: a source's tag, kept where it names the same layout
+    and depth class (C420mpeg2 stays C420mpeg2)"""
+    if layout not in LAYOUTS:
+        raise Y4MError(f"unknown chroma layout {layout!r}: one of {sorted(LAYOUTS)}")
+    if depth > 8:
+        return layout + "p10"
+    if like is not None and like in CHROMA_8 + tuple(t for t, (_, b) in CHROMA_WIDE.items() if b == 8) and layout_of(like) == layout:
+        return like
+    return "420jpeg" if layout == "420" else layout
 
 
 class Header:
@@ -39,12 +64,17 @@ class Header:
             raise Y4MError(f"y4m: bad frame size {self.width}x{self.height}")
         if self.fps_num <= 0 or self.fps_den <= 0:
             raise Y4MError(f"y4m: bad frame rate F{self.fps_num}:{self.fps_den}")
-        _check_chroma(self.chroma)
+        _check_chroma(self.chroma, ACCEPT_ALL)  # a header is built for a sink too: every tag the writer can carry
 
     @property
     def depth(self):
         """bits per sample: 8 or 10"""
-        return 10 if self.chroma in CHROMA_10 else 8
+        return 10 if self.chroma in CHROMA_10 or CHROMA_WIDE.get(self.chroma, ("", 8))[1] == 10 else 8
+
+    @property
+    def layout(self):
+        """the chroma layout, "420" | "422" | "444", from the C tag"""
+        return layout_of(self.chroma)
 
     @property
     def maxval(self):
@@ -56,7 +86,7 @@ class Header:
 
     @property
     def frame_bytes(self):
-        (h, w), (hc, wc) = plane_sizes(self.height, self.width)
+        (h, w), (hc, wc) = plane_sizes(self.height, self.width, self.layout)
         return (h * w + 2 * hc * wc) * (2 if self.depth > 8 else 1)
 
     def format(self):
@@ -79,20 +109,27 @@ class Header:
         return f"Header({self.format()[:-1].decode()!r})"
 
 
-def _check_chroma(tag):
-    if tag is None or tag in CHROMA_8 or tag in CHROMA_10:
+def _check_chroma(tag, accept=ACCEPT_420):
+    if tag is None or tag in accept:
         return
     if tag == "420paldv":
         raise Y4MError("y4m: C420paldv is not supported (its chroma samples are co-sited with alternate luma lines)")
     if tag.startswith("420"):
         raise Y4MError(f"y4m: C{tag} is not supported: 4:2:0 is read at 8 bits (C420, C420jpeg, C420mpeg2) or 10 (C420p10)")
+    if tag in CHROMA_WIDE:  # a stream this reader's caller did not ask for (parse_header's `accept`)
+        raise Y4MError(f"y4m: C{tag} is not supported here: only planar 4:2:0 is read (C420, C420jpeg, C420mpeg2, C420p10)")
     if tag.startswith(("422", "444", "411", "mono")):
-        raise Y4MError(f"y4m: C{tag} is not supported: only planar 4:2:0 is read (C420, C420jpeg, C420mpeg2, C420p10)")
+        raise Y4MError(f"y4m: C{tag} is not supported: planar 4:2:0, 4:2:2 and 4:4:4 are read at 8 or 10 bits, without alpha")
     raise Y4MError(f"y4m: unknown colour space tag C{tag}")
 
 
-def parse_header(line):
-    """The first line of a stream (bytes, with or without its newline) -> Header"""
+def parse_header(line, accept=ACCEPT_420):
+    """The first line of a stream (bytes, with or without its newline) -> Header.  `accept`: the C tags (without the C) the caller can
+    convert -- 4:2:0 only unless it says more (ACCEPT_ALL: 4:2:2 and 4:4:4 too); any other tag is refused by name."""
+    accept = tuple(accept)
+    for t in accept:
+        if t not in ACCEPT_ALL:
+            raise ValueError(f"y4m: accept names C{t}, which no reader here can carry (one of {ACCEPT_ALL})")
     if isinstance(line, str):
         line = line.encode("ascii")
     fields = line.rstrip(b"\n").decode("ascii", "replace").split(" ")
@@ -120,7 +157,7 @@ def parse_header(line):
         elif key == "A":
             aspect = val
         elif key == "C":
-            _check_chroma(val)
+            _check_chroma(val, accept)
             chroma = val
         elif key == "X":
             if val.startswith("COLORRANGE="):
@@ -147,20 +184,23 @@ def _int(s, field):
 
 
 class YuvFrame:
-    """One planar 4:2:0 frame: `data` holds Y, then U, then V as they stand in the stream (a 1-D uint8 array for 8-bit samples, a
-    1-D uint16 array for 10-bit ones).  `.shape` is (H, W, 3) -- the size a frame-shaped consumer asks for -- although no such array
-    exists."""
+    """One planar frame: `data` holds Y, then U, then V as they stand in the stream (a 1-D uint8 array for 8-bit samples, a
+    1-D uint16 array for 10-bit ones); `layout` ("420" | "422" | "444") says how large U and V are (plane_sizes).  `.shape` is
+    (H, W, 3) -- the size a frame-shaped consumer asks for -- although no such array exists."""
 
-    def __init__(self, data, height, width, depth=8):
+    def __init__(self, data, height, width, depth=8, layout="420"):
         if depth not in (8, 10):
             raise Y4MError(f"a YuvFrame holds 8- or 10-bit samples, got {depth}")
+        if layout not in LAYOUTS:
+            raise Y4MError(f"a YuvFrame is 4:2:0, 4:2:2 or 4:4:4 (layout one of {sorted(LAYOUTS)}), got {layout!r}")
         dtype = np.uint8 if depth == 8 else np.dtype("<u2")
         if not isinstance(data, np.ndarray):
             data = np.frombuffer(data, dtype=dtype)
-        self.height, self.width, self.depth = int(height), int(width), int(depth)
-        (h, w), (hc, wc) = plane_sizes(height, width)
+        self.height, self.width, self.depth, self.layout = int(height), int(width), int(depth), layout
+        (h, w), (hc, wc) = plane_sizes(height, width, layout)
         if data.dtype != dtype or data.ndim != 1 or data.size != h * w + 2 * hc * wc:
-            raise Y4MError(f"a {w}x{h} {depth}-bit 4:2:0 frame is {h * w + 2 * hc * wc} {np.dtype(dtype).name} samples, got {data.dtype} x {data.shape}")
+            raise Y4MError(f"a {w}x{h} {depth}-bit 4:{layout[1]}:{layout[2]} frame is {h * w + 2 * hc * wc} {np.dtype(dtype).name} samples, "
+                           f"got {data.dtype} x {data.shape}")
         self.data = data
 
     @property
@@ -173,14 +213,14 @@ class YuvFrame:
 
     def planes(self):
         """-> (y [H,W], u [Hc,Wc], v [Hc,Wc]) views"""
-        (h, w), (hc, wc) = plane_sizes(self.height, self.width)
+        (h, w), (hc, wc) = plane_sizes(self.height, self.width, self.layout)
         d = self.data
         return d[:h * w].reshape(h, w), d[h * w:h * w + hc * wc].reshape(hc, wc), d[h * w + hc * wc:].reshape(hc, wc)
 
     @classmethod
-    def from_planes(cls, y, u, v, depth=8):
+    def from_planes(cls, y, u, v, depth=8, layout="420"):
         dtype = np.uint8 if depth == 8 else np.dtype("<u2")
-        return cls(np.concatenate([np.asarray(p, dtype=dtype).reshape(-1) for p in (y, u, v)]), y.shape[0], y.shape[1], depth)
+        return cls(np.concatenate([np.asarray(p, dtype=dtype).reshape(-1) for p in (y, u, v)]), y.shape[0], y.shape[1], depth, layout)
 
 
 def _read_exact(f, n):
@@ -220,13 +260,13 @@ def _read_line(f):
 class Reader:
     """Frames of a stream, one read_frame() at a time; nothing is read ahead of the frame asked for."""
 
-    def __init__(self, fileobj):
+    def __init__(self, fileobj, accept=ACCEPT_420):
         self.f = fileobj
         line = _read_line(fileobj)
         if not line.endswith(b"\n"):
             raise Y4MError("y4m: the stream ends inside its header" if line else "y4m: the stream is empty")
         self.header_bytes = len(line)
-        self.header = parse_header(line)
+        self.header = parse_header(line, accept)
         self.frames_read = 0
 
     def read_frame(self):
@@ -241,7 +281,7 @@ class Reader:
         if len(data) != h.frame_bytes:
             raise Y4MError(f"y4m: frame {self.frames_read} is truncated: {len(data)} of {h.frame_bytes} bytes")
         self.frames_read += 1
-        return YuvFrame(data, h.height, h.width, h.depth)
+        return YuvFrame(data, h.height, h.width, h.depth, h.layout)
 
     def frame_count_estimate(self):
         """the number of frames from the file size (frame headers without parameters), 0 for a stream that cannot seek"""
@@ -265,13 +305,13 @@ class IndexedReader:
     integer per frame; no payload is read before its frame is asked for.  A file object that cannot seek raises Y4MError, and so does
     a truncated last frame, as in Reader."""
 
-    def __init__(self, fileobj):
+    def __init__(self, fileobj, accept=ACCEPT_420):
         seekable = getattr(fileobj, "seekable", None)
         if not (callable(seekable) and seekable() and hasattr(fileobj, "seek") and hasattr(fileobj, "tell")):
             raise Y4MError("y4m: random access needs a seekable stream (a file, not a pipe)")
         self.f = fileobj
         start = fileobj.tell()
-        head = Reader(fileobj)
+        head = Reader(fileobj, accept)
         self.header, self.header_bytes = head.header, head.header_bytes
         end = fileobj.seek(0, 2)
         size, pos, self._offsets = self.header.frame_bytes, start + head.header_bytes, []
@@ -299,7 +339,7 @@ class IndexedReader:
         data = _read_exact(self.f, h.frame_bytes)
         if len(data) != h.frame_bytes:  # (the file shrank after the scan)
             raise Y4MError(f"y4m: frame {k} is truncated: {len(data)} of {h.frame_bytes} bytes")
-        return YuvFrame(data, h.height, h.width, h.depth)
+        return YuvFrame(data, h.height, h.width, h.depth, h.layout)
 
     def __iter__(self):
         return (self.read_frame(k) for k in range(len(self._offsets)))

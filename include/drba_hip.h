@@ -38,7 +38,10 @@ extern "C" {
  * drba_to_out_crop / drba_to_out16_crop / drba_to_inp_yuv420_pad_x4 / drba_to_inp16_yuv420_pad_x4 / drba_to_out_yuv420_crop /
  * drba_to_out16_yuv420_crop (replicate padding on the way in, a crop on the way out, no interpolation): additions only; and, under the
  * same number again, drba_dup_stats_f32 / drba_dup_stats_ws_floats (the duplicate-frame statistic of --dedup): additions only (a library
- * without them does not load: drba_amd/_lib.py resolves every entry).  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
+ * without them does not load: drba_amd/_lib.py resolves every entry); and, under the same number once more, planar frames by chroma
+ * layout -- drba_to_inp_yuv_x4 / drba_to_inp16_yuv_x4 / drba_to_out_yuv / drba_to_out16_yuv / drba_to_inp_yuv_pad_x4 /
+ * drba_to_inp16_yuv_pad_x4 / drba_to_out_yuv_crop / drba_to_out16_yuv_crop (the eight planar conversions with a `layout` argument: 420,
+ * 422 or 444): additions only, the yuv420 entries keep their arguments and every value.  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
  * the splat entry points: drba_flow_reverse, drba_drm_rife_linear(_batch), drba_drm_rife_nonlinear(_batch), drba_softsplat and
  * drba_softsplat_index; while it is on, drba_rife_splat_ws_floats reports the larger workspace of the fixed-point accumulator):
  * additions only, nothing changes while the switch is off.  14: planar YCbCr 4:2:0 frames -- drba_to_inp_yuv420_x4 / drba_to_inp16_yuv420_x4 / drba_to_out_yuv420 /
@@ -324,6 +327,38 @@ int drba_to_out_yuv420_crop(const float *in, uint8_t *y, uint8_t *u, uint8_t *v,
                             int Hout, int Wout, int matrix, int full_range, void *stream);
 int drba_to_out16_yuv420_crop(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win,
                               int Hout, int Wout, int matrix, int full_range, float maxval, void *stream);
+/* ABI 16, planar frames by chroma layout: the eight planar conversions above with one more argument, `layout`, in front of maxval
+ * (16-bit entries) or of stream: 420 (the yuv420 entries themselves: same kernels, same values), 422 (u and v: [H][c_stride] samples,
+ * c_stride >= ceil(W/2)) or 444 (u and v: [H][c_stride], c_stride >= W); anything else is DRBA_EINVAL, as is every malformed argument
+ * of the yuv420 entries (a null plane, a stride below the plane width, a misaligned 16-bit plane, maxval outside (255, 65535]),
+ * before any launch.  Colour conversion, ranges, clamps, NaN -> 0, rounding and saturation are those of 4:2:0.
+ * Way in: along a subsampled axis the centre-sited tap pair of 4:2:0 (s = x / 2 - 0.25, clamped); along a full-resolution axis the
+ * sample itself.  4:2:2 interpolates horizontally only, 4:4:4 not at all.
+ * Way out: a 4:2:2 chroma sample is the mean of the two horizontal pixels of its pair (an odd last column repeats itself), a 4:4:4
+ * one is the pixel's own.  The pad / crop forms as for 4:2:0: the converted pixel of the clamped source coordinate on the way in,
+ * the window as it stands on the way out, the mean never reading the margin; they equal their resize siblings at an unchanged size
+ * bit for bit.
+ * The rows form under the rule of 4:2:0, the chroma rows aligned to the samples under 8 luma samples: 4 (4:2:2) or 8 (4:4:4). */
+int drba_to_inp_yuv_x4(const uint8_t *y, const uint8_t *u, const uint8_t *v, int y_stride, int c_stride, float *out, float *out_x4,
+                       int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range, int layout,
+                       void *stream);
+int drba_to_inp16_yuv_x4(const uint16_t *y, const uint16_t *u, const uint16_t *v, int y_stride, int c_stride, float *out,
+                         float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x, int matrix,
+                         int full_range, int layout, float maxval, void *stream);
+int drba_to_out_yuv(const float *in, uint8_t *y, uint8_t *u, uint8_t *v, int y_stride, int c_stride, int Hin, int Win, int Hout,
+                    int Wout, float scale_y, float scale_x, int matrix, int full_range, int layout, void *stream);
+int drba_to_out16_yuv(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win,
+                      int Hout, int Wout, float scale_y, float scale_x, int matrix, int full_range, int layout, float maxval,
+                      void *stream);
+int drba_to_inp_yuv_pad_x4(const uint8_t *y, const uint8_t *u, const uint8_t *v, int y_stride, int c_stride, float *out,
+                           float *out_x4, int Hin, int Win, int Hout, int Wout, int matrix, int full_range, int layout, void *stream);
+int drba_to_inp16_yuv_pad_x4(const uint16_t *y, const uint16_t *u, const uint16_t *v, int y_stride, int c_stride, float *out,
+                             float *out_x4, int Hin, int Win, int Hout, int Wout, int matrix, int full_range, int layout,
+                             float maxval, void *stream);
+int drba_to_out_yuv_crop(const float *in, uint8_t *y, uint8_t *u, uint8_t *v, int y_stride, int c_stride, int Hin, int Win,
+                         int Hout, int Wout, int matrix, int full_range, int layout, void *stream);
+int drba_to_out16_yuv_crop(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win,
+                           int Hout, int Wout, int matrix, int full_range, int layout, float maxval, void *stream);
 
 /* ---- scene-cut metric: tools.py:27-30 + pytorch_msssim/__init__.py:83-136 (ssim_matlab)
  * x1, x2: [1,3,32,32] thumbnails (already resized); out: 1 float on device. */
