@@ -188,6 +188,9 @@ static inline int tiles_for(int W, int H) { return ((W + kTileW - 1) / kTileW) *
 __device__ __forceinline__ void atomic_add_f32(float *p, float v) { unsafeAtomicAdd(p, v); }
 
 __device__ __forceinline__ float lrelu02(float v) { return v > 0.f ? v : 0.2f * v; }
+// ReLU as torch.relu defines it: +0 for every v <= 0 (-0.0 and -inf included), a NaN handed on.  fmaxf(v, 0.f) returns 0 for a
+// NaN (IEEE maxNum), so a layer would swallow it; every convolution epilogue takes this form.  The same bits as fmaxf for finite v.
+__device__ __forceinline__ float relu_nan(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
 
 // Lane exchanges inside a quad / a row of 16 as DPP operand modifiers of a VALU move (no LDS crossbar trip, no lgkmcnt wait):
 // __shfl_xor(v, 1 | 2 | 8) compiles to ds_bpermute_b32 -- the scale >= 2 stage-input gather issued 104 of them per lane for

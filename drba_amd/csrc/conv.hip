@@ -409,7 +409,7 @@ conv_mfma(const float *__restrict__ in, const float *__restrict__ wfrag, const f
   else switch (act) {
       case 1: finish([](float t) { return lrelu02(t); }); break;
       case 2: finish([post_slope](float t) { return t > 0.f ? t : post_slope * t; }); break;
-      case 3: finish([](float t) { return fmaxf(t, 0.f); }); break;
+      case 3: finish([](float t) { return relu_nan(t); }); break;
       case 4: finish([](float t) { return tanhf(t) * 10.f; }); break;
       default: finish([](float t) { return t; }); break;
     }

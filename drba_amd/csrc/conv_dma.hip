@@ -545,7 +545,7 @@ conv_dma1(const float *__restrict__ in, const u32x4 *__restrict__ wfrag, const f
       switch (act) {
         case 1: epilogue([](float v) { return lrelu02(v); }); break;
         case 2: epilogue([post_slope](float v) { return v > 0.f ? v : post_slope * v; }); break;
-        case 3: epilogue([](float v) { return fmaxf(v, 0.f); }); break;
+        case 3: epilogue([](float v) { return relu_nan(v); }); break;
         case 4: epilogue([](float v) { return tanhf(v) * 10.f; }); break;
         default: epilogue([](float v) { return v; }); break;
       }

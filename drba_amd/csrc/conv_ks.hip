@@ -324,7 +324,7 @@ conv_ks(const float *__restrict__ in, const u32x4 *__restrict__ wfrag, const flo
   switch (act) {
     case 1: finish([](float v) { return lrelu02(v); }); break;
     case 2: finish([post_slope](float v) { return v > 0.f ? v : post_slope * v; }); break;
-    case 3: finish([](float v) { return fmaxf(v, 0.f); }); break;
+    case 3: finish([](float v) { return relu_nan(v); }); break;
     case 4: finish([](float v) { return tanhf(v) * 10.f; }); break;
     default: finish([](float v) { return v; }); break;
   }

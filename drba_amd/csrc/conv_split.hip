@@ -441,7 +441,7 @@ conv_split_mfma(const float *__restrict__ in, const u32x4 *__restrict__ wfrag, c
       switch (act) {
         case 1: epilogue_ps([](float v) { return lrelu02(v); }); break;
         case 2: epilogue_ps([post_slope](float v) { return v > 0.f ? v : post_slope * v; }); break;
-        case 3: epilogue_ps([](float v) { return fmaxf(v, 0.f); }); break;
+        case 3: epilogue_ps([](float v) { return relu_nan(v); }); break;
         case 4: epilogue_ps([](float v) { return tanhf(v) * 10.f; }); break;
         default: epilogue_ps([](float v) { return v; }); break;
       }
@@ -570,12 +570,12 @@ conv_split_mfma(const float *__restrict__ in, const u32x4 *__restrict__ wfrag, c
           }
         };
         // activations 0-2 are one form, v > 0 ? v : slope * v with slope 1 / 0.2 / post_slope (exact: v * 1 == v); ReLU and
-        // tanh are their own instantiations.  ReLU as torch.relu and the other families' fmaxf(v, 0) define it: +0 for every
-        // v <= 0 (slope 0 would hand on -0.0, and NaN for -inf), a NaN kept.
+        // tanh are their own instantiations.  ReLU is relu_nan (common.hpp), as in every other store path and family: +0 for every
+        // v <= 0 (slope 0 would hand on -0.0, and NaN for -inf), a NaN kept -- fmaxf(v, 0) would return 0 for it.
         const float slope = act == 1 ? 0.2f : act == 2 ? post_slope : 1.f;
         auto with_act = [&](auto kind_) {
           if (act == 4) epilogue(kind_, [](float v) { return tanhf(v) * 10.f; });
-          else if (act == 3) epilogue(kind_, [](float v) { return v > 0.f ? v : (v != v ? v : 0.f); });
+          else if (act == 3) epilogue(kind_, [](float v) { return relu_nan(v); });
           else epilogue(kind_, [slope](float v) { return v > 0.f ? v : slope * v; });
         };
         if (beta) with_act(std::integral_constant<int, 3>{});
@@ -630,7 +630,7 @@ conv_split_mfma(const float *__restrict__ in, const u32x4 *__restrict__ wfrag, c
         switch (act) {
           case 1: epilogue([](float v) { return lrelu02(v); }); break;
           case 2: epilogue([post_slope](float v) { return v > 0.f ? v : post_slope * v; }); break;
-          case 3: epilogue([](float v) { return fmaxf(v, 0.f); }); break;
+          case 3: epilogue([](float v) { return relu_nan(v); }); break;
           case 4: epilogue([](float v) { return tanhf(v) * 10.f; }); break;
           default: epilogue([](float v) { return v; }); break;
         }

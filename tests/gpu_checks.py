@@ -140,23 +140,27 @@ def check_conv_layers(dev):
         # member refuses Cout = 40, the K-split member Cin = 32)
         dma = fam == 2 or (fam == 4 and lib.drba_conv3x3_packed_floats(32, 40, cfg) == 0 and lib.drba_conv3x3_packed_floats(32, 32, cfg) > 0)
         ks = fam == 3 or (fam == 4 and lib.drba_conv3x3_packed_floats(32, 32, cfg) == 0)
+        # ("res": the residual is a second device copy of the input; "res_same": it is the input tensor itself, which is what the
+        # launchers' "residual from LDS" instantiations are dispatched on)
         shapes = (((1, 32, 24, 11, 44, "conv"), (2, 32, 32, 9, 72, "res"), (1, 32, 32, 5, 132, "pre"), (2, 32, 32, 19, 36, "res"),
-                   (1, 32, 32, 8, 32, "conv")) if dma else
+                   (1, 32, 32, 8, 32, "conv"), (2, 32, 32, 9, 72, "res_same"), (2, 32, 32, 19, 36, "res_same")) if dma else
                   ((1, 64, 40, 11, 45, "conv"), (2, 96, 32, 9, 70, "res"), (1, 64, 16, 5, 130, "pre"), (2, 64, 64, 19, 36, "res"),
-                   (2, 192, 192, 17, 30, "res"), (1, 128, 128, 7, 33, "res")) if ks else
-                  ((1, 32, 40, 11, 45, "conv"), (2, 96, 32, 9, 70, "res"), (1, 64, 16, 5, 130, "pre"), (2, 64, 64, 19, 36, "res")))
+                   (2, 192, 192, 17, 30, "res"), (1, 128, 128, 7, 33, "res"), (2, 64, 64, 19, 36, "res_same"), (1, 128, 128, 7, 33, "res_same")) if ks else
+                  ((1, 32, 40, 11, 45, "conv"), (2, 96, 32, 9, 70, "res"), (1, 64, 16, 5, 130, "pre"), (2, 64, 64, 19, 36, "res"),
+                   (2, 64, 64, 19, 36, "res_same"), (2, 96, 32, 9, 72, "res_same")))
         for (nb, cin, cout, h, w, kind) in shapes:
             try:
                 x = torch.randn(nb, cin, h, w, generator=g) * 3.0
                 wt = torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5
                 b = torch.randn(cout, generator=g) * 0.1
                 xd, wd, bd = x.double(), wt.double(), b.double()
-                if kind == "res":
+                if kind in ("res", "res_same"):
                     wt = torch.randn(cin, cin, 3, 3, generator=g) / (cin * 9) ** 0.5
                     b = torch.randn(cin, generator=g) * 0.1
                     beta = torch.rand(1, cin, 1, 1, generator=g) + 0.5
                     ref = F.leaky_relu(F.conv2d(xd, wt.double(), b.double(), padding=1) * beta.double() + xd, 0.2)
-                    got = ops.Conv3x3(wt, b, 1, True, beta, device=dev, cfg=cfg)(x.to(dev), residual=x.to(dev))
+                    xg = x.to(dev)
+                    got = ops.Conv3x3(wt, b, 1, True, beta, device=dev, cfg=cfg)(xg, residual=xg if kind == "res_same" else x.to(dev))
                 elif kind == "pre":
                     ref = F.conv2d(F.prelu(xd, torch.tensor([0.25], dtype=torch.float64)), wd, bd, padding=1)
                     got = ops.Conv3x3(wt, b, 1, None, None, device=dev, cfg=cfg, pre_slope=0.25)(x.to(dev))

@@ -33,6 +33,10 @@ def main():
             import traceback
             traceback.print_exc()
             sections.append((title, [("EXC", float("inf"), 0.0, repr(e))]))
+    try:  # (the batch of 128 small maps: not one of CHECKS, which the CPU suite runs through its stand-in as well)
+        sections.append(("op conv epilogue forms, many items", op_checks.check_conv_many(hip.dev)))
+    except Exception as e:  # noqa: BLE001
+        sections.append(("op conv epilogue forms, many items", [("EXC", float("inf"), 0.0, repr(e))]))
     gold = np.load(os.path.join(GOLD, "rife.npz"))
     for scale, size in cases.RIFE_CONFIGS:
         try:

@@ -2,7 +2,8 @@
 splat_warp.hip and the layout kernels of ifnet_glue.hip and frame_io.hip), of the generic forward splat (splat_warp.hip:
 drba_softsplat, _index, _again, _gather_quad), of resize_bilinear_scale and flow_distance, and of the IFNet stage glue
 (ifnet_glue.hip, flow_terms.hpp, stage_conv.hip, stage_conv16.hip: stage-input gathers, the gathers fused with conv0[0], the
-flow update, the final warp + blend -- in the forms the pipeline runs them), shared by
+flow update, the final warp + blend -- in the forms the pipeline runs them), and of the 3x3 convolution's epilogue forms with
+every configuration id pinned (conv.hip, conv_split.hip, conv_dma.hip, conv_ks.hip; CONV_FORMS below), shared by
 tests/test_gpu_op_parity.py, tests/test_op_checks_cpu.py and the diagnostic report (python -m tests.gpu_report).
 
 Every check takes the device the inputs go to and the `ops` namespace under test (default: drba_amd.ops; the CPU test hands
@@ -32,6 +33,8 @@ the fp32 oracle's "error" against such a reference (1e-4 at 37 x 83, above 1 for
 that detects nothing.  A finite target beyond the int32 range contributes nothing (softsplat_ref), and flow_distance is +inf
 where the fp32 squares overflow (flow_distance_ref).
 Inputs regenerate from seeds (cases.rnd, synth._smooth_field)."""
+import collections
+
 import torch
 import torch.nn.functional as F
 
@@ -1339,6 +1342,420 @@ def check_warp_blend(dev, ops=None):
     return rows
 
 
+# ----------------------------------------------------------------------------------------- conv epilogue forms
+# Every configuration id of drba_conv3x3 carries its own copy of the epilogue (conv.hip, conv_split.hip, conv_dma.hip, conv_ks.hip):
+# bias, y * beta + x or + residual (+ residual2), five activations, the PReLU pre-activation of the loader, vector and element-wise
+# stores, and in three files an "RL" instantiation that rebuilds the residual from the input window when residual == in.  Each form
+# a model constructs is run here with every id pinned (cfg=), against F.conv2d in float64 and the epilogue formula of
+# include/drba_hip.h:432-438 written out.  Nothing is tuned or timed.
+ConvForm = collections.namedtuple("ConvForm", "name layer bias act post_slope pre_slope cout res beta")
+CONV_FORMS = (  # res: None, "in" (the input tensor itself), "other", "other2" (two other tensors), "same" / "copy" (ResConv, see below)
+    ConvForm("plain", "ResidualBlock.c1/c2, trident (gmflow.py)", False, None, 0.0, None, None, None, False),
+    ConvForm("bias+relu", "up0 (gmflow.py)", True, "relu", 0.0, None, None, None, False),
+    ConvForm("bias+prelu(0.1)", "tail_a (FusionNet.py)", True, "prelu", 0.1, None, None, None, False),
+    ConvForm("pre+tanh10 Cout=2", "conv_out (MetricNet.py)", True, "tanh10", 0.0, 0.25, 2, None, False),
+    ConvForm("Cout=3", "tail_last (FusionNet.py)", True, None, 0.0, None, 3, None, False),
+    ConvForm("bias+lrelu", "conv (IFNet_HDv3.py), as check_conv_layers", True, True, 0.0, None, None, None, False),
+    ConvForm("pre", "FeatureNet / FusionNet convs, as check_conv_layers", True, None, 0.0, 0.25, None, None, False),
+    ConvForm("pre+res=in", "mid[k] (MetricNet.py): residual=feat, the input itself, no beta", True, None, 0.0, 0.25, None, "in", False),
+    ConvForm("pre+res+res2", "_TwoConv.second (FusionNet.py)", True, None, 0.0, 0.25, None, "other2", False),
+    ConvForm("res", "one other-tensor residual", True, None, 0.0, None, None, "other", False),
+    ConvForm("resconv res is in", "ResConv (IFNet_HDv3.py): residual= the same tensor object as the input", True, True, 0.0, None, None, "same", True),
+    ConvForm("resconv res copy", "ResConv with a second copy of the input, as check_conv_layers", True, True, 0.0, None, None, "copy", True))
+CONV_PLAIN_FORMS = tuple(f.name for f in CONV_FORMS if f.res is None)     # what a stride-2 id takes
+CONV_RESIDUAL_FORMS = tuple(f.name for f in CONV_FORMS if f.res is not None)
+CONV_MAPS = ((2, 11, 44), (1, 9, 45))  # (N, H, W): W % 4 == 0 with partial tiles on both axes; W % 4 != 0 (element-wise stores).  Guarded.
+CONV_TINY = ((1, 1, 1), (1, 2, 5), (1, 3, 4), (1, 1, 4))  # maps inside one halo; the last two for the members that need W % 4 == 0
+# (Cin, Cout) per what an id accepts.  40 = 2 * 16 + 8: the second 8-cout half of the last tile is masked out entirely (coA + 8 < Cout)
+CONV_PAIRS = {"dma": ((32, 32), (32, 24)), "ks": ((64, 64), (64, 40)), "split": ((64, 64), (64, 40)), "fp32": ((39, 39), (7, 40)),
+              "s2": ((39, 40), (7, 24))}
+CONV_GUARD = 4096
+CONV_SENTINEL = 1.2345e-3
+CONV_REFUSED = []  # (cfg, what) of the documented refusals met by the last checks run: for the report
+_CONV_REFS = {}    # case key -> the inputs, fp64 / fp32 references and tolerance terms: once per process, never written to
+_CONV_DEV = {}     # (case key, device) -> the inputs on the device
+
+
+def conv_lib():
+    """the library's host-side table functions (family, stride, packed size per id): they need no device"""
+    from drba_amd import _lib
+    return _lib.load()
+
+
+def conv_id_class(lib, cfg):
+    """which layers an id accepts, asked of the library as check_conv_layers does: "s2" (a stride-2 tile), "fp32" (family 0), "dma"
+    (family 2 and its family-4 member: Cin = 32, Cout <= 32), "ks" (family 3 and its member: Cin = 64 .. 192), "split" (the rest)"""
+    fam = lib.drba_conv3x3_cfg_family(cfg)
+    pf = lambda ci, co: lib.drba_conv3x3_packed_floats(ci, co, cfg)  # noqa: E731
+    if lib.drba_conv3x3_cfg_stride(cfg) == 2:
+        return "s2"
+    if fam == 0:
+        return "fp32"
+    if fam == 2 or (fam == 4 and pf(32, 40) == 0 and pf(32, 32) > 0):
+        return "dma"
+    if fam == 3 or (fam == 4 and pf(32, 32) == 0):
+        return "ks"
+    return "split"
+
+
+def conv_form_pairs(form, cls):
+    pairs = CONV_PAIRS[cls]
+    if form.cout is not None:
+        return ((pairs[0][0], form.cout),)
+    if form.res in ("in", "same", "copy"):  # the residual is the input: Cin == Cout
+        return tuple(p for p in pairs if p[0] == p[1])[:1]
+    return pairs
+
+
+def conv_form_ref(form, x, wt, b, beta, res, res2, stride, dtype):
+    """include/drba_hip.h:432-438 in `dtype`: PReLU(pre_slope) on the input, the convolution, y = acc + bias, then y * beta[c] +
+    residual or y + residual (+ residual2), then the activation.  -> (output, y before the activation)"""
+    c = lambda t: None if t is None else t.to(dtype)  # noqa: E731
+    xin = c(x)
+    if form.pre_slope is not None:
+        xin = torch.where(xin > 0, xin, xin * form.pre_slope)
+    y = F.conv2d(xin, c(wt), c(b), stride=stride, padding=1)
+    r = c(x) if form.res in ("in", "same", "copy") else c(res)  # (the residual is the input as it is, not its pre-activation)
+    if beta is not None:
+        y = y * c(beta).view(1, -1, 1, 1) + r
+    else:
+        if r is not None:
+            y = y + r
+        if res2 is not None:
+            y = y + c(res2)
+    if form.act in (True, "lrelu"):
+        out = torch.where(y > 0, y, y * 0.2)
+    elif form.act == "prelu":
+        out = torch.where(y > 0, y, y * form.post_slope)
+    elif form.act == "relu":
+        out = torch.relu(y)
+    elif form.act == "tanh10":
+        out = torch.tanh(y) * 10.0
+    else:
+        out = y
+    return out, y
+
+
+def _finite_max(t):
+    fin = t[torch.isfinite(t)]
+    return float(fin.abs().max()) if fin.numel() else 0.0
+
+
+def conv_case(form, cin, cout, stride, n, h, w, plant=False):
+    """The inputs of one (form, channel pair, map) and their references, built at the first use and shared by every id.  The layer's
+    weights depend on (form, cin, cout) only.  plant: one NaN in the input and -inf as the bias of one output channel; plant="input":
+    the -inf is a second element of the input instead (its footprint's sums are -inf or +inf by the sign of the weight)."""
+    key = (form.name, cin, cout, stride, n, h, w, plant)
+    if key not in _CONV_REFS:
+        k = CONV_FORMS.index(form)
+        ws = 5000 + 97 * k + 13 * cin + cout                                  # the layer
+        xs = 7000 + 97 * k + 13 * cin + cout + 1009 * h + 31 * w + n + stride  # its input on this map
+        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+        # tanh * 10: inputs of unit scale, so that the outputs are not all saturated (asserted below)
+        x = cases.rnd((n, cin, h, w), xs, 1.0 if form.act == "tanh10" else 2.0)
+        wt = cases.rnd((cout, cin, 3, 3), ws, 1.0 / (cin * 9) ** 0.5)
+        b = cases.rnd((cout,), ws + 1, 0.1) if form.bias else None
+        beta = torch.rand(cout, generator=torch.Generator().manual_seed(ws + 2)) + 0.5 if form.beta else None
+        res = cases.rnd((n, cout, ho, wo), xs + 1, 1.0) if form.res in ("other", "other2") else None
+        res2 = cases.rnd((n, cout, ho, wo), xs + 2, 1.0) if form.res == "other2" else None
+        if plant:
+            x[0, min(1, cin - 1), h // 2, w // 3] = float("nan")
+            if plant == "input":
+                x[n - 1, 0, h - 1, w - 2] = float("-inf")
+            else:
+                b = b.clone()
+                b[min(5, cout - 1)] = float("-inf")
+        ref64, y64 = conv_form_ref(form, x, wt, b, beta, res, res2, stride, torch.float64)
+        ref32, y32 = conv_form_ref(form, x, wt, b, beta, res, res2, stride, torch.float32)
+        if form.act == "tanh10":  # the bar is set on y and multiplied by 10 (|tanh'| <= 1): a quarter of the |y| at least below 1
+            assert float((y64.abs() < 1.0).double().mean()) >= 0.25, key
+            a64, a32 = y64, y32
+        else:
+            a64, a32 = ref64, ref32
+        if plant:
+            assert bool(ref64.isnan().any()) and bool((y64 == float("-inf")).any()) and bool(torch.isfinite(ref64).any()), key
+            assert plant != "input" or bool((ref64 == float("inf")).any()), key
+        _CONV_REFS[key] = dict(x=x, wt=wt, b=b, beta=beta, res=res, res2=res2, ref64=ref64, refmax=_finite_max(a64), floor=_err(a32, a64),
+                               out_shape=(n, cout, ho, wo))
+    return _CONV_REFS[key]
+
+
+def conv_tol(fam, form, case):
+    """(tol, floor to carry in the row).  Families 1-4: 5e-6 max(1, |ref|max), the bar of check_conv_layers.  Family 0: rule_tol with
+    the floor of the fp32 F.conv2d form of the same layer.  tanh * 10: the bar of y, times 10."""
+    tol = rule_tol(case["refmax"], case["floor"]) if fam == 0 else 5e-6 * max(1.0, case["refmax"])
+    if form.act == "tanh10":
+        return 10.0 * tol, None
+    return tol, (case["floor"] if fam == 0 else None)
+
+
+def _conv_dev(key, case, dev):
+    if (key, str(dev)) not in _CONV_DEV:
+        _CONV_DEV[(key, str(dev))] = {k: None if case[k] is None else case[k].to(dev) for k in ("x", "res", "res2")}
+    return _CONV_DEV[(key, str(dev))]
+
+
+def conv_guarded(shape, dev):
+    """-> (the allocation, `out`): `out` is a view of `shape`, prefilled with NaN, in the middle of one allocation that holds
+    CONV_GUARD sentinel floats in front of it and behind it (the layout of test_softsplat_workspace_guard)"""
+    numel = 1
+    for s in shape:
+        numel *= s
+    buf = torch.full((numel + 2 * CONV_GUARD,), CONV_SENTINEL, device=dev)
+    buf[CONV_GUARD:CONV_GUARD + numel] = float("nan")
+    return buf, buf[CONV_GUARD:CONV_GUARD + numel].view(shape)
+
+
+def guard_row(op, name, buf, extra=""):
+    numel = buf.numel() - 2 * CONV_GUARD
+    return exact_row(op, f"{name}: the {CONV_GUARD} floats in front of and behind out", torch.cat([buf[:CONV_GUARD], buf[CONV_GUARD + numel:]]),
+                     torch.full((2 * CONV_GUARD,), CONV_SENTINEL), extra)
+
+
+def _refused(e):
+    return type(e).__name__ == "DrbaHipError" and "(-2)" in str(e)  # DRBA_EUNSUPPORTED through _lib.check
+
+
+def _tag(row, cfg, form, kind):
+    row.cfg, row.form, row.kind = cfg, form, kind
+    return row
+
+
+def _conv_form_rows(rows, layers, ops, dev, lib, cfg, form, cin, cout, n, h, w, guard, plant=False):
+    """the launch of one (id, form, channel pair, map): its value row, its guard row, or a failing row for anything but the one
+    documented refusal (include/drba_hip.h: family 2 and its family-4 member need W % 4 == 0)"""
+    op = "conv_forms"
+    fam, stride, cls = lib.drba_conv3x3_cfg_family(cfg), lib.drba_conv3x3_cfg_stride(cfg), conv_id_class(lib, cfg)
+    planted = " NaN, -inf in the input" if plant == "input" else " NaN, -inf" if plant else ""
+    name = f"cfg{cfg} fam{fam} {form.name}{planted} [{n}x{cin}->{cout} {h}x{w} s{stride}]"
+    try:
+        case = conv_case(form, cin, cout, stride, n, h, w, plant)
+        key = (form.name, cin, cout, stride, n, h, w, plant)
+        d = _conv_dev(key, case, dev)
+        if (form.name, cin, cout, cfg) not in layers:  # one layer per (form, channel pair, id): packed once, run on every map
+            layers[(form.name, cin, cout, cfg)] = ops.Conv3x3(case["wt"], case["b"], stride, form.act, case["beta"], device=dev, cfg=cfg,
+                                                              pre_slope=form.pre_slope, post_slope=form.post_slope)
+        layer = layers[(form.name, cin, cout, cfg)]
+        buf, out = conv_guarded(case["out_shape"], dev) if guard else (None, None)
+        residual = d["x"] if form.res in ("in", "same") else d["x"].clone() if form.res == "copy" else d["res"]
+        try:
+            got = layer(d["x"], residual=residual, out=out, residual2=d["res2"])
+        except Exception as e:  # noqa: BLE001
+            if _refused(e) and cls == "dma" and w % 4 != 0:
+                CONV_REFUSED.append((cfg, f"{n}x{h}x{w}"))
+                return
+            raise
+        tol, floor = conv_tol(fam, form, case)
+        if plant:
+            assert floor is None or floor < float("inf"), name  # the fp32 form keeps the non-finite values where the reference has them
+        extra = f"|ref|max={case['refmax']:.3g}" + ("" if fam else f" fp32_floor={case['floor']:.2e}")
+        rows.append(_tag(Row(op, name, _err(got, case["ref64"]), tol, extra, floor, case["refmax"]), cfg, form.name, "nonfinite" if plant else "value"))
+        if guard:
+            rows.append(_tag(guard_row(op, name, buf), cfg, form.name, "guard"))
+    except Exception as e:  # noqa: BLE001
+        rows.append(_tag(Row(op, name, float("inf"), 0.0, f"EXC {type(e).__name__}: {e}"), cfg, form.name, "error"))
+
+
+def check_conv_forms(dev, ops=None, cfgs=None, forms=None):
+    """Every id (or `cfgs`) x every form (or the named `forms`) that applies to its stride x the channel pairs it accepts x CONV_MAPS
+    (with out= guarded by sentinels) and, for the first pair, CONV_TINY."""
+    ops = ops or default_ops()
+    lib = conv_lib()
+    rows, layers = [], {}
+    del CONV_REFUSED[:]
+    for cfg in range(lib.drba_conv3x3_num_cfgs()) if cfgs is None else cfgs:
+        cls = conv_id_class(lib, cfg)
+        for form in CONV_FORMS:
+            if (forms is not None and form.name not in forms) or (cls == "s2" and form.res is not None):
+                continue
+            for k, (cin, cout) in enumerate(conv_form_pairs(form, cls)):
+                if lib.drba_conv3x3_packed_floats(cin, cout, cfg) == 0:
+                    continue
+                for (n, h, w) in CONV_MAPS + (CONV_TINY if k == 0 else ()):
+                    _conv_form_rows(rows, layers, ops, dev, lib, cfg, form, cin, cout, n, h, w, guard=(n, h, w) in CONV_MAPS)
+    return rows
+
+
+def conv_forms_missing(rows, lib, cfgs, forms=None):
+    """(cfg, form) pairs that apply and have no accepted launch among `rows`: the completeness rule of the GPU tests"""
+    have = {(r.cfg, r.form) for r in rows if getattr(r, "kind", None) == "value"}
+    want = [(c, f.name) for c in cfgs for f in CONV_FORMS
+            if (forms is None or f.name in forms) and not (conv_id_class(lib, c) == "s2" and f.res is not None)]
+    return [p for p in want if p not in have]
+
+
+def check_conv_relu_nonfinite(dev, ops=None, cfgs=None):
+    """ReLU on a non-finite sum, per id and store path (W % 4 == 0 and != 0): torch.relu keeps a NaN and answers +0 for -inf.  The
+    NaN is planted in the input (the sums of its 3 x 3 footprint are NaN in every output channel); the -inf is the bias of one
+    output channel, so that the sum itself is -inf in every family -- a -inf activation is not representable in the split-operand
+    loaders of families 1 - 4 (x - bf16(x) is NaN), which is the loader's matter and not the epilogue's.  Family 0 reads fp32
+    operands as they are: its ids also take the row with both the NaN and the -inf in the input."""
+    ops = ops or default_ops()
+    lib = conv_lib()
+    rows = []
+    form = CONV_FORMS[1]
+    assert form.act == "relu"
+    for cfg in range(lib.drba_conv3x3_num_cfgs()) if cfgs is None else cfgs:
+        cin, cout = conv_form_pairs(form, conv_id_class(lib, cfg))[0]
+        if lib.drba_conv3x3_packed_floats(cin, cout, cfg) == 0:
+            continue
+        for (n, h, w) in CONV_MAPS:
+            _conv_form_rows(rows, {}, ops, dev, lib, cfg, form, cin, cout, n, h, w, guard=False, plant=True)
+            if lib.drba_conv3x3_cfg_family(cfg) == 0:
+                _conv_form_rows(rows, {}, ops, dev, lib, cfg, form, cin, cout, n, h, w, guard=False, plant="input")
+    # The family-4 kernels report every NaN they store into the device's sticky status word (ops.check_overflow raises on it at a
+    # model's next step).  The NaN stored here is the one these rows ask for: the report is taken back once the kernels are done.
+    clear = getattr(ops, "overflow_groups", None)
+    if clear is not None:
+        if torch.device(dev).type == "cuda":
+            torch.cuda.synchronize(dev)
+        clear(dev)
+    return rows
+
+
+DECONV_GUARD_CASES = ((1, 32, 52, 11, 45, True), (2, 32, 40, 9, 44, False))  # (N, Cin, Cout, H, W, pixel_shuffle)
+
+
+def check_deconv_guard(dev, ops=None):
+    """Deconv4x4 of every id, one map per pixel_shuffle value, into a guarded out=: the fp64 value row and the sentinels"""
+    ops = ops or default_ops()
+    lib = conv_lib()
+    op, rows = "conv_forms", []
+    for i, (n, cin, cout, h, w, ps) in enumerate(DECONV_GUARD_CASES):
+        x = cases.rnd((n, cin, h, w), 9000 + i, 2.0)
+        wt = cases.rnd((cin, cout, 4, 4), 9010 + i, 1.0 / (cin * 4) ** 0.5)
+        b = cases.rnd((cout,), 9020 + i, 0.1)
+        sh = lambda t: F.pixel_shuffle(t, 2) if ps else t  # noqa: E731
+        ref64 = sh(F.conv_transpose2d(x.double(), wt.double(), b.double(), stride=2, padding=1))
+        ref32 = sh(F.conv_transpose2d(x, wt, b, stride=2, padding=1))
+        refmax, floor = _finite_max(ref64), _err(ref32, ref64)
+        xd = x.to(dev)
+        for cfg in range(lib.drba_deconv4x4_num_cfgs()):
+            fam = lib.drba_deconv4x4_cfg_family(cfg)
+            name = f"deconv cfg{cfg} fam{fam} [{n}x{cin}->{cout} {h}x{w} ps={int(ps)}]"
+            if lib.drba_deconv4x4_packed_floats(cin, cout, cfg) == 0:
+                continue
+            try:
+                buf, out = conv_guarded(tuple(ref64.shape), dev)
+                got = ops.Deconv4x4(wt, b, ps, device=dev, cfg=cfg)(xd, out=out)
+                tol = rule_tol(refmax, floor) if fam == 0 else 5e-6 * max(1.0, refmax)
+                rows.append(_tag(Row(op, name, _err(got, ref64), tol, f"|ref|max={refmax:.3g}", floor if fam == 0 else None, refmax), cfg, "deconv", "value"))
+                rows.append(_tag(guard_row(op, name, buf), cfg, "deconv", "guard"))
+            except Exception as e:  # noqa: BLE001
+                rows.append(_tag(Row(op, name, float("inf"), 0.0, f"EXC {type(e).__name__}: {e}"), cfg, "deconv", "error"))
+    return rows
+
+
+SHUFFLE_GUARD_CASES = ((2, 32, 72, 9, 68), (1, 64, 64, 11, 44))  # (N, Cin, Cout, H, W): W % 4 == 0, Cout % 4 == 0, ragged tiles
+
+
+def shuffle_launch(ops, layer, xd, out, cfg):
+    """drba_conv3x3_shuffle of `layer` with a pinned id storing to `out`, as check_conv_layers issues it; -> its return code
+    (a stand-in namespace brings its own conv3x3_shuffle_launch)"""
+    own = getattr(ops, "conv3x3_shuffle_launch", None)
+    if own is not None:
+        return own(layer, xd, out, cfg)
+    import ctypes as C
+    n, cin, h, w = xd.shape
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    return ops._lib.load().drba_conv3x3_shuffle(p(xd), p(layer._pack(cfg)), p(layer.bias), p(out), n, cin, h, w, layer.cout, layer.act,
+                                               layer.post_slope, cfg, ops._stream())
+
+
+def check_shuffle_guard(dev, ops=None):
+    """conv3x3 + PixelShuffle(2) in the store with act="prelu" (the existing shuffle rows use act 0 and 1 only): every family-4
+    stride-1 id that has the store form, pinned, into a guarded out; then the ops-level helper.  An id without the store form answers
+    DRBA_EUNSUPPORTED (include/drba_hip.h, drba_conv3x3_shuffle); any other code is a failing row."""
+    ops = ops or default_ops()
+    lib = conv_lib()
+    op, rows = "conv_forms", []
+    for i, (n, cin, cout, h, w) in enumerate(SHUFFLE_GUARD_CASES):
+        x = cases.rnd((n, cin, h, w), 9100 + i, 2.0)
+        wt = cases.rnd((cout, cin, 3, 3), 9110 + i, 1.0 / (cin * 9) ** 0.5)
+        b = cases.rnd((cout,), 9120 + i, 0.1)
+        y = F.conv2d(x.double(), wt.double(), b.double(), padding=1)
+        ref64 = F.pixel_shuffle(torch.where(y > 0, y, y * 0.1), 2)
+        refmax = _finite_max(ref64)
+        tol = 5e-6 * max(1.0, refmax)  # family 4's bar
+        layer = ops.Conv3x3(wt, b, 1, "prelu", None, device=dev, post_slope=0.1)
+        xd = x.to(dev)
+        accepted = 0
+        for cfg in range(lib.drba_conv3x3_num_cfgs()):
+            if lib.drba_conv3x3_cfg_family(cfg) != 4 or lib.drba_conv3x3_cfg_stride(cfg) != 1 or lib.drba_conv3x3_packed_floats(cin, cout, cfg) == 0:
+                continue
+            name = f"conv+shuffle prelu cfg{cfg} [{n}x{cin}->{cout} {h}x{w}]"
+            try:
+                buf, out = conv_guarded((n, cout // 4, 2 * h, 2 * w), dev)
+                rc = shuffle_launch(ops, layer, xd, out, cfg)
+                if rc == -2:
+                    continue  # (DRBA_EUNSUPPORTED: the tile has no shuffle store form)
+                if rc != 0:
+                    raise RuntimeError(f"drba_conv3x3_shuffle returned {rc}")
+                accepted += 1
+                rows.append(_tag(Row(op, name, _err(out, ref64), tol, f"|ref|max={refmax:.3g}", None, refmax), cfg, "shuffle", "value"))
+                rows.append(_tag(guard_row(op, name, buf), cfg, "shuffle", "guard"))
+            except Exception as e:  # noqa: BLE001
+                rows.append(_tag(Row(op, name, float("inf"), 0.0, f"EXC {type(e).__name__}: {e}"), cfg, "shuffle", "error"))
+        rows.append(Row(op, f"conv+shuffle prelu [{n}x{cin}->{cout} {h}x{w}]: configurations that accept", 0.0 if accepted >= 2 else float("inf"), 1.0,
+                        f"{accepted} ids"))
+        rows.append(Row(op, f"ops.conv3x3_shuffle prelu [{n}x{cin}->{cout} {h}x{w}]", _err(ops.conv3x3_shuffle(layer, xd), ref64), tol,
+                        f"|ref|max={refmax:.3g}", None, refmax))
+    return rows
+
+
+def check_conv_forms_all(dev, ops=None):
+    """the family as the report prints it: forms x ids, ReLU on non-finite sums, the transposed convolution's and the shuffle store's guards"""
+    return check_conv_forms(dev, ops) + check_conv_relu_nonfinite(dev, ops) + check_deconv_guard(dev, ops) + check_shuffle_guard(dev, ops)
+
+
+# The persistent loops of conv_split.hip and conv_dma.hip (a workgroup takes tile after tile) in the two forms the 1080p rows of
+# tests/test_gpu_fullsize.py do not cover: a batch of small maps, 32 -> 32, every stride-1 id that accepts the layer.
+MANY_N = 128
+MANY_MAP = (37, 76)
+MANY_FORMS = ("resconv res is in", "pre+res+res2")
+_MANY_DEV = {}
+
+
+def conv_many_layer(ops, dev, form, cfg, n=MANY_N):
+    """(layer, case) of a many-item row"""
+    case = conv_case(form, 32, 32, 1, n, MANY_MAP[0], MANY_MAP[1])
+    return ops.Conv3x3(case["wt"], case["b"], 1, form.act, case["beta"], device=dev, cfg=cfg, pre_slope=form.pre_slope, post_slope=form.post_slope), case
+
+
+def conv_many_inputs(dev, form, n=MANY_N):
+    """the case's inputs and its fp64 reference on the device (the error of 11.5 M elements is taken where they live)"""
+    key = (form.name, n, str(dev))
+    if key not in _MANY_DEV:
+        case = conv_case(form, 32, 32, 1, n, MANY_MAP[0], MANY_MAP[1])
+        _MANY_DEV[key] = {k: None if case[k] is None else case[k].to(dev) for k in ("x", "res", "res2", "ref64")}
+    return _MANY_DEV[key]
+
+
+def conv_many_ids(lib):
+    return [c for c in range(lib.drba_conv3x3_num_cfgs()) if lib.drba_conv3x3_cfg_stride(c) == 1 and lib.drba_conv3x3_packed_floats(32, 32, c) > 0]
+
+
+def check_conv_many(dev, ops=None, n=MANY_N, cfgs=None):
+    ops = ops or default_ops()
+    lib = conv_lib()
+    op, rows = "conv_forms", []
+    for form in (f for f in CONV_FORMS if f.name in MANY_FORMS):
+        for cfg in conv_many_ids(lib) if cfgs is None else cfgs:
+            fam = lib.drba_conv3x3_cfg_family(cfg)
+            name = f"cfg{cfg} fam{fam} {form.name} [{n}x32->32 {MANY_MAP[0]}x{MANY_MAP[1]}]"
+            try:
+                layer, case = conv_many_layer(ops, dev, form, cfg, n)
+                d = conv_many_inputs(dev, form, n)
+                got = layer(d["x"], residual=d["x"] if form.res == "same" else d["res"], residual2=d["res2"])
+                diff = (got.double() - d["ref64"]).abs().max()  # (all of the reference is finite: a NaN in `got` makes this NaN, a failing row)
+                err = float(diff) if bool(torch.isfinite(diff)) else float("inf")
+                tol, floor = conv_tol(fam, form, case)
+                rows.append(_tag(Row(op, name, err, tol, f"|ref|max={case['refmax']:.3g}", floor, case["refmax"]), cfg, form.name, "value"))
+            except Exception as e:  # noqa: BLE001
+                rows.append(_tag(Row(op, name, float("inf"), 0.0, f"EXC {type(e).__name__}: {e}"), cfg, form.name, "error"))
+    return rows
+
+
 SPLAT_CHECKS = (check_softsplat, check_softsplat_scan, check_softsplat_big)  # the generic splat's families, for tests that take them together
 CHECKS = (  # (section title, check): one operator family each
     ("op softmax_rows_", check_softmax_rows), ("op instance_norm", check_instance_norm), ("op conv_direct", check_conv_direct),
@@ -1349,5 +1766,6 @@ CHECKS = (  # (section title, check): one operator family each
     ("op metric_input", check_metric_input), ("op softsplat", check_softsplat), ("op softsplat scan geometry", check_softsplat_scan),
     ("op softsplat big map", check_softsplat_big), ("op resize_bilinear_scale", check_resize_scale), ("op flow_distance", check_flow_distance),
     ("op stage input, first stage", check_stage_input_first), ("op stage input, warped", check_stage_input_warped),
-    ("op stage input + conv0[0] fused", check_stage_conv_fused), ("op flow update", check_flow_update), ("op warp + blend", check_warp_blend))
+    ("op stage input + conv0[0] fused", check_stage_conv_fused), ("op flow update", check_flow_update), ("op warp + blend", check_warp_blend),
+    ("op conv epilogue forms", check_conv_forms_all))
 GLUE_CHECKS = (check_stage_input_first, check_stage_input_warped, check_stage_conv_fused, check_flow_update, check_warp_blend)

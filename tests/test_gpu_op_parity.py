@@ -3,7 +3,8 @@
 fused with conv0[0], flow update, final warp + blend: [H,W,4] frames, pair-only features, the flow as terms, the blend at the
 frame's own resolution) on their own against a float64 reference (tests/op_checks.py), at the sizes where kernels go wrong:
 image borders, partial tiles and blocks, every dispatch branch, batch > 1, grid-stride loops and scan rounds that go round
-twice.  One operator family per test, so that a failure names it.
+twice.  One operator family per test, so that a failure names it.  The 3x3 convolution's epilogue forms (op_checks.CONV_FORMS: what
+the GMFlow / GMFSS layers construct) run with every configuration id pinned, one test per kernel family and form group.
 
 Value rows: tol = max(2e-5 max(1, |ref|max), 3 x the fp32 oracle's own error on that input); decisions and data movement:
 bit-exact.  tests/test_op_checks_cpu.py shows on the CPU that these rows fail for a wrong operator."""
@@ -314,6 +315,118 @@ def test_softsplat_reuse_index_launches_one_gather(hip_backend):
     assert any("splat_sort_count" in n for n in names) and any("splat_sort_fill" in n for n in names), names
     rows.append(op_checks.value_row("softsplat", op_checks.REUSE_ROW + ", flow updated in place: rebuilt", got,
                                     *op_checks.splat_refs(op_checks.REUSE_ROW, xs[2], flow, metric, "soft")))
+    _assert_rows(rows)
+
+
+# ----------------------------------------------------------------------------------------- the convolution epilogue forms
+def _conv_ids(family):
+    lib = op_checks.conv_lib()
+    return lib, [c for c in range(lib.drba_conv3x3_num_cfgs()) if lib.drba_conv3x3_cfg_family(c) == family]
+
+
+@pytest.mark.parametrize("group", ("plain", "residual"))
+@pytest.mark.parametrize("family", (0, 1, 2, 3, 4))
+def test_conv_forms(hip_backend, family, group):
+    """Every id of the family, pinned, in every form of the group that applies to its stride (op_checks.CONV_FORMS), on the two
+    guarded maps and the tiny ones: value rows against fp64, sentinel rows around out=.  Completeness: every (id, form) that applies
+    has an accepted launch; the only refusals are the documented ones (W % 4 != 0 on the LDS-DMA members)."""
+    lib, ids = _conv_ids(family)
+    forms = op_checks.CONV_PLAIN_FORMS if group == "plain" else op_checks.CONV_RESIDUAL_FORMS
+    rows = op_checks.check_conv_forms(hip_backend.dev, cfgs=ids, forms=forms)
+    torch.cuda.synchronize()
+    print(f"  refused (documented): {sorted(set(op_checks.CONV_REFUSED))}")
+    assert all(op_checks.conv_id_class(lib, c) == "dma" and int(what.split("x")[2]) % 4 for c, what in op_checks.CONV_REFUSED)
+    missing = op_checks.conv_forms_missing(rows, lib, ids, forms)
+    assert not missing, f"no accepted row for (id, form): {missing}"
+    _assert_rows(rows)
+
+
+def test_conv_forms_cover_every_id():
+    """the five families of test_conv_forms are all 38 ids, the two groups all 12 forms"""
+    assert sorted(c for f in range(5) for c in _conv_ids(f)[1]) == list(range(38))
+    assert set(op_checks.CONV_PLAIN_FORMS) | set(op_checks.CONV_RESIDUAL_FORMS) == {f.name for f in op_checks.CONV_FORMS}
+    assert len(op_checks.CONV_FORMS) == 12
+
+
+def test_conv_relu_on_a_non_finite_sum(hip_backend):
+    """bias + ReLU with a NaN in the input and -inf as one channel's bias, every id, both store paths: the NaN stays, -inf gives +0"""
+    rows = op_checks.check_conv_relu_nonfinite(hip_backend.dev)
+    assert {r.cfg for r in rows if r.kind == "nonfinite"} == set(range(38))
+    _assert_rows(rows)
+
+
+def test_deconv_and_shuffle_store_guards(hip_backend):
+    """Deconv4x4 (all 15 ids, with and without PixelShuffle) and conv3x3 + PixelShuffle with act="prelu" into guarded outputs"""
+    rows = op_checks.check_deconv_guard(hip_backend.dev)
+    for ps in (0, 1):
+        assert {r.cfg for r in rows if r.kind == "guard" and f"ps={ps}" in r[0]} == set(range(15))
+    _assert_rows(rows + op_checks.check_shuffle_guard(hip_backend.dev))
+
+
+def _traced_recs(fn):
+    from drba_amd import ops
+    torch.cuda.synchronize()
+    ops.trace_begin()
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        recs = ops.trace_end()
+    return recs
+
+
+RL_KERNELS = {  # kernel -> its name with the RL template argument true, as the trace records it
+    "conv_split_mfma": r"conv_split_mfma<.*SplitCfg<[^>]*>, ?(true|false), ?true",
+    "conv_dma1": r"conv_dma1<(true|false), ?true",
+    "conv_ks": r"conv_ks<\d+, ?(true|false), ?true"}
+
+
+def test_same_tensor_resconv_rows_run_rl_kernels(hip_backend):
+    """The ResConv rows whose residual IS the input tensor launch the "residual from LDS" instantiation of conv_split_mfma, conv_dma1
+    and conv_ks at least once each; the rows with a second copy of the input launch none.  Read from the kernel names and template
+    arguments of the trace: a change of the launchers' res == in rule that un-covers RL fails here."""
+    import re
+    lib = op_checks.conv_lib()
+    ids = [c for c in range(lib.drba_conv3x3_num_cfgs()) if op_checks.conv_id_class(lib, c) in ("split", "dma", "ks")]
+    names, rows = {}, []
+    for form in ("resconv res is in", "resconv res copy"):
+        recs = _traced_recs(lambda: rows.extend(op_checks.check_conv_forms(hip_backend.dev, cfgs=ids, forms=(form,))))
+        names[form] = sorted({r["name"] for r in recs if "conv_" in r["name"]})
+        print(f"  {form}:\n    " + "\n    ".join(names[form]))
+    for kernel, rl in RL_KERNELS.items():
+        assert any(kernel in n for n in names["resconv res copy"]), (kernel, names["resconv res copy"])
+        assert any(re.search(rl, n) for n in names["resconv res is in"]), f"no RL instantiation of {kernel}: {names['resconv res is in']}"
+        assert not any(re.search(rl, n) for n in names["resconv res copy"]), f"RL {kernel} on a second copy: {names['resconv res copy']}"
+    _assert_rows(rows)
+
+
+def test_conv_many_items(hip_backend):
+    """A batch of 128 small maps, 32 -> 32, in the two forms the 1080p rows do not cover, on every stride-1 id that accepts the
+    layer.  That the batch is large enough for the persistent loops is read from the traced grid, not from restated tile sizes:
+    for every id of families 1 and 2 and their family-4 members the grid at N equals the grid at N / 2, so those workgroups take at
+    least two tiles each.  (fp32 and K-split grids grow with the batch: value rows only.)"""
+    from drba_amd import ops
+    dev = hip_backend.dev
+    lib = op_checks.conv_lib()
+    rows = op_checks.check_conv_many(dev)
+    ids = op_checks.conv_many_ids(lib)
+    assert {(r.cfg, r.form) for r in rows if r.kind == "value"} == {(c, f) for c in ids for f in op_checks.MANY_FORMS}
+    persistent = [c for c in ids if op_checks.conv_id_class(lib, c) in ("split", "dma")]
+    assert {lib.drba_conv3x3_cfg_family(c) for c in persistent} == {1, 2, 4} and len(persistent) >= 8
+    n = op_checks.MANY_N
+    for form in (f for f in op_checks.CONV_FORMS if f.name in op_checks.MANY_FORMS):
+        d = op_checks.conv_many_inputs(dev, form)
+        for cfg in persistent:
+            layer, _ = op_checks.conv_many_layer(ops, dev, form, cfg)
+            grids = []
+            for m in (n, n // 2):
+                x = d["x"][:m]
+                res, res2 = (x, None) if form.res == "same" else (d["res"][:m], d["res2"][:m])
+                recs = [r for r in _traced_recs(lambda: layer(x, residual=res, residual2=res2)) if "conv_" in r["name"]]
+                assert len(recs) == 1, recs
+                grids.append(recs[0]["grid"])
+            print(f"  cfg{cfg} {form.name}: grid {grids[0]} at N={n}, {grids[1]} at N={n // 2} ({recs[0]['name']})")
+            assert grids[0] == grids[1], f"cfg{cfg} {form.name}: the grid still grows with the batch ({grids[1]} -> {grids[0]}): N = {n} is too small"
     _assert_rows(rows)
 
 

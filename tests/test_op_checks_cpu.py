@@ -405,10 +405,98 @@ def _stage_inputs(items, flows, tmp_prev, prev_scale, scale, out, fold=False, ld
     return folded if fold else None
 
 
+_CONV_MEMO = {}  # the stand-in's result per (layer tensors, operands, epilogue, defect): an id picks no kernel here, 38 ids share one evaluation
+
+
+def _refuse():
+    from drba_amd import _lib
+    raise _lib.DrbaHipError("drba_conv3x3 failed: unsupported (-2)")
+
+
+def _ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
 class _Conv3x3:
-    def __init__(self, w, b, stride, act, beta, device=None):
-        assert stride == 2 and act and beta is None
-        self.w, self.b, self.cout = w, b, w.shape[0]
+    """ops.Conv3x3 in torch fp32: the same constructor and call.  `cfg` picks no kernel, but the one documented refusal is kept: the
+    library's host-side table functions say which ids are the LDS-DMA members, and those refuse W % 4 != 0.  `defect` names the
+    planted one-line variant (None: none)."""
+    ACTS = {None: 0, False: 0, "none": 0, True: 1, "lrelu": 1, "prelu": 2, "relu": 3, "tanh10": 4}
+    defect = None
+
+    def __init__(self, weight, bias, stride=1, act=True, beta=None, device=None, cfg=None, pre_slope=None, post_slope=0.0):
+        self.w, self.b, self.bias, self.cout, self.cin = weight, bias, bias, weight.shape[0], weight.shape[1]
+        self.stride, self.act, self.beta, self.cfg, self.pre_slope, self.post_slope = stride, self.ACTS[act], beta, cfg, pre_slope, post_slope
+
+    def _value(self, x, residual, residual2):
+        d = self.defect
+        xin = x if self.pre_slope is None else torch.where(x > 0, x, x * self.pre_slope)
+        b = self.b
+        if d == "bias_from_32" and b is not None:
+            b = b.clone()
+            b[32:] = 0.0
+        y = F.conv2d(xin, self.w, b, stride=self.stride, padding=1)
+        if d == "pre_on_residual" and residual is x:
+            residual = xin
+        if d == "res2_dropped":
+            residual2 = None
+        if self.beta is not None:
+            bt = self.beta.reshape(1, -1, 1, 1)
+            y = (y + residual) * bt if d == "beta_order" else y * bt + residual
+        else:
+            if residual is not None:
+                y = y + residual
+            if residual2 is not None:
+                y = y + residual2
+        if self.act == 1:
+            return torch.where(y > 0, y, 0.2 * y)
+        if self.act == 2:
+            return torch.where(y > 0, y, (0.2 if d == "post_slope_02" else self.post_slope) * y)
+        if self.act == 3:
+            zero = torch.zeros_like(y)
+            return torch.where(y > 0, y, zero) if d == "relu_swallows_nan" else torch.where(y > 0, y, torch.where(y != y, y, zero))
+        return torch.tanh(y) * 10.0 if self.act == 4 else y
+
+    def __call__(self, x, residual=None, out=None, residual2=None):
+        if self.cfg is not None and x.shape[3] % 4 and op_checks.conv_id_class(op_checks.conv_lib(), self.cfg) == "dma":
+            _refuse()
+        key = (_ptr(self.w), _ptr(self.b), _ptr(self.beta), _ptr(x), _ptr(residual), _ptr(residual2), residual is x, self.stride, self.act,
+               self.pre_slope, self.post_slope, self.defect)
+        if key not in _CONV_MEMO:
+            _CONV_MEMO[key] = (self._value(x, residual, residual2), x, residual, residual2)  # (the operands kept alive: their addresses are the key)
+        y = _CONV_MEMO[key][0]
+        if out is None:
+            return y.clone()
+        out.copy_(y)
+        end = out.storage_offset() + out.numel()
+        if self.defect == "store_past" and end < out.untyped_storage().nbytes() // 4:  # one element past the last output plane
+            out.as_strided((1,), (1,), end).fill_(0.0)
+        return out
+
+
+def _conv_defect(name):
+    return type(f"_Conv3x3_{name}", (_Conv3x3,), {"defect": name})
+
+
+class _Deconv4x4:
+    def __init__(self, weight, bias, pixel_shuffle=False, device=None, cfg=None, pre_slope=None):
+        self.w, self.b, self.ps, self.pre_slope = weight, bias, pixel_shuffle, pre_slope
+
+    def __call__(self, x, out=None):
+        xin = x if self.pre_slope is None else torch.where(x > 0, x, x * self.pre_slope)
+        y = F.conv_transpose2d(xin, self.w, self.b, stride=2, padding=1)
+        y = STANDIN["pixel_shuffle2"](y) if self.ps else y
+        return y if out is None else out.copy_(y)
+
+
+def _conv3x3_shuffle(layer, x):
+    return STANDIN["pixel_shuffle2"](layer(x))
+
+
+def _conv3x3_shuffle_launch(layer, x, out, cfg):
+    """drba_conv3x3_shuffle's return code; every family-4 stride-1 id is taken to carry the store form"""
+    out.copy_(_conv3x3_shuffle(layer, x))
+    return 0
 
 
 def _stage_conv0_ok(conv, H, W, scale, prev_scale, items=None):
@@ -473,6 +561,7 @@ STANDIN = dict(
     warp_blend=_warp_blend, warp_blend_fold=_warp_blend_fold, warp_blend_lazy=_warp_blend_lazy,
     fill_holes=lambda aligned, cover, value: torch.where(cover < 0.999, value, aligned),
     drm_retime=lambda d, t, precision=1e-3: odrm.drm_to_t(d, t, precision),
+    Deconv4x4=_Deconv4x4, conv3x3_shuffle=_conv3x3_shuffle, conv3x3_shuffle_launch=_conv3x3_shuffle_launch,
 )
 
 
@@ -613,6 +702,16 @@ DEFECTS = (  # (operator of the stand-in, its defective variant, the operator fa
     ("warp_blend_lazy", _with(_warp_blend_lazy, "neighbour"), "warp_blend_lazy", "S1 48x80"),
     ("flow_updates", _with(_flow_updates), "flow_updates", "item 1"),
     ("ifblock_input", _with(_ifblock_input, "pair_as_planar"), "ifblock_input", "features=pair-only features"),
+    # the convolution epilogue forms: residual2 dropped; (y + x) * beta for y * beta + x; post_slope read as LeakyReLU's 0.2; the
+    # pre-activation applied to a residual that is the input; bias zeroed from output channel 32 on; one store one element past the
+    # last output plane (the guard row's); a ReLU that answers 0 for a NaN
+    ("Conv3x3", _conv_defect("res2_dropped"), "conv_forms", "pre+res+res2"),
+    ("Conv3x3", _conv_defect("beta_order"), "conv_forms", "resconv res is in"),
+    ("Conv3x3", _conv_defect("post_slope_02"), "conv_forms", "bias+prelu(0.1)"),
+    ("Conv3x3", _conv_defect("pre_on_residual"), "conv_forms", "pre+res=in"),
+    ("Conv3x3", _conv_defect("bias_from_32"), "conv_forms", "64->40"),
+    ("Conv3x3", _conv_defect("store_past"), "conv_forms", "in front of and behind out"),
+    ("Conv3x3", _conv_defect("relu_swallows_nan"), "conv_forms", "NaN, -inf"),
 )
 DEFECT_IDS = [d[0] + (" " + d[1].defect if isinstance(getattr(d[1], "defect", None), str) else "") for d in DEFECTS]
 
@@ -627,3 +726,44 @@ def test_planted_defect_fails_its_row_and_only_its_operator(clean, name, variant
             failed += [r for r in check(CPU, Recorder(**{name: variant})) if not _passes(r)]
     assert any(r.op == family and must_fail in r[0] for r in failed), [r[0] for r in failed]
     assert all(r.op == family for r in failed), [r[0] for r in failed if r.op != family]
+
+
+# ----------------------------------------------------------------------------------------- 4. the convolution forms
+def test_conv_forms_matrix_is_complete(clean):
+    """Every id has an accepted row for every form that applies to its stride (the rule the GPU tests assert), the only refusals
+    are the LDS-DMA members' on W % 4 != 0, every transposed-convolution id has both of its guarded rows, and each planted defect
+    above fails rows of its own form only."""
+    lib = op_checks.conv_lib()
+    rows = clean["op conv epilogue forms"][0]
+    ids = list(range(lib.drba_conv3x3_num_cfgs()))
+    assert len(ids) == 38 and not op_checks.conv_forms_missing(rows, lib, ids)
+    assert len(op_checks.CONV_FORMS) == 12 and len({f.name for f in op_checks.CONV_FORMS}) == 12
+    assert not [r[0] for r in rows if getattr(r, "kind", None) == "error"]
+    for ps in (0, 1):
+        assert {r.cfg for r in rows if getattr(r, "form", None) == "deconv" and r.kind == "guard" and f"ps={ps}" in r[0]} == set(range(15))
+    assert {r.cfg for r in rows if getattr(r, "kind", None) == "nonfinite"} == set(ids)
+    guarded = {(r.cfg, r.form) for r in rows if getattr(r, "kind", None) == "guard" and r.form not in ("deconv", "shuffle")}
+    assert guarded == {(r.cfg, r.form) for r in rows if getattr(r, "kind", None) == "value" and r.form not in ("deconv", "shuffle")}
+
+
+def test_conv_form_defects_fail_rows_of_their_form_only():
+    lib = op_checks.conv_lib()
+    ids = [min(c for c in range(lib.drba_conv3x3_num_cfgs()) if op_checks.conv_id_class(lib, c) == cls) for cls in op_checks.CONV_PAIRS]
+    for defect, form in (("res2_dropped", "pre+res+res2"), ("beta_order", "resconv"), ("post_slope_02", "bias+prelu(0.1)"), ("pre_on_residual", "pre+res=in")):
+        with torch.no_grad():
+            rows = op_checks.check_conv_forms(CPU, Recorder(Conv3x3=_conv_defect(defect)), cfgs=ids)
+        failed = [r for r in rows if not _passes(r)]
+        assert failed and all(r.form.startswith(form) for r in failed), (defect, [r[0] for r in failed])
+        hit = {r.cfg for r in failed}
+        s2 = {c for c in ids if op_checks.conv_id_class(lib, c) == "s2"}  # (the forms with a residual have no stride-2 rows)
+        assert hit == set(ids) - (s2 if form not in op_checks.CONV_PLAIN_FORMS else set()), (defect, hit)
+
+
+def test_conv_many_rows_on_a_small_batch():
+    """check_conv_many's rows with the stand-in at N = 4: clean, and failing in the form whose operand a defect touches"""
+    with torch.no_grad():
+        rows = op_checks.check_conv_many(CPU, Recorder(), n=4)
+        assert len(rows) == 2 * len(op_checks.conv_many_ids(op_checks.conv_lib())) and all(_passes(r) for r in rows), [r[0] for r in rows if not _passes(r)]
+        for defect, form in (("res2_dropped", "pre+res+res2"), ("beta_order", "resconv res is in")):
+            bad = [r for r in op_checks.check_conv_many(CPU, Recorder(Conv3x3=_conv_defect(defect)), n=4) if not _passes(r)]
+            assert bad and all(r.form == form for r in bad) and len(bad) == len(rows) // 2, (defect, [r[0] for r in bad])
