@@ -3,7 +3,9 @@ splat_warp.hip and the layout kernels of ifnet_glue.hip and frame_io.hip), of th
 drba_softsplat, _index, _again, _gather_quad), of resize_bilinear_scale and flow_distance, and of the IFNet stage glue
 (ifnet_glue.hip, flow_terms.hpp, stage_conv.hip, stage_conv16.hip: stage-input gathers, the gathers fused with conv0[0], the
 flow update, the final warp + blend -- in the forms the pipeline runs them), and of the 3x3 convolution's epilogue forms with
-every configuration id pinned (conv.hip, conv_split.hip, conv_dma.hip, conv_ks.hip; CONV_FORMS below), shared by
+every configuration id pinned (conv.hip, conv_split.hip, conv_dma.hip, conv_ks.hip; CONV_FORMS below), and of the three
+GMFlow transformer kernels at their dispatch edges (window_attn.hip, global_corr.hip, linear_split.hip; ATTN_CASES, GCORR_MAPS,
+LIN_EDGES below), shared by
 tests/test_gpu_op_parity.py, tests/test_op_checks_cpu.py and the diagnostic report (python -m tests.gpu_report).
 
 Every check takes the device the inputs go to and the `ops` namespace under test (default: drba_amd.ops; the CPU test hands
@@ -17,7 +19,9 @@ cite (oracle/*.py restates them), never from the kernels.  Value rows use one ru
 
 where `floor` is the max error of the fp32 oracle / fp32 torch evaluation of the same formula on the same input against the
 fp64 reference: measured per row, printed in the row, never calibrated against the code under test.  Decisions (masks, hole
-tests, the DRM retiming walk) and pure data movement are compared bit for bit: err = number of differing elements, tol = 0.
+tests, the DRM retiming walk) and pure data movement are compared bit for bit: err = number of differing elements, tol = 0.  The transformer rows keep three bars of their own, named in
+Row.tol_rule: a two-term attention row max(rule, 3 x the format floor: the fp64 formula on operands rounded to two fp16 terms), the
+coordinate rows of global_expect2 and the linear_split rows the bars tests/gpu_checks.py already holds those kernels to.
 
 Three places where ATen's CPU result is not the specification are written out instead of taken from ATen:
   * a zeros-padding bilinear sample at a non-finite coordinate is 0 (every tap is outside the image; ATen's CPU kernel forms
@@ -1756,6 +1760,497 @@ def check_conv_many(dev, ops=None, n=MANY_N, cfgs=None):
     return rows
 
 
+# ----------------------------------------------------------------------------------------- the GMFlow transformer kernels
+# window_attn.hip, global_corr.hip, linear_split.hip at their dispatch edges.  The host rules that pick a form are restated here
+# (as SCAN_PER_BLOCK is in test_gpu_op_parity.py) so that the row lists can be chosen -- and asserted -- to reach every form; the
+# GPU tests read the form that actually ran from the kernel trace.
+ATTN_KEYS = 64         # kKeys, drba_amd/csrc/window_attn.hip:42 and global_corr.hip:26: keys per chunk
+ATTN_ROWS = 64         # kRows, window_attn.hip:41 and global_corr.hip:25: query rows per workgroup of the fp32 kernels
+ATTN_TAB_CAP = 3968    # kTabCap, window_attn.hip:297: keys of one walk the two-term kernel's token table holds
+LIN_WIDE_MIN = 1536    # wide_min, linear_split.hip:309: workgroups of 128 x 128 from which the two-term form takes 128-token tiles
+GUARD = 4096           # sentinel floats behind an output / a workspace
+SENTINEL = 1.2345e-3
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def attn16_waves(L):
+    """window_attn.hip:631-635"""
+    return 8 if L >= 192 else 4
+
+
+def attn_ksplit(nwin, L):
+    """window_attn.hip:637-642: key runs of the fp32 kernel"""
+    qtiles, chunks = _cdiv(L, ATTN_ROWS), _cdiv(L, ATTN_KEYS)
+    if _cdiv(nwin, 8) * 8 * qtiles >= 2 * 256 or chunks < 8:
+        return 1
+    return 4 if chunks >= 16 else 2
+
+
+def attn16_ksplit(nwin, L, waves):
+    """window_attn.hip:647-660: key runs of the two-term kernel"""
+    qtiles, chunks = _cdiv(L, 16 * waves), _cdiv(L, ATTN_KEYS)
+    per_run, slots = _cdiv(nwin, 8) * 8 * qtiles, 256 * (1 if waves == 8 else 2)
+    best, best_cost, ks = 1, -1, 1
+    while ks <= 10 and (ks == 1 or chunks // ks >= 4):
+        cost = _cdiv(per_run * ks, slots) * (2 * _cdiv(chunks, ks) + 5) + (3 if ks > 1 else 0)
+        if best_cost < 0 or cost < best_cost:
+            best, best_cost = ks, cost
+        ks += 1
+    return best
+
+
+def gcorr_ksplit(L):
+    """pick_ksplit, global_corr.hip:213-230"""
+    qtiles, chunks = _cdiv(L, ATTN_ROWS), _cdiv(L, ATTN_KEYS)
+    best, best_cost, ks = 1, 0x7fffffff, 1
+    while ks <= 12 and chunks // ks >= 4:
+        per_cu = _cdiv(qtiles * ks, 256)
+        if per_cu > 3 and ks > 1:
+            break
+        cost = per_cu * (_cdiv(chunks, ks) + 2)
+        if cost < best_cost:
+            best, best_cost = ks, cost
+        ks += 1
+    return best
+
+
+def attn_runs(c, terms):
+    """key runs per window the default dispatch takes for case c (a workspace given)"""
+    nwin, L = c.b * c.splits ** 2, (c.h // c.splits) * (c.w // c.splits)
+    return attn16_ksplit(nwin, L, attn16_waves(L)) if terms == 2 else attn_ksplit(nwin, L)
+
+
+def uneven(L, runs):
+    """the last key run is shorter than the others (in chunks)"""
+    return runs > 1 and _cdiv(L, ATTN_KEYS) % runs != 0
+
+
+def two_term(x, shift=0):
+    """x (fp32 values) as the two-term fp16 form holds it, in float64: h = fp16(x 2^-s), l = fp16((x 2^-s - h) 2048),
+    x' = (h + l / 2048) 2^s (split2h, window_attn.hip:304-315; K with s = 4, :316)"""
+    xs = x.double() * 2.0 ** -shift
+    h = xs.to(torch.float16).double()
+    lo = ((xs - h) * 2048.0).to(torch.float16).double()
+    return (h + lo / 2048.0) * 2.0 ** shift
+
+
+class AttnCase(collections.namedtuple("AttnCase", "name b h w splits shift amp scale seed kind")):
+    @property
+    def L(self):
+        return (self.h // self.splits) * (self.w // self.splits)
+
+    @property
+    def nwin(self):
+        return self.b * self.splits ** 2
+
+
+S128 = 128 ** 0.5
+
+
+def _ac(b, h, w, splits, shift, seed, amp=1.5, scale=S128, kind="plain", tag=""):
+    wh, ww = h // splits, w // splits
+    name = f"b{b} {h}x{w} splits{splits} shift{int(shift)} (L={wh * ww}={wh}x{ww}, {b * splits * splits} windows){tag}"
+    return AttnCase(name, b, h, w, splits, shift, amp, scale, seed, kind)
+
+
+ATTN_GEOMETRY = (
+    # both sides of the 64-key chunk / the 64-row query tile: L = 63, 64, 65 from 7 x 9, 8 x 8, 5 x 13 (odd wh and ww with a shift:
+    # sh = wh // 2 floors), with 4, 9 (splits 3) and 18 (b = 2, splits 3) windows
+    _ac(1, 14, 18, 2, True, 5000), _ac(1, 24, 24, 3, True, 5001), _ac(2, 15, 39, 3, True, 5002), _ac(1, 7, 9, 1, False, 5003),
+    # 127 (prime: one 1 x 127 window), 128 (8 x 16, 16 windows), 129 (3 x 43): the 128-row tile of the 8-wave form is not reached below 192
+    _ac(1, 1, 127, 1, False, 5004), _ac(1, 32, 64, 4, True, 5005), _ac(1, 6, 86, 2, True, 5006),
+    # the 4 / 8-wave switch at L = 192: 187 (11 x 17), 192 (12 x 16), 195 (13 x 15)
+    _ac(1, 22, 34, 2, True, 5007), _ac(1, 24, 32, 2, True, 5008), _ac(1, 24, 32, 2, False, 5009), _ac(1, 13, 15, 1, False, 5010),
+    # the two 128-row tiles of the 8-wave form: 255 (15 x 17), 256 (16 x 16), 257 (prime, 1 x 257)
+    _ac(1, 30, 34, 2, True, 5011), _ac(1, 32, 32, 2, True, 5012), _ac(1, 1, 257, 1, False, 5013),
+    # ww == 1 (the ww_magic special case, window_attn.hip:62, :685) on a window longer than one chunk: 70 x 1
+    _ac(1, 140, 2, 2, False, 5014),
+    # b = 2 with a shift on a shape whose default dispatch splits the keys (8 windows of 19 x 24 = 456: two runs in both kernels)
+    _ac(2, 38, 48, 2, True, 5015),
+)
+ATTN_RUNS = (  # one window each; the smallest shapes that give 1..6 key runs (two-term) and 1, 2, 4 (fp32); see test_..._run_counts
+    _ac(1, 13, 15, 1, False, 5020), _ac(1, 19, 24, 1, False, 5021), _ac(1, 18, 30, 1, False, 5022), _ac(1, 24, 30, 1, False, 5023),
+    _ac(1, 28, 29, 1, False, 5024), _ac(1, 22, 44, 1, False, 5025), _ac(1, 33, 32, 1, False, 5026), _ac(1, 46, 46, 1, False, 5027),
+    _ac(1, 58, 72, 1, False, 5028),
+)
+ATTN_PEAKED = (
+    # the -100 mask decides: amplitude 3, scale 1 -- a masked key that scores 100 above the best unmasked one still takes the row
+    _ac(1, 26, 30, 2, True, 5030, amp=3.0, scale=1.0, kind="mask", tag=" amp3 scale1"),
+    _ac(1, 22, 34, 2, True, 5031, amp=3.0, scale=1.0, kind="mask", tag=" amp3 scale1"),
+    # the running rescale: amplitude 6, the keys of the window in ascending order of their score for query rows 0..3
+    _ac(1, 12, 25, 1, False, 5032, amp=6.0, kind="late", tag=" amp6 late maximum"),
+)
+ATTN_CASES = ATTN_GEOMETRY + ATTN_RUNS + ATTN_PEAKED
+ATTN_TABLE = (  # through the C ABI with ws = NULL (one run walks every key), two-term: the table at its cap (62 chunks), and off
+    _ac(1, 62, 64, 1, False, 5040), _ac(1, 63, 64, 1, False, 5041), _ac(1, 126, 128, 2, True, 5042))
+ATTN_STRIDED = _ac(2, 14, 18, 2, True, 5050)
+LATE_ROWS = 4
+_MEMO = {}  # inputs and references per case: regenerated from seeds, computed once per process, never modified
+
+
+def _late_order(q, k, v, scale):
+    """keys (and their values) in ascending order of their score for query row 0; rows 1..3 are positive multiples of row 0"""
+    for j in range(1, LATE_ROWS):
+        q[:, j] = q[:, 0] * (1.0 + 0.25 * j)
+    order = torch.argsort((k[0].double() @ q[0, 0].double()) / scale)
+    return q, k[:, order].contiguous(), v[:, order].contiguous()
+
+
+def attn_inputs(c):
+    key = ("attn in", c)
+    if key not in _MEMO:
+        q, k, v = [cases.rnd((c.b, c.h * c.w, 128), c.seed * 3 + j, c.amp) for j in range(3)]
+        if c.kind == "late":
+            q, k, v = _late_order(q, k, v, c.scale)
+        _MEMO[key] = (q, k, v)
+    return _MEMO[key]
+
+
+def attn_ref(q, k, v, c, masked=-100.0):
+    """transformer.py:46-113 through the oracle, which divides by sqrt(C): a free scale goes into q"""
+    wh, ww = c.h // c.splits, c.w // c.splits
+    mask = None
+    if c.shift:
+        mask = ogm.shift_window_mask(c.h, c.w, wh, ww, wh // 2, ww // 2)
+        if masked != -100.0:
+            mask = mask.masked_fill(mask != 0, masked)
+    return ogm.window_attention(q * (S128 / c.scale), k, v, c.splits, c.shift, c.h, c.w, mask)
+
+
+def _attn_smax(q, k, c):
+    """the largest |score| inside a window: what the fp32 evaluation's own error scales with"""
+    def win(t):
+        t = t.view(c.b, c.h, c.w, 128)
+        if c.shift:
+            t = torch.roll(t, shifts=(-((c.h // c.splits) // 2), -((c.w // c.splits) // 2)), dims=(1, 2))
+        return ogm.split_feature(t, c.splits, channel_last=True).reshape(c.nwin, c.L, 128)
+    return float(torch.matmul(win(q), win(k).transpose(1, 2)).abs().max()) / c.scale
+
+
+def attn_refs(c):
+    """{ref64, ref32, fmt_floor, smax, ...} of a case, with the conditions a peaked case exists for asserted before anything runs"""
+    key = ("attn ref", c)
+    if key in _MEMO:
+        return _MEMO[key]
+    q, k, v = attn_inputs(c)
+    r = {"ref64": attn_ref(q.double(), k.double(), v.double(), c), "ref32": attn_ref(q, k, v, c), "smax": _attn_smax(q, k, c)}
+    r["fmt_floor"] = _err(attn_ref(two_term(q), two_term(k, 4), two_term(v), c), r["ref64"])
+    r["refmax"], r["floor"] = float(r["ref64"].abs().max()), _err(r["ref32"], r["ref64"])
+    if c.kind == "mask":
+        # decisive: with -inf for -100 the reference itself moves by >= 100 tolerances in >= 2 % of the output rows
+        d = (attn_ref(q.double(), k.double(), v.double(), c, float("-inf")) - r["ref64"]).abs().amax(-1)
+        tol = max(rule_tol(r["refmax"], r["floor"]), 3.0 * r["fmt_floor"])
+        r["mask_diff"], r["mask_share"] = float(d.max()), float((d >= 100.0 * tol).float().mean())
+        assert r["mask_share"] >= 0.02, (c.name, r["mask_diff"], r["mask_share"], tol)
+    if c.kind == "late":
+        s = (q[0, :LATE_ROWS].double() @ k[0].double().t()) / c.scale
+        r["late_argmax"] = [int(i) for i in s.argmax(-1)]
+        assert c.L > 4 * ATTN_KEYS and all(i // ATTN_KEYS == _cdiv(c.L, ATTN_KEYS) - 1 for i in r["late_argmax"]), r["late_argmax"]
+        assert bool((s[:, ATTN_KEYS - 1::ATTN_KEYS].diff(dim=-1) > 1.0).all())  # the maximum moves by more than 1 at every chunk
+    _MEMO[key] = r
+    return r
+
+
+def attn_row(op, c, terms, got, extra=""):
+    """value row of a case: rule_tol; a two-term row: max(rule_tol, 3 x the format floor)"""
+    r = attn_refs(c)
+    tol = rule_tol(r["refmax"], r["floor"])
+    if terms == 2:
+        tol = max(tol, 3.0 * r["fmt_floor"])
+    x = f"fp32_floor={r['floor']:.2e} fmt_floor={r['fmt_floor']:.2e} |ref|max={r['refmax']:.3g} |score|max={r['smax']:.3g}"
+    if c.kind == "mask":
+        x += f" -inf-mask moves the reference by {r['mask_diff']:.3g} in {100 * r['mask_share']:.1f} % of the rows"
+    row = Row(op, f"terms={terms} {c.name}", _err(got, r["ref64"]), tol, f"{x} {extra}".rstrip(), r["floor"], r["refmax"])
+    row.smax, row.fmt_floor, row.tol_rule, row.case, row.terms = r["smax"], r["fmt_floor"], "two-term" if terms == 2 else None, c, terms
+    return row
+
+
+def attn_layouts(q, k, v, dev):
+    """name -> (q, k, v) on dev as the model's layers pass them: views with unequal row strides and column offsets"""
+    b, n, _ = q.shape
+    kv = torch.cat((k, v), -1).to(dev)                                   # cross attention: q alone, k | v one projection (ld 128 / 256 / 256)
+    qkv = torch.cat((q, k, v), -1).to(dev)                               # self attention: one fused projection (ld 384)
+    wide = torch.cat((torch.zeros(b, n, 64), q, torch.zeros(b, n, 8)), -1).to(dev)  # q at column 64 of a [.., 200] tensor, k and v alone
+    return {"q contiguous, k | v of [.., 256]": (q.to(dev), kv[..., :128], kv[..., 128:]),
+            "q | k | v of [.., 384]": (qkv[..., :128], qkv[..., 128:256], qkv[..., 256:]),
+            "q at column 64 of [.., 200], k and v contiguous": (wide[..., 64:192], k.to(dev), v.to(dev))}
+
+
+def _note_views(views, *ts):
+    """the non-contiguous views a strided row hands to the operator (the GPU suite asserts that their addresses reach the C call)"""
+    if views is not None:
+        views.extend(t for t in ts if not t.is_contiguous())
+
+
+def attn_strided_rows(dev, ops, views=None):
+    """ATTN_STRIDED on views with unequal row strides, bit for bit against the same call on contiguous copies"""
+    op, rows, c = "window_attention", [], ATTN_STRIDED
+    q, k, v = attn_inputs(c)
+    for terms in (3, 2):
+        want = ops.window_attention(q.to(dev), k.to(dev), v.to(dev), c.h, c.w, c.splits, c.shift, c.scale, terms=terms)
+        rows.append(attn_row(op, c, terms, want))
+        for name, (qs, ks, vs) in attn_layouts(q, k, v, dev).items():
+            assert not (qs.is_contiguous() and ks.is_contiguous() and vs.is_contiguous())
+            _note_views(views, qs, ks, vs)
+            got = ops.window_attention(qs, ks, vs, c.h, c.w, c.splits, c.shift, c.scale, terms=terms)
+            rows.append(exact_row(op, f"terms={terms} b2 {name} == contiguous copies", got, want))
+    return rows
+
+
+def check_window_attention_edges(dev, ops=None):
+    """ops.window_attention with 3 and 2 terms on every case of ATTN_CASES against fp64, and on strided views bit for bit against
+    the same call on contiguous copies"""
+    ops = ops or default_ops()
+    op, rows = "window_attention", []
+    for c in ATTN_CASES:
+        attn_refs(c)  # (a peaked case asserts its condition here, before anything is launched)
+        q, k, v = [t.to(dev) for t in attn_inputs(c)]
+        for terms in (3, 2):
+            got = ops.window_attention(q, k, v, c.h, c.w, c.splits, c.shift, c.scale, terms=terms)
+            rows.append(attn_row(op, c, terms, got, f"runs={attn_runs(c, terms)}"))
+    return rows + attn_strided_rows(dev, ops)
+
+
+# ---- global_expect2
+GCORR_MAPS = (  # (h, w): L = 63, 64, 65, 127, 128, 129; 1 x 70 and 70 x 1 (y = key / w with h = 1 and with w = 1); w > h and h > w
+    (7, 9), (8, 8), (13, 5), (1, 127), (8, 16), (43, 3), (1, 70), (70, 1), (5, 31), (31, 5))
+GCORR_RUNS = (  # ragged maps for 2..8 key runs; pick_ksplit first gives them at L = 449, 705, 961, 1217, 1473, 1729, 1985
+    # one chunk past the first chunk count of 2, 3, 4 runs (9, 13, 17 chunks: uneven) and at the first chunk count of 5..8 (5..8 x 4 chunks)
+    (19, 27), (21, 37), (27, 38), (24, 51), (37, 40), (29, 60), (35, 57),  # L = 513, 777, 1026, 1224, 1480, 1740, 1995
+    (61, 21), (39, 46), (23, 89),  # L = 1281 (5 runs, the last of one chunk), 1794 (6, uneven), 2047 (8)
+    # at the first chunk count of 2, 3, 4 runs: 8, 12, 16 chunks as even runs of the minimum of 4 chunks (chunks / ks >= 4)
+    (19, 24), (24, 30), (22, 44))  # L = 456, 720, 968
+GCORR_SEEDS = {m: 5100 + 3 * i for i, m in enumerate(GCORR_MAPS + GCORR_RUNS)}
+GCORR_LATE = (12, 25)
+
+
+def gcorr_inputs(h, w, seed, amp=0.9, late=False):
+    key = ("gcorr in", h, w, seed, amp, late)
+    if key not in _MEMO:
+        L = h * w
+        t0, t1, flow = cases.rnd((L, 128), seed, amp), cases.rnd((L, 128), seed + 1, amp), cases.rnd((2, L), seed + 2, 5.0)
+        if late:
+            q3, k3, f3 = _late_order(t0[None].clone(), t1[None], flow.t()[None].contiguous(), S128)
+            t0, t1, flow = q3[0], k3[0], f3[0].t().contiguous()
+        _MEMO[key] = (t0, t1, flow)
+    return _MEMO[key]
+
+
+def gcorr_ref(t0, t1, flow, h, w):
+    """matching.py:7-38 through the oracle (features [1, C, h, w]) for the coordinate form; the same softmax applied to a flow
+    (transformer.py:355-372) for the value form"""
+    L = h * w
+    f0, f1 = t0.t().reshape(1, 128, h, w), t1.t().reshape(1, 128, h, w)
+    coords = ogm.global_correlation_softmax(f0, f1)[0].reshape(2, L)
+    p = torch.softmax((t0 @ t1.t()) / S128, -1)
+    return coords, (p @ flow.t()).t()
+
+
+def gcorr_refs(h, w, seed, amp=0.9, late=False):
+    key = ("gcorr ref", h, w, seed, amp, late)
+    if key not in _MEMO:
+        t0, t1, flow = gcorr_inputs(h, w, seed, amp, late)
+        if late:
+            s = (t0[:LATE_ROWS].double() @ t1.double().t()) / S128
+            assert all(int(i) // ATTN_KEYS == _cdiv(h * w, ATTN_KEYS) - 1 for i in s.argmax(-1)), s.argmax(-1)
+            assert bool((s[:, ATTN_KEYS - 1::ATTN_KEYS].diff(dim=-1) > 1.0).all())
+        _MEMO[key] = gcorr_ref(t0.double(), t1.double(), flow.double(), h, w) + gcorr_ref(t0, t1, flow, h, w)
+    return _MEMO[key]
+
+
+def gcorr_rows(op, name, h, w, got_c, got_v, refs):
+    """the coordinate row at the project's bar, max(2e-5, 3 floor) max(1, w / 16) (tests/gpu_checks.py check_global_expect2), and
+    the value row at rule_tol"""
+    c64, v64, c32, v32 = refs
+    floor, refmax = _err(c32, c64), float(c64.abs().max())
+    row = Row(op, f"coords {name}", _err(got_c, c64), max(2e-5, 3.0 * floor) * max(1.0, w / 16.0), f"fp32_floor={floor:.2e} |ref|max={refmax:.3g}",
+              floor, refmax)
+    row.tol_rule, row.w = "coords", w
+    return [row, value_row(op, f"values {name}", got_v, v64, v32)]
+
+
+def gcorr_strided_rows(dev, ops, views=None):
+    """q contiguous with k a slice of a [L, 256] tensor, and the reverse: the same bits as on contiguous copies"""
+    op, rows = "global_expect2", []
+    h, w = GCORR_RUNS[0]
+    t0, t1, flow = gcorr_inputs(h, w, GCORR_SEEDS[(h, w)])
+    q, k, f = t0.to(dev), t1.to(dev), flow.to(dev)
+    wide_k, wide_q = torch.cat((torch.zeros(h * w, 128), t1), 1).to(dev), torch.cat((t0, torch.zeros(h * w, 128)), 1).to(dev)
+    _note_views(views, wide_k[:, 128:], wide_q[:, :128])
+    for vals, what in ((None, "coords"), (f, "values")):
+        want = ops.global_expect2(q, k, vals, w, S128)
+        rows.append(exact_row(op, f"{what} {h}x{w} q contiguous, k = [:, 128:] of [L, 256] == contiguous copies",
+                              ops.global_expect2(q, wide_k[:, 128:], vals, w, S128), want))
+        rows.append(exact_row(op, f"{what} {h}x{w} q = [:, :128] of [L, 256], k contiguous == contiguous copies",
+                              ops.global_expect2(wide_q[:, :128], k, vals, w, S128), want))
+    return rows
+
+
+def check_global_expect2_edges(dev, ops=None):
+    ops = ops or default_ops()
+    op, rows = "global_expect2", []
+
+    def one(h, w, seed, tag="", **kw):
+        t0, t1, flow = gcorr_inputs(h, w, seed, **kw)
+        q, k = t0.to(dev), t1.to(dev)
+        name = f"{h}x{w} (L={h * w}, runs={gcorr_ksplit(h * w)}){tag}"
+        rows.extend(gcorr_rows(op, name, h, w, ops.global_expect2(q, k, None, w, S128), ops.global_expect2(q, k, flow.to(dev), w, S128),
+                               gcorr_refs(h, w, seed, **kw)))
+
+    for (h, w), seed in GCORR_SEEDS.items():
+        one(h, w, seed)
+    one(*GCORR_LATE, 5190, " amp3 late maximum", amp=3.0, late=True)
+    return rows + gcorr_strided_rows(dev, ops)
+
+
+# ---- linear_split
+LIN_EDGES = (  # (M, K, N, bias, gelu): every M of (1, 15..17, 63..65, 127..129), every N of (1, 15..17, 40, 127..129, 384), every K
+    (1, 32, 1, True, False), (15, 64, 15, False, True), (16, 128, 16, True, False), (17, 32, 17, False, False), (63, 64, 40, True, True),
+    (64, 128, 127, False, False), (65, 32, 128, True, True), (127, 64, 129, True, False), (128, 128, 384, False, True),
+    (129, 32, 129, False, True), (129, 128, 128, True, False), (65, 64, 129, True, True), (1, 128, 384, True, False))
+LIN_CAT = ((32, 32), (32, 96), (96, 32), (128, 128))  # (K1, K2): the split at the first chunk, at the last, and in the middle
+LIN_WIDE = ((6100, True), (6016, False))              # (M, the 128-token form runs) at K = 32, N = 4096, two terms
+LIN_WIDE_KN = (32, 4096)
+LIN_LN = ((70, 64), (129, 128), (1, 32))              # (M, K) of the LayerNorm rows: ragged against the 64-token tile
+LIN_LN_ILL_MIN_M = 64  # the ill-conditioned row's bar is 3 x a measured floor: not taken from a single row of 128 values
+LIN_TERMS = (3, 2)
+
+
+def lin_row(op, name, got, ref64, ref32, bar):
+    """the bar the project holds linear_split to (tests/gpu_checks.py check_linear_split): 5e-6 max(1, |ref|max) for the GEMM forms,
+    1e-5 max(1, |ref|max) with the LayerNorm epilogue; the fp32 torch floor is printed, it sets nothing"""
+    floor, refmax = _err(ref32, ref64), float(ref64.abs().max())
+    row = Row(op, name, _err(got, ref64), bar * max(1.0, refmax), f"fp32_floor={floor:.2e} |ref|max={refmax:.3g}", floor, refmax)
+    row.tol_rule, row.bar = "linear", bar
+    return row
+
+
+def _lin_ref(x, w, b, gelu=False):
+    y = F.linear(x, w, b)
+    return F.gelu(y) if gelu else y
+
+
+def _ln_ref(x, w, b, lw, lb, res):
+    y = F.layer_norm(F.linear(x, w, b), (128,), lw, lb, 1e-5)
+    return y if res is None else res + y
+
+
+def _dbl(*ts):
+    return [None if t is None else t.double() for t in ts]
+
+
+def _sliced(x, pad_front, pad_back, dev):
+    """x [M, K] as columns [pad_front : pad_front + K] of a wider tensor on dev (row stride and offset multiples of 4 floats)"""
+    m, k = x.shape
+    wide = torch.cat((torch.full((m, pad_front), 7.0), x, torch.full((m, pad_back), -7.0)), 1).to(dev)
+    return wide[:, pad_front:pad_front + k]
+
+
+def lin_ln_cases():
+    """name -> (x, w, b, ln_w, ln_b, residual, ill): the LayerNorm epilogue's designed rows"""
+    key = "lin ln"
+    if key in _MEMO:
+        return _MEMO[key]
+    out = {}
+    for i, (m, k) in enumerate(LIN_LN):
+        s = 5400 + 10 * i
+        x, w = cases.rnd((m, k), s, 2.0), cases.rnd((128, k), s + 1, 1.0 / k ** 0.5)
+        lw, lb, res = cases.rnd((128,), s + 2, 0.3) + 1.0, cases.rnd((128,), s + 3, 0.1), cases.rnd((m, 128), s + 4, 1.0)
+        b = cases.rnd((128,), s + 5, 0.1)
+        out[f"[{m}x{k}] bias=1 residual=1"] = (x, w, b, lw, lb, res, False)
+        out[f"[{m}x{k}] bias=0 residual=0"] = (x, w, None, lw, lb, None, False)
+        # rows whose 128 pre-norm outputs are all equal (zero input rows): variance 0, eps decides, the answer is ln_b (+ residual).
+        # The constant is 0.75: every partial sum of equal 0.75s is exact in fp32 in any order, so the mean is exact and no fp32
+        # evaluation is excused by its own rounding (with 0.7 a sum's last-bit error, times 1 / sqrt(eps) = 316, is 1e-4)
+        xz = x.clone()
+        xz[[0, m // 2, m - 1]] = 0.0
+        out[f"[{m}x{k}] zero rows, bias = 0.75: variance 0, residual=1"] = (xz, w, torch.full((128,), 0.75), lw, lb, res, False)
+        out[f"[{m}x{k}] zero rows, no bias: variance 0, residual=0"] = (xz, w, None, lw, lb, None, False)
+        # mean ~ 100, deviation ~ 0.1: a one-pass variance (E x^2 - mean^2) has nothing left of 0.01 next to 1e4 in fp32
+        bm = 100.0 + cases.rnd((128,), s + 6, 0.1)
+        if m >= LIN_LN_ILL_MIN_M:
+            out[f"[{m}x{k}] mean 100 deviation 0.1 residual=1"] = (x * 0.02, w, bm, lw, lb, res, True)
+    _MEMO[key] = out
+    return out
+
+
+def lin_gelu_case():
+    """pre-activations placed exactly: w[n, n % 32] = 1, so y[m, n] = x[m, n % 32]: [-12, 12], 0 and -0, the erf's saturation"""
+    x = torch.linspace(-12.0, 12.0, 65 * 32).view(65, 32).clone()
+    x[3, :4] = torch.tensor([0.0, -0.0, 12.0, -12.0])
+    x[64, 28:] = torch.tensor([-5.5, 5.5, -8.0, 8.0])
+    w = torch.zeros(64, 32)
+    w[torch.arange(64), torch.arange(64) % 32] = 1.0
+    return x, w
+
+
+def lin_cat_rows(dev, ops, views=None):
+    """cat(x1, x2) read in place, x1 and x2 views with different row strides and column offsets"""
+    op, rows = "linear_split", []
+    D = lambda t: None if t is None else t.to(dev)  # noqa: E731
+    for i, (k1, k2) in enumerate(LIN_CAT):
+        m, n, gelu = 70, 129, bool(i % 2)
+        x1, x2, w = cases.rnd((m, k1), 5300 + 4 * i, 2.0), cases.rnd((m, k2), 5301 + 4 * i, 2.0), cases.rnd((n, k1 + k2), 5302 + 4 * i, 1.0 / (k1 + k2) ** 0.5)
+        b = cases.rnd((n,), 5303 + 4 * i, 0.5)
+        xc = torch.cat((x1, x2), 1)
+        ref64, ref32 = _lin_ref(*_dbl(xc, w, b), gelu), _lin_ref(xc, w, b, gelu)
+        for terms in LIN_TERMS:
+            layer = ops.LinearSplit(w, b, gelu=gelu, device=dev, terms=terms)
+            v1, v2 = _sliced(x1, 8, 16, dev), _sliced(x2, 4, 4, dev)
+            assert v1.stride(0) != v2.stride(0) and not v1.is_contiguous() and not v2.is_contiguous()
+            _note_views(views, v1, v2)
+            got = layer.cat(v1, v2)
+            name = f"terms={terms} cat K1={k1} K2={k2} [{m}] -> {n} gelu={int(gelu)} strided views"
+            rows.append(lin_row(op, name, got, ref64, ref32, 5e-6))
+            rows.append(exact_row(op, f"{name} == the concatenated contiguous tensor", got, layer(D(xc))))
+    return rows
+
+
+def check_linear_split_edges(dev, ops=None):
+    ops = ops or default_ops()
+    op, rows = "linear_split", []
+    D = lambda t: None if t is None else t.to(dev)  # noqa: E731
+    for i, (m, k, n, bias, gelu) in enumerate(LIN_EDGES):
+        x, w = cases.rnd((m, k), 5200 + 3 * i, 2.0), cases.rnd((n, k), 5201 + 3 * i, 1.0 / k ** 0.5)
+        b = cases.rnd((n,), 5202 + 3 * i, 0.5) if bias else None
+        ref64, ref32 = _lin_ref(*_dbl(x, w, b), gelu), _lin_ref(x, w, b, gelu)
+        for terms in LIN_TERMS:
+            got = ops.LinearSplit(w, b, gelu=gelu, device=dev, terms=terms)(D(x))
+            rows.append(lin_row(op, f"terms={terms} [{m}x{k}] -> {n} gelu={int(gelu)} bias={int(bias)}", got, ref64, ref32, 5e-6))
+    rows += lin_cat_rows(dev, ops)
+    # the 128-token form of the two-term kernel and the last shape below it
+    k, n = LIN_WIDE_KN
+    xw, ww = cases.rnd((LIN_WIDE[0][0], k), 5350, 2.0), cases.rnd((n, k), 5351, 1.0 / k ** 0.5)
+    for gelu in (False, True):
+        r64, r32 = _lin_ref(xw.double(), ww.double(), None, gelu), _lin_ref(xw, ww, None, gelu)
+        layer = ops.LinearSplit(ww, None, gelu=gelu, device=dev, terms=2)
+        for m, wide in LIN_WIDE:
+            rows.append(lin_row(op, f"terms=2 [{m}x{k}] -> {n} gelu={int(gelu)} {'128' if wide else '64'}-token tiles", layer(D(xw[:m])), r64[:m], r32[:m], 5e-6))
+        del r64, r32
+    # GELU over [-12, 12]: 1 - erf underflows, x * (1 + erf) cancels: the fp32 formula's own error sets the bar
+    x, w = lin_gelu_case()
+    for terms in LIN_TERMS:
+        got = ops.LinearSplit(w, None, gelu=True, device=dev, terms=terms)(D(x))
+        ref64 = _lin_ref(x.double(), w.double(), None, True)
+        rows.append(value_row(op, f"terms={terms} GELU pre-activations in [-12, 12], 0 and -0", got, ref64, _lin_ref(x, w, None, True)))
+        # the sign of zero, which a difference cannot see: inputs 0 and -0 (features 0, 1 and 32, 33 of token 3) give the pre-activation
+        # +0 -- the sum also holds the +0 products of the other input zero -- and GELU(+0) is +0, not -0
+        zeros = ref64[3, [0, 1, 32, 33]].float()
+        assert _mismatches(zeros, torch.zeros(4)) == 0
+        rows.append(exact_row(op, f"terms={terms} GELU of the pre-activations from inputs 0 and -0 is +0", got[3, [0, 1, 32, 33]], zeros))
+    # LayerNorm epilogue
+    for name, (x, w, b, lw, lb, res, ill) in lin_ln_cases().items():
+        ref64, ref32 = _ln_ref(*_dbl(x, w, b, lw, lb, res)), _ln_ref(x, w, b, lw, lb, res)
+        for terms in LIN_TERMS:
+            got = ops.LinearSplit(w, b, device=dev, terms=terms).layernorm(D(x), D(lw), D(lb), D(res))
+            full = f"terms={terms} + LayerNorm {name}"
+            rows.append(value_row(op, full, got, ref64, ref32) if ill else lin_row(op, full, got, ref64, ref32, 1e-5))
+    return rows
+
+
 SPLAT_CHECKS = (check_softsplat, check_softsplat_scan, check_softsplat_big)  # the generic splat's families, for tests that take them together
 CHECKS = (  # (section title, check): one operator family each
     ("op softmax_rows_", check_softmax_rows), ("op instance_norm", check_instance_norm), ("op conv_direct", check_conv_direct),
@@ -1767,5 +2262,6 @@ CHECKS = (  # (section title, check): one operator family each
     ("op softsplat big map", check_softsplat_big), ("op resize_bilinear_scale", check_resize_scale), ("op flow_distance", check_flow_distance),
     ("op stage input, first stage", check_stage_input_first), ("op stage input, warped", check_stage_input_warped),
     ("op stage input + conv0[0] fused", check_stage_conv_fused), ("op flow update", check_flow_update), ("op warp + blend", check_warp_blend),
-    ("op conv epilogue forms", check_conv_forms_all))
+    ("op conv epilogue forms", check_conv_forms_all), ("op window attention edges", check_window_attention_edges),
+    ("op global_expect2 edges", check_global_expect2_edges), ("op linear_split edges", check_linear_split_edges))
 GLUE_CHECKS = (check_stage_input_first, check_stage_input_warped, check_stage_conv_fused, check_flow_update, check_warp_blend)

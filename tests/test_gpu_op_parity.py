@@ -4,7 +4,9 @@ fused with conv0[0], flow update, final warp + blend: [H,W,4] frames, pair-only 
 frame's own resolution) on their own against a float64 reference (tests/op_checks.py), at the sizes where kernels go wrong:
 image borders, partial tiles and blocks, every dispatch branch, batch > 1, grid-stride loops and scan rounds that go round
 twice.  One operator family per test, so that a failure names it.  The 3x3 convolution's epilogue forms (op_checks.CONV_FORMS: what
-the GMFlow / GMFSS layers construct) run with every configuration id pinned, one test per kernel family and form group.
+the GMFlow / GMFSS layers construct) run with every configuration id pinned, one test per kernel family and form group.  The fused
+window attention, the global expectation and the split linear layer run at every edge of their host dispatch (key runs, wave forms,
+token table, tile forms), with the form that ran read from the kernel trace and sentinels behind outputs and workspaces.
 
 Value rows: tol = max(2e-5 max(1, |ref|max), 3 x the fp32 oracle's own error on that input); decisions and data movement:
 bit-exact.  tests/test_op_checks_cpu.py shows on the CPU that these rows fail for a wrong operator."""
@@ -469,4 +471,263 @@ def test_documented_refusals(hip_backend):
     refused(lambda: ops.warp_blend_lazy([(img, img)], [(head(2), 2.0)], head(2), 2.0))                                  # a term at the last head's scale
     refused(lambda: ops.warp_blend_lazy([(img, img)], [(head(s), float(s)) for s in (32, 16, 8, 4, 2)], head(1), 1.0))  # > MAX_FLOW_TERMS terms
     assert _lib.MAX_FLOW_TERMS == 4
+    # the fused window attention: a shifted window one pixel wide or high (the reference's mask table is degenerate there: the model
+    # takes the drba_bmm path), a map the windows do not divide; a linear layer whose K is no multiple of the 32-feature chunk
+    qkv = z(1, 140 * 2, 128)
+    refused(lambda: ops.window_attention(qkv, qkv, qkv, 140, 2, 2, True, 128 ** 0.5))
+    refused(lambda: ops.window_attention(qkv, qkv, qkv, 2, 140, 2, True, 128 ** 0.5))
+    refused(lambda: ops.window_attention(qkv, qkv, qkv, 140, 2, 3, False, 128 ** 0.5))
+    with pytest.raises(_lib.DrbaHipError):
+        ops.LinearSplit(z(8, 48).cpu(), None, device=dev)  # K % 32 != 0
     torch.cuda.synchronize()
+
+
+# ----------------------------------------------------------------------------------------- the GMFlow transformer kernels
+def test_window_attention_edges(hip_backend):
+    """window_attn.hip with 3 and 2 terms on both sides of the key chunk, the query tiles and the 4 / 8-wave switch, odd windows with a
+    shift, ww == 1, 1 to 18 windows, 1 to 6 key runs, inputs on which the -100 mask and the running rescale decide, strided views"""
+    _assert_rows(op_checks.check_window_attention_edges(hip_backend.dev))
+
+
+def _attn_launch(recs, c, terms):
+    """(key runs per window, waves) of one traced ops.window_attention call, read from the grid and the kernel names"""
+    main = [r for r in recs if "window_attention" in r["name"] and "merge" not in r["name"]]
+    merges = [r for r in recs if "window_attention_merge" in r["name"]]
+    assert len(main) == 1 and len(merges) <= 1, [r["name"] for r in recs]
+    name = main[0]["name"]
+    waves = 8 if "window_attention16_kernel<8>" in name else 4
+    assert ("window_attention16_kernel<" in name) == (terms == 2), (terms, name)
+    per_run = 8 * -(-c.nwin // 8) * -(-c.L // (16 * waves))
+    runs, rest = divmod(main[0]["grid"][0], per_run)
+    assert rest == 0 and main[0]["grid"][1:] == (1, 1) and (runs > 1) == bool(merges), (main[0]["grid"], per_run, [r["name"] for r in recs])
+    return runs, waves
+
+
+def test_window_attention_dispatch_forms_ran(hip_backend):
+    """ATTN_RUNS (and the b = 2 shifted case that splits its keys) under the kernel trace: the run count launched is grid / (8
+    ceil(nwin / 8) qtiles), the merge is in the trace exactly when it is above 1.  1..6 runs of the two-term kernel and 1, 2, 4 of the
+    fp32 kernel, an uneven split of each, and both wave forms were launched -- and are what the restated rules say: a retune that
+    un-covers a count fails here."""
+    from drba_amd import ops
+    dev = hip_backend.dev
+    rows, seen = [], {2: set(), 3: set()}
+    forms, uneven_seen = set(), {2: 0, 3: 0}
+    for c in op_checks.ATTN_RUNS + tuple(c for c in op_checks.ATTN_GEOMETRY if c.b == 2 and op_checks.attn_runs(c, 2) > 1):
+        q, k, v = [t.to(dev) for t in op_checks.attn_inputs(c)]
+        for terms in (3, 2):
+            out = []
+            recs = _traced_recs(lambda: out.append(ops.window_attention(q, k, v, c.h, c.w, c.splits, c.shift, c.scale, terms=terms)))
+            runs, waves = _attn_launch(recs, c, terms)
+            print(f"  terms={terms} {c.name}: {[(r['name'], r['grid'][0]) for r in recs]} -> {runs} runs, {waves} waves")
+            assert runs == op_checks.attn_runs(c, terms), (c.name, terms, runs)
+            seen[terms].add(runs)
+            uneven_seen[terms] += op_checks.uneven(c.L, runs)
+            if terms == 2:
+                forms.add(waves)
+            rows.append(op_checks.attn_row("window_attention", c, terms, out[0], f"runs={runs} traced"))
+    # below the switch (the geometry rows run the 4-wave form; one of them again here for the trace)
+    c = next(c for c in op_checks.ATTN_GEOMETRY if c.L == 187)
+    q, k, v = [t.to(dev) for t in op_checks.attn_inputs(c)]
+    recs = _traced_recs(lambda: ops.window_attention(q, k, v, c.h, c.w, c.splits, c.shift, c.scale, terms=2))
+    forms.add(_attn_launch(recs, c, 2)[1])
+    assert seen[2] == {1, 2, 3, 4, 5, 6} and seen[3] == {1, 2, 4}, seen
+    assert forms == {4, 8} and uneven_seen[2] >= 2 and uneven_seen[3] >= 2, (forms, uneven_seen)
+    _assert_rows(rows)
+
+
+def _attn_direct(lib, dev, c, terms, ws_mode):
+    """drba_window_attention through the C ABI into out = [b, n, 128] + GUARD sentinels; ws_mode None: ws = NULL; "exact": a workspace of
+    exactly drba_window_attention_ws_floats floats + GUARD sentinels -> (out values, out sentinels, ws sentinels or None, ws floats)"""
+    import ctypes as C
+    from drba_amd import ops
+    q, k, v = [t.to(dev) for t in op_checks.attn_inputs(c)]
+    n = c.b * c.h * c.w * 128
+    out = torch.full((n + op_checks.GUARD,), op_checks.SENTINEL, device=dev)
+    ws, size = None, 0
+    if ws_mode == "exact":
+        size = lib.drba_window_attention_ws_floats(c.b, c.h, c.w, c.splits)
+        ws = torch.full((size + op_checks.GUARD,), op_checks.SENTINEL, device=dev)
+    ptr = lambda t: C.c_void_p(0 if t is None else t.data_ptr())  # noqa: E731
+    rc = lib.drba_window_attention(ptr(q), ptr(k), ptr(v), ptr(out), c.b, c.h, c.w, 128, c.splits, int(c.shift), float(c.scale), 128, 128, 128,
+                                   ptr(ws), terms, ops._stream())
+    assert rc == 0, (rc, c.name)
+    torch.cuda.synchronize()
+    return out[:n].view(c.b, c.h * c.w, 128), out[n:], None if ws is None else ws[size:], size
+
+
+def test_window_attention_token_table_forms(hip_backend):
+    """The two-term kernel walking every key of a window in one run (ws = NULL through the C ABI): 3968 keys -- kTabCap, the longest
+    walk that takes the token table -- and 4032, the first that evaluates token_row per chunk with 64-bit row offsets; and four
+    shifted windows of 4032 (regions from the per-chunk form).  Value rows against fp64; the trace shows one launch and no merge."""
+    from drba_amd import _lib
+    lib, dev = _lib.load(), hip_backend.dev
+    rows = []
+    sent = torch.full((op_checks.GUARD,), op_checks.SENTINEL)
+    for c in op_checks.ATTN_TABLE:
+        assert (c.L <= op_checks.ATTN_TAB_CAP) == (c is op_checks.ATTN_TABLE[0])  # window_attn.hip:695-698 with ksplit = 1
+        got = []
+        recs = _traced_recs(lambda: got.append(_attn_direct(lib, dev, c, 2, None)))
+        runs, waves = _attn_launch(recs, c, 2)
+        assert (runs, waves) == (1, 8), (runs, waves)
+        out, tail, _, _ = got[0]
+        table = "table" if c.L <= op_checks.ATTN_TAB_CAP else "token_row per chunk"
+        rows.append(op_checks.attn_row("window_attention", c, 2, out, f"ws=NULL: one walk of {c.L} keys, {table}"))
+        rows.append(op_checks.exact_row("window_attention", f"terms=2 {c.name}: the {op_checks.GUARD} floats behind out", tail, sent))
+    _assert_rows(rows)
+
+
+def test_window_attention_guards(hip_backend):
+    """out and the workspace of exactly drba_window_attention_ws_floats floats each followed by 4096 sentinels, one shape per key-run
+    count, both term counts: the sentinels are untouched and the values hold their fp64 row"""
+    from drba_amd import _lib
+    lib, dev = _lib.load(), hip_backend.dev
+    rows = []
+    sent = torch.full((op_checks.GUARD,), op_checks.SENTINEL)
+    shapes = {}
+    for c in op_checks.ATTN_RUNS + tuple(c for c in op_checks.ATTN_GEOMETRY if c.b == 2):
+        shapes.setdefault((op_checks.attn_runs(c, 2), op_checks.attn_runs(c, 3), c.b), c)
+    assert {k[0] for k in shapes} == {1, 2, 3, 4, 5, 6} and {k[1] for k in shapes} == {1, 2, 4}
+    for c in shapes.values():
+        for terms in (3, 2):
+            out, tail, ws_tail, size = _attn_direct(lib, dev, c, terms, "exact")
+            name = f"terms={terms} {c.name}"
+            rows.append(op_checks.attn_row("window_attention", c, terms, out, f"guarded, ws={size} floats, runs={op_checks.attn_runs(c, terms)}"))
+            rows.append(op_checks.exact_row("window_attention", f"{name}: the {op_checks.GUARD} floats behind out", tail, sent))
+            rows.append(op_checks.exact_row("window_attention", f"{name}: the {op_checks.GUARD} floats behind the workspace", ws_tail, sent))
+    _assert_rows(rows)
+
+
+def test_global_expect2_edges(hip_backend):
+    """global_corr.hip on both sides of the chunk and the query tile, 1 x 70 and 70 x 1 maps, w > h and h > w, 1 to 8 key runs with
+    even runs of the minimum of 4 chunks and uneven splits, a late maximum, strided q and k; coordinates and a flow as values at every shape"""
+    _assert_rows(op_checks.check_global_expect2_edges(hip_backend.dev))
+
+
+def test_global_expect2_dispatch_and_guards(hip_backend):
+    """Every map of GCORR_RUNS (and one below the first split) through the C ABI under the kernel trace, into out = [2, L] + 4096
+    sentinels with a workspace of exactly drba_global_expect2_ws_floats(L) floats + 4096 sentinels: the run count launched (grid /
+    qtiles; the merge in the trace exactly above 1) is what the restated rule says, 1..8 were all launched, the sentinels are
+    untouched and the values hold their rows."""
+    import ctypes as C
+    from drba_amd import _lib, ops
+    lib, dev = _lib.load(), hip_backend.dev
+    rows, seen, even_min = [], set(), {}
+    sent = torch.full((op_checks.GUARD,), op_checks.SENTINEL)
+    ptr = lambda t: C.c_void_p(0 if t is None else t.data_ptr())  # noqa: E731
+    maps = [(m, op_checks.GCORR_SEEDS[m]) for m in op_checks.GCORR_MAPS[:1] + op_checks.GCORR_RUNS]
+    for (h, w), seed in maps:
+        L = h * w
+        t0, t1, flow = [t.to(dev) for t in op_checks.gcorr_inputs(h, w, seed)]
+        size = lib.drba_global_expect2_ws_floats(L)
+        got = {}
+        for what, vals in (("coords", None), ("values", flow)):
+            out = torch.full((2 * L + op_checks.GUARD,), op_checks.SENTINEL, device=dev)
+            ws = torch.full((size + op_checks.GUARD,), op_checks.SENTINEL, device=dev)
+            recs = _traced_recs(lambda: got.__setitem__("rc", lib.drba_global_expect2(ptr(t0), ptr(t1), ptr(vals), ptr(out), ptr(ws), L, 128, w,
+                                                                                 float(op_checks.S128), 128, 128, ops._stream())))
+            assert got["rc"] == 0
+            main = [r for r in recs if "global_expect2_kernel" in r["name"]]
+            merges = [r for r in recs if "global_expect2_merge" in r["name"]]
+            assert len(main) == 1 and len(merges) <= 1, (L, recs)
+            runs, rest = divmod(main[0]["grid"][0], -(-L // op_checks.ATTN_ROWS))
+            assert rest == 0 and (runs > 1) == (len(merges) == 1) and runs == op_checks.gcorr_ksplit(L), (L, recs)
+            even_min[runs] = even_min.get(runs, False) or -(-L // op_checks.ATTN_KEYS) == 4 * runs
+            seen.add(runs)
+            got[what] = out[:2 * L].view(2, L)
+            name = f"{what} {h}x{w} (L={L}) runs={runs}"
+            rows.append(op_checks.exact_row("global_expect2", f"{name}: the {op_checks.GUARD} floats behind out", out[2 * L:], sent))
+            rows.append(op_checks.exact_row("global_expect2", f"{name}: the {op_checks.GUARD} floats behind the {size}-float workspace", ws[size:], sent))
+        rows.extend(op_checks.gcorr_rows("global_expect2", f"{h}x{w} (L={L}) guarded, traced", h, w, got["coords"], got["values"],
+                                         op_checks.gcorr_refs(h, w, seed)))
+    assert seen == {1, 2, 3, 4, 5, 6, 7, 8}, seen
+    assert all(even_min[k] for k in range(2, 9)), even_min  # each count also as even runs of the minimum of 4 chunks
+    _assert_rows(rows)
+
+
+def test_strided_views_reach_the_kernels_in_place(hip_backend, monkeypatch):
+    """The bit-equality rows on strided views say something only while ops.window_attention, ops.global_expect2 and LinearSplit.cat
+    hand the views themselves to the library: every pointer the wrappers pass goes through ops._p, so each view's address must be
+    among them -- a wrapper that started to copy such a view would pass the address of the copy and fail here."""
+    from drba_amd import ops
+    dev = hip_backend.dev
+    passed, real = set(), ops._p
+    monkeypatch.setattr(ops, "_p", lambda t: (passed.add(None if t is None else t.data_ptr()), real(t))[1])
+    for strided in (op_checks.attn_strided_rows, op_checks.gcorr_strided_rows, op_checks.lin_cat_rows):
+        views = []
+        passed.clear()
+        rows = strided(dev, ops, views)
+        torch.cuda.synchronize()
+        assert len(views) >= 2 and not any(v.is_contiguous() for v in views)
+        missing = [(tuple(v.shape), v.stride()) for v in views if v.data_ptr() not in passed]
+        assert not missing, f"{strided.__name__}: views copied before the call: {missing}"
+        _assert_rows(rows)
+
+
+def test_linear_split_edges(hip_backend):
+    """linear_split.hip with 3 and 2 terms at the token and feature tile edges, one K chunk, cat splits at the first and last chunk
+    on strided views, the 128-token form and the shape below it, GELU over [-12, 12], LayerNorm rows of variance 0 and of mean 100"""
+    _assert_rows(op_checks.check_linear_split_edges(hip_backend.dev))
+
+
+def test_linear_split_tile_forms_ran(hip_backend):
+    """K = 32, N = 4096, two terms: M = 6100 is 48 x 32 = 1536 workgroups of 128 x 128 (wide_min, linear_split.hip:309-310) and runs
+    LinCfg<2, 8, 2> with a ragged last 128-token tile, M = 6016 (1504) runs LinCfg<1, 8, 2> -- read from the traced kernel names, for
+    the plain and the GELU epilogue.  (The LayerNorm epilogue has one feature tile: its wide form needs M >= 196 481.)"""
+    import re
+    from drba_amd import ops
+    dev = hip_backend.dev
+    k, n = op_checks.LIN_WIDE_KN
+    x = op_checks.cases.rnd((op_checks.LIN_WIDE[0][0], k), 5350, 2.0).to(dev)
+    w = op_checks.cases.rnd((n, k), 5351, 1.0 / k ** 0.5)
+    for gelu in (False, True):
+        layer = ops.LinearSplit(w, None, gelu=gelu, device=dev, terms=2)
+        layer.packed
+        for m, wide in op_checks.LIN_WIDE:
+            assert (-(-m // 128) * -(-n // 128) >= op_checks.LIN_WIDE_MIN) == wide
+            recs = _traced_recs(lambda: layer(x[:m]))
+            names = [r["name"] for r in recs if "linear_split_kernel" in r["name"]]
+            print(f"  M={m} gelu={int(gelu)}: {names} grid {[r['grid'] for r in recs]}")
+            assert len(names) == 1 and re.search(rf"LinCfg<{2 if wide else 1}, ?8, ?2>, ?{int(gelu)}>", names[0]), names
+            assert recs[0]["grid"][0] == -(-m // (128 if wide else 64)) * (n // 128)
+    torch.cuda.synchronize()
+
+
+def test_linear_split_guards(hip_backend):
+    """drba_linear_split, _cat and _layernorm through the C ABI into out = [M, N] + 4096 sentinels at M = 65, N = 129 and M = 129,
+    N = 128, both term counts: sentinels untouched, values at the project's bar"""
+    import ctypes as C
+    from drba_amd import _lib, ops
+    lib, dev = _lib.load(), hip_backend.dev
+    rows = []
+    sent = torch.full((op_checks.GUARD,), op_checks.SENTINEL)
+    ptr = lambda t: C.c_void_p(0 if t is None else t.data_ptr())  # noqa: E731
+    rnd = op_checks.cases.rnd
+    for i, (m, n) in enumerate(((65, 129), (129, 128))):
+        k1, k2 = 32, 64
+        k = k1 + k2
+        x, w, b = rnd((m, k), 5500 + 5 * i, 2.0), rnd((n, k), 5501 + 5 * i, 1.0 / k ** 0.5), rnd((n,), 5502 + 5 * i, 0.5)
+        lw, lb, res = rnd((128,), 5503 + 5 * i, 0.3) + 1.0, rnd((128,), 5504 + 5 * i, 0.1), rnd((m, 128), 5505 + 5 * i, 1.0)
+        xd, x1, x2 = x.to(dev), x[:, :k1].contiguous().to(dev), x[:, k1:].contiguous().to(dev)
+        lwd, lbd, resd = lw.to(dev), lb.to(dev), res.to(dev)
+        for terms in (3, 2):
+            layer = ops.LinearSplit(w, b, device=dev, terms=terms)
+            calls = {
+                "linear": lambda o: lib.drba_linear_split(ptr(xd), ptr(layer.packed), ptr(layer.bias), ptr(o), m, k, n, k, 0, terms, ops._stream()),
+                "linear + GELU": lambda o: lib.drba_linear_split(ptr(xd), ptr(layer.packed), ptr(layer.bias), ptr(o), m, k, n, k, 1, terms, ops._stream()),
+                "cat": lambda o: lib.drba_linear_split_cat(ptr(x1), ptr(x2), ptr(layer.packed), ptr(layer.bias), ptr(o), m, k1, k2, n, k1, k2, 0, terms,
+                                                            ops._stream())}
+            if n == 128:
+                calls["LayerNorm"] = lambda o: lib.drba_linear_split_layernorm(ptr(xd), ptr(layer.packed), ptr(layer.bias), ptr(lwd), ptr(lbd), ptr(resd),
+                                                                               ptr(o), m, k, k, 1e-5, terms, ops._stream())
+            for what, call in calls.items():
+                out = torch.full((m * n + op_checks.GUARD,), op_checks.SENTINEL, device=dev)
+                assert call(out) == 0
+                torch.cuda.synchronize()
+                if what == "LayerNorm":
+                    r64, r32, bar = op_checks._ln_ref(*op_checks._dbl(x, w, b, lw, lb, res)), op_checks._ln_ref(x, w, b, lw, lb, res), 1e-5
+                else:
+                    r64, r32, bar = op_checks._lin_ref(*op_checks._dbl(x, w, b), what.endswith("GELU")), op_checks._lin_ref(x, w, b, what.endswith("GELU")), 5e-6
+                name = f"terms={terms} {what} [{m}x{k}] -> {n} guarded"
+                rows.append(op_checks.lin_row("linear_split", name, out[:m * n].view(m, n), r64, r32, bar))
+                rows.append(op_checks.exact_row("linear_split", f"{name}: the {op_checks.GUARD} floats behind out", out[m * n:], sent))
+    _assert_rows(rows)

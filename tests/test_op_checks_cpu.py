@@ -539,7 +539,113 @@ def _warp_blend_lazy(items, terms, tmp_last, scale, defect=None):
                    _up(tmp_last[k:k + 1, 4:5], scale)) for k, it in enumerate(items)]
 
 
+# ---- the GMFlow transformer kernels: attention window by window with an explicit roll index map and region ids, both attentions
+# as a running (max, sum, weighted sum) over 64-key chunks, the linear layer with its epilogues written out
+def _flash(Q, K, vals, scale, L, bias=None, tail_keys=False, no_rescale=False):
+    """softmax(Q K^T / scale + bias) vals over chunks of 64 keys, the last chunk padded with copies of key L - 1 that take no part"""
+    n = Q.shape[0]
+    m, l, acc = torch.full((n,), float("-inf")), torch.zeros(n), torch.zeros(n, vals.shape[1])
+    for c0 in range(0, L, 64):
+        pos = c0 + torch.arange(64)
+        idx = pos.clamp(max=L - 1)
+        s = (Q @ K[idx].t()) / scale
+        if bias is not None:
+            s = s + bias[:, idx]
+        if not tail_keys:
+            s[:, pos >= L] = float("-inf")
+        m_new = torch.maximum(m, s.max(1).values)
+        ref = torch.where(torch.isinf(m_new), torch.zeros_like(m_new), m_new)  # (a chunk that is masked out altogether: planted -inf mask only)
+        alpha = torch.ones(n) if no_rescale else torch.exp(m - ref)
+        p = torch.exp(s - ref[:, None])
+        l, acc, m = l * alpha + p.sum(1), acc * alpha[:, None] + p @ vals[idx], m_new
+    return acc / l[:, None]
+
+
+def _window_attention(q, k, v, h, w, splits, shift, scale, terms=None, defect=None):
+    b, n, c = q.shape
+    wh, ww = h // splits, w // splits
+    sh, sw = (wh // 2, ww // 2) if shift else (0, 0)
+    L = wh * ww
+    t = torch.arange(L)
+    ly, lx = t // ww, t % ww
+    out = torch.zeros(b, n, c)
+    for win in range(b * splits * splits):
+        bi, wi = divmod(win, splits * splits)
+        y, x = (wi // splits) * wh + ly, (wi % splits) * ww + lx  # position in the rolled image
+        rows, bias = ((y + sh) % h) * w + (x + sw) % w, None    # the row it came from
+        if shift:
+            second = h - wh if defect == "region_bound" else h - sh
+            region = 3 * ((y >= h - wh).long() + (y >= second).long()) + (x >= w - ww).long() + (x >= w - sw).long()
+            bias = torch.where(region[:, None] != region[None, :], float("-inf") if defect == "mask_inf" else -100.0, 0.0)
+        src = 0 if defect == "no_batch" else bi
+        res = _flash(q[src, rows], k[src, rows], v[src, rows], scale, L, bias, defect == "tail_keys", defect == "no_rescale")
+        out[bi, (y * w + x) if defect == "unrolled_out" else rows] = res
+    return out
+
+
+def _global_expect2(q_tok, k_tok, vals, w, scale, defect=None):
+    L = q_tok.shape[0]
+    key = torch.arange(L)
+    cx, cy = (key % w).float(), (key // w).float()
+    v2 = torch.stack((cy, cx) if defect == "xy_exchanged" else (cx, cy), 1) if vals is None else vals.t()
+    out = _flash(q_tok, k_tok, v2, scale, L).t()
+    if vals is None and defect != "own_coordinate":
+        out = out - torch.stack((cx, cy))
+    return out.contiguous()
+
+
+class _LinearSplit:
+    """ops.LinearSplit in torch fp32: y = x w^T as a sum over 32-feature chunks, + bias, then the epilogue written out"""
+    defect = None
+
+    def __init__(self, weight, bias=None, gelu=False, device=None, terms=None):
+        self.w, self.b, self.gelu = weight, bias, gelu
+        self.n, self.k = weight.shape
+
+    def _gemm(self, x):
+        y = torch.zeros(x.shape[0], self.n)
+        for c0 in range(0, self.k, 32):
+            y += x[:, c0:c0 + 32] @ self.w[:, c0:c0 + 32].t()
+        if self.b is not None:
+            b = self.b.clone()
+            if self.defect == "bias_to_128":
+                b[128:] = 0.0
+            y = y + b
+        return y
+
+    def __call__(self, x):
+        y = self._gemm(x.reshape(-1, self.k))
+        if self.gelu:
+            if self.defect == "tanh_gelu":
+                y = 0.5 * y * (1 + torch.tanh(0.7978845608028654 * (y + 0.044715 * y ** 3)))
+            else:
+                y = 0.5 * y * (1 + torch.erf(y * 0.7071067811865476))
+        return y.view(*x.shape[:-1], self.n)
+
+    def cat(self, x1, x2):
+        x = torch.cat((x1, x2), -1)
+        if self.defect == "cat_split":  # the chunk behind the split still read from x1's side
+            k1 = x1.shape[-1]
+            x[..., k1:k1 + 32] = x[..., k1 - 32:k1]
+        return self(x)
+
+    def layernorm(self, x, ln_w, ln_b, residual=None, eps=1e-5):
+        y = self._gemm(x.reshape(-1, self.k))
+        mean = y.sum(1, keepdim=True) / 128
+        if self.defect == "one_pass_variance":
+            var = (y * y).sum(1, keepdim=True) / 128 - mean * mean
+        else:
+            var = ((y - mean) ** 2).sum(1, keepdim=True) / (127 if self.defect == "unbiased_variance" else 128)
+        out = (y - mean) / torch.sqrt(var + eps) * ln_w + ln_b
+        return out if residual is None else residual + out
+
+
+def _lin_defect(name):
+    return type(f"_LinearSplit_{name}", (_LinearSplit,), {"defect": name})
+
+
 STANDIN = dict(
+    window_attention=_window_attention, global_expect2=_global_expect2, LinearSplit=_LinearSplit,
     softmax_rows_=_softmax_rows_, instance_norm=_instance_norm, conv_direct=_conv_direct, local_corr_flow=_local_corr_flow,
     local_attn_flow=_local_attn_flow, convex_upsample=_convex_upsample, flow_warp=_flow_warp, backwarp=_backwarp,
     resize_bilinear_ac=_resize_bilinear_ac, layernorm=_layernorm, timestep_fix=_timestep_fix, drm_ratio=_drm_ratio,
@@ -605,6 +711,9 @@ FLOOR_BOUNDS = (
     ("instance_norm", "constant plane", 16 * EPS32 * 3.7 / 1e-5 ** 0.5),
     # exp(s - max) with |s| up to ~4 * 80: the fp32 score difference carries 2^-24 * 640 relative error into every term
     ("softmax_rows_", "|scores|~80", 4 * EPS32 * 640),
+    # LayerNorm of 100 +- 0.1: the pre-norm value rounds to fp32 with 2^-24 * 128 (the binade of 100), the mean likewise; over a
+    # deviation of 0.1, times a gain of up to 2
+    ("linear_split", "mean 100 deviation 0.1", 2 * EPS32 * 128 / 0.1 * 2),
 )
 
 
@@ -612,7 +721,27 @@ def _floor_bound(row):
     for op, key, bound in FLOOR_BOUNDS:
         if row.op == op and key in row[0]:
             return bound
-    return 2e-5 * max(1.0, row.refmax)
+    base = 2e-5 * max(1.0, row.refmax)
+    if row.op == "window_attention":
+        # a score is a sum of 128 products, off by a few 2^-24 |score|max in fp32 (more where the scale is folded into q first); exp
+        # carries that absolute error of its argument into every probability as a relative one, twice (numerator, normaliser)
+        return base + 16 * EPS32 * row.smax * max(1.0, row.refmax)
+    return base
+
+
+def _row_tol(row):
+    """the tolerance a row's rule gives, from what the row records: the one rule of the series, or one of the three bars the
+    transformer rows keep (tests/op_checks.py attn_row, gcorr_rows, lin_row)"""
+    rule = getattr(row, "tol_rule", None)
+    if rule == "two-term":
+        return max(op_checks.rule_tol(row.refmax, row.floor), 3.0 * row.fmt_floor)
+    if rule == "coords":
+        return max(2e-5, 3.0 * row.floor) * max(1.0, row.w / 16.0)
+    if rule == "linear":
+        assert row.bar in (5e-6, 1e-5)
+        return row.bar * max(1.0, row.refmax)
+    assert rule is None
+    return op_checks.rule_tol(row.refmax, row.floor)
 
 
 def test_fp64_references_agree_with_the_fp32_forms(clean):
@@ -623,7 +752,7 @@ def test_fp64_references_agree_with_the_fp32_forms(clean):
                 continue
             n += 1
             assert row.floor <= _floor_bound(row), f"{row[0]}: fp32 form vs fp64 reference {row.floor:.3e} > {_floor_bound(row):.3e}"
-            assert row[2] == op_checks.rule_tol(row.refmax, row.floor)  # the one tolerance rule, nothing else
+            assert row[2] == _row_tol(row)  # the one tolerance rule (or the named bar of a transformer row), nothing else
     assert n > 200
 
 
@@ -712,6 +841,26 @@ DEFECTS = (  # (operator of the stand-in, its defective variant, the operator fa
     ("Conv3x3", _conv_defect("bias_from_32"), "conv_forms", "64->40"),
     ("Conv3x3", _conv_defect("store_past"), "conv_forms", "in front of and behind out"),
     ("Conv3x3", _conv_defect("relu_swallows_nan"), "conv_forms", "NaN, -inf"),
+    # the transformer kernels.  Window attention: the region mask as -inf; the second row boundary of the region ids at h - wh
+    # instead of h - sh (the exchange the other way round -- h - sh for the first boundary -- labels the same partition of every window
+    # and is no defect); the padding keys of the last chunk left in; no rescale when the running maximum moves; the output row
+    # written at the rolled position; every window read from image 0
+    ("window_attention", _with(_window_attention, "mask_inf"), "window_attention", "amp3 scale1"),
+    ("window_attention", _with(_window_attention, "region_bound"), "window_attention", "shift1"),
+    ("window_attention", _with(_window_attention, "tail_keys"), "window_attention", "(L=65="),
+    ("window_attention", _with(_window_attention, "no_rescale"), "window_attention", "late maximum"),
+    ("window_attention", _with(_window_attention, "unrolled_out"), "window_attention", "shift1"),
+    ("window_attention", _with(_window_attention, "no_batch"), "window_attention", "b2 "),
+    # the global expectation: the query's own coordinate left in; x and y of the key coordinates exchanged
+    ("global_expect2", _with(_global_expect2, "own_coordinate"), "global_expect2", "coords 5x31"),
+    ("global_expect2", _with(_global_expect2, "xy_exchanged"), "global_expect2", "coords 31x5"),
+    # the linear layer: the tanh approximation for the erf GELU; the LayerNorm's variance over 127, and as E x^2 - mean^2; the split
+    # of the concatenated input one chunk late; no bias past the first 128-feature tile
+    ("LinearSplit", _lin_defect("tanh_gelu"), "linear_split", "gelu=1"),
+    ("LinearSplit", _lin_defect("unbiased_variance"), "linear_split", "+ LayerNorm [70x64] bias=1"),
+    ("LinearSplit", _lin_defect("one_pass_variance"), "linear_split", "mean 100 deviation 0.1"),
+    ("LinearSplit", _lin_defect("cat_split"), "linear_split", "cat K1=32 K2=32"),
+    ("LinearSplit", _lin_defect("bias_to_128"), "linear_split", "-> 129 gelu=0 bias=1"),
 )
 DEFECT_IDS = [d[0] + (" " + d[1].defect if isinstance(getattr(d[1], "defect", None), str) else "") for d in DEFECTS]
 
@@ -767,3 +916,85 @@ def test_conv_many_rows_on_a_small_batch():
         for defect, form in (("res2_dropped", "pre+res+res2"), ("beta_order", "resconv res is in")):
             bad = [r for r in op_checks.check_conv_many(CPU, Recorder(Conv3x3=_conv_defect(defect)), n=4) if not _passes(r)]
             assert bad and all(r.form == form for r in bad) and len(bad) == len(rows) // 2, (defect, [r[0] for r in bad])
+
+
+# ----------------------------------------------------------------------------------------- 5. the transformer rows reach what they name
+def test_transformer_row_lists_reach_every_dispatch_form():
+    """From the restated host rules (op_checks.attn16_ksplit, attn_ksplit, gcorr_ksplit, LIN_WIDE_MIN): the row lists hold every
+    key-run count the rules can choose, uneven splits, both wave forms, both sides of every tile, and the two linear tile forms.  The
+    GPU tests read the same from the kernel trace."""
+    oc = op_checks
+    runs2 = {k: min(c.L for c in oc.ATTN_RUNS if oc.attn_runs(c, 2) == k) for k in {oc.attn_runs(c, 2) for c in oc.ATTN_RUNS}}
+    assert set(runs2) == {1, 2, 3, 4, 5, 6} and {oc.attn_runs(c, 3) for c in oc.ATTN_RUNS} == {1, 2, 4}
+    first = {}
+    for L in range(1, 4200):
+        first.setdefault(oc.attn16_ksplit(1, L, oc.attn16_waves(L)), L)
+    assert first == {1: 1, 2: 449, 3: 705, 4: 961, 5: 2113, 6: 4161}  # the rule's own thresholds for one window
+    assert all(first[k] <= runs2[k] < first[k] + 64 for k in (2, 3, 4, 5, 6))  # each count at the smallest chunk count that gives it
+    assert sum(oc.uneven(c.L, oc.attn_runs(c, 2)) for c in oc.ATTN_RUNS) >= 2 and sum(oc.uneven(c.L, oc.attn_runs(c, 3)) for c in oc.ATTN_RUNS) >= 2
+    assert {oc.attn16_waves(c.L) for c in oc.ATTN_CASES} == {4, 8} and {187, 192, 195} <= {c.L for c in oc.ATTN_GEOMETRY}
+    assert {63, 64, 65, 127, 128, 129, 255, 256, 257, 70} <= {c.L for c in oc.ATTN_GEOMETRY}
+    assert {1, 4, 9, 16, 18} <= {c.nwin for c in oc.ATTN_GEOMETRY}
+    assert any(c.w // c.splits == 1 and c.L > 64 and not c.shift for c in oc.ATTN_GEOMETRY)
+    assert any(c.shift and (c.h // c.splits) % 2 and (c.w // c.splits) % 2 for c in oc.ATTN_GEOMETRY)
+    assert any(c.b == 2 and c.shift and oc.attn_runs(c, 2) > 1 and oc.attn_runs(c, 3) > 1 for c in oc.ATTN_GEOMETRY)
+    assert [c.L for c in oc.ATTN_TABLE] == [oc.ATTN_TAB_CAP, oc.ATTN_TAB_CAP + 64, oc.ATTN_TAB_CAP + 64] and oc.ATTN_TABLE[2].shift  # the last walk that takes the table, the first that cannot
+    got = {oc.gcorr_ksplit(h * w) for h, w in oc.GCORR_RUNS} | {oc.gcorr_ksplit(h * w) for h, w in oc.GCORR_MAPS}
+    assert got == {1, 2, 3, 4, 5, 6, 7, 8}
+    first = {}
+    for L in range(1, 2100):
+        first.setdefault(oc.gcorr_ksplit(L), L)
+    assert first == {1: 1, 2: 449, 3: 705, 4: 961, 5: 1217, 6: 1473, 7: 1729, 8: 1985}
+    # every count at the smallest chunk count that gives it -- even runs of the minimum of 4 chunks -- on a ragged map (L no multiple of 64)
+    smallest = {k: min(h * w for h, w in oc.GCORR_RUNS if oc.gcorr_ksplit(h * w) == k) for k in range(2, 9)}
+    assert all(first[k] <= smallest[k] < first[k] + 64 and smallest[k] % 64 and -(-smallest[k] // 64) == 4 * k for k in range(2, 9)), smallest
+    assert len(set(oc.GCORR_MAPS + oc.GCORR_RUNS)) == len(oc.GCORR_SEEDS) == len(oc.GCORR_MAPS) + len(oc.GCORR_RUNS)
+    assert sum(oc.uneven(h * w, oc.gcorr_ksplit(h * w)) for h, w in oc.GCORR_RUNS) >= 3
+    assert {h * w for h, w in oc.GCORR_MAPS} >= {63, 64, 65, 127, 128, 129, 70} and (1, 70) in oc.GCORR_MAPS and (70, 1) in oc.GCORR_MAPS
+    k, n = oc.LIN_WIDE_KN
+    wgs = [-(-m // 128) * -(-n // 128) for m, _ in oc.LIN_WIDE]
+    assert wgs == [1536, 1504] and [w >= oc.LIN_WIDE_MIN for w in wgs] == [wide for _, wide in oc.LIN_WIDE] and oc.LIN_WIDE[0][0] % 128
+    ms, ns, ks = ({c[i] for c in oc.LIN_EDGES} for i in (0, 2, 1))
+    assert ms == {1, 15, 16, 17, 63, 64, 65, 127, 128, 129} and ns == {1, 15, 16, 17, 40, 127, 128, 129, 384} and ks == {32, 64, 128}
+    assert {c[3] for c in oc.LIN_EDGES} == {True, False} and any(c[2] == 129 and c[3] for c in oc.LIN_EDGES)
+
+
+def test_restated_attention_rules_match_the_library():
+    """drba_window_attention_ws_floats / drba_global_expect2_ws_floats are host functions of the library (no device): the restated
+    rules give the same workspace sizes, i.e. the same larger run count, for every row of the lists and along a sweep of L"""
+    lib, oc = op_checks.conv_lib(), op_checks
+    shapes = [(c.b, c.h, c.w, c.splits) for c in oc.ATTN_CASES + oc.ATTN_TABLE] + [(b, 1, L, 1) for L in range(1, 4300, 7) for b in (1, 8)]
+    for b, h, w, s in shapes:
+        nwin, L = b * s * s, (h // s) * (w // s)
+        ks = max(oc.attn_ksplit(nwin, L), oc.attn16_ksplit(nwin, L, oc.attn16_waves(L)))
+        assert lib.drba_window_attention_ws_floats(b, h, w, s) == (nwin * L * ks * 132 if ks > 1 else 0), (b, h, w, s)
+    for L in list(range(1, 2200, 3)) + [h * w for h, w in oc.GCORR_RUNS + oc.GCORR_MAPS] + [8640]:
+        ks = oc.gcorr_ksplit(L)
+        assert lib.drba_global_expect2_ws_floats(L) == (L * ks * 4 if ks > 1 else 0), L
+
+
+def test_peaked_rows_are_decisive(clean):
+    """the mask rows move by >= 100 tolerances in >= 2 % of their rows under a -inf mask; the late-maximum rows have their maximum in
+    the last chunk (asserted in op_checks.attn_refs / gcorr_refs before anything runs; the figures are in the rows)"""
+    rows = clean["op window attention edges"][0]
+    masks = [c for c in op_checks.ATTN_PEAKED if c.kind == "mask"]
+    assert len(masks) >= 2 and any((c.h // c.splits) % 2 for c in masks)
+    for c in masks:
+        r = op_checks.attn_refs(c)
+        assert r["mask_share"] >= 0.02 and r["mask_diff"] >= 100 * max(row[2] for row in rows if getattr(row, "case", None) == c)
+    late = [c for c in op_checks.ATTN_PEAKED if c.kind == "late"]
+    assert late and all(i // 64 == -(-c.L // 64) - 1 for c in late for i in op_checks.attn_refs(c)["late_argmax"])
+    # on the inputs of the older check (amplitude 1.5, scale sqrt(128)) the mask value is invisible: what these rows are for
+    plain = next(c for c in op_checks.ATTN_GEOMETRY if (c.h, c.w, c.splits, c.shift) == (22, 34, 2, True))
+    q, k, v = (t.double() for t in op_checks.attn_inputs(plain))
+    assert float((op_checks.attn_ref(q, k, v, plain, float("-inf")) - op_checks.attn_refs(plain)["ref64"]).abs().max()) < 1e-12
+
+
+def test_token_table_rows_with_the_standin():
+    """the three C-ABI rows of the GPU suite (3968 and 4032 keys in one walk, and four shifted windows of 4032) on the CPU: the
+    stand-in holds their fp64 rows"""
+    for c in op_checks.ATTN_TABLE:
+        q, k, v = op_checks.attn_inputs(c)
+        with torch.no_grad():
+            row = op_checks.attn_row("window_attention", c, 2, _window_attention(q, k, v, c.h, c.w, c.splits, c.shift, c.scale))
+        assert _passes(row), row
