@@ -5,7 +5,8 @@ drba_softsplat, _index, _again, _gather_quad), of resize_bilinear_scale and flow
 flow update, the final warp + blend -- in the forms the pipeline runs them), and of the 3x3 convolution's epilogue forms with
 every configuration id pinned (conv.hip, conv_split.hip, conv_dma.hip, conv_ks.hip; CONV_FORMS below), and of the three
 GMFlow transformer kernels at their dispatch edges (window_attn.hip, global_corr.hip, linear_split.hip; ATTN_CASES, GCORR_MAPS,
-LIN_EDGES below), shared by
+LIN_EDGES below), and of IFNet's context encoder as one kernel in its two forms at every tile, border and store edge (head_fused.hip,
+head_fused16.hip; HEAD_CASES below), shared by
 tests/test_gpu_op_parity.py, tests/test_op_checks_cpu.py and the diagnostic report (python -m tests.gpu_report).
 
 Every check takes the device the inputs go to and the `ops` namespace under test (default: drba_amd.ops; the CPU test hands
@@ -21,7 +22,8 @@ where `floor` is the max error of the fp32 oracle / fp32 torch evaluation of the
 fp64 reference: measured per row, printed in the row, never calibrated against the code under test.  Decisions (masks, hole
 tests, the DRM retiming walk) and pure data movement are compared bit for bit: err = number of differing elements, tol = 0.  The transformer rows keep three bars of their own, named in
 Row.tol_rule: a two-term attention row max(rule, 3 x the format floor: the fp64 formula on operands rounded to two fp16 terms), the
-coordinate rows of global_expect2 and the linear_split rows the bars tests/gpu_checks.py already holds those kernels to.
+coordinate rows of global_expect2 and the linear_split rows the bars tests/gpu_checks.py already holds those kernels to.  The fused
+encoder's two-term rows stay on the one rule: their format floor is printed, and the CPU suite asserts that three times it is below the rule.
 
 Three places where ATen's CPU result is not the specification are written out instead of taken from ATen:
   * a zeros-padding bilinear sample at a non-finite coordinate is 0 (every tap is outside the image; ATen's CPU kernel forms
@@ -2251,6 +2253,188 @@ def check_linear_split_edges(dev, ops=None):
     return rows
 
 
+# ----------------------------------------------------------------------------------------- the fused IFNet encoder
+# head_fused.hip (exact-fp32 MFMA) and head_fused16.hip (two fp16 terms per operand; what the pipeline runs): Head (IFNet_HDv3.py:23-47)
+# as one kernel.  A workgroup owns a 16 x 64 output tile = 8 x 32 half-resolution positions and computes a 14 x 38 region (row
+# stride 40) of cnn0 around it; the tile geometry is restated here so that the shapes can be chosen -- and asserted -- to reach every
+# edge of it.  The GPU tests read the kernel that ran and its grid from the trace.
+HEAD_H2, HEAD_W2 = 8, 32    # H2, W2, head_fused.hip:37 / head_fused16.hip:37: half-resolution positions per workgroup
+HEAD_RR, HEAD_RS = 14, 40   # RR, RS, head_fused.hip:38-39: region rows, region row stride (what the `interior` test of :98 uses)
+HEAD_ACT_SHIFT = 4          # kSplitActShift: the two-term form holds an activation as two fp16 terms of x / 16
+HEAD_EDGES = ("one tile", "W%8==4", "ring", "interior", "tiles_x>8", "tiles_y>8")
+
+
+def head_tiles(h, w):
+    """(tiles_x, tiles_y) of the launch"""
+    return _cdiv(w // 2, HEAD_W2), _cdiv(h // 2, HEAD_H2)
+
+
+def head_edges(h, w):
+    """which edges of the tile geometry an H x W frame reaches, from H, W and the constants above"""
+    hh, wh = h // 2, w // 2
+    nx, ny = head_tiles(h, w)
+    rows_in = any(HEAD_H2 * ty - 3 >= 0 and HEAD_H2 * ty - 3 + HEAD_RR <= hh for ty in range(ny))   # rm >= 0 && rm + RR <= Hh
+    cols_in = any(HEAD_W2 * tx - 3 >= 0 and HEAD_W2 * tx - 3 + HEAD_RS <= wh for tx in range(nx))   # rn >= 0 && rn + RS <= Wh
+    is_ = {"one tile": nx == 1 and ny == 1, "W%8==4": w % 8 == 4, "interior": rows_in and cols_in, "tiles_x>8": nx > 8, "tiles_y>8": ny > 8,
+           "ring": (nx, ny) == (2, 2) and hh - HEAD_H2 == 3 and wh - HEAD_W2 == 6}  # the second tiles hold exactly the three rings
+    return frozenset(k for k, v in is_.items() if v)
+
+
+HEAD_CASES = (  # (H, W, the edges it reaches): the smallest frame of each
+    (2, 4, ("one tile", "W%8==4")),      # the smallest accepted frame (Hh 1, Wh 2): every position of every layer is border
+    (6, 12, ("one tile", "W%8==4")),     # odd Hh
+    (16, 64, ("one tile",)),             # exactly one full tile
+    (18, 68, ("W%8==4",)),               # one row / two columns into a second tile each way
+    (22, 76, ("ring", "W%8==4")),
+    (38, 140, ("interior", "W%8==4")),   # 3 x 3 tiles, tile (1, 1): rm + 14 = 19 <= 19, rn + 40 = 69 <= 70
+    (40, 144, ("interior",)),
+    (16, 516, ("tiles_x>8", "W%8==4")),  # 1 x 9 tiles: a full strip of 8 and the narrow last strip
+    (130, 4, ("tiles_y>8", "W%8==4")))   # 9 x 1 tiles: two tile rows per band, the last band short
+for _h, _w, _e in HEAD_CASES:
+    assert _h % 2 == 0 and _w % 4 == 0 and head_edges(_h, _w) == frozenset(_e), (_h, _w, sorted(head_edges(_h, _w)))
+assert frozenset().union(*(c[2] for c in HEAD_CASES)) == frozenset(HEAD_EDGES)
+assert (16, 64) in [c[:2] for c in HEAD_CASES] and head_tiles(18, 68) == (2, 2) and head_tiles(38, 140) == (3, 3)
+HEAD_EXTRA = ((18, 68), (38, 140))          # the shapes that also take the frames that are not rand
+HEAD_NAN = (38, 140, 1, 15, 63)             # (H, W, channel, y, x) of the NaN pixel: the seam of tiles (0, 0), (1, 0), (0, 1), (1, 1)
+HEAD_NAN_CONE = ((9, 22), (57, 70))         # rows, columns (inclusive) of all 16 channels it reaches: 7 pixels each way, from (14, 62) / (15, 63)
+HEAD_REFUSED = ((2, 16, 24), (1, 17, 36), (1, 18, 70))  # (N, H, W) ops.head_fused does not take: a batch, odd H, W % 4 == 2
+HEAD_BATCH = (3, 18, 68)                    # (N, H, W) of the C-ABI rows of the GPU suite
+
+
+def head_weights(kind):
+    """[w0, b0, w1, b1, w2, b2, w3, b3] (fp32): "synth": encode.* of synth.ifnet_state_dict(seed=0) (biases of 0.02); "unit bias": a
+    seeded set with fan-in scaled weights and N(0, 1) biases -- a ring that is not zeroed holds lrelu(bias) and the like, loud in every layer"""
+    key = ("head w", kind)
+    if key not in _MEMO:
+        if kind == "synth":
+            sd = synth.ifnet_state_dict(seed=0)
+            _MEMO[key] = [sd[f"encode.cnn{k}.{p}"] for k in range(4) for p in ("weight", "bias")]
+        else:
+            shapes = ((16, 3, 3, 3), (16, 16, 3, 3), (16, 16, 3, 3), (16, 16, 4, 4))
+            fan = (27, 144, 144, 64)
+            _MEMO[key] = [t for k in range(4) for t in (cases.rnd(shapes[k], 6100 + 2 * k, 1.0 / fan[k] ** 0.5), cases.rnd((16,), 6101 + 2 * k, 1.0))]
+    return _MEMO[key]
+
+
+def head_ref(x, wts, dtype=torch.float64, fmt=False):
+    """Head (IFNet_HDv3.py:23-47) in `dtype`.  fmt: the float64 layers on what the two-term form can hold -- weights as two fp16 terms,
+    the frame and every intermediate as two fp16 terms of x / 16 (split again at every layer, as the kernel writes its LDS planes)"""
+    wt = (lambda t: two_term(t)) if fmt else (lambda t: t.to(dtype))          # noqa: E731
+    act = (lambda t: two_term(t, HEAD_ACT_SHIFT)) if fmt else (lambda t: t)   # noqa: E731
+    w0, b0, w1, b1, w2, b2, w3, b3 = wts
+    y = F.leaky_relu(F.conv2d(act(x.to(dtype)), wt(w0), b0.to(dtype), stride=2, padding=1), 0.2)
+    y = F.leaky_relu(F.conv2d(act(y), wt(w1), b1.to(dtype), padding=1), 0.2)
+    y = F.leaky_relu(F.conv2d(act(y), wt(w2), b2.to(dtype), padding=1), 0.2)
+    return F.conv_transpose2d(act(y), wt(w3), b3.to(dtype), stride=2, padding=1)
+
+
+def head_frame(h, w, kind, n=1):
+    """the frame [n, 3, h, w] of an input kind, from a seed of (h, w, kind)"""
+    seed = 6200 + 7 * h + w + 1000 * HEAD_KINDS.index("rand" if kind == "NaN pixel" else kind)  # (the NaN goes into the rand frame)
+    if kind == "zero frame":
+        return torch.zeros(n, 3, h, w)
+    if kind in ("rand", "NaN pixel"):
+        x = torch.rand(n, 3, h, w, generator=torch.Generator().manual_seed(seed))
+        if kind == "NaN pixel":
+            assert (h, w) == HEAD_NAN[:2]
+            x[0, HEAD_NAN[2], HEAD_NAN[3], HEAD_NAN[4]] = float("nan")
+        return x
+    return cases.rnd((n, 3, h, w), seed, {"randn*1e3": 1e3, "randn*1e-3": 1e-3}[kind])
+
+
+HEAD_KINDS = ("rand", "zero frame", "randn*1e3", "randn*1e-3", "NaN pixel")
+HEAD_WEIGHTS = {"zero frame": "unit bias"}  # input kind -> weight set (default "synth")
+
+
+def head_inputs():
+    """[(H, W, input kind, the forms it runs in: two-term False / True)]"""
+    out = [(h, w, "rand", (False, True)) for h, w, _ in HEAD_CASES]
+    for h, w in HEAD_EXTRA:
+        out += [(h, w, kind, (False, True)) for kind in HEAD_KINDS[1:4]]
+    return out + [HEAD_NAN[:2] + ("NaN pixel", (False,))]  # (the two-term form reports a NaN it stores: the GPU suite's own test)
+
+
+def head_refs(h, w, kind, n=1):
+    """{x, wkind, ref64, ref32, fmt_floor} of an input: computed once per process, never written to"""
+    key = ("head ref", h, w, kind, n)
+    if key not in _MEMO:
+        x, wkind = head_frame(h, w, kind, n), HEAD_WEIGHTS.get(kind, "synth")
+        wts = head_weights(wkind)
+        r = {"x": x, "wkind": wkind, "ref64": head_ref(x, wts), "ref32": head_ref(x, wts, torch.float32)}
+        r["fmt_floor"] = _err(head_ref(x, wts, fmt=True), r["ref64"])
+        _MEMO[key] = r
+    return _MEMO[key]
+
+
+def head_layers(ops, dev, wkind):
+    """((cnn0, cnn1, cnn2, cnn3), holder) as ops.head_fused takes them, built from the namespace's own layer classes"""
+    import types
+    w0, b0, w1, b1, w2, b2, w3, b3 = head_weights(wkind)
+    return (ops.Conv3x3(w0, b0, stride=2, act=True, device=dev), ops.Conv3x3(w1, b1, stride=1, act=True, device=dev),
+            ops.Conv3x3(w2, b2, stride=1, act=True, device=dev), ops.Deconv4x4(w3, b3, pixel_shuffle=False, device=dev)), types.SimpleNamespace()
+
+
+def pair_layout(f):
+    """[1, 16, H, W] -> [8, H, W, 2] by torch indexing (as check_layouts states pair_interleaved)"""
+    _, c, h, w = f.shape
+    return f.detach().cpu()[0].view(c // 2, 2, h, w).permute(0, 2, 3, 1).contiguous()
+
+
+def head_value_row(op, name, got, r, two, extra=""):
+    """the planar result against fp64 under the series' one rule; a two-term row also carries and prints the format floor (no bar of
+    its own: tests/test_op_checks_cpu.py asserts that 3 x fmt_floor stays below the rule's tolerance on every row)"""
+    row = value_row(op, name, got, r["ref64"], r["ref32"], (f"fmt_floor={r['fmt_floor']:.2e} " if two else "") + extra)
+    row.two, row.fmt_floor = two, r["fmt_floor"]
+    return row
+
+
+def check_head_fused(dev, ops=None):
+    """ops.head_fused in both forms (HEAD_TWO_TERM False: head_fused.hip, True: head_fused16.hip) on every shape of HEAD_CASES with
+    uniform [0, 1) frames, and at HEAD_EXTRA on an all-zero frame (unit-bias weights), on signed frames of scale 1e3 and 1e-3 and, fp32
+    form, with one NaN pixel at a seam of four tiles.  Per (input, form): the planar result against the four fp64 layers; the pair
+    copy attached to it, the planar=False result and features_planar of that, each bit for bit against the layout they restate; the
+    pair-only tag.  Then the shapes ops.head_fused does not take (None).  There is no inf input: both kernels pad K with zero-weight
+    taps that read a tap of the same position again, so 0 * inf gives NaN where the reference keeps inf, and inf is outside the
+    documented input range of both forms."""
+    ops = ops or default_ops()
+    op, rows, inf = "head_fused", [], float("inf")
+    try:
+        for two in (False, True):
+            ops.HEAD_TWO_TERM = two
+            form = "two-term" if two else "fp32"
+            built = {k: head_layers(ops, dev, k) for k in ("synth", "unit bias")}
+            for h, w, kind, forms in head_inputs():
+                if two not in forms:
+                    continue
+                name = f"{form} {kind} {h}x{w}"
+                try:
+                    r = head_refs(h, w, kind)
+                    layers, holder = built[r["wkind"]]
+                    x = r["x"].to(dev)
+                    f = ops.head_fused(x, layers, holder)
+                    fp = getattr(f, "_drba_pair", None)
+                    if f is None or fp is None:
+                        rows.append(Row(op, f"{name}: planar", inf, 0.0, "not taken" if f is None else "no _drba_pair copy on the result"))
+                        continue
+                    nx, ny = head_tiles(h, w)
+                    rows.append(head_value_row(op, f"{name}: planar vs fp64", f, r, two, f"tiles={nx}x{ny}"))
+                    rows.append(exact_row(op, f"{name}: pair copy == the pair layout of the planar result", fp, pair_layout(f)))
+                    f2 = ops.head_fused(x, layers, holder, planar=False)
+                    rows.append(exact_row(op, f"{name}: planar=False == the pair copy of the planar call", f2, fp))
+                    tagged = bool(getattr(f2, "_drba_is_pair", False)) and bool(ops.is_pair(f2))  # (at H = 2 the shape alone does not say so)
+                    rows.append(Row(op, f"{name}: planar=False result carries the pair tag", 0.0 if tagged else inf, 0.0, f"shape {tuple(f2.shape)}"))
+                    rows.append(exact_row(op, f"{name}: features_planar(planar=False) == planar", ops.features_planar(f2), f))
+                except Exception as e:  # noqa: BLE001
+                    rows.append(Row(op, name, inf, 0.0, f"EXC {type(e).__name__}: {e}"))
+            layers, holder = built["synth"]
+            for n, h, w in HEAD_REFUSED:
+                got = ops.head_fused(head_frame(h, w, "rand", n).to(dev), layers, holder)
+                rows.append(Row(op, f"{form} [{n}, 3, {h}, {w}] is not taken", 0.0 if got is None else inf, 0.0, "None: the caller runs the layers"))
+    finally:
+        ops.HEAD_FUSED, ops.HEAD_TWO_TERM = True, None
+    return rows
+
+
 SPLAT_CHECKS = (check_softsplat, check_softsplat_scan, check_softsplat_big)  # the generic splat's families, for tests that take them together
 CHECKS = (  # (section title, check): one operator family each
     ("op softmax_rows_", check_softmax_rows), ("op instance_norm", check_instance_norm), ("op conv_direct", check_conv_direct),
@@ -2263,5 +2447,6 @@ CHECKS = (  # (section title, check): one operator family each
     ("op stage input, first stage", check_stage_input_first), ("op stage input, warped", check_stage_input_warped),
     ("op stage input + conv0[0] fused", check_stage_conv_fused), ("op flow update", check_flow_update), ("op warp + blend", check_warp_blend),
     ("op conv epilogue forms", check_conv_forms_all), ("op window attention edges", check_window_attention_edges),
-    ("op global_expect2 edges", check_global_expect2_edges), ("op linear_split edges", check_linear_split_edges))
+    ("op global_expect2 edges", check_global_expect2_edges), ("op linear_split edges", check_linear_split_edges),
+    ("op fused encoder", check_head_fused))
 GLUE_CHECKS = (check_stage_input_first, check_stage_input_warped, check_stage_conv_fused, check_flow_update, check_warp_blend)

@@ -6,7 +6,10 @@ image borders, partial tiles and blocks, every dispatch branch, batch > 1, grid-
 twice.  One operator family per test, so that a failure names it.  The 3x3 convolution's epilogue forms (op_checks.CONV_FORMS: what
 the GMFlow / GMFSS layers construct) run with every configuration id pinned, one test per kernel family and form group.  The fused
 window attention, the global expectation and the split linear layer run at every edge of their host dispatch (key runs, wave forms,
-token table, tile forms), with the form that ran read from the kernel trace and sentinels behind outputs and workspaces.
+token table, tile forms), with the form that ran read from the kernel trace and sentinels behind outputs and workspaces.  IFNet's
+context encoder as one kernel runs in both of its forms (head_fused.hip, head_fused16.hip) at every tile, border and store edge
+(op_checks.HEAD_CASES), on zero, signed and NaN-pixel frames, as a batch through the C ABI into guarded outputs, at its refusals and at
+the shapes that fall back to the layer chain.
 
 Value rows: tol = max(2e-5 max(1, |ref|max), 3 x the fp32 oracle's own error on that input); decisions and data movement:
 bit-exact.  tests/test_op_checks_cpu.py shows on the CPU that these rows fail for a wrong operator."""
@@ -730,4 +733,202 @@ def test_linear_split_guards(hip_backend):
                 name = f"terms={terms} {what} [{m}x{k}] -> {n} guarded"
                 rows.append(op_checks.lin_row("linear_split", name, out[:m * n].view(m, n), r64, r32, bar))
                 rows.append(op_checks.exact_row("linear_split", f"{name}: the {op_checks.GUARD} floats behind out", out[m * n:], sent))
+    _assert_rows(rows)
+
+
+# ----------------------------------------------------------------------------------------- the fused IFNet encoder
+HEAD_GUARDED = ((2, 4), (6, 12), (130, 4), (16, 516))  # single frames of op_checks.HEAD_CASES that also run into guarded outputs
+HEAD_FORMS = ((False, "fp32", ""), (True, "two-term", "16"))  # (HEAD_TWO_TERM, row label, suffix of the entry point and of the holder's pack)
+
+
+def _drain_status(ops, dev):
+    """the device's overflow word asked for, every kernel finished, and whatever earlier tests left taken out of it"""
+    ops.status_init(dev)
+    torch.cuda.synchronize()
+    ops.overflow_groups(dev)
+
+
+def test_head_fused(hip_backend):
+    """head_fused.hip and head_fused16.hip on the nine shapes of op_checks.HEAD_CASES (the smallest frame, one tile, one position past it,
+    exactly the rings in the second tile, an interior tile with W % 8 == 4 and == 0, nine tiles in a row and in a column), on zero,
+    signed 1e3 / 1e-3 and (fp32) NaN-pixel frames: planar against fp64 under the one rule, both layouts and the planar=False call bit for
+    bit.  Nothing of it is reported as an overflow: every input is inside the two-term form's documented range."""
+    from drba_amd import ops
+    dev = hip_backend.dev
+    _drain_status(ops, dev)
+    rows = op_checks.check_head_fused(dev)
+    torch.cuda.synchronize()
+    reported = ops.overflow_groups(dev)
+    for form in ("fp32", "two-term"):
+        worst = max((r for r in rows if r.floor is not None and f" {form} " in r[0]), key=lambda r: r[1] / r[2])
+        print(f"  largest err / tol, {form}: {worst[1] / worst[2]:.3f} ({worst[0]})")
+    _assert_rows(rows)
+    assert reported == [], reported
+
+
+def test_head_fused_forms_ran(hip_backend):
+    """Under the kernel trace: with HEAD_TWO_TERM False every call is one launch of head_fused, with True one of head_fused16, planar
+    or pair-only, on a grid of (tiles_x * tiles_y, 1) -- the tile counts the case table's edge conditions are computed from."""
+    from drba_amd import ops
+    dev = hip_backend.dev
+    seen = set()
+    try:
+        for two, form, sfx in HEAD_FORMS:
+            ops.HEAD_TWO_TERM = two
+            layers, holder = op_checks.head_layers(ops, dev, "synth")
+            for h, w, _ in op_checks.HEAD_CASES:
+                x = op_checks.head_refs(h, w, "rand")["x"].to(dev)
+                nx, ny = op_checks.head_tiles(h, w)
+                for planar in (True, False):
+                    recs = _traced_recs(lambda: ops.head_fused(x, layers, holder, planar=planar))
+                    print(f"  {form} {h}x{w} planar={int(planar)}: {[(r['name'], tuple(r['grid'])) for r in recs]}")
+                    assert len(recs) == 1 and "head_fused" in recs[0]["name"], recs
+                    assert ("head_fused16" in recs[0]["name"]) == two, (two, recs[0]["name"])
+                    assert tuple(recs[0]["grid"][:2]) == (nx * ny, 1), (h, w, recs[0]["grid"])
+                    seen.add(recs[0]["name"])
+    finally:
+        ops.HEAD_FUSED, ops.HEAD_TWO_TERM = True, None
+    assert len(seen) == 2, seen
+
+
+def test_head_fused_batch_and_guards(hip_backend):
+    """drba_head_fused / drba_head_fused16 through the C ABI with N = 3 different 18 x 68 frames (blockIdx.y offsets of 3 P and 16 P),
+    f_out and f_pair_out each in the middle of a NaN-prefilled allocation between sentinels: every item against fp64 and bit for bit
+    equal to the N = 1 launch of its frame, no NaN left (every element written), the sentinels untouched; then f_out = NULL, which
+    leaves the same f_pair_out; then the four most cut single frames (HEAD_GUARDED) between the same sentinels."""
+    import ctypes as C
+    from drba_amd import _lib, ops
+    lib, dev = _lib.load(), hip_backend.dev
+    n, h, w = op_checks.HEAD_BATCH
+    r = op_checks.head_refs(h, w, "rand", n)
+    x = r["x"].to(dev)
+    ptr = lambda t: C.c_void_p(0 if t is None else t.data_ptr())  # noqa: E731
+    op, rows = "head_fused", []
+    nx, ny = op_checks.head_tiles(h, w)
+    try:
+        for two, form, sfx in HEAD_FORMS:
+            ops.HEAD_TWO_TERM = two
+            layers, holder = op_checks.head_layers(ops, dev, "synth")
+            singles = [ops.head_fused(x[k:k + 1].clone(), layers, holder) for k in range(n)]  # the N = 1 launches (the first packs the weights)
+            pk, launch = getattr(holder, "_fused_pack" + sfx), getattr(lib, "drba_head_fused" + sfx)
+            name = f"{form} N={n} {h}x{w}"
+            bf, f = op_checks.conv_guarded((n, 16, h, w), dev)
+            bp, fp = op_checks.conv_guarded((n, 8, h, w, 2), dev)
+            rc = []
+            recs = _traced_recs(lambda: rc.append(launch(ptr(x), ptr(pk), ptr(f), ptr(fp), n, h, w, ops._stream())))
+            print(f"  {name}: {[(q['name'], tuple(q['grid'])) for q in recs]}")
+            assert rc == [0] and len(recs) == 1 and tuple(recs[0]["grid"][:2]) == (nx * ny, n), (rc, recs)
+            for k in range(n):
+                rows.append(op_checks.value_row(op, f"{name} item {k}: planar vs fp64", f[k:k + 1], r["ref64"][k:k + 1], r["ref32"][k:k + 1]))
+                rows.append(op_checks.exact_row(op, f"{name} item {k}: planar == the N=1 launch of frame {k}", f[k:k + 1], singles[k]))
+                rows.append(op_checks.exact_row(op, f"{name} item {k}: pair layout == the N=1 launch of frame {k}", fp[k], singles[k]._drba_pair))
+            left = int(f.isnan().sum()) + int(fp.isnan().sum())
+            rows.append(op_checks.Row(op, f"{name}: NaN left of the prefill in f_out / f_pair_out", float(left), 0.0, "every element written"))
+            rows.append(op_checks.guard_row(op, f"{name} f_out", bf))
+            rows.append(op_checks.guard_row(op, f"{name} f_pair_out", bp))
+            bp2, fp2 = op_checks.conv_guarded((n, 8, h, w, 2), dev)
+            assert launch(ptr(x), ptr(pk), ptr(None), ptr(fp2), n, h, w, ops._stream()) == 0
+            torch.cuda.synchronize()
+            rows.append(op_checks.exact_row(op, f"{name} f_out=NULL: f_pair_out == the launch that also writes planes", fp2, fp))
+            rows.append(op_checks.guard_row(op, f"{name} f_out=NULL f_pair_out", bp2))
+            # the frames whose last tile is cut the most, one each, between the same sentinels: the smallest, one tile with a half
+            # tile's tail, nine tiles in a column of a 4-pixel row, nine in a row with the tail in the narrow last strip
+            for gh, gw in HEAD_GUARDED:
+                g = op_checks.head_refs(gh, gw, "rand")
+                xg = g["x"].to(dev)
+                bf, f = op_checks.conv_guarded((1, 16, gh, gw), dev)
+                bp, fp = op_checks.conv_guarded((8, gh, gw, 2), dev)
+                assert launch(ptr(xg), ptr(pk), ptr(f), ptr(fp), 1, gh, gw, ops._stream()) == 0
+                torch.cuda.synchronize()
+                rows.append(op_checks.head_value_row(op, f"{form} guarded {gh}x{gw}: planar vs fp64", f, g, two))
+                rows.append(op_checks.exact_row(op, f"{form} guarded {gh}x{gw}: pair layout == the pair layout of the planar result", fp, op_checks.pair_layout(f)))
+                rows.append(op_checks.guard_row(op, f"{form} guarded {gh}x{gw} f_out", bf))
+                rows.append(op_checks.guard_row(op, f"{form} guarded {gh}x{gw} f_pair_out", bp))
+    finally:
+        ops.HEAD_FUSED, ops.HEAD_TWO_TERM = True, None
+    _assert_rows(rows)
+
+
+def test_head_fused16_nan_pixel(hip_backend):
+    """The NaN pixel at the seam of four tiles in the two-term form: NaN in exactly the cone the reference has (rows 9..22, columns
+    57..70, all 16 channels), fp64 values elsewhere, both layouts alike -- and the kernel reports the NaN it stored: the status word
+    names head_fused16 and nothing else.  Reading it takes it back, so later tests see the word clean."""
+    from drba_amd import ops
+    dev = hip_backend.dev
+    h, w = op_checks.HEAD_NAN[:2]
+    r = op_checks.head_refs(h, w, "NaN pixel")
+    _drain_status(ops, dev)
+    try:
+        ops.HEAD_TWO_TERM = True
+        layers, holder = op_checks.head_layers(ops, dev, "synth")
+        x = r["x"].to(dev)
+        (f, f2), names = _traced(lambda: (ops.head_fused(x, layers, holder), ops.head_fused(x, layers, holder, planar=False)))
+        groups = ops.overflow_groups(dev)  # (_traced synchronises: both launches are done)
+    finally:
+        ops.HEAD_FUSED, ops.HEAD_TWO_TERM = True, None
+    assert len(names) == 2 and all("head_fused16" in k for k in names), names
+    (ra, rb), (ca, cb) = op_checks.HEAD_NAN_CONE
+    want = torch.zeros(1, 16, h, w, dtype=torch.bool)
+    want[:, :, ra:rb + 1, ca:cb + 1] = True
+    name = f"two-term NaN pixel {h}x{w}"
+    rows = [op_checks.head_value_row("head_fused", f"{name}: planar vs fp64", f, r, True),
+            op_checks.exact_row("head_fused", f"{name}: NaN exactly in rows {ra}..{rb} x columns {ca}..{cb}", f.isnan(), want),
+            op_checks.exact_row("head_fused", f"{name}: pair copy == the pair layout of the planar result", f._drba_pair, op_checks.pair_layout(f)),
+            op_checks.exact_row("head_fused", f"{name}: planar=False == the pair copy of the planar call", f2, f._drba_pair)]
+    print(f"  reported: {groups}")
+    _assert_rows(rows)
+    assert groups == ["head_fused16"], groups
+    assert ops.overflow_groups(dev) == []
+
+
+def test_head_fused_refusals(hip_backend):
+    """The return codes of both entry points on tiny real buffers: DRBA_EUNSUPPORTED (-2) for odd H, W % 4 != 0 and N > 65535,
+    DRBA_EINVAL (-1) for N = 0, H = 0 and an output that is not 16-byte aligned -- nothing is launched for any of them -- and 0 for the
+    smallest frame, N = 1, H = 2, W = 4, which launches one workgroup."""
+    import ctypes as C
+    from drba_amd import _lib, ops
+    lib, dev = _lib.load(), hip_backend.dev
+    x = op_checks.head_refs(2, 4, "rand")["x"].to(dev)
+    f, fp = torch.zeros(16 * 2 * 4 + 4, device=dev), torch.zeros(16 * 2 * 4 + 4, device=dev)
+    at = lambda t, off=0: C.c_void_p(t.data_ptr() + off)  # noqa: E731
+    try:
+        for two, form, sfx in HEAD_FORMS:
+            ops.HEAD_TWO_TERM = two
+            layers, holder = op_checks.head_layers(ops, dev, "synth")
+            want = ops.head_fused(x, layers, holder)  # (packs the weights)
+            pk, launch = getattr(holder, "_fused_pack" + sfx), getattr(lib, "drba_head_fused" + sfx)
+            call = lambda n, h, w, fo=0, po=0: launch(at(x), at(pk), at(f, fo), at(fp, po), n, h, w, ops._stream())  # noqa: E731
+            table = (("H = 7", lambda: call(1, 7, 4), -2), ("W = 10", lambda: call(1, 2, 10), -2), ("N = 65536", lambda: call(65536, 2, 4), -2),
+                     ("N = 0", lambda: call(0, 2, 4), -1), ("H = 0", lambda: call(1, 0, 4), -1),
+                     ("f_pair_out + 4 bytes", lambda: call(1, 2, 4, po=4), -1), ("f_out + 4 bytes", lambda: call(1, 2, 4, fo=4), -1),
+                     ("N = 1, H = 2, W = 4", lambda: call(1, 2, 4), 0))
+            for what, go, code in table:
+                rc, names = _traced(go)
+                print(f"  {form} {what}: {rc}, launched {names}")
+                assert rc == code, (form, what, rc, code)
+                assert len(names) == (1 if code == 0 else 0), (form, what, names)
+            torch.cuda.synchronize()
+            assert op_checks._mismatches(f[:16 * 2 * 4].view(1, 16, 2, 4), want) == 0 and float(f[16 * 2 * 4:].abs().max()) == 0.0
+    finally:
+        ops.HEAD_FUSED, ops.HEAD_TWO_TERM = True, None
+
+
+def test_head_fused_fallback_runs_the_layers(hip_backend):
+    """What ops.head_fused does not take -- a batch of two (16 x 24), odd H (17 x 36), W % 4 == 2 (18 x 70) -- goes through Head's
+    layer chain: Head(x) holds the fp64 layers under the same rule, and the trace shows layer kernels and no head_fused launch."""
+    from drba_amd import ops
+    from drba_amd.models.rife_426_heavy.IFNet_HDv3 import Head
+    from drba_amd.utils import synth
+    dev = hip_backend.dev
+    head = Head(synth.ifnet_state_dict(seed=0), "encode.", dev)
+    wts = op_checks.head_weights("synth")
+    rows = []
+    assert ops.HEAD_FUSED is True and ops.HEAD_TWO_TERM is None
+    for n, h, w in op_checks.HEAD_REFUSED:
+        x = op_checks.head_frame(h, w, "rand", n)
+        got, names = _traced(lambda: head(x.to(dev)))
+        print(f"  [{n}, 3, {h}, {w}]: {sorted(set(names))}")
+        assert names and not any("head_fused" in k for k in names), names
+        rows.append(op_checks.value_row("head_fused", f"Head([{n}, 3, {h}, {w}]) through the layer chain vs fp64", got, op_checks.head_ref(x, wts),
+                                        op_checks.head_ref(x, wts, torch.float32)))
     _assert_rows(rows)

@@ -3,7 +3,8 @@
 The "implementation under test" here is a torch-fp32 stand-in for drba_amd.ops, written tap by tap the way the kernels are
 (explicit window loops, explicit bilinear gathers, explicit index arithmetic; the forward splat as a key per source, the
 sources ordered by key and the outputs summing their four segments; the IFNet stage glue with a source index and weight per
-axis, 2 x 2 gathers at clamped coordinates and the running flow summed term by term) -- not with the unfold / grid_sample / F.interpolate /
+axis, 2 x 2 gathers at clamped coordinates and the running flow summed term by term; IFNet's encoder as the four layers with both
+output layouts taken from the same values) -- not with the unfold / grid_sample / F.interpolate /
 corner-by-corner scatter forms the fp64 references use -- so that two independent statements of every formula meet:
   1. every fp64 reference agrees with the fp32 oracle / torch form of the same formula within fp32 roundoff (the measured
      floor of each row is bounded by a figure derived from the number format and the operation's conditioning);
@@ -644,7 +645,55 @@ def _lin_defect(name):
     return type(f"_LinearSplit_{name}", (_LinearSplit,), {"defect": name})
 
 
+# ---- IFNet's encoder as one call: the four layers in fp32, both layouts from the same values
+def _head_layers(x, layers):
+    c0, c1, c2, c3 = layers
+    y = F.leaky_relu(F.conv2d(x, c0.w, c0.b, stride=2, padding=1), 0.2)
+    y = F.leaky_relu(F.conv2d(y, c1.w, c1.b, padding=1), 0.2)
+    y = F.leaky_relu(F.conv2d(y, c2.w, c2.b, padding=1), 0.2)
+    return F.conv_transpose2d(y, c3.w, c3.b, stride=2, padding=1)
+
+
+def _head_fused(img, layers, holder, planar=True, defect=None):
+    n, c, h, w = img.shape
+    if n != 1 or c != 3 or h % 2 or w % 4:
+        return None
+    if defect == "ring_not_zero":  # the positions outside the map hold what the layers make of zeros, not zero
+        f = _head_layers(F.pad(img, (8, 8, 8, 8)), layers)[:, :, 8:-8, 8:-8].contiguous()
+    elif defect == "window_one_short":  # every 16 x 64 tile from a frame window with a halo of 6 pixels where 7 are read
+        f = torch.empty(1, 16, h, w)
+        for y0 in range(0, h, 16):
+            for x0 in range(0, w, 64):
+                ya, xa = max(y0 - 6, 0), max(x0 - 6, 0)
+                t = _head_layers(img[:, :, ya:min(y0 + 22, h), xa:min(x0 + 70, w)], layers)
+                f[:, :, y0:y0 + 16, x0:x0 + 64] = t[:, :, y0 - ya:y0 - ya + 16, x0 - xa:x0 - xa + 64]
+    else:
+        f = _head_layers(img, layers)
+    fp = torch.stack([f[0, 0::2], f[0, 1::2]], -1).contiguous()
+    if defect == "pair_swapped":
+        fp = fp.flip(-1).contiguous()
+    if defect == "tail_unwritten" and w % 8 == 4:  # the planar tail store of a last half tile: the buffer is left as allocated
+        f[..., w - 4:] = float("nan")
+    if not planar:
+        fp._drba_is_pair = True
+        return fp
+    f._drba_pair = fp
+    return f
+
+
+def _is_pair(f):
+    return bool(getattr(f, "_drba_is_pair", False)) or bool(f.dim() == 4 and f.shape[0] == 8 and f.shape[3] == 2 and f.shape[1] > 2 and f.shape[2] > 2)
+
+
+def _features_planar(f):
+    if not _is_pair(f):
+        return f
+    c2, h, w, _ = f.shape
+    return f.permute(0, 3, 1, 2).reshape(1, 2 * c2, h, w).contiguous()
+
+
 STANDIN = dict(
+    head_fused=_head_fused, is_pair=_is_pair, features_planar=_features_planar,
     window_attention=_window_attention, global_expect2=_global_expect2, LinearSplit=_LinearSplit,
     softmax_rows_=_softmax_rows_, instance_norm=_instance_norm, conv_direct=_conv_direct, local_corr_flow=_local_corr_flow,
     local_attn_flow=_local_attn_flow, convex_upsample=_convex_upsample, flow_warp=_flow_warp, backwarp=_backwarp,
@@ -861,6 +910,12 @@ DEFECTS = (  # (operator of the stand-in, its defective variant, the operator fa
     ("LinearSplit", _lin_defect("one_pass_variance"), "linear_split", "mean 100 deviation 0.1"),
     ("LinearSplit", _lin_defect("cat_split"), "linear_split", "cat K1=32 K2=32"),
     ("LinearSplit", _lin_defect("bias_to_128"), "linear_split", "-> 129 gelu=0 bias=1"),
+    # the fused encoder: the out-of-map rings of the intermediates not zeroed; the frame window one pixel short of the 7 a tile reads
+    # beyond its edge; the last four planar columns of a W % 8 == 4 frame not stored; the two channels of a pair exchanged
+    ("head_fused", _with(_head_fused, "ring_not_zero"), "head_fused", "zero frame 18x68"),
+    ("head_fused", _with(_head_fused, "window_one_short"), "head_fused", "38x140"),
+    ("head_fused", _with(_head_fused, "tail_unwritten"), "head_fused", "18x68"),
+    ("head_fused", _with(_head_fused, "pair_swapped"), "head_fused", "pair copy"),
 )
 DEFECT_IDS = [d[0] + (" " + d[1].defect if isinstance(getattr(d[1], "defect", None), str) else "") for d in DEFECTS]
 
@@ -988,6 +1043,86 @@ def test_peaked_rows_are_decisive(clean):
     plain = next(c for c in op_checks.ATTN_GEOMETRY if (c.h, c.w, c.splits, c.shift) == (22, 34, 2, True))
     q, k, v = (t.double() for t in op_checks.attn_inputs(plain))
     assert float((op_checks.attn_ref(q, k, v, plain, float("-inf")) - op_checks.attn_refs(plain)["ref64"]).abs().max()) < 1e-12
+
+
+# ----------------------------------------------------------------------------------------- 6. the fused encoder's rows
+def _head_failed(defect):
+    with torch.no_grad():
+        rows = op_checks.check_head_fused(CPU, Recorder(head_fused=_with(_head_fused, defect)))
+    return rows, [r for r in rows if not _passes(r)]
+
+
+def test_head_case_table_reaches_every_edge(clean):
+    """The case table's edge conditions, recomputed from H, W and the tile constants (op_checks asserts the table against them at
+    import), every shape and input kind among the rows in both forms, and the two-term rows' format floor below the one rule."""
+    oc = op_checks
+    assert [c[:2] for c in oc.HEAD_CASES] == [(2, 4), (6, 12), (16, 64), (18, 68), (22, 76), (38, 140), (40, 144), (16, 516), (130, 4)]
+    by = {c[:2]: oc.head_edges(*c[:2]) for c in oc.HEAD_CASES}
+    assert "interior" in by[(38, 140)] and "W%8==4" in by[(38, 140)] and "interior" in by[(40, 144)] and "W%8==4" not in by[(40, 144)]
+    assert not any("interior" in oc.head_edges(h - 2, w) or "interior" in oc.head_edges(h, w - 4) for h, w in ((38, 140),))  # the smallest such frame
+    assert "tiles_x>8" in by[(16, 516)] and "tiles_y>8" in by[(130, 4)] and "ring" in by[(22, 76)] and "W%8==4" in by[(18, 68)]
+    assert all(by[s] == {"one tile", "W%8==4"} for s in ((2, 4), (6, 12))) and by[(16, 64)] == {"one tile"}
+    rows = clean["op fused encoder"][0]
+    names = [r[0] for r in rows]
+    for form in ("fp32", "two-term"):
+        for h, w, _ in oc.HEAD_CASES:
+            assert sum(f"{form} rand {h}x{w}:" in n for n in names) == 5, (form, h, w)
+        for h, w in oc.HEAD_EXTRA:
+            for kind in ("zero frame", "randn*1e3", "randn*1e-3"):
+                assert sum(f"{form} {kind} {h}x{w}:" in n for n in names) == 5, (form, kind, h, w)
+        assert sum(n.startswith(f"head_fused {form} [") and "is not taken" in n for n in names) == len(oc.HEAD_REFUSED)
+    assert sum("fp32 NaN pixel 38x140:" in n for n in names) == 5 and not any("two-term NaN" in n for n in names)
+    assert any("carries the pair tag" in n and " 2x4:" in n for n in names)
+    two = [r for r in rows if getattr(r, "two", False)]
+    assert len(two) == len(oc.HEAD_CASES) + 3 * len(oc.HEAD_EXTRA)
+    for r in two:  # no second bar for the two-term form: what the format can hold stays well inside the rule
+        assert 3.0 * r.fmt_floor <= r[2] and r[2] == oc.rule_tol(r.refmax, r.floor), (r[0], r.fmt_floor, r[2])
+    big = [r for r in rows if "randn*1e3" in r[0] and r.refmax is not None]
+    assert big and all(1e3 < r.refmax < 65504 for r in big)  # far below the two-term form's documented 65504 * 16
+
+
+def test_head_nan_pixel_reaches_the_cone_of_four_tiles():
+    """One NaN at channel 1, pixel (15, 63) of 38 x 140: the reference is NaN in exactly rows 9..22 x columns 57..70 of all 16
+    channels, in float64 and in float32, across the seam of tiles (0, 0), (0, 1), (1, 0), (1, 1), and finite everywhere else."""
+    oc = op_checks
+    h, w = oc.HEAD_NAN[:2]
+    r = oc.head_refs(h, w, "NaN pixel")
+    assert int(r["x"].isnan().sum()) == 1 and bool(r["x"][0, oc.HEAD_NAN[2], oc.HEAD_NAN[3], oc.HEAD_NAN[4]].isnan())
+    (ra, rb), (ca, cb) = oc.HEAD_NAN_CONE
+    want = torch.zeros(1, 16, h, w, dtype=torch.bool)
+    want[:, :, ra:rb + 1, ca:cb + 1] = True
+    for ref in (r["ref64"], r["ref32"]):
+        assert torch.equal(ref.isnan(), want) and bool(torch.isfinite(ref[~want]).all())
+    assert ra < 16 <= rb and ca < 64 <= cb  # both sides of the 16 x 64 tile seam, on both axes
+
+
+def test_head_window_defect_needs_more_than_one_tile():
+    """A frame window one pixel short is invisible where there is one tile (2x4, 6x12, 16x64) and on a zero frame; every rand row of a
+    frame with more than one tile fails its value row -- what the multi-tile shapes are in the list for."""
+    rows, failed = _head_failed("window_one_short")
+    bad = {r[0] for r in failed}
+    assert all(r.op == "head_fused" and "planar vs fp64" in r[0] for r in failed), sorted(bad)
+    for form in ("fp32", "two-term"):
+        for h, w, edges in op_checks.HEAD_CASES:
+            hit = f"head_fused {form} rand {h}x{w}: planar vs fp64" in bad
+            assert hit == ("one tile" not in edges), (form, h, w, hit)
+        assert not any(f"{form} zero frame" in n for n in bad)
+    assert all(r[1] > 1000 * r[2] for r in failed if " rand " in r[0])  # (a 1e-3 frame moves by ~10 tolerances: the bias dominates it)
+
+
+def test_head_tail_defect_fails_exactly_the_w4_shapes():
+    rows, failed = _head_failed("tail_unwritten")
+    shapes = {(h, w) for h, w, e in op_checks.HEAD_CASES if "W%8==4" in e}
+    hit = {(h, w) for h, w, _ in op_checks.HEAD_CASES if any(f" {h}x{w}:" in r[0] for r in failed)}
+    assert hit == shapes and (40, 144) not in hit and (16, 64) not in hit, sorted(hit)
+    assert not any("planar=False == the pair copy" in r[0] for r in failed)  # the pair layout is stored from the same registers, whole
+
+
+def test_head_pair_defect_fails_no_value_row():
+    rows, failed = _head_failed("pair_swapped")
+    assert failed and all(r[2] == 0.0 and r.floor is None for r in failed), [r[0] for r in failed if r[2] != 0.0]
+    n_inputs = sum(len(forms) for *_, forms in op_checks.head_inputs())
+    assert sum("pair copy == the pair layout" in r[0] for r in failed) == n_inputs == sum("features_planar" in r[0] for r in failed)
 
 
 def test_token_table_rows_with_the_standin():
