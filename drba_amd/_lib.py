@@ -108,7 +108,17 @@ SIGNATURES = {
     "drba_to_inp16_yuv_pad_x4": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
     "drba_to_out_yuv_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "drba_to_out16_yuv_crop": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
+    "drba_to_inp_win_x4": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _f, _f, _p]),
+    "drba_to_inp16_win_x4": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _f, _f, _f, _p]),
+    "drba_to_out_win": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p]),
+    "drba_to_out16_win": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _f, _p]),
+    "drba_to_inp_pad_win_x4": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _p]),
+    "drba_to_inp16_pad_win_x4": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _f, _p]),
+    "drba_to_out_crop_win": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "drba_to_out16_crop_win": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "drba_ssim3d_32": (_i, [_p, _p, _p, _p]),
+    "drba_edge_max_u8": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
+    "drba_edge_max_u16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "drba_dup_stats_ws_floats": (_z, [_i, _i, _i]),
     "drba_dup_stats_f32": (_i, [_p, _p, _i, _i, _i, _f, _p, _p, _p]),
     "drba_ssim3d_ws_floats": (_z, [_i, _i, _i]),

@@ -135,11 +135,12 @@ __device__ __forceinline__ unsigned block_dim_x() { return __builtin_amdgcn_work
 // [Hout,Wout,4] = (c0, c1, c2, 0), when out_x4 is given.
 template <class S>
 __device__ __forceinline__ void to_inp_body(const S s, const typename S::sample_t *__restrict__ in, float *__restrict__ out,
-                                            float *__restrict__ out_x4, int Hin, int Win, int Hout, int Wout, float sy, float sx) {
+                                            float *__restrict__ out_x4, int Hin, int Win, int Hout, int Wout, float sy, float sx,
+                                            size_t pitch) {
   const Tile2D p = tile_pixel(Wout, Hout);
   if (!p.valid) return;
   const Lerp ly = lerp_src_aten(p.y, sy, Hin), lx = lerp_src_aten(p.x, sx, Win);
-  const typename S::sample_t *r0 = in + (size_t)ly.i0 * Win * 3, *r1 = in + (size_t)ly.i1 * Win * 3;
+  const typename S::sample_t *r0 = in + (size_t)ly.i0 * pitch, *r1 = in + (size_t)ly.i1 * pitch;
   const size_t P = (size_t)Hout * Wout, o = (size_t)p.y * Wout + p.x;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -156,12 +157,12 @@ __device__ __forceinline__ void to_inp_body(const S s, const typename S::sample_
 // channels reversed when `rev` (the BGR -> RGB flip of the encoder pipe, tools.py:202, otherwise a host-side copy).
 template <class S>
 __device__ __forceinline__ void to_out_body(const S s, const float *__restrict__ in, typename S::sample_t *__restrict__ out, int Hin,
-                                            int Win, int Hout, int Wout, float sy, float sx, int rev) {
+                                            int Win, int Hout, int Wout, float sy, float sx, int rev, size_t pitch) {
   const Tile2D p = tile_pixel(Wout, Hout);
   if (!p.valid) return;
   const Lerp ly = lerp_out<S>(p.y, sy, Hin, Hout), lx = lerp_out<S>(p.x, sx, Win, Wout);
   const size_t P = (size_t)Hin * Win;
-  typename S::sample_t *o = out + ((size_t)p.y * Wout + p.x) * 3;
+  typename S::sample_t *o = out + (size_t)p.y * pitch + (size_t)p.x * 3;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float *r0 = in + c * P + (size_t)ly.i0 * Win, *r1 = in + c * P + (size_t)ly.i1 * Win;
@@ -178,15 +179,15 @@ __device__ __forceinline__ void to_out_body(const S s, const float *__restrict__
 typedef float f32x4g __attribute__((ext_vector_type(4)));
 template <class S>
 __device__ __forceinline__ void to_inp_rows_body(const S s, const typename S::sample_t *__restrict__ in, float *__restrict__ out,
-                                                 float *__restrict__ out_x4, int Hin, int W, int Hout, float sy) {
+                                                 float *__restrict__ out_x4, int Hin, int W, int Hout, float sy, size_t pitch) {
   const int W4 = W >> 2;
   const size_t total = (size_t)W4 * Hout, P = (size_t)Hout * W;
   for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
     const int y = (int)(i / W4), x = (int)(i - (size_t)y * W4) * 4;
     const Lerp ly = lerp_src_aten(y, sy, Hin);
     Packed<S> a, b;
-    S::load12(in + ((size_t)ly.i0 * W + x) * 3, a.w);
-    S::load12(in + ((size_t)ly.i1 * W + x) * 3, b.w);
+    S::load12(in + (size_t)ly.i0 * pitch + (size_t)x * 3, a.w);
+    S::load12(in + (size_t)ly.i1 * pitch + (size_t)x * 3, b.w);
     f32x4g o[3];
 #pragma unroll
     for (int px = 0; px < 4; ++px)
@@ -208,7 +209,7 @@ __device__ __forceinline__ void to_inp_rows_body(const S s, const typename S::sa
 // finite a, NaN otherwise.
 template <class S>
 __device__ __forceinline__ void to_out_rows_body(const S s, const float *__restrict__ in, typename S::sample_t *__restrict__ out,
-                                                 int Hin, int W, int Hout, float sy, int rev) {
+                                                 int Hin, int W, int Hout, float sy, int rev, size_t pitch) {
   const int W4 = W >> 2;
   const size_t total = (size_t)W4 * Hout, P = (size_t)Hin * W;
   for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
@@ -230,7 +231,7 @@ __device__ __forceinline__ void to_out_rows_body(const S s, const float *__restr
         q[px * 3 + (rev ? 2 - c : c)] = s.quantise(v);
       }
     }
-    S::store12(out + ((size_t)y * W + x) * 3, q);
+    S::store12(out + (size_t)y * pitch + (size_t)x * 3, q);
   }
 }
 
@@ -275,10 +276,10 @@ __device__ __forceinline__ float crop_value(float a) {
 // the general form of the way in: one output pixel per lane, any size
 template <class S>
 __device__ __forceinline__ void to_inp_pad_body(const S s, const typename S::sample_t *__restrict__ in, float *__restrict__ out,
-                                                float *__restrict__ out_x4, int Hin, int Win, int Hout, int Wout) {
+                                                float *__restrict__ out_x4, int Hin, int Win, int Hout, int Wout, size_t pitch) {
   const Tile2D p = tile_pixel(Wout, Hout);
   if (!p.valid) return;
-  const typename S::sample_t *px = in + ((size_t)min(p.y, Hin - 1) * Win + min(p.x, Win - 1)) * 3;
+  const typename S::sample_t *px = in + (size_t)min(p.y, Hin - 1) * pitch + (size_t)min(p.x, Win - 1) * 3;
   const size_t P = (size_t)Hout * Wout, o = (size_t)p.y * Wout + p.x;
   float v[3];
 #pragma unroll
@@ -291,13 +292,13 @@ __device__ __forceinline__ void to_inp_pad_body(const S s, const typename S::sam
 // the rows form (an unchanged width that is a multiple of 4: only rows are added): four pixels per lane, as to_inp_rows_body
 template <class S>
 __device__ __forceinline__ void to_inp_pad_rows_body(const S s, const typename S::sample_t *__restrict__ in, float *__restrict__ out,
-                                                     float *__restrict__ out_x4, int Hin, int W, int Hout) {
+                                                     float *__restrict__ out_x4, int Hin, int W, int Hout, size_t pitch) {
   const int W4 = W >> 2;
   const size_t total = (size_t)W4 * Hout, P = (size_t)Hout * W;
   for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
     const int y = (int)(i / W4), x = (int)(i - (size_t)y * W4) * 4;
     Packed<S> a;
-    S::load12(in + ((size_t)min(y, Hin - 1) * W + x) * 3, a.w);
+    S::load12(in + (size_t)min(y, Hin - 1) * pitch + (size_t)x * 3, a.w);
     f32x4g o[3];
 #pragma unroll
     for (int px = 0; px < 4; ++px)
@@ -315,18 +316,18 @@ __device__ __forceinline__ void to_inp_pad_rows_body(const S s, const typename S
 // the way out: pixel (y, x) of the Hout x Wout window of fp32 [1,3,Hin,Win] -> * scale, quantised
 template <class S>
 __device__ __forceinline__ void to_out_crop_body(const S s, const float *__restrict__ in, typename S::sample_t *__restrict__ out, int Hin,
-                                                 int Win, int Hout, int Wout, int rev) {
+                                                 int Win, int Hout, int Wout, int rev, size_t pitch) {
   const Tile2D p = tile_pixel(Wout, Hout);
   if (!p.valid) return;
   const size_t P = (size_t)Hin * Win, i = (size_t)p.y * Win + p.x;
-  typename S::sample_t *o = out + ((size_t)p.y * Wout + p.x) * 3;
+  typename S::sample_t *o = out + (size_t)p.y * pitch + (size_t)p.x * 3;
 #pragma unroll
   for (int c = 0; c < 3; ++c)
     o[rev ? 2 - c : c] = (typename S::sample_t)s.quantise(__fmul_rn(crop_value<S>(in[c * P + i]), s.scale()));
 }
 template <class S>
 __device__ __forceinline__ void to_out_crop_rows_body(const S s, const float *__restrict__ in, typename S::sample_t *__restrict__ out,
-                                                      int Hin, int W, int Hout, int rev) {
+                                                      int Hin, int W, int Hout, int rev, size_t pitch) {
   const int W4 = W >> 2;
   const size_t total = (size_t)W4 * Hout, P = (size_t)Hin * W;
   for (size_t i = (size_t)blockIdx.x * block_dim_x() + threadIdx.x; i < total; i += (size_t)gridDim.x * block_dim_x()) {
@@ -338,72 +339,74 @@ __device__ __forceinline__ void to_out_crop_rows_body(const S s, const float *__
 #pragma unroll
       for (int px = 0; px < 4; ++px) q[px * 3 + (rev ? 2 - c : c)] = s.quantise(__fmul_rn(crop_value<S>(t[px]), s.scale()));
     }
-    S::store12(out + ((size_t)y * W + x) * 3, q);
+    S::store12(out + (size_t)y * pitch + (size_t)x * 3, q);
   }
 }
 
 // ---- one kernel symbol per depth and form ---------------------------------------------------------------------------------------
 #define DRBA_FRAME_KERNEL __global__ void __launch_bounds__(256)
 DRBA_FRAME_KERNEL to_inp_pad_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,
-                                    int Hout, int Wout) {
-  to_inp_pad_body(Samples8{}, in, out, out_x4, Hin, Win, Hout, Wout);
+                                    int Hout, int Wout, size_t pitch) {
+  to_inp_pad_body(Samples8{}, in, out, out_x4, Hin, Win, Hout, Wout, pitch);
 }
 DRBA_FRAME_KERNEL to_inp16_pad_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,
-                                      int Hout, int Wout, float maxval) {
-  to_inp_pad_body(Samples16{maxval}, in, out, out_x4, Hin, Win, Hout, Wout);
+                                      int Hout, int Wout, size_t pitch, float maxval) {
+  to_inp_pad_body(Samples16{maxval}, in, out, out_x4, Hin, Win, Hout, Wout, pitch);
 }
 DRBA_FRAME_KERNEL to_inp_pad_rows_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int W,
-                                         int Hout) {
-  to_inp_pad_rows_body(Samples8{}, in, out, out_x4, Hin, W, Hout);
+                                         int Hout, size_t pitch) {
+  to_inp_pad_rows_body(Samples8{}, in, out, out_x4, Hin, W, Hout, pitch);
 }
 DRBA_FRAME_KERNEL to_inp16_pad_rows_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin,
-                                           int W, int Hout, float maxval) {
-  to_inp_pad_rows_body(Samples16{maxval}, in, out, out_x4, Hin, W, Hout);
+                                           int W, int Hout, size_t pitch, float maxval) {
+  to_inp_pad_rows_body(Samples16{maxval}, in, out, out_x4, Hin, W, Hout, pitch);
 }
-DRBA_FRAME_KERNEL to_out_crop_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int Win, int Hout, int Wout, int rev) {
-  to_out_crop_body(Samples8{}, in, out, Hin, Win, Hout, Wout, rev);
+DRBA_FRAME_KERNEL to_out_crop_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int Win, int Hout, int Wout, int rev,
+                                     size_t pitch) {
+  to_out_crop_body(Samples8{}, in, out, Hin, Win, Hout, Wout, rev, pitch);
 }
 DRBA_FRAME_KERNEL to_out16_crop_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int Hin, int Win, int Hout, int Wout, int rev,
-                                       float maxval) {
-  to_out_crop_body(Samples16{maxval}, in, out, Hin, Win, Hout, Wout, rev);
+                                       size_t pitch, float maxval) {
+  to_out_crop_body(Samples16{maxval}, in, out, Hin, Win, Hout, Wout, rev, pitch);
 }
-DRBA_FRAME_KERNEL to_out_crop_rows_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int W, int Hout, int rev) {
-  to_out_crop_rows_body(Samples8{}, in, out, Hin, W, Hout, rev);
+DRBA_FRAME_KERNEL to_out_crop_rows_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int W, int Hout, int rev, size_t pitch) {
+  to_out_crop_rows_body(Samples8{}, in, out, Hin, W, Hout, rev, pitch);
 }
 DRBA_FRAME_KERNEL to_out16_crop_rows_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int Hin, int W, int Hout, int rev,
-                                            float maxval) {
-  to_out_crop_rows_body(Samples16{maxval}, in, out, Hin, W, Hout, rev);
+                                            size_t pitch, float maxval) {
+  to_out_crop_rows_body(Samples16{maxval}, in, out, Hin, W, Hout, rev, pitch);
 }
 DRBA_FRAME_KERNEL to_inp_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,
-                                int Hout, int Wout, float sy, float sx) {
-  to_inp_body(Samples8{}, in, out, out_x4, Hin, Win, Hout, Wout, sy, sx);
+                                int Hout, int Wout, float sy, float sx, size_t pitch) {
+  to_inp_body(Samples8{}, in, out, out_x4, Hin, Win, Hout, Wout, sy, sx, pitch);
 }
 DRBA_FRAME_KERNEL to_inp16_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int Win,
-                                  int Hout, int Wout, float sy, float sx, float maxval) {
-  to_inp_body(Samples16{maxval}, in, out, out_x4, Hin, Win, Hout, Wout, sy, sx);
+                                  int Hout, int Wout, float sy, float sx, size_t pitch, float maxval) {
+  to_inp_body(Samples16{maxval}, in, out, out_x4, Hin, Win, Hout, Wout, sy, sx, pitch);
 }
 DRBA_FRAME_KERNEL to_out_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int Win, int Hout, int Wout, float sy,
-                                float sx, int rev) {
-  to_out_body(Samples8{}, in, out, Hin, Win, Hout, Wout, sy, sx, rev);
+                                float sx, int rev, size_t pitch) {
+  to_out_body(Samples8{}, in, out, Hin, Win, Hout, Wout, sy, sx, rev, pitch);
 }
 DRBA_FRAME_KERNEL to_out16_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int Hin, int Win, int Hout, int Wout, float sy,
-                                  float sx, int rev, float maxval) {
-  to_out_body(Samples16{maxval}, in, out, Hin, Win, Hout, Wout, sy, sx, rev);
+                                  float sx, int rev, size_t pitch, float maxval) {
+  to_out_body(Samples16{maxval}, in, out, Hin, Win, Hout, Wout, sy, sx, rev, pitch);
 }
 DRBA_FRAME_KERNEL to_inp_rows_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int W,
-                                     int Hout, float sy) {
-  to_inp_rows_body(Samples8{}, in, out, out_x4, Hin, W, Hout, sy);
+                                     int Hout, float sy, size_t pitch) {
+  to_inp_rows_body(Samples8{}, in, out, out_x4, Hin, W, Hout, sy, pitch);
 }
 DRBA_FRAME_KERNEL to_inp16_rows_kernel(const uint16_t *__restrict__ in, float *__restrict__ out, float *__restrict__ out_x4, int Hin, int W,
-                                       int Hout, float sy, float maxval) {
-  to_inp_rows_body(Samples16{maxval}, in, out, out_x4, Hin, W, Hout, sy);
+                                       int Hout, float sy, size_t pitch, float maxval) {
+  to_inp_rows_body(Samples16{maxval}, in, out, out_x4, Hin, W, Hout, sy, pitch);
 }
-DRBA_FRAME_KERNEL to_out_rows_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int W, int Hout, float sy, int rev) {
-  to_out_rows_body(Samples8{}, in, out, Hin, W, Hout, sy, rev);
+DRBA_FRAME_KERNEL to_out_rows_kernel(const float *__restrict__ in, uint8_t *__restrict__ out, int Hin, int W, int Hout, float sy, int rev,
+                                     size_t pitch) {
+  to_out_rows_body(Samples8{}, in, out, Hin, W, Hout, sy, rev, pitch);
 }
 DRBA_FRAME_KERNEL to_out16_rows_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int Hin, int W, int Hout, float sy, int rev,
-                                       float maxval) {
-  to_out_rows_body(Samples16{maxval}, in, out, Hin, W, Hout, sy, rev);
+                                       size_t pitch, float maxval) {
+  to_out_rows_body(Samples16{maxval}, in, out, Hin, W, Hout, sy, rev, pitch);
 }
 DRBA_FRAME_KERNEL u8_to_f32_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, int H, int W) {
   samples_to_f32_body(Samples8{}, in, out, H, W);
@@ -1221,36 +1224,41 @@ DRBA_YUVL_KERNELS(16, uint16_t, 444, 1)
 // (The launch trace names a kernel by its address, so it reads the same as when the entries launched their kernels by name; only
 // DRBA_LAUNCH's textual fallback for an address without a name would now read `one` / `rows` / `kernel`.)
 template <class T>
-bool rows_form_ok(int Win, int Wout, float scale_x, const T *samples, const float *planes) {
-  return Win == Wout && scale_x == 1.f && (Wout & 3) == 0 && (((uintptr_t)samples & (4 * sizeof(T) - 1)) | ((uintptr_t)planes & 15)) == 0;
+bool rows_form_ok(int Win, int Wout, float scale_x, const T *samples, const float *planes, size_t pitch) {
+  return Win == Wout && scale_x == 1.f && (Wout & 3) == 0 && (pitch & 3) == 0 &&
+         (((uintptr_t)samples & (4 * sizeof(T) - 1)) | ((uintptr_t)planes & 15)) == 0;
 }
+// `pitch`: samples from one row of the packed frame to the next.  The entries without one pass 3 * W (rows without padding); the
+// windowed entries (drba_*_win*) the pitch of the frame their rectangle lies in, which must hold a row of the rectangle.
+bool pitch_ok(int pitch, int W) { return pitch > 0 && (size_t)pitch >= 3 * (size_t)W; }
 
 template <class T, class... M>
-int to_inp_launch(void (*one)(const T *, float *, float *, int, int, int, int, float, float, M...),
-                  void (*rows)(const T *, float *, float *, int, int, int, float, M...), const T *img_hwc, float *out, float *out_x4, int Hin,
-                  int Win, int Hout, int Wout, float scale_y, float scale_x, void *stream, M... maxval) {
-  if (!img_hwc || !out || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || ((uintptr_t)out_x4 & 15) != 0) return DRBA_EINVAL;
-  if (rows_form_ok(Win, Wout, scale_x, img_hwc, out))
+int to_inp_launch(void (*one)(const T *, float *, float *, int, int, int, int, float, float, size_t, M...),
+                  void (*rows)(const T *, float *, float *, int, int, int, float, size_t, M...), const T *img_hwc, int pitch, float *out,
+                  float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x, void *stream, M... maxval) {
+  if (!img_hwc || !out || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || ((uintptr_t)out_x4 & 15) != 0 || !pitch_ok(pitch, Win))
+    return DRBA_EINVAL;
+  if (rows_form_ok(Win, Wout, scale_x, img_hwc, out, pitch))
     DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4, Hin, Wout,
-                Hout, scale_y, maxval...);
+                Hout, scale_y, (size_t)pitch, maxval...);
   else
     DRBA_LAUNCH(one, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4, Hin, Win, Hout, Wout, scale_y,
-                scale_x, maxval...);
+                scale_x, (size_t)pitch, maxval...);
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }
 
 template <class T, class... M>
-int to_out_launch(void (*one)(const float *, T *, int, int, int, int, float, float, int, M...),
-                  void (*rows)(const float *, T *, int, int, int, float, int, M...), const float *in, T *out_hwc, int Hin, int Win, int Hout,
-                  int Wout, float scale_y, float scale_x, int reverse_channels, void *stream, M... maxval) {
-  if (!in || !out_hwc || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0) return DRBA_EINVAL;
-  if (rows_form_ok(Win, Wout, scale_x, out_hwc, in))
+int to_out_launch(void (*one)(const float *, T *, int, int, int, int, float, float, int, size_t, M...),
+                  void (*rows)(const float *, T *, int, int, int, float, int, size_t, M...), const float *in, T *out_hwc, int pitch, int Hin,
+                  int Win, int Hout, int Wout, float scale_y, float scale_x, int reverse_channels, void *stream, M... maxval) {
+  if (!in || !out_hwc || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || !pitch_ok(pitch, Wout)) return DRBA_EINVAL;
+  if (rows_form_ok(Win, Wout, scale_x, out_hwc, in, pitch))
     DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Wout, Hout,
-                scale_y, reverse_channels, maxval...);
+                scale_y, reverse_channels, (size_t)pitch, maxval...);
   else
     DRBA_LAUNCH(one, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Win, Hout, Wout, scale_y,
-                scale_x, reverse_channels, maxval...);
+                scale_x, reverse_channels, (size_t)pitch, maxval...);
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }
@@ -1258,28 +1266,32 @@ int to_out_launch(void (*one)(const float *, T *, int, int, int, int, float, flo
 // fit = pad: the network tensor is at least the frame (way in) and the frame at most the network tensor (way out); the rows form
 // under the same rule as above, the width being unchanged where only rows are added or dropped
 template <class T, class... M>
-int to_inp_pad_launch(void (*one)(const T *, float *, float *, int, int, int, int, M...), void (*rows)(const T *, float *, float *, int, int, int, M...),
-                      const T *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, void *stream, M... maxval) {
-  if (!img_hwc || !out || Hin <= 0 || Win <= 0 || Hout < Hin || Wout < Win || ((uintptr_t)out_x4 & 15) != 0) return DRBA_EINVAL;
-  if (rows_form_ok(Win, Wout, 1.f, img_hwc, out))
+int to_inp_pad_launch(void (*one)(const T *, float *, float *, int, int, int, int, size_t, M...),
+                      void (*rows)(const T *, float *, float *, int, int, int, size_t, M...), const T *img_hwc, int pitch, float *out,
+                      float *out_x4, int Hin, int Win, int Hout, int Wout, void *stream, M... maxval) {
+  if (!img_hwc || !out || Hin <= 0 || Win <= 0 || Hout < Hin || Wout < Win || ((uintptr_t)out_x4 & 15) != 0 || !pitch_ok(pitch, Win))
+    return DRBA_EINVAL;
+  if (rows_form_ok(Win, Wout, 1.f, img_hwc, out, pitch))
     DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4, Hin, Wout,
-                Hout, maxval...);
+                Hout, (size_t)pitch, maxval...);
   else
-    DRBA_LAUNCH(one, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4, Hin, Win, Hout, Wout, maxval...);
+    DRBA_LAUNCH(one, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, img_hwc, out, out_x4, Hin, Win, Hout, Wout,
+                (size_t)pitch, maxval...);
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }
 
 template <class T, class... M>
-int to_out_crop_launch(void (*one)(const float *, T *, int, int, int, int, int, M...), void (*rows)(const float *, T *, int, int, int, int, M...),
-                       const float *in, T *out_hwc, int Hin, int Win, int Hout, int Wout, int reverse_channels, void *stream, M... maxval) {
-  if (!in || !out_hwc || Hout <= 0 || Wout <= 0 || Hout > Hin || Wout > Win) return DRBA_EINVAL;
-  if (rows_form_ok(Win, Wout, 1.f, out_hwc, in))
+int to_out_crop_launch(void (*one)(const float *, T *, int, int, int, int, int, size_t, M...),
+                       void (*rows)(const float *, T *, int, int, int, int, size_t, M...), const float *in, T *out_hwc, int pitch, int Hin,
+                       int Win, int Hout, int Wout, int reverse_channels, void *stream, M... maxval) {
+  if (!in || !out_hwc || Hout <= 0 || Wout <= 0 || Hout > Hin || Wout > Win || !pitch_ok(pitch, Wout)) return DRBA_EINVAL;
+  if (rows_form_ok(Win, Wout, 1.f, out_hwc, in, pitch))
     DRBA_LAUNCH(rows, dim3(grid_for((size_t)(Wout >> 2) * Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Wout, Hout,
-                reverse_channels, maxval...);
+                reverse_channels, (size_t)pitch, maxval...);
   else
     DRBA_LAUNCH(one, dim3(tiles_for(Wout, Hout)), dim3(kBlock), 0, (hipStream_t)stream, in, out_hwc, Hin, Win, Hout, Wout, reverse_channels,
-                maxval...);
+                (size_t)pitch, maxval...);
   DRBA_CHECK_LAUNCH();
   return DRBA_OK;
 }
@@ -1443,7 +1455,7 @@ int drba_f32nchw_to_u8hwc(const float *in, uint8_t *out, int H, int W, void *str
 
 int drba_to_inp_x4(const uint8_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
                    void *stream) {
-  return to_inp_launch(to_inp_kernel, to_inp_rows_kernel, img_hwc, out, out_x4, Hin, Win, Hout, Wout, scale_y, scale_x, stream);
+  return to_inp_launch(to_inp_kernel, to_inp_rows_kernel, img_hwc, 3 * Win, out, out_x4, Hin, Win, Hout, Wout, scale_y, scale_x, stream);
 }
 
 int drba_to_inp(const uint8_t *img_hwc, float *out, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
@@ -1453,7 +1465,7 @@ int drba_to_inp(const uint8_t *img_hwc, float *out, int Hin, int Win, int Hout, 
 
 int drba_to_out(const float *in, uint8_t *out_hwc, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
                 int reverse_channels, void *stream) {
-  return to_out_launch(to_out_kernel, to_out_rows_kernel, in, out_hwc, Hin, Win, Hout, Wout, scale_y, scale_x, reverse_channels, stream);
+  return to_out_launch(to_out_kernel, to_out_rows_kernel, in, out_hwc, 3 * Wout, Hin, Win, Hout, Wout, scale_y, scale_x, reverse_channels, stream);
 }
 
 int drba_u16hwc_to_f32nchw(const uint16_t *in, float *out, int H, int W, float maxval, void *stream) {
@@ -1469,14 +1481,14 @@ int drba_f32nchw_to_u16hwc(const float *in, uint16_t *out, int H, int W, float m
 int drba_to_inp16_x4(const uint16_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y,
                      float scale_x, float maxval, void *stream) {
   if (!maxval_ok(maxval) || ((uintptr_t)img_hwc & 1) != 0) return DRBA_EINVAL;
-  return to_inp_launch(to_inp16_kernel, to_inp16_rows_kernel, img_hwc, out, out_x4, Hin, Win, Hout, Wout, scale_y, scale_x, stream, maxval);
+  return to_inp_launch(to_inp16_kernel, to_inp16_rows_kernel, img_hwc, 3 * Win, out, out_x4, Hin, Win, Hout, Wout, scale_y, scale_x, stream, maxval);
 }
 
 int drba_to_out16(const float *in, uint16_t *out_hwc, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
                   int reverse_channels, float maxval, void *stream) {
   if (!maxval_ok(maxval) || ((uintptr_t)out_hwc & 1) != 0) return DRBA_EINVAL;
-  return to_out_launch(to_out16_kernel, to_out16_rows_kernel, in, out_hwc, Hin, Win, Hout, Wout, scale_y, scale_x, reverse_channels, stream,
-                       maxval);
+  return to_out_launch(to_out16_kernel, to_out16_rows_kernel, in, out_hwc, 3 * Wout, Hin, Win, Hout, Wout, scale_y, scale_x, reverse_channels,
+                       stream, maxval);
 }
 
 int drba_to_inp_yuv420_x4(const uint8_t *y, const uint8_t *u, const uint8_t *v, int y_stride, int c_stride, float *out, float *out_x4, int Hin,
@@ -1506,22 +1518,23 @@ int drba_to_out16_yuv420(const float *in, uint16_t *y, uint16_t *u, uint16_t *v,
 
 // ---- fit = pad: each entry takes its resize sibling's arguments without the two scale factors -----------------------------------
 int drba_to_inp_pad_x4(const uint8_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, void *stream) {
-  return to_inp_pad_launch(to_inp_pad_kernel, to_inp_pad_rows_kernel, img_hwc, out, out_x4, Hin, Win, Hout, Wout, stream);
+  return to_inp_pad_launch(to_inp_pad_kernel, to_inp_pad_rows_kernel, img_hwc, 3 * Win, out, out_x4, Hin, Win, Hout, Wout, stream);
 }
 
 int drba_to_inp16_pad_x4(const uint16_t *img_hwc, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float maxval, void *stream) {
   if (!maxval_ok(maxval) || ((uintptr_t)img_hwc & 1) != 0) return DRBA_EINVAL;
-  return to_inp_pad_launch(to_inp16_pad_kernel, to_inp16_pad_rows_kernel, img_hwc, out, out_x4, Hin, Win, Hout, Wout, stream, maxval);
+  return to_inp_pad_launch(to_inp16_pad_kernel, to_inp16_pad_rows_kernel, img_hwc, 3 * Win, out, out_x4, Hin, Win, Hout, Wout, stream, maxval);
 }
 
 int drba_to_out_crop(const float *in, uint8_t *out_hwc, int Hin, int Win, int Hout, int Wout, int reverse_channels, void *stream) {
-  return to_out_crop_launch(to_out_crop_kernel, to_out_crop_rows_kernel, in, out_hwc, Hin, Win, Hout, Wout, reverse_channels, stream);
+  return to_out_crop_launch(to_out_crop_kernel, to_out_crop_rows_kernel, in, out_hwc, 3 * Wout, Hin, Win, Hout, Wout, reverse_channels, stream);
 }
 
 int drba_to_out16_crop(const float *in, uint16_t *out_hwc, int Hin, int Win, int Hout, int Wout, int reverse_channels, float maxval,
                        void *stream) {
   if (!maxval_ok(maxval) || ((uintptr_t)out_hwc & 1) != 0) return DRBA_EINVAL;
-  return to_out_crop_launch(to_out16_crop_kernel, to_out16_crop_rows_kernel, in, out_hwc, Hin, Win, Hout, Wout, reverse_channels, stream, maxval);
+  return to_out_crop_launch(to_out16_crop_kernel, to_out16_crop_rows_kernel, in, out_hwc, 3 * Wout, Hin, Win, Hout, Wout, reverse_channels, stream,
+                            maxval);
 }
 
 int drba_to_inp_yuv420_pad_x4(const uint8_t *y, const uint8_t *u, const uint8_t *v, int y_stride, int c_stride, float *out, float *out_x4,
@@ -1546,6 +1559,57 @@ int drba_to_out16_yuv420_crop(const float *in, uint16_t *y, uint16_t *u, uint16_
                               int Wout, int matrix, int full_range, float maxval, void *stream) {
   return to_out_yuv_crop_launch(to_out16_yuv_crop_kernel, to_out16_yuv_crop_rows_kernel, in, y, u, v, y_stride, c_stride, Hin, Win, Hout, Wout,
                                 matrix, full_range, maxval, stream);
+}
+
+// ---- a window of a packed frame (--crop): the eight packed entries above with the frame's row pitch -----------------------------------
+// `img_hwc` / `out_hwc` point at the window's first sample, `pitch` counts the samples from one row of the FRAME to the next
+// (>= 3 * the window's width, otherwise DRBA_EINVAL); the window is converted exactly as a frame of its own size: same kernels, the
+// clamps at its edges.  The rows form also asks for pitch % 4 == 0, so that every row of the window is aligned as its first.
+int drba_to_inp_win_x4(const uint8_t *img_hwc, int pitch, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y,
+                       float scale_x, void *stream) {
+  return to_inp_launch(to_inp_kernel, to_inp_rows_kernel, img_hwc, pitch, out, out_x4, Hin, Win, Hout, Wout, scale_y, scale_x, stream);
+}
+
+int drba_to_inp16_win_x4(const uint16_t *img_hwc, int pitch, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y,
+                         float scale_x, float maxval, void *stream) {
+  if (!maxval_ok(maxval) || ((uintptr_t)img_hwc & 1) != 0) return DRBA_EINVAL;
+  return to_inp_launch(to_inp16_kernel, to_inp16_rows_kernel, img_hwc, pitch, out, out_x4, Hin, Win, Hout, Wout, scale_y, scale_x, stream,
+                       maxval);
+}
+
+int drba_to_out_win(const float *in, uint8_t *out_hwc, int pitch, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
+                    int reverse_channels, void *stream) {
+  return to_out_launch(to_out_kernel, to_out_rows_kernel, in, out_hwc, pitch, Hin, Win, Hout, Wout, scale_y, scale_x, reverse_channels,
+                       stream);
+}
+
+int drba_to_out16_win(const float *in, uint16_t *out_hwc, int pitch, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
+                      int reverse_channels, float maxval, void *stream) {
+  if (!maxval_ok(maxval) || ((uintptr_t)out_hwc & 1) != 0) return DRBA_EINVAL;
+  return to_out_launch(to_out16_kernel, to_out16_rows_kernel, in, out_hwc, pitch, Hin, Win, Hout, Wout, scale_y, scale_x, reverse_channels,
+                       stream, maxval);
+}
+
+int drba_to_inp_pad_win_x4(const uint8_t *img_hwc, int pitch, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, void *stream) {
+  return to_inp_pad_launch(to_inp_pad_kernel, to_inp_pad_rows_kernel, img_hwc, pitch, out, out_x4, Hin, Win, Hout, Wout, stream);
+}
+
+int drba_to_inp16_pad_win_x4(const uint16_t *img_hwc, int pitch, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout,
+                             float maxval, void *stream) {
+  if (!maxval_ok(maxval) || ((uintptr_t)img_hwc & 1) != 0) return DRBA_EINVAL;
+  return to_inp_pad_launch(to_inp16_pad_kernel, to_inp16_pad_rows_kernel, img_hwc, pitch, out, out_x4, Hin, Win, Hout, Wout, stream, maxval);
+}
+
+int drba_to_out_crop_win(const float *in, uint8_t *out_hwc, int pitch, int Hin, int Win, int Hout, int Wout, int reverse_channels,
+                         void *stream) {
+  return to_out_crop_launch(to_out_crop_kernel, to_out_crop_rows_kernel, in, out_hwc, pitch, Hin, Win, Hout, Wout, reverse_channels, stream);
+}
+
+int drba_to_out16_crop_win(const float *in, uint16_t *out_hwc, int pitch, int Hin, int Win, int Hout, int Wout, int reverse_channels,
+                           float maxval, void *stream) {
+  if (!maxval_ok(maxval) || ((uintptr_t)out_hwc & 1) != 0) return DRBA_EINVAL;
+  return to_out_crop_launch(to_out16_crop_kernel, to_out16_crop_rows_kernel, in, out_hwc, pitch, Hin, Win, Hout, Wout, reverse_channels,
+                            stream, maxval);
 }
 
 // ---- planar frames by layout: 420 (the entries above), 422, 444; anything else is DRBA_EINVAL ---------------------------------------

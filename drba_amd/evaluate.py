@@ -6,6 +6,7 @@
                                         [--dedup [--dedup-hi X] [--dedup-lo X] [--dedup-frac X] [--dedup-max N]] [--json PATH]
     python -m drba_amd.evaluate dups CLIP [-m rife] [-scale 1.0] [--fit resize|pad] [--dedup-hi X] [--dedup-lo X] [--dedup-frac X]
                                           [--dedup-max N] [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--json PATH]
+    python -m drba_amd.evaluate bars CLIP [--crop-limit 0.094]
 
 `compare` reads two clips frame by frame (the sources infer.py reads: .npz, .npy + .json, a .y4m stream -- below --, a container
 when OpenCV is installed) and prints one JSON line: PSNR, ssim_matlab, the largest difference in LSB and the number of differing bytes, per
@@ -47,6 +48,12 @@ went in.  The report names the mode in "fit".
 prints the duplicate statistic of the two network inputs -- `max_block`, `n_above / n_blocks` (drba_amd.ops.dup_stats; the frames are
 converted as infer.py converts them for the model named by -m / -scale / --fit) -- and the decision, then the runs of repeats and how many
 frames the filter keeps, and one JSON line with the kept indices.  `holdout --dedup` runs the hold-out with the filter on.
+
+`bars` is what `infer.py --crop auto` does before it runs, as a command: for every frame of a clip (.npz, .npy, .y4m; `-` is a Y4M
+stream on stdin) the box of its active picture as W:H:X:Y, or `empty` (drba_amd.crop: ffmpeg cropdetect's rule on the row and column
+maxima, taken on the device -- of a planar clip, on luma), then the union over the clip as `crop=W:H:X:Y` -- the string `--crop` takes
+-- and the share of the frame it covers.  The union is grown outward to the clip's own chroma alignment; a run whose sink has a
+coarser layout validates the box again.
 
 Non-finite JSON numbers are written as the strings "inf" / "-inf" / "nan" (float() reads them back).
 """
@@ -494,6 +501,33 @@ def dups(src, settings=None, model_type="rife", scale=1.0, fit="resize", yuv_mat
     return {"pairs": pairs, "runs": runs, "kept": kept, "frames": n}
 
 
+# ----------------------------------------------------------------------------------------------------------------- bars
+def bars(src, limit=None, stat=None, out=None):
+    """The active picture of every frame of a ClipSource and of the clip (drba_amd.crop).  Prints one line per frame -- its box as
+    W:H:X:Y, or `empty` -- then `crop=W:H:X:Y` of the union, grown outward to the clip's chroma alignment, and the share of the frame
+    it covers, to `out` (None: nothing); -> {"boxes": [str | None], "crop": str | None, "share": float | None, "frames", "size"}.
+    stat(frame) -> (row_max, col_max): the device's (ops.edge_max) unless given."""
+    from drba_amd import crop as _crop
+    limit = _crop.LIMIT if limit is None else limit
+    sized, boxes = _crop._sized(src), []
+    for k, box in enumerate(_crop.frame_boxes(sized, limit, stat)):
+        boxes.append(box)
+        if out is not None:
+            print(f"{k:6d} {'empty' if box is None else box}", file=out)
+    u = _crop.union(boxes)
+    if u is not None:
+        u = _crop.aligned(u, sized.size, _crop.alignment_of(getattr(src, "pixfmt", "bgr")))
+    share = None if u is None else u.w * u.h / float(sized.size[0] * sized.size[1])
+    if out is not None:
+        if u is None:
+            print(f"no picture above the limit in {len(boxes)} frames: nothing to crop", file=out)
+        else:
+            print(f"crop={u}  {100.0 * share:.1f}% of the {sized.size[1]}x{sized.size[0]} frame"
+                  + ("  (the whole frame: nothing to crop)" if _crop.whole(u, sized.size) else ""), file=out)
+    return {"boxes": [None if b is None else str(b) for b in boxes], "crop": None if u is None else str(u), "share": share,
+            "frames": len(boxes), "size": None if sized.size is None else list(sized.size)}
+
+
 # ----------------------------------------------------------------------------------------------------------------- command line
 def _dedup_flags(p):
     from drba_amd import dedup as _dedup
@@ -542,6 +576,10 @@ def parse_args(argv=None):
     d.add_argument("--yuv-range", dest="yuv_range", type=str, default="source", choices=("source", "limited", "full"))
     _dedup_flags(d)
     d.add_argument("--json", dest="json_path", type=str, default=None)
+    b = sub.add_parser("bars", help="the active picture of every frame of a clip and the box `infer.py --crop` takes")
+    b.add_argument("clip")
+    b.add_argument("--crop-limit", dest="crop_limit", type=float, default=None,
+                   help="a row or column is picture when a sample of it exceeds this, on the [0, 1] scale (default 24/255, as in infer.py)")
     return p.parse_args(argv)
 
 
@@ -570,6 +608,9 @@ def main(argv=None, backend=None):
             rep = {"command": "dups", "input": args.clip, "frames": res["frames"], "kept": res["kept"], "runs": res["runs"]}
             print(json.dumps(_jsonable(rep)))
             _write_json(args.json_path, rep, {"pairs": res["pairs"]})
+            return 0
+        if args.command == "bars":
+            bars(ClipSource(args.clip), args.crop_limit, out=sys.stdout)
             return 0
         src = ClipSource(args.input)
         if not src.random_access:

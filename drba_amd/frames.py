@@ -5,6 +5,8 @@
 get their hooks here, so a new frame property (another chroma layout, a transfer function, an alpha plane) is a field of `FrameFormat`,
 a line in `inp_keywords` / `out_keywords`, and whoever fills the field in (tools.VideoFI_IO, source_format).
 
+`hooks(..., crop=box)` (--crop) adds `window` to both keyword sets; without a box nothing is added.
+
 The rule of the keyword sets: A DEFAULT IS LEFT OUT.  A plain 8-bit BGR resize run calls tools.to_inp(frame, size) and
 tools.to_out(x, size) with no keyword at all, as the reference does, and every keyword appears only for the frames that need it
 (two exceptions are kept as they always were: a 16-bit BGR sink names `rgb` even when it is False, and a planar sink names all five
@@ -105,12 +107,21 @@ def out_keywords(fmt, fit, on_device=False):
     return {**({"rgb": True} if fmt.rgb and not on_device else {}), **_fit_keywords(fit)}
 
 
-def hooks(src_format, sink_format, fit, on_device=False):
+def _crop_keywords(crop):
+    """--crop: the box (drba_amd.crop.Box, or anything with .window = (x, y, w, h)) as the `window` keyword; no box, no keyword"""
+    return {} if crop is None else {"window": tuple(int(v) for v in crop.window)}
+
+
+def hooks(src_format, sink_format, fit, on_device=False, crop=None):
     """-> (to_inp, to_out) for interpolate_stream: tools.to_inp / tools.to_out with the keywords of the two formats (looked up on
     the module at every call: a test may replace them).  on_device: to_out leaves the finished frame on the device (ops.to_out /
-    ops.to_out_yuv) -- what a hold-out compares there and a frame-sharded run gathers from there."""
+    ops.to_out_yuv) -- what a hold-out compares there and a frame-sharded run gathers from there.
+    crop (--crop; a drba_amd.crop.Box): both hooks name `window`: to_inp reads that rectangle of the source frame, to_out writes it
+    into a frame of the size it is given -- the source's -- whose remainder is black.  The sizes stay the caller's: interpolate_stream
+    computes the network size from the box (its `crop`) and hands to_out the frame size."""
     from drba_amd.models.utils import tools
-    kin, kout = inp_keywords(src_format, fit), out_keywords(sink_format, fit, on_device)
+    win = _crop_keywords(crop)
+    kin, kout = {**inp_keywords(src_format, fit), **win}, {**out_keywords(sink_format, fit, on_device), **win}
 
     def to_inp(frame, size):
         return tools.to_inp(frame, size, **kin)

@@ -3,6 +3,7 @@
     python infer.py -m rife -i in.npz -o out.npz [-fps 60 | -t 2] [-s] [-st 0.3] [-hw] [-scale 1.0] [--out-depth source|8|16]
                     [--nonlinear] [--yuv-matrix bt709|bt601] [--yuv-range source|limited|full] [--deterministic] [--fit resize|pad]
                     [--dedup [--dedup-hi 0.047] [--dedup-lo 0.0196] [--dedup-frac 0.33] [--dedup-max 3]] [--out-chroma source|420|422|444]
+                    [--crop off|auto|W:H:X:Y] [--crop-limit 0.094]
 
 `--out-depth` is not in the reference: a .npz / .npy clip may hold uint16 frames, and the written frames are 8 or 16 bits deep
 (default: as the source, so an 8-bit clip is handled exactly as before).  `--nonlinear` is not in the reference either: its driver
@@ -34,14 +35,27 @@ row, and the steps are retimed across the gaps (drba_amd/dedup.py): the clip wri
 motion of a drawing held for two frames is spread over both instead of being packed into the interval where it changes.  With every
 source and sink; `python -m drba_amd.evaluate dups clip` prints the figures the thresholds are chosen from.
 
+`--crop` (not in the reference): letterbox / pillarbox bars stay out of the network.  `--crop W:H:X:Y` (ffmpeg's crop=, as `ffmpeg -vf
+cropdetect` prints it; a leading `crop=` is accepted) names the active picture; `--crop auto` finds it first, in one pass over the clip
+(drba_amd/crop.py: cropdetect's rule on the row and column maxima of every frame, `--crop-limit` on the [0, 1] scale, the union over
+the clip grown outward to the chroma alignment) -- for sources that can be opened twice, .npz / .npy / .y4m files; for stdin and
+containers it is refused before the model is built (`python -m drba_amd.evaluate bars clip` prints the box to pass explicitly).  The
+hooks then read and write that window of every frame (drba_amd.frames.hooks(..., crop=box)), the network size follows from the box
+(1440x1080 inside 1920x1080 runs at 1440x1088), and the written frames keep the source's size with exact black outside the box.  The
+scene test and `--dedup` see the cropped network input, so their decisions may differ from an uncropped run.  Not in the frame-sharded
+run.
+
 The driver logic is host-side Python like the reference; the model calls it makes run on
 the HIP library.  `interpolate_stream` is the loop of reference infer.py:58-174 (drba_amd/driver.py) with the
 module globals turned into arguments, so tests can drive it with any model object.
 """
 import argparse
 import os
+import sys
 import time
+from types import SimpleNamespace
 
+from drba_amd import crop as _crop
 from drba_amd import dedup as _dedup
 from drba_amd import driver
 from drba_amd import frames as _frames
@@ -95,7 +109,90 @@ def parse_args(argv=None):
     p.add_argument("--dedup-frac", dest="dedup_frac", type=float, default=_dedup.FRAC, help="see --dedup-lo (default 0.33)")
     p.add_argument("--dedup-max", dest="dedup_max", type=int, default=_dedup.MAX_RUN,
                    help="at most this many frames in a row are dropped; the next one is kept whatever the test says (default 3)")
+    p.add_argument("--crop", dest="crop", type=str, default="off",
+                   help="keep letterbox / pillarbox bars out of the network: off (default), auto (one pass over the clip finds the active "
+                        "picture first; .npz / .npy / .y4m files) or W:H:X:Y, ffmpeg's crop= as cropdetect prints it.  The written frames "
+                        "keep the source's size, exact black outside the box (not in the frame-sharded run)")
+    p.add_argument("--crop-limit", dest="crop_limit", type=float, default=_crop.LIMIT,
+                   help="--crop auto: a row or column is picture when a sample of it exceeds this, on the [0, 1] scale (default 24/255, "
+                        "cropdetect's limit)")
     return p.parse_args(argv)
+
+
+RESCANNABLE = (".npz", ".npy", ".y4m")  # sources --crop auto can read twice
+
+
+def crop_of(args):
+    """--crop as the driver takes it: None (off), "auto", or a drba_amd.crop.Box (ValueError for anything else).  A namespace built
+    without the flag means off."""
+    v = getattr(args, "crop", "off")
+    if v is None or v == "off":
+        return None
+    if isinstance(v, _crop.Box) or v == "auto":
+        return v
+    return _crop.parse(v)
+
+
+def crop_limit_of(args):
+    """--crop-limit, checked (0 <= limit < 1).  A namespace built without the flag means 24/255."""
+    v = getattr(args, "crop_limit", _crop.LIMIT)
+    _crop.threshold_of(v, 255)
+    return float(v)
+
+
+def check_crop(args):
+    """What can be refused about --crop without reading a frame, before the model is built: a malformed box or limit, and `auto` for a
+    source that cannot be opened twice.  -> crop_of(args)."""
+    c = crop_of(args)
+    crop_limit_of(args)
+    if c == "auto" and (args.input == "-" or os.path.splitext(args.input)[1].lower() not in RESCANNABLE):
+        raise ValueError(f"--crop auto reads the clip twice, which it can do for {' / '.join(RESCANNABLE)} files, not for "
+                         f"{'stdin' if args.input == '-' else args.input}: run `python -m drba_amd.evaluate bars CLIP` on a copy or an "
+                         "excerpt of the clip (or ffmpeg's cropdetect) and pass the box it prints as --crop W:H:X:Y")
+    return c
+
+
+def _resolve_crop(args, c, size, src_pixfmt, sink_pixfmt):
+    """auto -> the scan's box (None, and one line on stderr, when there is nothing to crop); an explicit box -> itself, validated."""
+    align = _crop.alignment_of(src_pixfmt, sink_pixfmt)
+    if c == "auto":
+        box = _crop.scan(args.input, crop_limit_of(args), align)
+        if box is None:
+            print(f"--crop auto: no bars found in {args.input} (every frame empty, or the picture fills the frame): running without a "
+                  "crop", file=sys.stderr)
+        return box
+    return _crop.validate(c, size, align)
+
+
+def plan_crop(args):
+    """main() calls this before the model is built: check_crop, and for a source whose size can be read from the file (.npz / .npy /
+    .y4m) the box itself -- `auto` scanned, an explicit one validated against the frame size and the chroma alignment of the two ends
+    -- stored back as args.crop (a Box, or "off").  An explicit box on a stream or a container is validated when its header has been
+    read (inference)."""
+    c = check_crop(args)
+    ext = os.path.splitext(args.input)[1].lower()
+    if c is None or args.input == "-" or ext not in RESCANNABLE:
+        return c
+    if ext == ".y4m":
+        from drba_amd import y4m
+        with open(args.input, "rb") as f:
+            hdr = y4m.Reader(f, accept=y4m.ACCEPT_ALL).header
+        size, src_pixfmt, src_layout = (hdr.height, hdr.width), "yuv" + hdr.layout, hdr.layout
+    else:
+        frames, _, _ = _frames.open_array_clip(args.input)
+        size, src_pixfmt, src_layout = (int(frames.shape[1]), int(frames.shape[2])), "bgr", None
+    layout = _tools.out_layout(getattr(args, "out_chroma", "source"), args.output, src_layout)
+    box = _resolve_crop(args, c, size, src_pixfmt, "bgr" if layout is None else "yuv" + layout)
+    args.crop = "off" if box is None else box
+    return box
+
+
+def crop_box(args, video_io):
+    """--crop for an opened clip -> a drba_amd.crop.Box or None: what inference hands the hooks and the loop."""
+    c = check_crop(args)
+    if c is None:
+        return None
+    return _resolve_crop(args, c, (video_io.height, video_io.width), video_io.src_format.pixfmt, video_io.sink_format.pixfmt)
 
 
 def dedup_of(args):
@@ -156,13 +253,16 @@ def load_model(model_type, scale=1.0, device=None, weights=None):
 
 
 def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, scdet_threshold=0.3,
-                       to_inp=None, to_out=None, check_scene=None, on_step=None, linear=True, dedup=None, check_dup=None, on_kept=None):
+                       to_inp=None, to_out=None, check_scene=None, on_step=None, linear=True, dedup=None, check_dup=None, on_kept=None,
+                       crop=None):
     """Run the whole clip: drba_amd.driver.run from a cold start, head and tail included.  Returns the number of frames written.
     linear=False: every DRBA step with the non-linear DistanceRatioMap (--nonlinear).
     dedup (--dedup; None: off, True: the defaults, a drba_amd.dedup.Settings or a dict of its fields): repeated source frames are
     dropped before the model sees them and the steps are retimed across the gaps -- the same number of frames at the same instants is
     written (drba_amd.dedup).  check_dup(a, b) -> bool replaces the device test; on_kept(k) fires for every kept source index k, in
-    order; on_step then fires once per source frame the finished steps have passed (a progress bar counts source frames)."""
+    order; on_step then fires once per source frame the finished steps have passed (a progress bar counts source frames).
+    crop (--crop; a drba_amd.crop.Box, with hooks built for it: frames.hooks(..., crop=box)): the network size is computed from the box
+    instead of the frame; to_out is still given the frame's size, which is the size of what it writes."""
     to_inp = to_inp or _tools.to_inp
     to_out = to_out or _tools.to_out
     src_fps = video_io.src_fps
@@ -177,6 +277,12 @@ def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, s
             video_io.write_frame(to_out(x, src_size))
             written += 1
 
+    def sizes(raw):  # the frame's size, and the network size of what the model sees of it
+        s = _tools.get_valid_net_inp_size(raw, model.scale, div=model.pad_size)
+        if crop is not None:
+            s["dst_size"] = _tools.get_valid_net_inp_size(SimpleNamespace(shape=tuple(crop.size)), model.scale, div=model.pad_size)["dst_size"]
+        return s
+
     mapper = _tools.TMapper(src_fps, dst_fps, times)
     cuts = driver.SceneCuts(enable_scdet, scdet_threshold, check_scene)
     settings = _dedup.settings_of(dedup)
@@ -185,7 +291,7 @@ def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, s
 
         def convert(raw):
             if not size:
-                size.update(_tools.get_valid_net_inp_size(raw, model.scale, div=model.pad_size))
+                size.update(sizes(raw))
             return to_inp(raw, size["dst_size"])
 
         def intake():  # the stream driver.run takes its frames in on, when the model offers one (decided once the first frame is here)
@@ -217,7 +323,7 @@ def interpolate_stream(model, video_io, dst_fps, times=-1, enable_scdet=False, s
         return written
 
     i0, i1 = video_io.read_frame(), video_io.read_frame()
-    size = _tools.get_valid_net_inp_size(i0, model.scale, div=model.pad_size)
+    size = sizes(i0)
     src_size, dst_size = size["src_size"], size["dst_size"]
     driver.run(model, lambda k: video_io.read_frame(), [to_inp(i0, dst_size), to_inp(i1, dst_size)], 0,
                to_inp=lambda raw: to_inp(raw, dst_size), emit=emit, cuts=cuts,
@@ -244,10 +350,15 @@ def inference(model, args):
         video_io.frames_are_rgb = True
     # the hooks carry what the two ends' frames are (depth and maxval, planar 4:2:0, RGB order) and --fit: the loop between them
     # never looks at a frame, and a plain 8-bit resize run makes the calls it always made
-    to_inp, to_out = _frames.hooks(video_io.src_format, video_io.sink_format, fit_of(args))
+    try:
+        box = crop_box(args, video_io)  # --crop: None, the box given, or the one a scan of the clip finds
+    except ValueError:
+        video_io.close()
+        raise
+    to_inp, to_out = _frames.hooks(video_io.src_format, video_io.sink_format, fit_of(args), **({} if box is None else {"crop": box}))
     n = interpolate_stream(model, video_io, args.dst_fps, times=args.times, enable_scdet=args.enable_scdet,
                            scdet_threshold=args.scdet_threshold, to_inp=to_inp, to_out=to_out, on_step=step,
-                           linear=not getattr(args, "nonlinear", False), dedup=dedup_of(args))
+                           linear=not getattr(args, "nonlinear", False), dedup=dedup_of(args), **({} if box is None else {"crop": box}))
     while not video_io.finish_writing():
         time.sleep(0.01)
     video_io.close()
@@ -269,6 +380,9 @@ def inference_sharded(model, args, rank, world, to_inp=None, to_out=None, check_
     if dedup_of(args) is not None:
         raise ValueError("the frame-sharded run does not take --dedup (which frames are kept decides every rank's share of the clip "
                          "and its schedule): run --dedup on one GPU")
+    if crop_of(args) is not None:
+        raise ValueError("the frame-sharded run does not take --crop (the ranks' hooks and the gather carry whole frames): run --crop on "
+                         "one GPU")
     apply_deterministic(args)
     if os.path.splitext(args.input)[1].lower() not in (".npz", ".npy"):
         raise RuntimeError("the frame-sharded run needs random access to the clip: use a .npz / .npy source")
@@ -314,7 +428,10 @@ def main(argv=None):
     out_chroma_of(args)  # refuses --out-chroma with a sink that is not Y4M before the model is built
     apply_deterministic(args)  # before the model is built: nothing it does at load is timed in this mode
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != 1 and check_crop(args) is not None:  # every rank, before the process group exists
+        raise ValueError("the frame-sharded run does not take --crop: run --crop on one GPU")
     if world == 1:
+        plan_crop(args)  # refuses what --crop can be refused for, and finds / validates the box of a file source, before the model is built
         model = load_model(args.model_type, scale=args.scale)
         return inference(model, args)
     import torch

@@ -97,14 +97,20 @@ def _fit_kw(fit):
     return {} if fit == "resize" else {"fit": fit}
 
 
-def to_inp(npInp, dst_size, device=None, maxval=None, matrix="bt709", full_range=False, fit="resize"):
+def _window_kw(window):
+    """`window` as the ops entries take it; the default is left out, as `fit`"""
+    return {} if window is None else {"window": tuple(int(v) for v in window)}
+
+
+def to_inp(npInp, dst_size, device=None, maxval=None, matrix="bt709", full_range=False, fit="resize", window=None):
     """resize(to_tensor(npInp), dst_size) (tools.py:59-60) as one kernel on the uploaded uint8 frame (the full-size
     fp32 frame of the reference is never materialised); bit-exact with the two-step form.  A uint16 frame goes through the
     16-bit kernel with its `maxval` (65535 unless given).  A planar frame (y4m.YuvFrame: 4:2:0, 4:2:2 or 4:4:4) is uploaded as it
     stands -- half the bytes of a BGR frame at 4:2:0 -- and converted with `matrix` / `full_range` inside the kernel
     (ops.to_inp_yuv); the frame knows its own depth and layout.  fit="pad" (not in the reference): the frame is replicate-padded to `dst_size` at the bottom and right instead of
-    resized (ops.to_inp)."""
-    fit_kw = _fit_kw(fit)
+    resized (ops.to_inp).  window=(x, y, w, h) (--crop, not in the reference): the whole frame is uploaded as it stands and that
+    rectangle of it is converted as if it were the frame (ops.to_inp / ops.to_inp_yuv: no copy in between)."""
+    fit_kw = {**_fit_kw(fit), **_window_kw(window)}
     device = _ops.default_device() if device is None else device
     if isinstance(npInp, _y4m.YuvFrame):
         if maxval not in (None, npInp.maxval):
@@ -124,16 +130,19 @@ def to_inp(npInp, dst_size, device=None, maxval=None, matrix="bt709", full_range
     return _ops.to_inp(u8, dst_size, **fit_kw)
 
 
-def to_out(tenInp, src_size, rgb=False, depth=8, maxval=None, pixfmt="bgr", matrix="bt709", full_range=False, fit="resize"):
+def to_out(tenInp, src_size, rgb=False, depth=8, maxval=None, pixfmt="bgr", matrix="bt709", full_range=False, fit="resize",
+           window=None):
     """to_cv2(resize(tenInp, src_size)) (tools.py:63-64) as one kernel + the D2H copy.  rgb=True returns the frame in RGB
     order (the flip the reference's writer thread does on the host, tools.py:202, done on the device instead).  depth=16
     returns a uint16 frame scaled to `maxval` (65535 unless given), rounded and saturated (ops.to_out).  pixfmt="yuv420" returns
     the frame as planar 4:2:0 instead, one 1-D array holding Y, U, V (ops.to_out_yuv; at depth 16 scaled to 1023 unless given);
     "yuv422" and "yuv444" the same with those chroma layouts.
     fit="pad" (not in the reference): the top-left `src_size` window of tenInp is converted as it stands -- the counterpart of
-    to_inp(..., fit="pad") -- instead of the resize."""
+    to_inp(..., fit="pad") -- instead of the resize.
+    window=(x, y, w, h) (--crop, not in the reference): the frame returned is still `src_size`; tenInp is converted to that rectangle
+    of it and everything outside is the format's black (ops.to_out / ops.to_out_yuv)."""
     _check_depth(depth, maxval)
-    fit_kw = _fit_kw(fit)
+    fit_kw = {**_fit_kw(fit), **_window_kw(window)}
     if pixfmt != "bgr" and pixfmt not in _frames.YUV_PIXFMTS:
         raise ValueError(f"pixfmt must be bgr, yuv420, yuv422 or yuv444, got {pixfmt!r}")
     if pixfmt in _frames.YUV_PIXFMTS:

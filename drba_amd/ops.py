@@ -618,34 +618,62 @@ def _plane_ptrs(planes, ny, nc):
     return C.c_void_p(base), C.c_void_p(base + ny * es), C.c_void_p(base + (ny + nc) * es)
 
 
-def to_inp(img_u8, dst_size, maxval=None, fit="resize"):
+def _window(window, frame, sub=(1, 1), what="frame"):
+    """`window` = (x, y, w, h) of the four frame conversions (--crop; ffmpeg's crop= names the same four numbers as w:h:x:y), checked
+    against the frame (H, W): inside it, and for a planar frame -- sub = the layout's (horizontal, vertical) subsampling -- x, y
+    multiples of it, w, h too unless the window reaches the frame's right / bottom edge (a chroma sample belongs to one side)."""
+    try:
+        x, y, w, h = (int(v) for v in window)
+    except (TypeError, ValueError):
+        raise ValueError(f"window must be (x, y, w, h), got {window!r}") from None
+    fh, fw = int(frame[0]), int(frame[1])
+    if x < 0 or y < 0 or w < 1 or h < 1 or x + w > fw or y + h > fh:
+        raise ValueError(f"window {w}x{h} at ({x}, {y}) does not lie inside the {fw}x{fh} {what}")
+    for name, at, ext, full, m in (("x", x, w, fw, sub[0]), ("y", y, h, fh, sub[1])):
+        if at % m or (ext % m and at + ext != full):
+            raise ValueError(f"window {w}x{h} at ({x}, {y}): {name} and the extent along it must be multiples of {m} for this chroma "
+                             f"layout (the extent may be odd where the window reaches the {what}'s edge)")
+    return x, y, w, h
+
+
+def to_inp(img_u8, dst_size, maxval=None, fit="resize", window=None):
     """tools.to_inp on a device-resident frame: uint8 [H,W,3] -> fp32 [1,3,*dst_size] in [0,1], one kernel.  A uint16 [H,W,3]
     frame takes the 16-bit kernel: its samples are divided by `maxval` (65535 unless given; 255 < maxval <= 65535).
-    fit="pad": replicate padding to `dst_size` instead of the resize (_fit)."""
+    fit="pad": replicate padding to `dst_size` instead of the resize (_fit).
+    window=(x, y, w, h) (--crop): that rectangle of the frame is read in place, exactly as if it were the whole frame -- the values
+    of to_inp on a contiguous copy of it, without the copy (the drba_to_inp*_win_x4 entries: a pointer and the frame's row pitch)."""
     if not (_is_frame(img_u8, torch.uint8) or _is_frame(img_u8, torch.uint16)):
         raise _lib.DrbaHipError("expected a CUDA uint8 or uint16 [H,W,3] tensor")
     size, tag, mv = _sample_kind(img_u8.dtype, maxval)
     img = img_u8.contiguous()
     h, w = img.shape[:2]
     ho, wo = int(dst_size[0]), int(dst_size[1])
+    src, win, wtag = _p(img), (), ""  # no window: the entries the call always made
+    if window is not None:
+        x0, y0, ww, wh = _window(window, (h, w))
+        src, win, wtag = C.c_void_p(img.data_ptr() + (y0 * w + x0) * 3 * size), (3 * w,), "_win"  # its first sample, the frame's pitch
+        h, w = wh, ww
     out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=img.device)
     x4 = _x4_like(out)
     pad = _fit(fit, "in", (h, w), (ho, wo))
     scales = _scales(pad, (h, w), (ho, wo))
-    entry = f"drba_to_inp{tag}_pad_x4" if pad else f"drba_to_inp{tag}_x4"
+    entry = f"drba_to_inp{tag}_pad{wtag}_x4" if pad else f"drba_to_inp{tag}{wtag}_x4"
     _lib.check(_timed("to_inp" + tag + ("_pad" if pad else ""), (h, w, ho, wo),
                       3.0 * size * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
-                      lambda: getattr(_lib.load(), entry)(_p(img), _p(out), _p(x4), h, w, ho, wo, *scales, *mv, _stream())), entry)
+                      lambda: getattr(_lib.load(), entry)(src, *win, _p(out), _p(x4), h, w, ho, wo, *scales, *mv, _stream())), entry)
     return _with_x4(out, x4)
 
 
-def to_out(x, src_size, rgb=False, depth=8, maxval=None, fit="resize"):
+def to_out(x, src_size, rgb=False, depth=8, maxval=None, fit="resize", window=None):
     """tools.to_out without the D2H copy: fp32 [1,3,h,w] -> uint8 [*src_size,3] on the device, one kernel
     (resize + *255. truncation; rgb=True also flips BGR -> RGB for the encoder pipe).
     depth=16: a torch.uint16 [*src_size,3] frame instead -- resize, * maxval (65535 unless given), rounded to nearest even and
     saturated to [0, maxval], NaN -> 0: the 8-bit path keeps the reference's truncation because its bytes must equal the
     reference's, a 16-bit frame has no reference to equal.
-    fit="pad": the top-left `src_size` window of x is quantised as it stands instead of the resize (_fit)."""
+    fit="pad": the top-left `src_size` window of x is quantised as it stands instead of the resize (_fit).
+    window=(x, y, w, h) (--crop): the frame is still [*src_size,3], but x is converted to the w x h rectangle at (x, y) of it -- the
+    samples of to_out(x, (h, w)) -- and everything outside the rectangle is black, 0, 0, 0: what this conversion writes for an
+    all-zero tensor (one fill, then the drba_to_out*_win entries: a pointer and the frame's row pitch)."""
     if depth not in (8, 16):
         raise ValueError(f"depth must be 8 or 16, got {depth!r}")
     if depth == 8 and maxval is not None:
@@ -654,14 +682,21 @@ def to_out(x, src_size, rgb=False, depth=8, maxval=None, fit="resize"):
     assert x.shape[0] == 1 and x.shape[1] == 3
     h, w = x.shape[2:]
     ho, wo = int(src_size[0]), int(src_size[1])
-    pad = _fit(fit, "out", (ho, wo), (h, w))
-    scales = _scales(pad, (h, w), (ho, wo))
     dtype = torch.uint16 if depth == 16 else torch.uint8
     size, tag, mv = _sample_kind(dtype, maxval)
-    out = torch.empty((ho, wo, 3), dtype=dtype, device=x.device)
-    entry = "drba_to_out" + tag + ("_crop" if pad else "")
+    if window is None:
+        out = torch.empty((ho, wo, 3), dtype=dtype, device=x.device)
+        dst, win, wtag = _p(out), (), ""  # the entries the call always made
+    else:
+        x0, y0, ww, wh = _window(window, (ho, wo))
+        out = torch.zeros((ho, wo, 3), dtype=dtype, device=x.device)
+        dst, win, wtag = C.c_void_p(out.data_ptr() + (y0 * wo + x0) * 3 * size), (3 * wo,), "_win"  # its first sample, the frame's pitch
+        ho, wo = wh, ww
+    pad = _fit(fit, "out", (ho, wo), (h, w))
+    scales = _scales(pad, (h, w), (ho, wo))
+    entry = "drba_to_out" + tag + ("_crop" if pad else "") + wtag
     _lib.check(_timed("to_out" + tag + ("_crop" if pad else ""), (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + 3.0 * size * ho * wo, "byte",
-                      lambda: getattr(_lib.load(), entry)(_p(x), _p(out), h, w, ho, wo, *scales, 1 if rgb else 0, *mv, _stream())), entry)
+                      lambda: getattr(_lib.load(), entry)(_p(x), dst, *win, h, w, ho, wo, *scales, 1 if rgb else 0, *mv, _stream())), entry)
     return out
 
 
@@ -709,14 +744,48 @@ def _yuv_name(layout):
     return "4:" + ":".join(layout[1:])
 
 
-def to_inp_yuv(planes, size, dst_size, matrix="bt709", full_range=False, maxval=None, fit="resize", layout="420"):
+def _plane_window(base, es, frame, layout, window, what):
+    """A window of a packed planar frame at address `base` -> ((Y, U, V) pointers of its first samples, (h, w) of the window): pointer
+    arithmetic only, the strides stay the frame's (W and the chroma width).  The chroma offset is the window's origin divided by the
+    layout's subsampling, which is why _window asks for multiples of it."""
+    sx, sy = YUV_LAYOUTS[layout]
+    x0, y0, ww, wh = _window(window, frame, (sx, sy), what)
+    ny, nc, _, wc = yuv_layout(frame, layout)
+    off_y, off_c = y0 * int(frame[1]) + x0, (y0 // sy) * wc + x0 // sx
+    return (C.c_void_p(base + off_y * es), C.c_void_p(base + (ny + off_c) * es), C.c_void_p(base + (ny + nc + off_c) * es)), (wh, ww)
+
+
+_BLACK_YUV = {}  # (device, dtype, size, layout, matrix, range, maxval) -> the planar frame to_out_yuv writes for an all-zero tensor
+_BLACK_YUV_KEPT = 4  # formats kept: a run has one; each is one frame of device memory (3 MB at 1080p 4:2:0) held until it is pushed out
+
+
+def _black_yuv(device, size, matrix, full_range, depth, maxval, layout):
+    """The planar frame of `size` that to_out_yuv writes for an all-zero network tensor -- the range's black code, mid-grey chroma --,
+    made once per format by that very conversion (one stream synchronisation, on that first call only) and kept in device memory for
+    the life of the process, the last _BLACK_YUV_KEPT formats: a windowed frame starts as a copy of it."""
+    key = (str(device), depth, tuple(size), layout, matrix, bool(full_range), maxval)
+    t = _BLACK_YUV.get(key)
+    if t is None:
+        if len(_BLACK_YUV) >= _BLACK_YUV_KEPT:
+            _BLACK_YUV.pop(next(iter(_BLACK_YUV)))  # the oldest
+        t = to_out_yuv(torch.zeros((1, 3, 8, 8), dtype=torch.float32, device=device), size, matrix=matrix, full_range=full_range,
+                       depth=depth, maxval=maxval, layout=layout)
+        torch.cuda.current_stream(t.device).synchronize()  # made on this stream, copied from on whichever stream asks later
+        _BLACK_YUV[key] = t
+    return t
+
+
+def to_inp_yuv(planes, size, dst_size, matrix="bt709", full_range=False, maxval=None, fit="resize", layout="420", window=None):
     """to_inp for a planar YCbCr frame on the device: `planes` is one contiguous 1-D tensor holding Y [H,W], then U, then V
     ([ceil(H/2),ceil(W/2)] for layout "420", [H,ceil(W/2)] for "422", [H,W] for "444") of a frame of `size` = (H, W) -- uint8
     samples, or uint16 ones in [0, maxval] (1023 unless given) -- -> fp32 [1,3,*dst_size] in [0,1], BGR channel order, one kernel:
     chroma interpolation (along the subsampled axes only), colour conversion and the resize (include/drba_hip.h, ABI 14 and 16).
     The [H,W,4] copy is written in the same pass, as in to_inp.
     fit="pad": the converted frame is replicate-padded to `dst_size` instead of resized (_fit); a margin pixel is the converted
-    pixel of the clamped source coordinate."""
+    pixel of the clamped source coordinate.
+    window=(x, y, w, h) (--crop): that rectangle of the frame is converted in place as if it were the whole frame (plane pointers
+    moved, strides kept: _plane_window); x, y -- and w, h unless the window reaches the right / bottom edge -- are multiples of the
+    layout's subsampling."""
     if not (torch.is_tensor(planes) and planes.is_cuda and planes.dim() == 1 and planes.dtype in (torch.uint8, torch.uint16)):
         raise _lib.DrbaHipError("expected a CUDA uint8 or uint16 1-D tensor of packed Y, U, V planes")
     mid, dtype, tag, mv = _yuv_args(matrix, 8 if planes.dtype == torch.uint8 else 16, maxval)
@@ -728,42 +797,56 @@ def to_inp_yuv(planes, size, dst_size, matrix="bt709", full_range=False, maxval=
     ho, wo = int(dst_size[0]), int(dst_size[1])
     out = torch.empty((1, 3, ho, wo), dtype=torch.float32, device=planes.device)
     x4 = _x4_like(out)
+    es, (y, u, v) = planes.element_size(), _plane_ptrs(planes, ny, nc)
+    fw = w  # the luma stride is the frame's width, whatever is read of it
+    if window is not None:
+        (y, u, v), (h, w) = _plane_window(planes.data_ptr(), es, (h, w), layout, window, "frame")
     pad = _fit(fit, "in", (h, w), (ho, wo))
     scales = _scales(pad, (h, w), (ho, wo))
-    es, (y, u, v) = planes.element_size(), _plane_ptrs(planes, ny, nc)
     # 4:2:0 keeps its own entries (and names in the trace and the profiles); the other layouts say which they are
     fmt, lay = ("yuv420", ()) if layout == "420" else ("yuv", (int(layout),))
     entry = f"drba_to_inp{tag}_{fmt}_pad_x4" if pad else f"drba_to_inp{tag}_{fmt}_x4"
     name = "to_inp_yuv" + ("" if layout == "420" else layout) + tag + ("_pad" if pad else "")
     _lib.check(_timed(name, (h, w, ho, wo),
                       YUV_SAMPLES_PER_PIXEL[layout] * es * min(h * w, 4 * ho * wo) + (28.0 if IMG_X4 else 12.0) * ho * wo, "byte",
-                      lambda: getattr(_lib.load(), entry)(y, u, v, w, wc, _p(out), _p(x4), h, w, ho, wo, *scales, mid, 1 if full_range else 0,
+                      lambda: getattr(_lib.load(), entry)(y, u, v, fw, wc, _p(out), _p(x4), h, w, ho, wo, *scales, mid, 1 if full_range else 0,
                                                           *lay, *mv, _stream())), entry)
     return _with_x4(out, x4)
 
 
-def to_out_yuv(x, src_size, matrix="bt709", full_range=False, depth=8, maxval=None, fit="resize", layout="420"):
+def to_out_yuv(x, src_size, matrix="bt709", full_range=False, depth=8, maxval=None, fit="resize", layout="420", window=None):
     """to_out to a planar YCbCr frame on the device: fp32 [1,3,h,w] (BGR) -> ONE contiguous 1-D tensor holding Y [*src_size],
     then U, then V (their sizes by `layout`, as in to_inp_yuv), uint8 (depth 8) or uint16 scaled to `maxval` (depth 16; 1023 unless
     given): resize, clamp, colour conversion, the chroma mean (2 x 2 for "420", the horizontal pair for "422", none for "444"),
     round to nearest even, in one kernel.  One D2H copy and one write per frame.
     fit="pad": the top-left `src_size` window of x is converted as it stands instead of the resize (_fit); the chroma mean never
-    reads the margin."""
+    reads the margin.
+    window=(x, y, w, h) (--crop): the frame is still that of `src_size`, but x is converted to the w x h rectangle at (x, y) of it --
+    the samples of to_out_yuv(x, (h, w)) -- and everything outside is black: the samples this conversion writes for an all-zero
+    tensor (_black_yuv, copied per frame).  x, y, w, h as in to_inp_yuv."""
     mid, dtype, tag, mv = _yuv_args(matrix, depth, maxval)
     x = _f32(x)
     assert x.shape[0] == 1 and x.shape[1] == 3
     h, w = x.shape[2:]
     ho, wo = int(src_size[0]), int(src_size[1])
     ny, nc, _, wc = yuv_layout((ho, wo), layout)
-    pad = _fit(fit, "out", (ho, wo), (h, w))
-    scales = _scales(pad, (h, w), (ho, wo))
-    out = torch.empty(ny + 2 * nc, dtype=dtype, device=x.device)
-    es, (y, u, v) = out.element_size(), _plane_ptrs(out, ny, nc)
+    fw = wo  # the luma stride is the frame's width, whatever is written of it
+    if window is None:
+        pad = _fit(fit, "out", (ho, wo), (h, w))
+        scales = _scales(pad, (h, w), (ho, wo))
+        out = torch.empty(ny + 2 * nc, dtype=dtype, device=x.device)
+        es, (y, u, v) = out.element_size(), _plane_ptrs(out, ny, nc)
+    else:
+        out = _black_yuv(x.device, (ho, wo), matrix, full_range, depth, maxval, layout).clone()
+        es = out.element_size()
+        (y, u, v), (ho, wo) = _plane_window(out.data_ptr(), es, (ho, wo), layout, window, "frame")
+        pad = _fit(fit, "out", (ho, wo), (h, w))
+        scales = _scales(pad, (h, w), (ho, wo))
     fmt, lay = ("yuv420", ()) if layout == "420" else ("yuv", (int(layout),))
     entry = f"drba_to_out{tag}_{fmt}" + ("_crop" if pad else "")
     name = "to_out_yuv" + ("" if layout == "420" else layout) + tag + ("_crop" if pad else "")
     _lib.check(_timed(name, (h, w, ho, wo), 12.0 * min(h * w, 4 * ho * wo) + YUV_SAMPLES_PER_PIXEL[layout] * es * ho * wo, "byte",
-                      lambda: getattr(_lib.load(), entry)(_p(x), y, u, v, wo, wc, h, w, ho, wo, *scales, mid, 1 if full_range else 0, *lay,
+                      lambda: getattr(_lib.load(), entry)(_p(x), y, u, v, fw, wc, h, w, ho, wo, *scales, mid, 1 if full_range else 0, *lay,
                                                           *mv, _stream())), entry)
     return out
 
@@ -793,6 +876,53 @@ def ssim_thumb32_async(x1, x2):
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(out.device))
     return host, ev
+
+
+def _edge_max_enqueue(frame, group=None):
+    """drba_edge_max_u8 / _u16 on the current stream -> (one device int32 tensor holding row_max then col_max, the number of rows)."""
+    if not (torch.is_tensor(frame) and frame.is_cuda and frame.dtype in (torch.uint8, torch.uint16) and frame.dim() in (2, 3)):
+        raise _lib.DrbaHipError("edge_max takes a CUDA uint8 or uint16 tensor: a packed frame [H,W,c] or a plane [rows,cols]")
+    if frame.dim() == 3:  # a packed frame, seen as H x cW samples
+        rows, cols, pitch = int(frame.shape[0]), int(frame.shape[1] * frame.shape[2]), int(frame.stride(0))
+        ok = frame.stride(2) == 1 and frame.stride(1) == frame.shape[2]
+        group = int(frame.shape[2]) if group is None else int(group)
+    else:
+        rows, cols, pitch = int(frame.shape[0]), int(frame.shape[1]), int(frame.stride(0))
+        ok = frame.stride(1) == 1
+        group = 1 if group is None else int(group)
+    if rows == 1:
+        pitch = max(pitch, cols)  # (the stride of an axis of size 1 is arbitrary)
+    if not ok or rows < 1 or cols < 1 or pitch < cols:
+        raise _lib.DrbaHipError(f"edge_max reads rows of contiguous samples, got shape {tuple(frame.shape)} strides {tuple(frame.stride())}")
+    if group < 1 or cols % group:
+        raise ValueError(f"group must divide the {cols} samples of a row, got {group}")
+    out = torch.empty(rows + cols // group, dtype=torch.int32, device=frame.device)
+    entry = "drba_edge_max_u8" if frame.dtype == torch.uint8 else "drba_edge_max_u16"
+    first = _trace_pos()
+    _lib.check(getattr(_lib.load(), entry)(_p(frame), rows, cols, pitch, group, _p(out), C.c_void_p(out.data_ptr() + 4 * rows), _stream()),
+               entry)
+    _tag(first, [None, (float(frame.element_size()) * rows * cols, "byte", f"edge_max {(rows, cols, group)}")])  # the zeroing, then the pass
+    return out, rows
+
+
+def edge_max(frame, group=None):
+    """The active-picture statistic of --crop (include/drba_hip.h: drba_edge_max_u8 / _u16) -> (row_max [rows], col_max [cols / group]),
+    two device int32 tensors: the largest sample of every row, and of every pixel column over the rows and the `group` samples of a
+    pixel.  `frame`: a packed uint8 / uint16 frame [H,W,3] (group 3 unless given: H x 3W samples) or a plane [rows,cols] (group 1),
+    whose rows may be a view with a pitch.  drba_amd.crop.box_of turns the two arrays into the picture's box."""
+    out, rows = _edge_max_enqueue(frame, group)
+    return out[:rows], out[rows:]
+
+
+def edge_max_async(frame, group=None):
+    """The same without waiting for it: -> (pinned host int32 tensor holding row_max then col_max, event, rows), as dup_stats_async;
+    the arrays are read after event.synchronize()."""
+    out, rows = _edge_max_enqueue(frame, group)
+    host = torch.empty(out.numel(), dtype=torch.int32, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(out.device))
+    return host, ev, rows
 
 
 def _dup_stats_enqueue(x1, x2, lo):

@@ -41,7 +41,11 @@ extern "C" {
  * without them does not load: drba_amd/_lib.py resolves every entry); and, under the same number once more, planar frames by chroma
  * layout -- drba_to_inp_yuv_x4 / drba_to_inp16_yuv_x4 / drba_to_out_yuv / drba_to_out16_yuv / drba_to_inp_yuv_pad_x4 /
  * drba_to_inp16_yuv_pad_x4 / drba_to_out_yuv_crop / drba_to_out16_yuv_crop (the eight planar conversions with a `layout` argument: 420,
- * 422 or 444): additions only, the yuv420 entries keep their arguments and every value.  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
+ * 422 or 444): additions only, the yuv420 entries keep their arguments and every value; and, under the same number, the entries of --crop --
+ * drba_edge_max_u8 / drba_edge_max_u16 (row and column maxima of a frame, from which the active picture is found) and the eight packed
+ * conversions on a window of a frame, drba_to_inp_win_x4 / drba_to_inp16_win_x4 / drba_to_out_win / drba_to_out16_win /
+ * drba_to_inp_pad_win_x4 / drba_to_inp16_pad_win_x4 / drba_to_out_crop_win / drba_to_out16_crop_win (their siblings with a row pitch):
+ * additions only, every earlier entry keeps its arguments and every value it writes.  15: the deterministic mode -- drba_set_deterministic / drba_get_deterministic (a process-wide switch read at launch by
  * the splat entry points: drba_flow_reverse, drba_drm_rife_linear(_batch), drba_drm_rife_nonlinear(_batch), drba_softsplat and
  * drba_softsplat_index; while it is on, drba_rife_splat_ws_floats reports the larger workspace of the fixed-point accumulator):
  * additions only, nothing changes while the switch is off.  14: planar YCbCr 4:2:0 frames -- drba_to_inp_yuv420_x4 / drba_to_inp16_yuv420_x4 / drba_to_out_yuv420 /
@@ -327,6 +331,30 @@ int drba_to_out_yuv420_crop(const float *in, uint8_t *y, uint8_t *u, uint8_t *v,
                             int Hout, int Wout, int matrix, int full_range, void *stream);
 int drba_to_out16_yuv420_crop(const float *in, uint16_t *y, uint16_t *u, uint16_t *v, int y_stride, int c_stride, int Hin, int Win,
                               int Hout, int Wout, int matrix, int full_range, float maxval, void *stream);
+/* ABI 16, a window of a packed frame (--crop): the eight packed conversions (drba_to_inp_x4, drba_to_inp16_x4, drba_to_out,
+ * drba_to_out16 and their fit = pad siblings) with one more argument behind the frame pointer, `pitch`: the samples from one row of
+ * the FRAME to the next, >= 3 * the window's width (otherwise DRBA_EINVAL).  img_hwc / out_hwc point at the window's first sample
+ * (frame + y * pitch + 3 * x) and Hin, Win (way in) or Hout, Wout (way out) are the window's size: the window is converted exactly as
+ * a frame of that size -- the same kernels, the taps of the resize and the replicate padding clamped at the WINDOW's edges, every
+ * value that of the sibling called on a contiguous copy of the window -- and nothing outside it is read or written.  The rows form
+ * is taken under its sibling's rule and pitch % 4 == 0 (every row of the window aligned as its first).  A planar window needs no
+ * entry: the planar conversions take plane pointers and strides. */
+int drba_to_inp_win_x4(const uint8_t *img_hwc, int pitch, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout, float scale_y,
+                       float scale_x, void *stream);
+int drba_to_inp16_win_x4(const uint16_t *img_hwc, int pitch, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout,
+                         float scale_y, float scale_x, float maxval, void *stream);
+int drba_to_out_win(const float *in, uint8_t *out_hwc, int pitch, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
+                    int reverse_channels, void *stream);
+int drba_to_out16_win(const float *in, uint16_t *out_hwc, int pitch, int Hin, int Win, int Hout, int Wout, float scale_y, float scale_x,
+                      int reverse_channels, float maxval, void *stream);
+int drba_to_inp_pad_win_x4(const uint8_t *img_hwc, int pitch, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout,
+                           void *stream);
+int drba_to_inp16_pad_win_x4(const uint16_t *img_hwc, int pitch, float *out, float *out_x4, int Hin, int Win, int Hout, int Wout,
+                             float maxval, void *stream);
+int drba_to_out_crop_win(const float *in, uint8_t *out_hwc, int pitch, int Hin, int Win, int Hout, int Wout, int reverse_channels,
+                         void *stream);
+int drba_to_out16_crop_win(const float *in, uint16_t *out_hwc, int pitch, int Hin, int Win, int Hout, int Wout, int reverse_channels,
+                           float maxval, void *stream);
 /* ABI 16, planar frames by chroma layout: the eight planar conversions above with one more argument, `layout`, in front of maxval
  * (16-bit entries) or of stream: 420 (the yuv420 entries themselves: same kernels, same values), 422 (u and v: [H][c_stride] samples,
  * c_stride >= ceil(W/2)) or 444 (u and v: [H][c_stride], c_stride >= W); anything else is DRBA_EINVAL, as is every malformed argument
@@ -428,6 +456,17 @@ int drba_frame_error_u16(const uint16_t *a, const uint16_t *b, unsigned long lon
  * and more: DRBA_EUNSUPPORTED (the query returns 0 for both). */
 size_t drba_dup_stats_ws_floats(int c, int h, int w);
 int drba_dup_stats_f32(const float *a, const float *b, int c, int h, int w, float lo, void *out, float *ws, void *stream);
+/* The active-picture statistic (--crop; ffmpeg cropdetect's rule is applied to it on the host, drba_amd/crop.py): `in` is a 2-D array
+ * of rows x cols samples, row r at sample r * pitch (pitch >= cols), and `group` g samples make one pixel of a column -- 3: a packed
+ * BGR frame seen as H x 3W samples, 1: a luma plane.  row_max[rows]: the largest sample of each row; col_max[cols / g]: the largest
+ * sample of each pixel column, over the rows and the pixel's g samples.  Both uint32 (4-byte aligned); every element of both is
+ * written, whatever they held.  One streaming pass, 16-byte loads where `in` and the pitch in bytes are multiples of 16 (then every
+ * row start is), 4-byte or single-sample loads otherwise, the tail of a row sample by sample: nothing outside the rows x cols samples
+ * is read.  Integer maxima folded with integer atomics: exact, the same for every launch geometry.
+ * Null pointers, rows, cols or group < 1, pitch < cols, cols % group != 0, a misaligned pointer: DRBA_EINVAL; more than 2^20 - 16 rows:
+ * DRBA_EUNSUPPORTED. */
+int drba_edge_max_u8(const uint8_t *in, int rows, int cols, int pitch, int group, uint32_t *row_max, uint32_t *col_max, void *stream);
+int drba_edge_max_u16(const uint16_t *in, int rows, int cols, int pitch, int group, uint32_t *row_max, uint32_t *col_max, void *stream);
 
 /* ---- convolutions (models/rife_426_heavy/IFNet_HDv3.py:11-16, :28-47, :50-59, :65-82) ------
  * fp32 implicit GEMM on v_mfma_f32_16x16x4_f32.  Weights must be pre-packed by the matching
