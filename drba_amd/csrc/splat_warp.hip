@@ -104,6 +104,9 @@ __device__ __forceinline__ void scatter_avg(float *__restrict__ acc, int x, int 
                                             int tiles_x = 0, const SplatFx &fxp = SplatFx()) {
   const float X = (float)x + fx_, Y = (float)y + fy_;
   if (!(isfinite(X) && isfinite(Y))) return;
+  // a finite target beyond the int range has no corner in the image either: its (int) is undefined, and where the conversion
+  // saturates at INT_MAX the `x0 + 1 >= 0` below is compiled as `x0 >= -1` (signed overflow), which let that corner through
+  if (!(fabsf(X) < 1073741824.f && fabsf(Y) < 1073741824.f)) return;
   const float fx = floorf(X), fy = floorf(Y);
   const int x0 = (int)fx, y0 = (int)fy;
   const float wx0 = (fx + 1.f) - X, wx1 = X - fx, wy0 = (fy + 1.f) - Y, wy1 = Y - fy;

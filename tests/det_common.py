@@ -1,5 +1,7 @@
 """Inputs and CPU-side conditions shared by tests/test_gpu_deterministic.py: flows at 70 x 100 (5 x 4 output tiles of 32 x 16, ragged on
-both edges) that together reach every path of the fused splats, and the share of output pixels whose sum has more than one term."""
+both edges) that together reach every path of the fused splats, and the share of output pixels whose sum has more than one term.
+Below them, the host-visible rules of the fused splats' kernels restated (source class, reach, halo variant, records per tile): what
+tests/op_checks.py chooses and asserts the cases of the fused RIFE splats with."""
 import functools
 
 import numpy as np
@@ -104,3 +106,92 @@ def halo_variant(flow):
     v = np.where(short, f, 0.0)
     r = np.where(v < 0, np.ceil(-v), np.floor(v) + 2).max()
     return 4 if r <= 4 else 8 if r <= 8 else 16
+
+
+# ----------------------------------------------------------------------------------------- the kernels' host-visible rules, restated
+# What splat_long_prepass / splat_tiled decide per source and per tile, from the fp32 splat flow [N, 2, H, W] alone (det_common.splat_flow
+# for the DRM entry points).  Used to CHOOSE inputs and to ASSERT what a case reaches (tests/op_checks.py, the fused RIFE splats),
+# never as a reference of values.
+def _grid(h, w):
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    return xs, ys
+
+
+def tiles_of(h, w):
+    """(tiles_y, tiles_x) of an h x w map"""
+    return (h + TY - 1) // TY, (w + TX - 1) // TX
+
+
+def source_class(flow):
+    """-> (finite, short) [N, H, W] bool: splat_source_from's `finite` (the fp32 target x + f is finite) and `is_short`
+    (f >= -RMAX and f < RMAX - 1 on both axes)."""
+    flow = flow.float()
+    xs, ys = _grid(*flow.shape[2:])
+    finite = torch.isfinite(xs + flow[:, 0]) & torch.isfinite(ys + flow[:, 1])
+    short = (flow[:, 0] >= -RMAX) & (flow[:, 0] < RMAX - 1) & (flow[:, 1] >= -RMAX) & (flow[:, 1] < RMAX - 1)
+    return finite, short
+
+
+def source_reach(flow, tight=0):
+    """[N, H, W] int: the halo a finite short source asks for, as the pre-pass rounds it (f < 0: ceil(-f), else floor(f) + 2, the
+    larger of the two axes); 0 for every other source.  tight=1, 2: floor(f) + 1 and floor(f), the roundings a later author may try."""
+    flow = flow.float()
+    finite, short = source_class(flow)
+    r = torch.where(flow < 0, torch.ceil(-flow), torch.floor(flow) + (2 - int(tight)))
+    r = torch.where((finite & short).unsqueeze(1).expand_as(r), r, torch.zeros_like(r))
+    return torch.nan_to_num(r, 0.0, 0.0, 0.0).amax(1).long()
+
+
+def tile_reach(flow, tight=0):
+    """[N, tiles_y, tiles_x] int: the reach map, the max of source_reach over the sources of a 32 x 16 tile."""
+    r = source_reach(flow, tight)
+    n, h, w = r.shape
+    ty, tx = tiles_of(h, w)
+    pad = torch.zeros(n, ty * TY, tx * TX, dtype=r.dtype)
+    pad[:, :h, :w] = r
+    return pad.view(n, ty, TY, tx, TX).amax((2, 4))
+
+
+def tile_variant(flow, use_map=None, tight=0, own_only=False):
+    """[N, tiles_y, tiles_x] int in (4, 8, 16): the halo variant an output tile takes, the max of the reach map over its 3 x 3
+    neighbourhood (inside the map), <= 4 -> 4, <= 8 -> 8, else 16; without the map (N * tiles > REACH_WORDS) every tile takes 16."""
+    reach = tile_reach(flow, tight)
+    n, ty, tx = reach.shape
+    if use_map is None:
+        use_map = n * ty * tx <= REACH_WORDS
+    if not use_map:
+        return torch.full_like(reach, RMAX)
+    if not own_only:
+        reach = torch.nn.functional.max_pool2d(reach[:, None].float(), 3, 1, 1)[:, 0].long()  # (reach >= 0: the padding never wins)
+    return torch.where(reach <= 4, 4, torch.where(reach <= 8, 8, 16))
+
+
+def record_keys(flow):
+    """-> (kx, ky, is_record): the footprint origin floor(x + f) of every source as the fp32 sum gives it, and whether the tile
+    kernel can hold the source as a record at all (finite and short)."""
+    flow = flow.float()
+    xs, ys = _grid(*flow.shape[2:])
+    finite, short = source_class(flow)
+    ok = finite & short
+    kx = torch.where(ok, torch.floor(xs + flow[:, 0]), torch.full_like(flow[:, 0], -9.0)).long()
+    ky = torch.where(ok, torch.floor(ys + flow[:, 1]), torch.full_like(flow[:, 1], -9.0)).long()
+    return kx, ky, ok
+
+
+def tile_record_totals(flow):
+    """[N, tiles_y, tiles_x] int: the records of every output tile, the short sources whose footprint origin lies on the tile's
+    33 x 17 key grid (-1 .. 31) x (-1 .. 15).  A source on a tile edge is a record of up to four tiles."""
+    kx, ky, ok = record_keys(flow)
+    n, h, w = ok.shape
+    ty, tx = tiles_of(h, w)
+    tot = torch.zeros(n, ty, tx, dtype=torch.long)
+    item = torch.arange(n).view(n, 1, 1).expand(n, h, w)
+    for dy in (0, 1):      # the tile of the footprint's lower right corner, and the tiles left of / above it that share the corner
+        for dx in (0, 1):
+            cx, cy = kx + dx, ky + dy
+            # corner (cx, cy) names a tile; count the source once per distinct tile among its four corners
+            first = ((dx == 0) | ((cx % TX) == 0)) & ((dy == 0) | ((cy % TY) == 0))
+            m = ok & first & (cx >= 0) & (cy >= 0) & (cx // TX < tx) & (cy // TY < ty)
+            # (a footprint origin at -1 has no tile of its own; one at tiles * 32 - 1 or beyond has none for its right corner)
+            tot.index_put_((item[m], (cy // TY)[m], (cx // TX)[m]), torch.ones(int(m.sum()), dtype=torch.long), accumulate=True)
+    return tot

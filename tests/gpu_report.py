@@ -37,6 +37,10 @@ def main():
         sections.append(("op conv epilogue forms, many items", op_checks.check_conv_many(hip.dev)))
     except Exception as e:  # noqa: BLE001
         sections.append(("op conv epilogue forms, many items", [("EXC", float("inf"), 0.0, repr(e))]))
+    try:  # (12.6 M pixels: not one of CHECKS either; the CPU suite runs it with a smaller reach map)
+        sections.append(("op fused RIFE splats, launches without the reach map", op_checks.check_rife_splats_nomap(hip.dev)))
+    except Exception as e:  # noqa: BLE001
+        sections.append(("op fused RIFE splats, launches without the reach map", [("EXC", float("inf"), 0.0, repr(e))]))
     gold = np.load(os.path.join(GOLD, "rife.npz"))
     for scale, size in cases.RIFE_CONFIGS:
         try:

@@ -6,7 +6,8 @@ flow update, the final warp + blend -- in the forms the pipeline runs them), and
 every configuration id pinned (conv.hip, conv_split.hip, conv_dma.hip, conv_ks.hip; CONV_FORMS below), and of the three
 GMFlow transformer kernels at their dispatch edges (window_attn.hip, global_corr.hip, linear_split.hip; ATTN_CASES, GCORR_MAPS,
 LIN_EDGES below), and of IFNet's context encoder as one kernel in its two forms at every tile, border and store edge (head_fused.hip,
-head_fused16.hip; HEAD_CASES below), shared by
+head_fused16.hip; HEAD_CASES below), and of the fused RIFE splats -- the pre-pass / tile kernel pair behind flow_reverse and the
+linear and non-linear DRM maps -- at every halo, window and spill edge (splat_warp.hip; rife_cases below), shared by
 tests/test_gpu_op_parity.py, tests/test_op_checks_cpu.py and the diagnostic report (python -m tests.gpu_report).
 
 Every check takes the device the inputs go to and the `ops` namespace under test (default: drba_amd.ops; the CPU test hands
@@ -40,6 +41,7 @@ that detects nothing.  A finite target beyond the int32 range contributes nothin
 where the fp32 squares overflow (flow_distance_ref).
 Inputs regenerate from seeds (cases.rnd, synth._smooth_field)."""
 import collections
+import math
 
 import torch
 import torch.nn.functional as F
@@ -2435,6 +2437,530 @@ def check_head_fused(dev, ops=None):
     return rows
 
 
+# ----------------------------------------------------------------------------------------- the fused RIFE splats
+# splat_long_prepass / splat_tiled (and the _det pair) of splat_warp.hip: all of drba_flow_reverse, drba_drm_rife_linear(_batch) and
+# drba_drm_rife_nonlinear(_batch), against rife.py:59-73 and drm.py:65-107 as oracle/ops.py and oracle/drm.py restate them:
+#   flow reversal        -2 * avg-splat(flow, flow), holes 2 * max(H, W);
+#   linear / non-linear  avg-splat(u, self * u), holes u; u = r * 2t or get_drm_t(r, t), r = d_other / (d_self + d_other), in fp32
+#                        as decisions._ratio_maps / decisions._retime evaluate it.
+# The hole test happens inside the kernels, so every value row is decisions.two_branch_rows on the reference's hole mask and its
+# unstable set, at the bars gpu_checks.check_glue already holds these entry points to (2e-4 / 2e-5).  The targets are the fp32 sums
+# x + flow (softsplat_ref); a finite target beyond the int32 range contributes nothing.  Which path a case takes is chosen and
+# asserted from the kernels' host-visible rules as tests/det_common.py restates them (source class, reach, halo variant, records).
+RIFE_OP = "rife_splats"
+RIFE_BARS = {"flow_reverse": 2e-4, "drm_rife_linear": 2e-5, "drm_rife_nonlinear": 2e-5}
+RIFE_EPS = 1e-4
+RIFE_FLOW = (("flow_reverse", None),)
+RIFE_DRM = (("drm_rife_linear", 0.25), ("drm_rife_nonlinear", 0.3), ("drm_rife_nonlinear", 0.8))
+RIFE_MAP = (100, 200)      # 7 x 7 tiles of 32 x 16, the last ragged on both axes (8 columns, 4 rows)
+RIFE_SMALL = (48, 96)      # 3 x 3 whole tiles
+RIFE_INTERIOR, RIFE_LAST = (2, 2), (6, 6)  # (tx, ty) of the tiles the window rows aim at on RIFE_MAP
+RIFE_SIZES = ((1, 1), (1, 40), (17, 1), (5, 7), (16, 32), (17, 33), (15, 31))
+RIFE_GROUPS = ("window", "reach", "neighbour", "long", "capacity", "small", "nonfinite", "items")
+RIFE_FAR = (float("nan"), float("inf"), float("-inf"), 1e30, -1e30, 3e9, -3e9, 2.0 ** 31, -(2.0 ** 31))
+ALONE = 1e4                # an unplanted source of an "alone" map: it leaves the map (and is long: the pre-pass finds no corner)
+_RIFE_MEMO = {}            # cases, inputs and references: regenerated from seeds, computed once per process, never written to
+
+
+class RifeCase(collections.namedtuple("RifeCase", "group name flow drm_flow planted claims")):
+    """flow: the [N, 2, H, W] flow of flow_reverse; drm_flow: the splat flow the DRM inputs are constructed for (None: no DRM rows);
+    planted: (item, y, x) of the sources whose loss must show; claims: what the CPU suite asserts from the restated rules."""
+
+
+def _memo(key, fn):
+    if key not in _RIFE_MEMO:
+        _RIFE_MEMO[key] = fn()
+    return _RIFE_MEMO[key]
+
+
+def rife_u(op, fs, fo, t):
+    """u of a DRM entry point in the dtype of its inputs, as the reference evaluates it"""
+    from tests import decisions
+    _, r = decisions._ratio_maps(fs, fo, RIFE_EPS)
+    return decisions._retime(r, t, op == "drm_rife_linear")
+
+
+def rife_splat_flow(op, fs, fo, t):
+    """the fp32 flow an entry point splats along"""
+    return fs if op == "flow_reverse" else fs * rife_u(op, fs, fo, t)
+
+
+def rife_inputs(op, t, flow, planted, seed):
+    """(flow_self, flow_other) of a DRM entry point whose splat flow self * u is `flow` up to fp32 rounding (the precedent:
+    det_common.other_for): a ratio r0 per pixel -- 0.5 at a planted source, 0.8 .. 0.9 elsewhere, so that a planted source's value
+    differs from every other by 0.05 or more at the three timesteps of the rows (the retimed ratio is not monotonic) --, self = flow / u(r0) and an other flow of the length that gives r0."""
+    if op == "flow_reverse":
+        return flow.contiguous(), None
+    from tests import decisions
+    n, _, h, w = flow.shape
+    r0 = 0.8 + 0.1 * torch.rand(n, 1, h, w, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+    for k, y, x in planted:
+        r0[k, 0, y, x] = 0.5
+    u0 = decisions._retime(r0, t, op == "drm_rife_linear")
+    fs = (flow.double() / u0).float()
+    ds = (fs[:, 0:1].double() ** 2 + fs[:, 1:].double() ** 2).sqrt() + RIFE_EPS
+    d_o = ds * r0 / (1 - r0) - RIFE_EPS
+    return fs.contiguous(), torch.cat([d_o, torch.zeros_like(d_o)], 1).float().contiguous()
+
+
+def _rife_holes(op, t):
+    """the reference's hole test in the dtype of its inputs: ones-splat along the splat flow, mode avg, < 0.999"""
+    from tests import decisions
+
+    def fn(fs, fo=None):
+        f = rife_splat_flow(op, fs, fo, t)
+        tgt = _grid32(*f.shape[2:]).to(f.dtype) + f
+        f = torch.where(tgt.abs() > 2.0 ** 30, torch.full_like(f, float("inf")), f)  # (beyond int32: no corner, as softsplat_ref)
+        return {"hole": oops.softsplat(torch.ones_like(f[:, :1]), f, None, "avg") < decisions.HOLE}
+    return fn
+
+
+def rife_refs(op, t, fs, fo):
+    """-> (aligned fp64, fill, hole, unstable) of an entry point on fp32 inputs"""
+    from tests import decisions
+    _, _, h, w = fs.shape
+    if op == "flow_reverse":
+        aligned = -2.0 * softsplat_ref(fs, fs, None, "avg")
+        fill = torch.full_like(aligned, 2.0 * max(h, w))
+        m, u = decisions.unstable(_rife_holes(op, t), [fs])
+    else:
+        val = rife_u(op, fs, fo, t)
+        aligned = softsplat_ref(val, fs * val, None, "avg")
+        fill = val
+        m, u = decisions.unstable(_rife_holes(op, t), [fs, fo])
+    return aligned, fill, m["hole"], u["hole"]
+
+
+def rife_value(ref):
+    """the reference's output: the fill value on its holes, the aligned value elsewhere"""
+    aligned, fill, hole, _ = ref
+    return torch.where(hole.expand_as(aligned), fill.double().expand_as(aligned), aligned)
+
+
+def rife_run(ops, dev, op, t, fs, fo):
+    if op == "flow_reverse":
+        return ops.flow_reverse(fs.to(dev))
+    if op == "drm_rife_linear":
+        return ops.drm_rife_linear(fs.to(dev), fo.to(dev), t, RIFE_EPS)
+    return ops.drm_rife_nonlinear(fs.to(dev), fo.to(dev), t, RIFE_EPS)
+
+
+def rife_rows(group, name, op, got, ref, extra=""):
+    from tests import decisions
+    aligned, fill, hole, unst = ref
+    fillv = float(fill.flatten()[0])
+    rows = []
+    for nm, e, tol, x in decisions.two_branch_rows(name, got, aligned, fill, hole, unst, RIFE_BARS[op],
+                                                   fill_mask_of=(lambda g: g == fillv) if op == "flow_reverse" else None):
+        row = Row(RIFE_OP, nm, e, tol, f"{x} {extra}".strip())
+        row.group = group
+        rows.append(row)
+    return rows
+
+
+def _rife_bg(kind, n, h, w):
+    return torch.full((n, 2, h, w), ALONE) if kind == "alone" else torch.zeros(n, 2, h, w)
+
+
+def _plant(flow, planted, k, y, x, fx, fy):
+    _, _, h, w = flow.shape
+    if 0 <= x < w and 0 <= y < h:
+        flow[k, 0, y, x], flow[k, 1, y, x] = fx, fy
+        planted.append((k, y, x))
+
+
+def rife_window_cases():
+    """Case 1.  Per halo variant R and background, on RIFE_MAP: sources at the window columns tx0 - R, tx0 - R + 1, tx0 + 32 + R - 1 and
+    tx0 + 32 + R (one beyond) of an interior tile and of the ragged last one, on x, on y and on the diagonal, with the flows that
+    bring the footprint just into the tile's first / last column (-R, -R + 0.25, R - 1.25, just under R - 1) and those that stop one
+    short of it.  Nothing else on the map reaches further than R (identity: reach 2; alone: reach 0)."""
+    h, w = RIFE_MAP
+    out = []
+    for R in (4, 8, 16):
+        for bg in ("alone", "identity"):
+            flows = []
+            for exact in (True, False):  # the DRM form keeps clear of the exact bounds: self * u moves a flow by a few ulps
+                lo, under = (-float(R), _f32_next(R - 1, 0)) if exact else (-R + 2.0 ** -8, R - 1 - 2.0 ** -8)
+                right = ((R - 1, lo), (R - 1, -R + 0.25), (R - 1, -R + 1.0), (R, lo), (R, -R + 0.25))  # (column past the tile, flow)
+                left = ((-R + 1, R - 1.25), (-R + 1, under), (-R + 1, R - 2.0), (-R, R - 1.25), (-R, under))  # (column before tx0, flow)
+                f, planted = _rife_bg(bg, 1, h, w), []
+                for (tx, ty), spare in ((RIFE_INTERIOR, (2, 2)), (RIFE_LAST, (3, 3))):
+                    tx0, ty0, sx0, sy0 = tx * 32, ty * 16, spare[0] * 32, spare[1] * 16
+                    for k, (c, v) in enumerate(right):
+                        _plant(f, planted, 0, sy0 + 1 + k, tx0 + 32 + c, v, 0.0)            # x axis: a row of its own in tile row `spare`
+                        _plant(f, planted, 0, ty0 + 16 + c, sx0 + 1 + k, 0.0, v)            # y axis: a column of its own
+                    for k, (c, v) in enumerate(left):
+                        _plant(f, planted, 0, sy0 + 7 + k, tx0 + c, v, 0.0)
+                        _plant(f, planted, 0, ty0 + c, sx0 + 7 + k, 0.0, v)
+                    _plant(f, planted, 0, ty0 + 16 + R - 1, tx0 + 32 + R - 1, lo, lo)           # diagonal: onto the far corner pixel
+                    _plant(f, planted, 0, ty0 + 16 + R, tx0 + 32 + R, lo, lo)                   # one beyond on both axes
+                    _plant(f, planted, 0, ty0 - R + 1, tx0 - R + 1, R - 1.25, R - 1.25)         # onto the near corner pixel
+                    _plant(f, planted, 0, ty0 - R, tx0 - R, R - 1.25, R - 1.25)                 # one short on both axes
+                flows.append((f, planted))
+            assert flows[0][1] == flows[1][1]
+            out.append(RifeCase("window", f"window R={R} {bg} {h}x{w}", flows[0][0], flows[1][0], tuple(flows[0][1]),
+                                {"variant": R, "tiles": (RIFE_INTERIOR, RIFE_LAST)}))
+    return out
+
+
+REACH_VALUES = (-4.0, _f32_next(-4, -5), 2.75, 3.0, _f32_next(3, 0), -8.0, _f32_next(-8, -9), 6.75, 7.0, _f32_next(7, 0), -16.0,
+                _f32_next(-16, -17), 14.75, _f32_next(15, 0), 15.0, -0.0,
+                4.5, 8.5, -4.5, -8.5)  # (beyond the issue's list: just past the bounds of the 4- and 8-pixel variants on both sides)
+
+
+def rife_reach_cases():
+    """Case 2.  One source per item on an "alone" 48 x 96 map, so that its tile's reach -- 4, 8, 16, or none: long -- is that source's
+    alone.  Every value once in x and once in y only, from the middle of the middle tile and from the place where the far corner of
+    the footprint is the first column (row) of the next tile, or the last one of the tile before: the pixel a halo chosen one too
+    small does not bring in."""
+    h, w = RIFE_SMALL
+    n = 4 * len(REACH_VALUES)
+    f, planted = _rife_bg("alone", n, h, w), []
+    for k, v in enumerate(REACH_VALUES):
+        _plant(f, planted, 4 * k, 24, 48, v, 0.0)
+        _plant(f, planted, 4 * k + 1, 24, 48, 0.0, v)
+        _plant(f, planted, 4 * k + 2, 24, 31 - math.ceil(v) if v < 0 else 64 - (math.floor(v) + 1), v, 0.0)  # onto column 31 / corner on 64
+        _plant(f, planted, 4 * k + 3, 15 - math.ceil(v) if v < 0 else 32 - (math.floor(v) + 1), 48, 0.0, v)  # onto row 15 / corner on 32
+    assert len(planted) == n
+    return [RifeCase("reach", f"reach rounding N={n} alone {h}x{w}", f, None, tuple(planted), {"values": REACH_VALUES})]
+
+
+def rife_neighbour_cases():
+    """Case 3.  Items 0-3: the middle tile of a 3 x 3 tile map is all holes (reach 0) and its right, lower, diagonal or upper-left
+    neighbour holds one source of reach 16 that lands on the quiet tile's corner pixel; items 4, 5: the quiet tile is a corner tile
+    of the map (some neighbours do not exist); item 6, the mirror: the middle tile's sources have reach 16 and land inside their own
+    tile, so that the eight neighbours scan 64 x 48 windows and find nothing."""
+    h, w = RIFE_SMALL
+    f, planted = _rife_bg("alone", 7, h, w), []
+    lo = -16.0
+    _plant(f, planted, 0, 31, 79, lo, 0.0)      # right neighbour (2, 1) -> (63, 31), the far corner of tile (1, 1)
+    _plant(f, planted, 1, 47, 63, 0.0, lo)      # lower neighbour (1, 2)
+    _plant(f, planted, 2, 47, 79, lo, lo)       # diagonal (2, 2)
+    _plant(f, planted, 3, 1, 17, 14.75, 14.75)  # upper left (0, 0) -> (31.75, 15.75): the near corner (32, 16)
+    _plant(f, planted, 4, 17, 49, 14.75, 14.75)  # quiet corner tile (2, 2): from (1, 1) onto (64, 32)
+    _plant(f, planted, 5, 31, 47, lo, lo)       # quiet corner tile (0, 0): from (1, 1) onto its far corner (31, 15)
+    _plant(f, planted, 6, 17, 33, 14.75, 10.5)
+    _plant(f, planted, 6, 30, 62, lo, -12.0)
+    quiet = {0: (1, 1), 1: (1, 1), 2: (1, 1), 3: (1, 1), 4: (2, 2), 5: (0, 0)}
+    return [RifeCase("neighbour", f"neighbour reach N=7 alone {h}x{w}", f, None, tuple(planted), {"quiet": quiet, "mirror": 6})]
+
+
+def rife_long_cases():
+    """Case 4.  Long sources on an "alone" map whose footprint has exactly one corner inside the map, one per map corner, and the
+    short-only flow of the call that follows on the same workspace."""
+    h, w = RIFE_MAP
+    f, planted = _rife_bg("alone", 1, h, w), []
+    for y, x, tx, ty in ((30, 40, -0.5, -0.5), (31, 150, w - 0.5, -0.5), (70, 41, -0.5, h - 0.5), (71, 151, w - 0.5, h - 0.5)):
+        _plant(f, planted, 0, y, x, tx - x, ty - y)
+    quiet = cases.rnd((1, 2, h, w), 3400, 1.0).clamp(-2.9, 2.9)
+    return [RifeCase("long", f"long, one corner inside, alone {h}x{w}", f, f.clone(), tuple(planted), {"long": len(planted)}),
+            RifeCase("long", f"short only, after the long call {h}x{w}", quiet, quiet.clone(), (), {"long": 0})]
+
+
+PINCH = (2, 2)  # (tx, ty) of the tile the capacity rows contract a patch into
+CAPACITY_TOTALS = (("CAP-1", 1535, False, False), ("CAP", 1536, False, False), ("CAP+1", 1537, False, True), ("CAP+1 and a long source", 1537, True, True),
+                   ("1.5 CAP", 2304, False, True), ("1.5 CAP and a long source", 2304, True, True))  # (label, records, long source, DRM rows)
+
+
+def pinch_flow(h, w, tile=PINCH, n=1):
+    """[n, 2, h, w] "alone" map with a 67 x 50 patch contracted about the centre of `tile`, by 0.45 in x and 0.6 in y: every source of
+    the patch is short (|f| < 14.9) and lands within 14.9 columns and 9.8 rows of the centre -- inside the tile in x, and over its
+    upper and lower edge in y, so that the patch holds records that straddle the edge.  About 2900 records of `tile`."""
+    from tests import det_common
+    cx, cy = tile[0] * det_common.TX + 15.5, tile[1] * det_common.TY + 7.5
+    g = _grid32(h, w)
+    f = _rife_bg("alone", n, h, w)
+    py, px = slice(int(cy - 24.5), int(cy - 24.5) + 50), slice(int(cx - 32.5), int(cx - 32.5) + 67)
+    f[:, 0, py, px] = -0.45 * (g[0, py, px] - cx)
+    f[:, 1, py, px] = -0.6 * (g[1, py, px] - cy)
+    return f
+
+
+def _pinch_to(op, t, fs, fo, tile, total, seed):
+    """Sources of `tile`'s records taken out (sent off the map) one by one, in a seeded order and only those that are records of no
+    other tile, until the restated record total of the tile is `total`; in place."""
+    from tests import det_common
+    flow = rife_splat_flow(op, fs, fo, t)
+    have = int(det_common.tile_record_totals(flow)[0, tile[1], tile[0]])
+    assert have >= total, (have, total)
+    kx, ky, ok = det_common.record_keys(flow)
+    tx0, ty0 = tile[0] * det_common.TX, tile[1] * det_common.TY
+    inner = ok[0] & (kx[0] >= tx0) & (kx[0] <= tx0 + 30) & (ky[0] >= ty0) & (ky[0] <= ty0 + 14)  # on no other tile's key grid
+    idx = inner.flatten().nonzero()[:, 0]
+    idx = idx[torch.randperm(idx.numel(), generator=torch.Generator().manual_seed(seed))][:have - total]
+    w = fs.shape[3]
+    if op == "flow_reverse":
+        fs[0, :, idx // w, idx % w] = ALONE
+    else:  # self == other: r = 0.5, u about t, and self * u still leaves the map
+        fs[0, :, idx // w, idx % w] = ALONE / 0.1
+        fo[0, :, idx // w, idx % w] = ALONE / 0.1
+    assert int(det_common.tile_record_totals(rife_splat_flow(op, fs, fo, t))[0, tile[1], tile[0]]) == total
+
+
+def capacity_inputs(label, op, t):
+    """inputs of one capacity row: the pinch, a long source onto the pinch tile where the row names one, and sources removed until
+    the tile's records are exactly those the row claims -- counted on the flow the entry point splats along"""
+    def make():
+        h, w = RIFE_MAP
+        _, total, with_long, _ = next(c for c in CAPACITY_TOTALS if c[0] == label)
+        f = pinch_flow(h, w)
+        planted = []
+        if with_long:
+            _plant(f, planted, 0, 90, 170, (PINCH[0] * 32 + 6.5) - 170, (PINCH[1] * 16 + 8.5) - 90)
+        fs, fo = rife_inputs(op, t, f, planted, 3500)
+        _pinch_to(op, t, fs, fo, PINCH, total, 3501)
+        return fs, fo, tuple(planted)
+    return _memo(("capacity", label, op, t), make)
+
+
+def rife_small_flow(h, w, seed):
+    """sigma = 2 noise, and sources whose x (then y) target walks over -1, 0, W - 1, W and their fp32 neighbours (border_flow's walk,
+    on the sources a small map has): asserted as the fp32 sums they are"""
+    f = cases.rnd((1, 2, h, w), seed, 2.0)
+    want = {}
+    for axis, size in ((0, w), (1, h)):
+        k = 0
+        for edge in (-1.0, 0.0, size - 1.0, float(size)):
+            for side in (0, -1, 1):  # the integer, then the nearest targets this source can have below and above it
+                p = (k * 5 + 17 * axis + 2) % (h * w)
+                y, x = p // w, p % w
+                tgt = edge if side == 0 else _f32_next(edge, edge + side)
+                f[0, axis, y, x] = tgt - (x, y)[axis]
+                want[(axis, y, x)] = (edge, side, tgt)
+                k += 1
+    tg = _grid32(h, w) + f[0]
+    hit = 0
+    for (axis, y, x), (edge, side, tgt) in want.items():  # (a neighbour finer than the source's own flow can express lands on the edge itself)
+        got = float(tg[axis, y, x])
+        assert got == tgt or got == edge, (h, w, axis, y, x, edge, side, got)
+        hit += got == tgt and side != 0
+    assert hit >= min(3, h * w - 1), (h, w, hit)
+    return f
+
+
+def rife_small_cases():
+    """Case 6.  Maps smaller than a tile, one tile exactly, and one pixel more / less than a tile on both axes."""
+    return [RifeCase("small", f"small {h}x{w}", rife_small_flow(h, w, 3600 + k), None, (), {}) for k, (h, w) in enumerate(RIFE_SIZES)]
+
+
+def rife_nonfinite_cases():
+    """Case 7.  NaN, +-inf, +-1e30, +-3e9 and +-2^31 in either component, on sigma = 2 noise: at the corner pixels of tiles and at
+    the border pixels a border tile's window clamps its out-of-map positions to."""
+    h, w = RIFE_SMALL
+    f = cases.rnd((1, 2, h, w), 3700, 2.0)
+    spots = ((16, 32), (31, 63), (15, 31), (32, 64), (0, 0), (47, 95), (0, 95), (47, 0), (16, 0), (31, 95), (0, 32), (47, 63),  # (y, x)
+             (15, 0), (32, 95), (0, 31), (47, 64), (20, 0), (25, 95))
+    assert len(spots) == 2 * len(RIFE_FAR)
+    for k, (y, x) in enumerate(spots):
+        f[0, k % 2, y, x] = RIFE_FAR[k // 2]
+    return [RifeCase("nonfinite", f"NaN inf 1e30 3e9 2^31 {h}x{w}", f, None, (), {"spots": spots})]
+
+
+ITEMS = 8
+ITEM_REACH16 = ((0, 0), (1, 0), (2, 0), (3, 0), (4, 0), (5, 0), (5, 5), (6, 5))  # (tx, ty) of item k's reach-16 tile; item k + 1's quiet tile
+ITEM_PINCH = ((1, 3), (2, 4), (3, 3), (4, 4), (1, 4), (2, 3), (3, 2), (4, 2))
+ITEM_FP64 = (0, 3, 7)
+ITEM_T = {"drm_rife_linear": (0.25, 0.2, 0.3, 0.35, 0.4, 0.45, 0.55, 0.6), "drm_rife_nonlinear": (0.3, 0.8, 0.25, 0.4, 0.6, 0.7, 0.35, 0.65)}
+
+
+def rife_item_flow():
+    """Case 8.  [8, 2, 100, 200]: per item its own reach-4 noise, a pinch of more than kCAP records, a 6 x 6 block of 40-pixel flows
+    and a reach-16 tile, each at another place; the reach-16 tile of item k - 1 is all NaN (reach 0, no flag) in item k."""
+    def make():
+        h, w = RIFE_MAP
+        f = cases.rnd((ITEMS, 2, h, w), 3800, 1.0).clamp(-2.9, 2.9)
+        planted = []
+        for k in range(ITEMS):
+            p = pinch_flow(h, w, ITEM_PINCH[k])[0]
+            patch = p[0] != ALONE
+            f[k] = torch.where(patch, p, f[k])
+            f[k, 0, 84:90, 4 + 12 * k:10 + 12 * k] = 40.0
+            tx0, ty0 = ITEM_REACH16[k][0] * 32, ITEM_REACH16[k][1] * 16
+            qx0, qy0 = ITEM_REACH16[k - 1][0] * 32, ITEM_REACH16[k - 1][1] * 16
+            f[k, :, qy0:qy0 + 16, qx0:qx0 + 32] = float("nan")
+            _plant(f, planted, k, ty0 + 5, min(tx0 + 20, w - 1), -16.0, 0.0)
+            _plant(f, planted, k, 86, 6 + 12 * k, 40.0, 0.0)
+        return f, tuple(planted)
+    return _memo("items", make)
+
+
+def rife_cases(groups=RIFE_GROUPS):
+    """the table of cases 1-4, 6 and 7 (one flow per case); the capacity and item rows build their inputs per entry point"""
+    def make():
+        return rife_window_cases() + rife_reach_cases() + rife_neighbour_cases() + rife_long_cases() + rife_small_cases() + rife_nonfinite_cases()
+    return [c for c in _memo("cases", make) if c.group in groups]
+
+
+def rife_case_inputs(case, op, t):
+    def make():
+        if op == "flow_reverse":
+            return case.flow.contiguous(), None
+        return rife_inputs(op, t, case.drm_flow, case.planted, 3300)
+    return _memo(("inputs", case.name, op, t), make)
+
+
+def rife_case_refs(name, op, t, fs, fo):
+    return _memo(("refs", name, op, t), lambda: rife_refs(op, t, fs, fo))
+
+
+def rife_workspace(ops, dev):
+    """the zeroed buffer the fused entry points share, as allocated by the calls made so far"""
+    return ops._zero_workspace(dev, 1)
+
+
+def _ws_row(group, name, ops, dev):
+    from tests import det_common
+    ws = rife_workspace(ops, dev)
+    row = Row(RIFE_OP, f"{name}: non-zero workspace words past the reach map", float((ws[det_common.REACH_WORDS:] != 0).sum()), 0.0,
+              f"{ws.numel() - det_common.REACH_WORDS} words")
+    row.group = group
+    return row
+
+
+def _item_rows(rows, ops, dev, tag):
+    """Case 8: the single-tensor form at N = 8 and the two batch forms with 8 jobs, against fp64 on items 0, 3, 7 and against the
+    N = 1 calls on every item"""
+    f, planted = rife_item_flow()
+    for op in ("flow_reverse", "drm_rife_linear", "drm_rife_nonlinear"):
+        if op == "flow_reverse":
+            ins = [(f[k:k + 1].contiguous(), None, None) for k in range(ITEMS)]
+            got = ops.flow_reverse(f.to(dev))
+            got = [got[k:k + 1] for k in range(ITEMS)]
+        else:
+            def make(op=op):
+                return [rife_inputs(op, ITEM_T[op][k], f[k:k + 1], [(0, y, x) for i, y, x in planted if i == k], 3810 + k) + (ITEM_T[op][k],)
+                        for k in range(ITEMS)]
+            ins = _memo(("item inputs", op), make)
+            many = ops.drm_rife_linear_many if op == "drm_rife_linear" else ops.drm_rife_nonlinear_many
+            got = many([(a.to(dev), b.to(dev), t) for a, b, t in ins], RIFE_EPS)
+        worst = 0.0
+        for k, (a, b, t) in enumerate(ins):
+            one = rife_run(ops, dev, op, t, a, b)
+            worst = max(worst, _err(got[k], one.double()))
+            if k in ITEM_FP64:
+                name = f"{op} item {k} of {ITEMS}" + ("" if t is None else f" t={t}")
+                rows += rife_rows("items", f"{name}{tag}", op, got[k], rife_case_refs(f"item {k}", op, t, a, b))
+        row = Row(RIFE_OP, f"{op} {ITEMS} items vs the N=1 calls{tag}", worst, RIFE_BARS[op], "")
+        row.group = "items"
+        rows.append(row)
+
+
+def check_rife_splats(dev, ops=None, groups=RIFE_GROUPS, modes=(False, True)):
+    """Cases 1-8 of the fused RIFE splats and the t_dev row, in the default and in the deterministic mode, against the same references
+    at the same bars: window edges per halo variant, reach rounding, neighbour reach, long sources and the flags, the record capacity,
+    small and ragged maps, non-finite and far flows, items."""
+    ops = ops or default_ops()
+    rows = []
+    was = ops.set_deterministic(False)
+    try:
+        for det in modes:
+            ops.set_deterministic(det)
+            tag = " det" if det else ""
+            for case in rife_cases(groups):
+                for op, t in RIFE_FLOW + (RIFE_DRM if case.drm_flow is not None else ()):
+                    fs, fo = rife_case_inputs(case, op, t)
+                    name = f"{op}{'' if t is None else f' t={t}'} {case.name}{tag}"
+                    got = rife_run(ops, dev, op, t, fs, fo)
+                    rows += rife_rows(case.group, name, op, got, rife_case_refs(case.name, op, t, fs, fo))
+                    if case.group == "long":  # the accumulators and the flags behind them are zero again after every call
+                        rows.append(_ws_row("long", name, ops, dev))
+            if "capacity" in groups:
+                for label, total, with_long, drm in CAPACITY_TOTALS:
+                    for op, t in RIFE_FLOW + (RIFE_DRM if drm else ()):
+                        fs, fo, _ = capacity_inputs(label, op, t)
+                        name = f"{op}{'' if t is None else f' t={t}'} capacity {label}{tag}"
+                        got = rife_run(ops, dev, op, t, fs, fo)
+                        rows += rife_rows("capacity", name, op, got, rife_case_refs(f"capacity {label}", op, t, fs, fo), f"records={total}")
+                        rows.append(_ws_row("capacity", name, ops, dev))
+            if "items" in groups:
+                _item_rows(rows, ops, dev, tag)
+            if "long" in groups and not det:  # case 10: t from device memory == t from the host, bit for bit
+                case = rife_cases(("long",))[0]
+                fs, fo = rife_case_inputs(case, "drm_rife_linear", 0.25)
+                a, b = fs.to(dev), fo.to(dev)
+                host = ops.drm_rife_linear(a, b, 0.25, RIFE_EPS)
+                devt = ops.drm_rife_linear(a, b, 0.75, RIFE_EPS, t_dev=torch.tensor([0.25]).to(dev))
+                row = exact_row(RIFE_OP, "drm_rife_linear t_dev == host t", devt, host)
+                row.group = "long"
+                rows.append(row)
+    finally:
+        ops.set_deterministic(was)
+    return rows
+
+
+# ---- case 9: launches without the reach map
+NOMAP_W = 3  # one tile column; the smallest width of the issue's range, i.e. the fewest pixels
+
+
+def nomap_geometry(reach_words, with_map):
+    """(N, H) with N * tiles == reach_words (the map is used) or one tile row more per item (skipped); N is the largest power of two
+    that keeps H below 2^15 + 16 rows and the grid's y below 65536"""
+    n = max(4, reach_words >> 11)
+    ty = reach_words // n
+    assert n * ty == reach_words
+    return (n, ty * 16 - 3) if with_map else (n, ty * 16 + 5)
+
+
+def nomap_flow(n, h, seed):
+    """[n, 2, h, NOMAP_W]: noise of reach at most 4, and in the first, a middle and the last item a few long and non-finite sources"""
+    w = NOMAP_W
+    f = torch.randn(n, 2, h, w, generator=torch.Generator().manual_seed(seed)).clamp(-2.9, 2.9)
+    f[:, 0] *= 0.3
+    planted = []
+    for k in (0, n // 2, n - 1):
+        _plant(f, planted, k, 5, 1, 0.25, 40.5)
+        _plant(f, planted, k, h - 3, 0, 1.5, -60.75)  # (flows stay below 2^7: the 2e-4 bar is absolute, and an fp32 ulp of a longer flow is not below it)
+        _plant(f, planted, k, h // 2, 2, -1.25, 17.0)
+        _plant(f, planted, k, 79, 1, 0.0, -16.0)      # reach 16, from the last row of a tile's 16-pixel window onto its last row
+        _plant(f, planted, k, 113, 1, 0.25, 14.75)    # reach 16, from the second row of the window onto the first row of tile 8
+        f[k, 0, 9, 1], f[k, 1, h - 9, 2], f[k, 0, h // 2 + 3, 0] = float("nan"), float("inf"), 3e9
+    return f, tuple(planted)
+
+
+def check_rife_splats_nomap(dev, ops=None, reach_words=None):
+    """Case 9.  flow_reverse on one tile column (W = 3) with N * tiles == REACH_WORDS -- the largest launch that uses the reach map: noise
+    of reach <= 4 takes the 40 x 24 windows -- and with one tile row more per item: the map is skipped and every tile scans 64 x 48.
+    Against fp64 on the first, a middle and the last item, against the same entry point on two chunks of N / 2 items (which use the
+    map) on every item, and in deterministic mode bit for bit against the chunks; each launch once with the reach words set to 0 and
+    once to 0x7f7f7f7f beforehand.  At REACH_WORDS = 2^18: N = 128, H = 32765 / 32773, 12.6 M pixels; on the device 101 MB of flow, as
+    much output and the same again for the chunks' results, and a workspace of 152 MB (303 MB in deterministic mode): 0.7 GB.
+    reach_words: the CPU suite runs the same rows on a stand-in with a smaller map."""
+    from tests import det_common
+    ops = ops or default_ops()
+    rw = reach_words or det_common.REACH_WORDS
+    rows = []
+    was = ops.set_deterministic(False)
+    try:
+        for with_map in (True, False):
+            n, h = nomap_geometry(rw, with_map)
+            f, _ = _memo(("nomap", rw, with_map), lambda: nomap_flow(n, h, 3900 + int(with_map)))
+            fd = f.to(dev)
+            what = f"N={n} {h}x{NOMAP_W} tiles={n * ((h + 15) // 16)} ({'with' if with_map else 'without'} the reach map)"
+            for det in (False, True):
+                ops.set_deterministic(det)
+                tag = " det" if det else ""
+                chunks = torch.cat([ops.flow_reverse(fd[:n // 2].contiguous()), ops.flow_reverse(fd[n // 2:].contiguous())], 0)
+                ops.flow_reverse(fd)  # (the workspace of this geometry and mode is allocated from here on)
+                for fillv in (0, 0x7f7f7f7f):
+                    rife_workspace(ops, dev)[:rw].view(torch.int32).fill_(fillv)
+                    got = ops.flow_reverse(fd)
+                    name = f"flow_reverse {what} reach words {fillv:#x}{tag}"
+                    for k in (0, n // 2, n - 1):
+                        a = f[k:k + 1].contiguous()
+                        rows += rife_rows("nomap", f"{name} item {k}", "flow_reverse", got[k:k + 1], rife_case_refs(f"nomap {rw} {with_map} {k}", "flow_reverse", None, a, None))
+                    if det:
+                        row = exact_row(RIFE_OP, f"{name}: == two chunks of N/2", got, chunks)
+                    else:
+                        row = Row(RIFE_OP, f"{name}: vs two chunks of N/2", _err(got, chunks.double()), RIFE_BARS["flow_reverse"], "")
+                    row.group = "nomap"
+                    rows += [row, _ws_row("nomap", name, ops, dev)]
+                    del got
+                del chunks
+    finally:
+        ops.set_deterministic(was)
+    return rows
+
+
 SPLAT_CHECKS = (check_softsplat, check_softsplat_scan, check_softsplat_big)  # the generic splat's families, for tests that take them together
 CHECKS = (  # (section title, check): one operator family each
     ("op softmax_rows_", check_softmax_rows), ("op instance_norm", check_instance_norm), ("op conv_direct", check_conv_direct),
@@ -2448,5 +2974,5 @@ CHECKS = (  # (section title, check): one operator family each
     ("op stage input + conv0[0] fused", check_stage_conv_fused), ("op flow update", check_flow_update), ("op warp + blend", check_warp_blend),
     ("op conv epilogue forms", check_conv_forms_all), ("op window attention edges", check_window_attention_edges),
     ("op global_expect2 edges", check_global_expect2_edges), ("op linear_split edges", check_linear_split_edges),
-    ("op fused encoder", check_head_fused))
+    ("op fused encoder", check_head_fused), ("op fused RIFE splats", check_rife_splats))
 GLUE_CHECKS = (check_stage_input_first, check_stage_input_warped, check_stage_conv_fused, check_flow_update, check_warp_blend)

@@ -9,7 +9,9 @@ window attention, the global expectation and the split linear layer run at every
 token table, tile forms), with the form that ran read from the kernel trace and sentinels behind outputs and workspaces.  IFNet's
 context encoder as one kernel runs in both of its forms (head_fused.hip, head_fused16.hip) at every tile, border and store edge
 (op_checks.HEAD_CASES), on zero, signed and NaN-pixel frames, as a batch through the C ABI into guarded outputs, at its refusals and at
-the shapes that fall back to the layer chain.
+the shapes that fall back to the layer chain.  The fused RIFE splats (splat_long_prepass / splat_tiled and the _det pair) run on
+sources planted at the window edges of every halo variant, at the reach roundings, next to quiet tiles, at the record capacity, on
+maps smaller than a tile, with non-finite and far flows, as 8 items, and in launches too large for the reach map.
 
 Value rows: tol = max(2e-5 max(1, |ref|max), 3 x the fp32 oracle's own error on that input); decisions and data movement:
 bit-exact.  tests/test_op_checks_cpu.py shows on the CPU that these rows fail for a wrong operator."""
@@ -931,4 +933,57 @@ def test_head_fused_fallback_runs_the_layers(hip_backend):
         assert names and not any("head_fused" in k for k in names), names
         rows.append(op_checks.value_row("head_fused", f"Head([{n}, 3, {h}, {w}]) through the layer chain vs fp64", got, op_checks.head_ref(x, wts),
                                         op_checks.head_ref(x, wts, torch.float32)))
+    _assert_rows(rows)
+
+
+# ----------------------------------------------------------------------------------------- the fused RIFE splats
+@pytest.mark.parametrize("group", op_checks.RIFE_GROUPS)
+def test_rife_splats(hip_backend, group):
+    """splat_long_prepass / splat_tiled and their _det forms -- all of flow_reverse, drm_rife_linear(_many) and drm_rife_nonlinear(_many)
+    -- against fp64 under the two-branch rule, at the 2e-4 / 2e-5 bars these entry points already hold, one case group per test:
+    the window edges of every halo variant, the reach rounding, neighbour reach, long sources and the flags, the record capacity,
+    small maps, non-finite and far flows, items.  Each group in the default and in the deterministic mode."""
+    rows = op_checks.check_rife_splats(hip_backend.dev, groups=(group,))
+    assert {r.group for r in rows} == {group} and any(" det" in r[0] for r in rows)
+    _assert_rows(rows)
+
+
+def _fused_launches(recs):
+    fused = [r for r in recs if r["name"].startswith(("splat_long_prepass", "splat_tiled"))]
+    other = sorted({r["name"] for r in recs} - {r["name"] for r in fused})
+    return fused, other
+
+
+def test_rife_splats_launch_the_fused_kernels(hip_backend):
+    """From the launch trace: a default-mode group launches splat_long_prepass and splat_tiled in pairs and nothing else -- no
+    generic splat, no composition --, a deterministic one the _det pair."""
+    dev = hip_backend.dev
+    for det, pre, tile in ((False, "splat_long_prepass<", "splat_tiled<"), (True, "splat_long_prepass_det<", "splat_tiled_det<")):
+        rows = []
+        recs = _traced_recs(lambda: rows.extend(op_checks.check_rife_splats(dev, groups=("neighbour", "nonfinite", "small", "long"), modes=(det,))))
+        fused, other = _fused_launches(recs)
+        print(f"  det={det}: {sorted({r['name'] for r in fused})} other: {other}")
+        assert not other, other
+        assert len(fused) >= 2 * 9 and len(fused) % 2 == 0
+        for a, b in zip(fused[0::2], fused[1::2]):
+            assert a["name"].startswith(pre) and b["name"].startswith(tile) and a["grid"] == b["grid"], (a, b)
+        _assert_rows(rows)
+
+
+def test_rife_splats_without_the_reach_map(hip_backend):
+    """flow_reverse at N * tiles == REACH_WORDS and at one tile row more per item, where the kernels skip the reach map and every tile
+    scans the 16-pixel halo (op_checks.check_rife_splats_nomap: 12.6 M pixels, 0.7 GB on the device; fp64 on three items).  The
+    trace shows that the second geometry did launch more than REACH_WORDS workgroups, in both modes, and the first exactly that many."""
+    from tests import det_common
+    rows = []
+    recs = _traced_recs(lambda: rows.extend(op_checks.check_rife_splats_nomap(hip_backend.dev)))
+    fused, other = _fused_launches(recs)
+    assert not [n for n in other if "splat" in n], other
+    groups = {}
+    for r in fused:
+        groups.setdefault(r["name"], set()).add(r["grid"][0] * r["grid"][1] * r["grid"][2])
+    print("  " + "\n  ".join(f"{k}: workgroups {sorted(v)}" for k, v in sorted(groups.items())))
+    n, h = op_checks.nomap_geometry(det_common.REACH_WORDS, False)
+    for name in ("splat_long_prepass<0>", "splat_tiled<0>", "splat_long_prepass_det<0>", "splat_tiled_det<0>"):
+        assert det_common.REACH_WORDS in groups[name] and max(groups[name]) == n * ((h + 15) // 16) > det_common.REACH_WORDS, (name, groups[name])
     _assert_rows(rows)

@@ -4,7 +4,8 @@ The "implementation under test" here is a torch-fp32 stand-in for drba_amd.ops, 
 (explicit window loops, explicit bilinear gathers, explicit index arithmetic; the forward splat as a key per source, the
 sources ordered by key and the outputs summing their four segments; the IFNet stage glue with a source index and weight per
 axis, 2 x 2 gathers at clamped coordinates and the running flow summed term by term; IFNet's encoder as the four layers with both
-output layouts taken from the same values) -- not with the unfold / grid_sample / F.interpolate /
+output layouts taken from the same values; the fused RIFE splats as a reach map, a halo variant per tile, a window test per
+(source, corner) pair and a record capacity per tile) -- not with the unfold / grid_sample / F.interpolate /
 corner-by-corner scatter forms the fp64 references use -- so that two independent statements of every formula meet:
   1. every fp64 reference agrees with the fp32 oracle / torch form of the same formula within fp32 roundoff (the measured
      floor of each row is bounded by a figure derived from the number format and the operation's conditioning);
@@ -16,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import drm as odrm
-from tests import op_checks
+from tests import det_common, op_checks
 
 CPU = torch.device("cpu")
 EPS32 = 2.0 ** -24
@@ -692,7 +693,155 @@ def _features_planar(f):
     return f.permute(0, 3, 1, 2).reshape(1, 2 * c2, h, w).contiguous()
 
 
+class _RifeSplats:
+    """The fused RIFE splats in the kernels' form: a reach per source tile as the pre-pass rounds it, a halo variant per output tile
+    from the 3 x 3 reach entries around it (16 everywhere when the launch has more tiles than the reach map has words), and every
+    (source, corner) pair added once -- a short source by the tile that owns the corner, if the source lies in that tile's window;
+    a long one by the pre-pass, which also leaves a flag for the tile.  A tile holds kCAP records in key order; the rest go through the
+    accumulator, corner by corner of that tile.  The workspace is the zeroed buffer the entry points share: reach words in front,
+    everything behind them zero again on return.  `defect`: one rule of the above changed (RIFE_DEFECTS below)."""
+
+    def __init__(self, defect=None, reach_words=det_common.REACH_WORDS):
+        self.defect, self.reach_words, self.det = defect, reach_words, False
+        self.ws = torch.zeros(det_common.REACH_WORDS + (1 << 16))
+
+    def namespace(self):
+        return {k: getattr(self, k) for k in ("flow_reverse", "drm_rife_linear", "drm_rife_linear_many", "drm_rife_nonlinear",
+                                              "drm_rife_nonlinear_many", "set_deterministic", "_zero_workspace")}
+
+    def set_deterministic(self, on):
+        was, self.det = self.det, bool(on)
+        return was
+
+    def _zero_workspace(self, device, nfloats):
+        return self.ws
+
+    def _slots(self, kx, ky, ok, item, src, n, h, w):
+        """per corner (dy, dx): the slot of the source among the records of the corner's tile, in key order (-1: the corner is not the
+        first of the source's footprint in that tile, or names no tile)"""
+        ty_n, tx_n = det_common.tiles_of(h, w)
+        keys, tiles, masks = [], [], []
+        for dy in (0, 1):
+            for dx in (0, 1):
+                cx, cy = kx + dx, ky + dy
+                first = ((dx == 0) | (cx % det_common.TX == 0)) & ((dy == 0) | (cy % det_common.TY == 0))
+                m = ok & first & (cx >= 0) & (cy >= 0) & (cx // det_common.TX < tx_n) & (cy // det_common.TY < ty_n)
+                tX, tY = cx // det_common.TX, cy // det_common.TY
+                tile = (item * ty_n + tY) * tx_n + tX
+                key = (ky - tY * det_common.TY + 1) * (det_common.TX + 1) + (kx - tX * det_common.TX + 1)
+                keys.append(((tile * 600 + key) * (h * w) + src)[m])
+                tiles.append(tile[m])
+                masks.append(m)
+        key, tile = torch.cat(keys), torch.cat(tiles)
+        order = torch.argsort(key)
+        ts = tile[order]
+        pos = torch.arange(ts.numel())
+        new = torch.ones_like(ts, dtype=torch.bool)
+        new[1:] = ts[1:] != ts[:-1]
+        start = torch.cummax(torch.where(new, pos, torch.zeros_like(pos)), 0).values
+        rank = torch.empty_like(pos)
+        rank[order] = pos - start
+        out, at = [], 0
+        for m in masks:
+            s = torch.full((n, h, w), -1, dtype=torch.long)
+            k = int(m.sum())
+            s[m] = rank[at:at + k]
+            at += k
+            out.append(s)
+        return out  # index 2 * dy + dx
+
+    def _splat(self, flow, val, fill, mode0):
+        d, TX, TY = self.defect, det_common.TX, det_common.TY
+        n, _, h, w = flow.shape
+        nv = val.shape[1]
+        ty_n, tx_n = det_common.tiles_of(h, w)
+        finite, short = det_common.source_class(flow)
+        reach = det_common.tile_reach(flow, tight=1 if d == "reach_tight" else 2 if d == "reach_too_tight" else 0)
+        if d == "item0_reach":
+            reach = reach[0:1].expand(n, ty_n, tx_n)
+        if n * ty_n * tx_n <= self.reach_words:
+            self.ws[:n * ty_n * tx_n] = reach.flatten().float()
+            nb = reach if d == "own_reach_only" else F.max_pool2d(reach[:, None].float(), 3, 1, 1)[:, 0].long()
+            variant = torch.where(nb <= 4, 4, torch.where(nb <= 8, 8, 16))
+        else:
+            variant = torch.full((n, ty_n, tx_n), 4 if d == "no_map_as_r4" else 16)
+        xs, ys = _grid(n, h, w)
+        X = torch.where(finite, xs + flow[:, 0], torch.zeros_like(xs))
+        Y = torch.where(finite, ys + flow[:, 1], torch.zeros_like(ys))
+        fx, fy = X.floor(), Y.floor()
+        kx, ky = fx.clamp(-1e9, 1e9).long(), fy.clamp(-1e9, 1e9).long()
+        xi, yi = xs.long(), ys.long()
+        item = torch.arange(n).view(n, 1, 1).expand(n, h, w)
+        src = yi * w + xi
+        slots = None
+        if d in ("spill_dropped", "spill_all_corners") and int(det_common.tile_record_totals(flow).max()) > det_common.CAP:
+            slots = self._slots(kx, ky, finite & short, item, src, n, h, w)
+        vals = torch.cat([val, torch.ones_like(val[:, :1])], 1).permute(0, 2, 3, 1)
+        acc = torch.zeros(n * h * w, nv + 1)
+        corner, long_landed = {}, False
+        for dy in (0, 1):
+            for dx in (0, 1):
+                px, py = kx + dx, ky + dy
+                wgt = (X - fx if dx else (fx + 1) - X) * (Y - fy if dy else (fy + 1) - Y)
+                inmap = finite & (px >= 0) & (px < w) & (py >= 0) & (py < h)
+                tX, tY = (px // TX).clamp(0, tx_n - 1), (py // TY).clamp(0, ty_n - 1)
+                R = variant[item, tY, tX]
+                x0, y0 = tX * TX, tY * TY
+                far = 1 if d == "window_one_short" else 0
+                inwin = (xi >= x0 - R) & (xi <= x0 + TX + R - 1 - far) & (yi >= y0 - R) & (yi <= y0 + TY + R - 1 - far)
+                keep = inmap & (~short | inwin)
+                long_landed = long_landed or bool((inmap & ~short).any())
+                corner[(dy, dx)] = (px, py, wgt, inmap, (item * ty_n + tY) * tx_n + tX)
+                if slots is not None:
+                    fdx = torch.where(px % TX == 0, dx, 0) if dx else torch.zeros_like(px)  # the first corner of the footprint in this tile
+                    fdy = torch.where(py % TY == 0, dy, 0) if dy else torch.zeros_like(py)
+                    slot = torch.stack(slots)[2 * fdy + fdx, item, yi, xi]
+                    if d == "spill_dropped":
+                        keep = keep & ~(short & (slot >= det_common.CAP))
+                acc.index_add_(0, (item * h * w + py * w + px)[keep], vals[keep] * wgt[keep].unsqueeze(1))
+        if slots is not None and d == "spill_all_corners":
+            for c, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+                spilled = slots[c] >= det_common.CAP  # the source is a spilled record of the tile of this corner
+                for px, py, wgt, inmap, tile in corner.values():
+                    extra = spilled & inmap & (tile != corner[(dy, dx)][4])
+                    acc.index_add_(0, (item * h * w + py * w + px)[extra], vals[extra] * wgt[extra].unsqueeze(1))
+        if d == "stale_dirty" and long_landed:
+            self.ws[det_common.REACH_WORDS + 17] = 1e-45  # a flag of the pre-pass nobody cleared
+        acc = acc.view(n, h, w, nv + 1).permute(0, 3, 1, 2)
+        sw = acc[:, nv:]
+        nrm = sw + 0.0000001
+        gap = (sw / nrm) < 0.999
+        if mode0:
+            return torch.where(gap, torch.full_like(flow, float(max(h, w))), -1.0 * (acc[:, :nv] / nrm)) * 2.0
+        return torch.where(gap, fill, acc[:, :nv] / nrm).contiguous()
+
+    def flow_reverse(self, flow):
+        return self._splat(flow, flow, None, True)
+
+    def drm_rife_linear(self, a, b, t, eps=1e-4, t_dev=None):
+        u = _drm_ratio(a, b, eps)[1] * (float(t_dev[0]) if t_dev is not None else t) * 2
+        return self._splat(a * u, u, u, False)
+
+    def drm_rife_nonlinear(self, a, b, t, eps=1e-4, precision=1e-3):
+        u = odrm.drm_to_t(_drm_ratio(a, b, eps)[1], t, precision)
+        return self._splat(a * u, u, u, False)
+
+    def _many(self, jobs, fn):
+        """(one launch: the jobs are the items of one reach map)"""
+        a, b = torch.cat([j[0] for j in jobs]), torch.cat([j[1] for j in jobs])
+        us = torch.cat([fn(j[0], j[1], j[2]) for j in jobs])
+        out = self._splat(a * us, us, us, False)
+        return [out[k:k + 1] for k in range(len(jobs))]
+
+    def drm_rife_linear_many(self, jobs, eps=1e-4):
+        return self._many(jobs, lambda a, b, t: _drm_ratio(a, b, eps)[1] * t * 2)
+
+    def drm_rife_nonlinear_many(self, jobs, eps=1e-4, precision=1e-3):
+        return self._many(jobs, lambda a, b, t: odrm.drm_to_t(_drm_ratio(a, b, eps)[1], t, precision))
+
+
 STANDIN = dict(
+    _RifeSplats().namespace(),
     head_fused=_head_fused, is_pair=_is_pair, features_planar=_features_planar,
     window_attention=_window_attention, global_expect2=_global_expect2, LinearSplit=_LinearSplit,
     softmax_rows_=_softmax_rows_, instance_norm=_instance_norm, conv_direct=_conv_direct, local_corr_flow=_local_corr_flow,
@@ -1133,3 +1282,222 @@ def test_token_table_rows_with_the_standin():
         with torch.no_grad():
             row = op_checks.attn_row("window_attention", c, 2, _window_attention(q, k, v, c.h, c.w, c.splits, c.shift, c.scale))
         assert _passes(row), row
+
+
+# ----------------------------------------------------------------------------------------- 8. the fused RIFE splats
+RIFE_TITLE = "op fused RIFE splats"
+ALONE_MIN = 1e3         # a source of an "alone" background: its flow leaves the map (it is long, and lands nowhere)
+RIFE_NOMAP_WORDS = 64  # the reach map of the stand-in that runs the no-map rows here: N = 4 items of 16 / 17 tiles
+RIFE_DEFECTS = (  # (the stand-in's changed rule, the case group that must fail, part of the name of a row that must fail)
+    ("window_one_short", "window", "window R="),          # sources at the far window column / row dropped
+    ("reach_too_tight", "reach", "reach rounding"),        # the reach of a positive flow as floor(f): one pixel short (see reach_tight below)
+    ("own_reach_only", "neighbour", "neighbour reach"),    # the 3 x 3 neighbourhood ignored
+    ("spill_dropped", "capacity", "capacity CAP+1"),       # records at or beyond kCAP lost
+    ("spill_all_corners", "capacity", "capacity CAP+1"),   # a spilled straddling record adds the corners the neighbour owns, too
+    ("stale_dirty", "long", "non-zero workspace words"),   # a flag left set
+    ("item0_reach", "items", "item 3 of 8"),               # every item reads item 0's reach entries
+)
+
+
+def _rife_ns(defect=None, reach_words=det_common.REACH_WORDS):
+    return Recorder(**_RifeSplats(defect, reach_words).namespace())
+
+
+def _rife_cases_with_inputs():
+    """(case name, group, op, t, flow_self, flow_other, planted, claims) of every row's inputs: the table, the capacity rows, the items"""
+    out = []
+    for case in op_checks.rife_cases():
+        for op, t in op_checks.RIFE_FLOW + (op_checks.RIFE_DRM if case.drm_flow is not None else ()):
+            out.append((case.name, case.group, op, t) + op_checks.rife_case_inputs(case, op, t) + (case.planted, case.claims))
+    for label, total, _, drm in op_checks.CAPACITY_TOTALS:
+        for op, t in op_checks.RIFE_FLOW + (op_checks.RIFE_DRM if drm else ()):
+            fs, fo, planted = op_checks.capacity_inputs(label, op, t)
+            out.append((f"capacity {label}", "capacity", op, t, fs, fo, planted, {"records": total}))
+    f, planted = op_checks.rife_item_flow()
+    out.append(("items", "items", "flow_reverse", None, f, None, planted, {}))
+    return out
+
+
+@pytest.mark.parametrize("defect,group,must_fail", RIFE_DEFECTS, ids=[d[0] for d in RIFE_DEFECTS])
+def test_rife_planted_defect_fails_its_case_and_only_this_operator(clean, defect, group, must_fail):
+    with torch.no_grad():
+        failed = [r for r in op_checks.check_rife_splats(CPU, _rife_ns(defect)) if not _passes(r)]
+    assert any(r.group == group and must_fail in r[0] for r in failed), [r[0] for r in failed]
+    assert all(r.op == op_checks.RIFE_OP for r in failed)
+    fused = set(_RifeSplats().namespace())  # no other family calls a fused entry point: its rows are the clean ones
+    assert all(not (fused & used) for title, (_, used) in clean.items() if title != RIFE_TITLE)
+    if defect == "window_one_short":  # per halo variant, on both backgrounds, in both modes
+        for R in (4, 8, 16):
+            for bg in ("alone", "identity"):
+                for tag in ("", " det"):
+                    assert any(f"window R={R} {bg} 100x200{tag}:" in r[0] for r in failed), (R, bg, tag)
+    if defect in ("spill_dropped", "spill_all_corners"):  # at kCAP and below nothing spills: those rows hold
+        assert not any("capacity CAP:" in r[0] or "capacity CAP det:" in r[0] or "capacity CAP-1" in r[0] for r in failed), [r[0] for r in failed]
+        assert any("capacity 1.5 CAP" in r[0] for r in failed)
+
+
+def test_rife_reach_from_floor_plus_one_is_a_correct_tightening():
+    """The pre-pass rounds the reach of a positive flow to floor(f) + 2.  floor(f) + 1 ("reach_tight") still covers the footprint: its
+    far corner is x + floor(f) + 1, and the window of halo R begins at tx0 - R.  The rows must tell that tightening (every row
+    passes) from floor(f), which loses the far column ("reach_too_tight", above) -- they do not assert the path, only the values."""
+    with torch.no_grad():
+        rows = op_checks.check_rife_splats(CPU, _rife_ns("reach_tight"))
+    assert all(_passes(r) for r in rows), [r[0] for r in rows if not _passes(r)]
+    flow = op_checks.rife_cases(("reach",))[0].flow
+    assert not torch.equal(det_common.tile_variant(flow), det_common.tile_variant(flow, tight=1))  # (the tightening does change variants here)
+
+
+def test_rife_nomap_rows_on_a_small_reach_map():
+    """check_rife_splats_nomap's rows with stand-ins whose reach map has 64 words: clean; the launch that skips the map scanning
+    the 4-pixel halo fails the rows of that launch only.  And the geometry the GPU suite runs, from the restated constants."""
+    rw = RIFE_NOMAP_WORDS
+    with torch.no_grad():
+        rows = op_checks.check_rife_splats_nomap(CPU, _rife_ns(None, rw), reach_words=rw)
+        bad = [r for r in op_checks.check_rife_splats_nomap(CPU, _rife_ns("no_map_as_r4", rw), reach_words=rw) if not _passes(r)]
+    assert len(rows) >= 2 * 2 * 2 * (3 * 4 + 2) and all(_passes(r) for r in rows), [r[0] for r in rows if not _passes(r)]
+    assert bad and all("(without the reach map)" in r[0] and r.op == op_checks.RIFE_OP for r in bad), [r[0] for r in bad]
+    assert any(" det" in r[0] and "== two chunks" in r[0] for r in bad) and any("item 0" in r[0] for r in bad)
+    for words in (rw, det_common.REACH_WORDS):
+        (n, h), (n2, h2) = op_checks.nomap_geometry(words, True), op_checks.nomap_geometry(words, False)
+        tiles, tiles2 = det_common.tiles_of(h, op_checks.NOMAP_W), det_common.tiles_of(h2, op_checks.NOMAP_W)
+        assert tiles[1] == tiles2[1] == 1 and n == n2 and n * tiles[0] == words and n2 * tiles2[0] == words + n
+        assert (n // 2) * tiles2[0] <= words  # the chunks use the map
+    assert n * h * op_checks.NOMAP_W < 12.7e6 and h2 < 65536
+    for with_map in (True, False):  # the two launches take different halo variants, and the planted sources are what they claim
+        n, h = op_checks.nomap_geometry(rw, with_map)
+        f, planted = op_checks.nomap_flow(n, h, 3900 + int(with_map))
+        v = det_common.tile_variant(f, use_map=with_map)
+        assert set(v.unique().tolist()) == ({4, 16} if with_map else {16})
+        assert float((det_common.tile_variant(f, use_map=True) == 4).float().mean()) > 0.5
+        finite, short = det_common.source_class(f)
+        assert int((finite & ~short).sum()) >= 9 and int((~finite).sum()) >= 6 and int((det_common.source_reach(f) == 16).sum()) >= 6
+        _assert_decisive("nomap", "flow_reverse", None, f, None, planted)
+
+
+def _loo_effect(op, t, fs, fo, planted):
+    """per planted source: the largest change of the reference's output over the pixels of its footprint when that source alone is
+    taken out -- from the fp64 sums of the reference (value * weight and weight per pixel), minus the source's own terms"""
+    n, _, h, w = fs.shape
+    flow = op_checks.rife_splat_flow(op, fs, fo, t)
+    val = fs if op == "flow_reverse" else op_checks.rife_u(op, fs, fo, t)
+    nv = val.shape[1]
+    sums = op_checks.softsplat_ref(torch.cat([val, torch.ones_like(val[:, :1])], 1), flow, None, "sum")
+    tgt = op_checks._grid32(h, w) + flow
+
+    def value(num, den, k, py, px):
+        if den / (den + 1e-7) < 0.999:
+            return [2.0 * max(h, w)] * nv if op == "flow_reverse" else [float(val[k, 0, py, px])]
+        return [(-2.0 if op == "flow_reverse" else 1.0) * float(a) / (den + 1e-7) for a in num]
+
+    out = []
+    for k, y, x in planted:
+        X, Y = float(tgt[k, 0, y, x]), float(tgt[k, 1, y, x])
+        assert abs(X) < 2.0 ** 30 and abs(Y) < 2.0 ** 30, (k, y, x)  # (a planted source is one that contributes)
+        x0, y0 = int(X // 1), int(Y // 1)
+        eff = 0.0
+        for dy in (0, 1):
+            for dx in (0, 1):
+                px, py = x0 + dx, y0 + dy
+                if not (0 <= px < w and 0 <= py < h):
+                    continue
+                wgt = ((X - x0) if dx else (x0 + 1 - X)) * ((Y - y0) if dy else (y0 + 1 - Y))
+                num, den = sums[k, :nv, py, px], float(sums[k, nv, py, px])
+                before = value(num, den, k, py, px)
+                after = value(num - val[k, :, y, x].double() * wgt, den - wgt, k, py, px)
+                eff = max([eff] + [abs(a - b) for a, b in zip(before, after)])
+        out.append(eff)
+    return out
+
+
+def _assert_decisive(name, op, t, fs, fo, planted):
+    eff = _loo_effect(op, t, fs, fo, planted)
+    weak = [(p, e) for p, e in zip(planted, eff) if not e >= 100.0 * op_checks.RIFE_BARS[op]]
+    assert not weak, (name, op, t, weak[:5])
+    return len(eff)
+
+
+def test_rife_planted_sources_are_decisive():
+    """Leave-one-out: the reference without a planted source differs from the reference by at least 100 tolerances at some pixel,
+    for every planted source of every row -- none is one whose loss the row would forgive."""
+    n = sum(_assert_decisive(name, op, t, fs, fo, planted) for name, _, op, t, fs, fo, planted, _ in _rife_cases_with_inputs())
+    assert n > 500, n
+
+
+def test_rife_rows_are_stable_enough(clean):
+    """the unstable share of every row, from the reference alone, is under decisions.UNSTABLE_SHARE -- and a map of one pixel has none"""
+    from tests import decisions
+    shares = [r for r in clean[RIFE_TITLE][0] if "unstable share" in r[0]]
+    assert len(shares) > 100 and all(r[1] <= decisions.UNSTABLE_SHARE == r[2] for r in shares), [r[0] for r in shares if r[1] > r[2]]
+    assert all(r[1] == 0.0 for r in shares if "small 1x1" in r[0])
+    bars = {r[2] for r in clean[RIFE_TITLE][0] if ": stable pixels" in r[0] or "nearer branch" in r[0]}
+    assert bars == {2e-4, 2e-5}  # the two bars gpu_checks.check_glue holds these entry points to
+
+
+REACH_EXPECTED = (4, 5, 4, 5, 4, 8, 9, 8, 9, 8, 16, None, 16, 16, None, 2, 6, 10, 5, 9)  # per REACH_VALUES; None: long
+
+
+def test_rife_case_table_reaches_what_it_names():
+    """From the restated rules (tests/det_common.py), on the flow every entry point splats along: the window rows take exactly
+    their variant at both tiles; the reach rows hold every rounding on both sides of 4, 8 and 16 and both long bounds; a quiet tile
+    has reach 0 and scans 16; long, non-finite and far sources are where the rows say; the record totals are exactly those claimed
+    and the spilled records straddle the tile edge; every item has its pinch, its long block, its reach-16 tile and the quiet one."""
+    TX, TY, CAP = det_common.TX, det_common.TY, det_common.CAP
+    seen = set()
+    for name, group, op, t, fs, fo, planted, claims in _rife_cases_with_inputs():
+        flow = op_checks.rife_splat_flow(op, fs, fo, t)
+        finite, short = det_common.source_class(flow)
+        variant, reach = det_common.tile_variant(flow), det_common.tile_reach(flow)
+        seen.add(group)
+        if group == "window":
+            for tx, ty in claims["tiles"]:
+                assert int(variant[0, ty, tx]) == claims["variant"], (name, op, t, tx, ty)
+            assert all(bool(finite[p] & short[p]) for p in planted) and len(planted) >= 30
+            if "identity" in name:
+                assert set(reach.unique().tolist()) <= {2, claims["variant"]}
+        elif group == "reach":
+            assert len(REACH_EXPECTED) == len(claims["values"])
+            r = det_common.source_reach(flow)
+            for i, (k, y, x) in enumerate(planted):
+                want = REACH_EXPECTED[i // 4]
+                assert bool(finite[k, y, x]) and bool(short[k, y, x]) == (want is not None) and int(r[k, y, x]) == (want or 0), (i, k, y, x)
+                assert int(reach[k].max()) == (want or 0)  # the item's only source
+        elif group == "neighbour":
+            for k, (tx, ty) in claims["quiet"].items():
+                assert int(reach[k, ty, tx]) == 0 and int(variant[k, ty, tx]) == 16 and int(reach[k].max()) == 16, (k, tx, ty)
+            k = claims["mirror"]
+            tot = det_common.tile_record_totals(flow)[k]
+            assert int(reach[k, 1, 1]) == 16 and bool((variant[k] == 16).all()) and int(tot.sum()) == int(tot[1, 1]) == 2
+        elif group == "long":
+            assert int((finite & ~short).sum()) == claims["long"] + (0 if claims["long"] == 0 else int((flow[:, 0] >= ALONE_MIN).sum()))
+            if claims["long"]:
+                tg = op_checks._grid32(*flow.shape[2:]) + flow[0]
+                for _, y, x in planted:  # exactly one corner of the footprint inside the map
+                    cx, cy = int(tg[0, y, x].floor()), int(tg[1, y, x].floor())
+                    inside = [(a, b) for a in (cx, cx + 1) for b in (cy, cy + 1) if 0 <= a < flow.shape[3] and 0 <= b < flow.shape[2]]
+                    assert len(inside) == 1 and not bool(short[0, y, x]), (y, x, inside)
+        elif group == "nonfinite":
+            ys, xs = zip(*claims["spots"])
+            assert int((~finite[0, list(ys), list(xs)]).sum()) == 6 and int((finite & ~short)[0, list(ys), list(xs)].sum()) == 12
+        elif group == "capacity":
+            tot = det_common.tile_record_totals(flow)
+            tx, ty = op_checks.PINCH
+            assert int(tot[0, ty, tx]) == claims["records"], (name, op, t)
+            kx, ky, ok = det_common.record_keys(flow)
+            mine = ok[0] & (kx[0] >= tx * TX - 1) & (kx[0] <= tx * TX + 31) & (ky[0] >= ty * TY - 1) & (ky[0] <= ty * TY + 15)
+            assert int(mine.sum()) == claims["records"]
+            last = ky[0][mine].max()  # the records in the last key row spill first
+            assert int(last) == ty * TY + 15 and int((mine & (ky[0] == last)).sum()) >= 2 and int((mine & (ky[0] == ty * TY - 1)).sum()) >= 2
+            assert ("long source" in name) == bool((finite & ~short & (flow[:, 0].abs() < 1e3)).any())
+        elif group == "items":
+            tot = det_common.tile_record_totals(flow)
+            for k in range(op_checks.ITEMS):
+                (ax, ay), (qx, qy), (px, py) = op_checks.ITEM_REACH16[k], op_checks.ITEM_REACH16[k - 1], op_checks.ITEM_PINCH[k]
+                assert int(reach[k, ay, ax]) == 16 and int(reach[k, qy, qx]) == 0 and int(reach[k - 1, qy, qx]) == 16, k
+                assert int(tot[k, py, px]) > CAP and int((finite & ~short)[k].sum()) == 36, (k, int(tot[k, py, px]))
+                assert len({op_checks.ITEM_PINCH[k], op_checks.ITEM_REACH16[k], op_checks.ITEM_REACH16[k - 1]}) == 3
+            assert len(set(op_checks.ITEM_PINCH)) == len(set(op_checks.ITEM_REACH16)) == op_checks.ITEMS
+    assert seen == set(op_checks.RIFE_GROUPS)
+    assert [tuple(c.flow.shape[2:]) for c in op_checks.rife_cases(("small",))] == list(op_checks.RIFE_SIZES)
+    totals = {c[1] for c in op_checks.CAPACITY_TOTALS}
+    assert {CAP - 1, CAP, CAP + 1} <= totals and any(abs(v - 1.5 * CAP) < 1 for v in totals)
+
